@@ -9,7 +9,9 @@ anatomix/registration/convex_adam_utils.py:202-219; the reference feeds sw_batch
 per call, the result is independent of that batching (BatchNorm in eval mode), B = 4 here), fp32
 [B,16,128,128,128] features written to HBM.  Ranks are independent replicas on different windows (no data-path collective): weak scaling.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs DIR is given, and prints the line.  --full adds everything else: the parity checks, the sustained run, the secondary
+workloads (other variants, precisions, sizes, the training step) and these extra objects:
   roofline     -- dominant kernel (largest share of the step), ALGORITHMIC flops per launch /
                   hipEvent-measured average launch duration, against the dense 16-bit MFMA peak;
   cpu_baseline -- the CPU restatement (oracle, torch.nn.functional = the ATen/oneDNN kernels the
@@ -29,6 +31,8 @@ MFMA_PEAK_TFLOPS = 2500.0      # dense bf16/f16 MFMA, /opt/skills/guides/MI355X_
 HBM_PEAK_GBS = 8000.0
 GFLOP_PER_VOLUME_6M = 346.986381312
 GFLOP_PER_VOLUME_DEV = 1418.75         # SURVEY.md section 8(d), anatomix-dev
+DUMP_SAMPLE = 1 << 22                  # --dump-outputs: elements kept of a larger output (values 16 MB + flat indices 32 MB)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse():
@@ -49,9 +53,16 @@ def parse():
                          "strict precision) that are reported in the `secondary` object of the JSON line")
     ap.add_argument("--all-secondary", action="store_true",
                     help="also run the non-compliant / duplicate secondaries (anatomix-dev in f16 and bf16x2, the ViT at batch 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, cpu_baseline, parity, sustained run and the secondary workloads (the options "
+                         "--no-secondary, --all-secondary, --no-cpu-baseline, --cpu-forwards, --no-parity and --sustain act on these); "
+                         "a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path returned in its last step to DIR/<name>.npy "
+                         "(fp32 / fp64; an output larger than %d elements as a fixed, seeded sample)" % DUMP_SAMPLE)
     ap.add_argument("--full-line", action="store_true",
-                    help="print the full result (per-kernel tables, workload descriptions) instead of the compact line; the full result is "
-                         "always written to gpurun_out/bench_full.json when that directory can be created")
+                    help="print the full result (per-kernel tables, workload descriptions) instead of the compact line; with --full "
+                         "the full result is also written to bench_full.json in the repository's run-output folder")
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous plumbing only (gloo, no GPU work): prints a stub line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true",
@@ -491,11 +502,40 @@ def build_model(ctx, variant, precision):
     return model.to(ctx.dev).eval()
 
 
+def dump_outputs(torch, out_dir, arrays):
+    """--dump-outputs: the arrays a caller of the timed path received from its last step, one DIR/<name>.npy each (tensors fp32,
+    scalars fp64).  A tensor of more than DUMP_SAMPLE elements is written as the values at DUMP_SAMPLE flat indices drawn from a fixed
+    seed (<name>_sample.npy) and those indices (<name>_sample_index.npy, fp64): the same arguments give the same indices in every run."""
+    import numpy as np
+    files = {}
+    for name, a in arrays.items():
+        if not torch.is_tensor(a):
+            files[name] = np.asarray(a, dtype=np.float64)
+            continue
+        flat = a.detach().reshape(-1)
+        if flat.numel() <= DUMP_SAMPLE:
+            files[name] = flat.float().cpu().numpy().reshape(tuple(a.shape))
+            continue
+        idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        files[name + "_sample"] = flat[idx.to(flat.device)].float().cpu().numpy()
+        files[name + "_sample_index"] = idx.double().numpy()
+    total = sum(v.nbytes for v in files.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def run_workload(ctx, variant="anatomix", workload="forward", sw_volume=0, precision="f16", steps=100, warmup=10, batch=4, size=128,
-                 no_graph=False, with_cpu=True, cpu_forwards=6, with_parity=True, sustain_s=0.0):
-    """One measured workload -> the result dict of the JSON line (rank 0; None on the other ranks)."""
+                 no_graph=False, with_cpu=True, cpu_forwards=6, with_parity=True, sustain_s=0.0, with_roofline=True, dump_dir=None):
+    """One measured workload -> the result dict of the JSON line (rank 0; None on the other ranks).  with_roofline / with_cpu /
+    with_parity / sustain_s: the measurements and checks beside the timed steps; dump_dir: where the last timed step's outputs go."""
     torch, dist, dev, world, rank = ctx.torch, ctx.dist, ctx.dev, ctx.world, ctx.rank
     from oracle import unet_ref as R
+    # the step's projection heads are initialised from torch's global generator and its patch coordinates drawn from it: seeded, so
+    # that the same arguments give the same inputs in every run (and the same head weights on every rank)
+    torch.manual_seed(0)
     model = build_model(ctx, variant, precision)
     S, B = size, batch
     x = R.synthetic_input(100 + rank, B, (S, S, S)).to(dev)      # resident before the timed region
@@ -547,9 +587,12 @@ def run_workload(ctx, variant="anatomix", workload="forward", sw_volume=0, preci
         buckets = GradientBuckets((model, netF), bucket_mb=16.0, overlap=no_graph) if world > 1 else None
         if buckets is not None:
             dp_note = f"; gradients in {len(buckets.buckets)} flat buckets ({buckets.nbytes / 1e6:.1f} MB), async all_reduce each"
+        last_record = {}
         if no_graph:
-            step = lambda: contrastive_step(model, netF, crits, vA, vB, seg, PI.NCE_LAYERS, num_patches=512, optimizers=opts,
-                                            grad_buckets=buckets)["out"]
+            def step():
+                last_record["r"] = contrastive_step(model, netF, crits, vA, vB, seg, PI.NCE_LAYERS, num_patches=512, optimizers=opts,
+                                                    grad_buckets=buckets)
+                return last_record["r"]["out"]
         else:
             # the whole step replayed from a HIP graph (1 GPU: optimizers included; data parallel: forward + backward in the
             # graph, then the RCCL all-reduces of the buckets, gradient norms and AdamW)
@@ -560,7 +603,6 @@ def run_workload(ctx, variant="anatomix", workload="forward", sw_volume=0, preci
             # than the ~0.15 ms host gap they remove, so the bench reads the scalars every step like the reference does.
             graphed = GraphedContrastiveStep(model, netF, crits, PI.NCE_LAYERS, opts, num_patches=512, grad_buckets=buckets,
                                              lazy_scalars=os.environ.get("AMX_LAZY_SCALARS", "0") == "1")
-            last_record = {}
 
             def step():
                 last_record["r"] = graphed(vA, vB, seg)
@@ -593,6 +635,13 @@ def run_workload(ctx, variant="anatomix", workload="forward", sw_volume=0, preci
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    if dump_dir and rank == 0:
+        if workload == "step":
+            r = last_record["r"]
+            dump_outputs(torch, dump_dir, {"output": y, "loss": r["loss"], "per_layer_loss": list(r["per_layer"].values()),
+                                           "grad_norm": [r["grad_norm_G"], r["grad_norm_F"]]})
+        else:
+            dump_outputs(torch, dump_dir, {"features": y})
     if not on_gpu:        # plumbing run: no kernel roofline, no host baseline -- the line only proves the N-rank path end to end
         if rank != 0:
             return None
@@ -620,7 +669,9 @@ def run_workload(ctx, variant="anatomix", workload="forward", sw_volume=0, preci
     result = None
     if rank == 0:
         vit = variant == "anatomix-dev-vit"
-        if workload == "step":
+        if not with_roofline:
+            roofline = None
+        elif workload == "step":
             roofline = step_roofline(torch, dev, S)
         elif vit:
             roofline = vit_roofline(ctx, model, B)
@@ -685,8 +736,9 @@ def run_workload(ctx, variant="anatomix", workload="forward", sw_volume=0, preci
                        "parallelism": par},
             "end_to_end_TFLOPs": round(value * gflop_vol / 1e3, 1),
             "end_to_end_mfma_frac": round(value / world * gflop_vol / 1e3 / MFMA_PEAK_TFLOPS, 4),
-            "roofline": roofline,
         }
+        if roofline is not None:
+            result["roofline"] = roofline
         if sustained is not None:
             result["sustained"] = sustained
         if world == 1 and with_cpu:
@@ -843,10 +895,11 @@ def main():
         args.precision = "f16"
     result = run_workload(ctx, variant=args.variant, workload=args.workload, sw_volume=args.sw_volume, precision=args.precision,
                           steps=args.steps, warmup=args.warmup, batch=args.batch, size=args.size, no_graph=args.no_graph,
-                          with_cpu=not args.no_cpu_baseline, cpu_forwards=args.cpu_forwards, with_parity=not args.no_parity,
-                          sustain_s=args.sustain)
+                          with_cpu=args.full and not args.no_cpu_baseline, cpu_forwards=args.cpu_forwards,
+                          with_parity=args.full and not args.no_parity, sustain_s=args.sustain if args.full else 0.0,
+                          with_roofline=args.full, dump_dir=args.dump_outputs)
     headline = args.variant == "anatomix" and args.workload == "forward" and not args.sw_volume and args.precision == "f16"
-    if rank == 0 and world == 1 and headline and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and headline and not args.no_secondary:
         result["secondary"] = secondary_workloads(ctx, args)
         # The precision contract of the headline, in the line itself.  f16 storage meets the north-star tolerance (<= 1e-3 relative
         # to the fp32 reference) in rel-L2 (parity.rel_l2_vs_fp32_cpu_oracle) but NOT always in the max-norm (0.86e-3 .. 1.4e-3 over
@@ -869,13 +922,14 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
             with open(os.path.join(ROOT, "gpurun_out", "bench_full.json"), "w") as fh:
                 fh.write(json.dumps(result) + "\n")
         except OSError:
             pass
+    if rank == 0:
         print(json.dumps(result if args.full_line else compact_line(result)))
 
 
@@ -899,7 +953,8 @@ def compact_line(result):
     """The ONE JSON line the driver records (it keeps ~9 KB of stdout): every contract field of the headline, short secondaries,
     and -- last -- one `summary` object with value / ms_per_step / dtype / roofline fraction / parity of every BASELINE config."""
     out = {k: v for k, v in result.items() if k not in ("roofline", "secondary", "parity", "value_dev_compliant", "value_strict", "sustained")}
-    out["roofline"] = _short_roofline(result.get("roofline"))
+    if "roofline" in result:
+        out["roofline"] = _short_roofline(result["roofline"])
     if "parity" in result:
         out["parity"] = _short_parity(result["parity"])
     if isinstance(result.get("sustained"), dict):

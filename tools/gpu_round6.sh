@@ -8,7 +8,7 @@ TAG=${1:-r06}
 REPO=$PWD
 OUT=$PWD/gpurun_out
 mkdir -p $OUT
-timeout 1000 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout 1000 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 cp $OUT/bench_full.json $OUT/${TAG}_bench_full.json 2>/dev/null
 wc -c $OUT/${TAG}_bench.json; tail -c 700 $OUT/${TAG}_bench.json; echo
 (timeout 300 python tools/layer_profile.py anatomix 4) > $OUT/${TAG}_layers_6m.txt 2>/dev/null
