@@ -47,14 +47,6 @@ struct DeviceOnce {
   }
 };
 
-// Experiment / ablation switches are environment variables ONLY in a -DAMX_EXPERIMENT build (make EXTRA=-DAMX_EXPERIMENT); the
-// product library reads no environment on any path: every switch is a compile-time "unset".
-#ifdef AMX_EXPERIMENT
-inline const char* exp_env(const char* name) { return getenv(name); }
-#else
-inline const char* exp_env(const char*) { return nullptr; }
-#endif
-
 // Parameters of one 3x3x3 reflect-padded convolution launch.  All tensors are channels-last
 // (N, D, H, W, C) 16-bit unless noted.  Strides are in BYTES.
 struct ConvParams {
@@ -82,7 +74,7 @@ struct ConvParams {
   long long qn, qz, qy, qx;    //   into the epilogue of the z-marching kernel (nn.MaxPool3d(2), network.py:368)
   int* oflow;                  // optional device flag: set to 1 when a value that is about to be stored in f16 is out of the
                                //   f16 range (|v| > 65504) or NaN -- see amx_unet_numerics_status (include/anatomix_amd.h)
-  int dbg;                     // ablation switches (env AMX_DBG; 0 in production): 1 no DMA after the first, 2 no MFMA sweep, 4 no stores
+  int dbg;                     // kernel ablation bits, always 0 (memset): 1 no DMA after the first, 2 no MFMA sweep, 4 no stores
   const int* mxs;              // AMX_PREC_F16X2_MX: device word holding the E8M0 block-scale byte (x4) of this layer's fp8 weights
   int raw_halo;                // 1: src0 is the INTERIOR of a zero-framed buffer (frame >= 1 voxel): halo voxels are read from the frame at
                                //   coordinates -1 / n instead of being reflected (the data gradient's interior part, amx_train.hip)
@@ -101,8 +93,6 @@ struct ConvParams {
 //          voxels of 128 .. 6144 bytes a stage used 32 bytes of every cache line it touched: LDS-DMA ran at 11-15 B/clk/CU instead
 //          of 44-48, profiles/r03_dma_stride_ubench.txt, and bounded the generic kernel.)
 //          byte(n, z, y, x, plane P, b) = ((n D + z) H + y) * 6 C W + P * 32 W + 32 x + b
-//   FMT 3  single 16-bit values stored ROW-PLANAR like FMT 2 (2C bytes per voxel, C/16 planes of W x 32 bytes per row): the wide
-//          (>= 64-channel) tensors of the f16 / bf16 forward, for the same reason -- byte(n, z, y, x, P, b) = ((n D + z) H + y) * 2 C W + P * 32 W + 32 x + b
 __host__ __device__ constexpr int fmt_of_precision(int precision) { return precision < 2 ? 0 : (precision == 4 ? 2 : 1); }
 __host__ __device__ constexpr int fmt_elem_bytes(int fmt) { return fmt == 0 ? 2 : (fmt == 1 ? 4 : 6); }
 
@@ -116,16 +106,6 @@ inline void pick_z_segments(int tiles, int D, int unit, int slots, int* zseg_out
   const int fill = 6;                                   // ring fill + first-step latency, in plane-times
   long long best = -1;
   int bz = D, bn = 1;
-  static const bool old_rule = exp_env("AMX_OLD_ZSEG") != nullptr;     // experiment builds: the rule until round 4, for A/B
-  if (old_rule) {
-    int n = (slots + tiles - 1) / tiles;
-    if (n < 1) n = 1;
-    int zs = ((D + n - 1) / n + unit - 1) / unit * unit;
-    if (zs < 8) zs = 8;
-    *zseg_out = zs;
-    *nseg_out = (D + zs - 1) / zs;
-    return;
-  }
   for (int n = 1; n <= 32; ++n) {
     int zs = (D + n - 1) / n;
     zs = (zs + unit - 1) / unit * unit;
@@ -177,7 +157,7 @@ struct WgradParams {
   float* partial;                       // [nchunk][npairs][27][16][16]
   int nchunk, items_per_chunk, nitems, nyt;
   int nxt, ppc, cpx, nplanes;            // transpose-read kernel: x tiles, planes per chunk, (chunk, pair) entries per XCD, tiles * D
-  int dbg;                               // experiment builds: 1 = no MFMA sweep, 2 = no DMA
+  int dbg;                               // kernel ablation bits, always 0 (memset): 1 = no MFMA sweep, 2 = no DMA
   float* dw;                             // nchunk == 1: the workgroup writes dW[Cout][cin_real][27] itself (no partials, no reduce launch)
   int cin_real, accumulate;
 };

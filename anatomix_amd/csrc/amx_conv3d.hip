@@ -197,11 +197,11 @@ __global__ void fold_norm_kernel(const float* gamma, const float* beta, const fl
 template <typename T, int AVG, int FMT>
 __global__ void pool2_kernel(const char* __restrict__ in, char* __restrict__ out, int N, int Do,
                              int Ho, int Wo, int C, int skip_lo) {
-  constexpr bool SPLIT = FMT == 1 || FMT == 2, PLANAR = FMT >= 2;      // FMT 3: single values, row-planar (amx_common.h)
+  constexpr bool SPLIT = FMT == 1 || FMT == 2, PLANAR = FMT == 2;
   const int c8n = C >> 3;
   const long long total = (long long)N * Do * Ho * Wo * c8n;
   // FMT 2 (row-planar, amx_common.h): 32 bytes per voxel inside plane c8 >> 1 of its row; rows are C * 6 * W bytes in every layout
-  constexpr int EB = FMT == 3 ? 2 : fmt_elem_bytes(FMT);
+  constexpr int EB = fmt_elem_bytes(FMT);
   const long long sx = PLANAR ? 32 : (long long)C * EB, sy = (long long)C * EB * (Wo * 2), sz = sy * (Ho * 2);
   const long long lo_in = FMT == 2 ? 2ll * C * (Wo * 2) : 2 * C, lo_out = FMT == 2 ? 2ll * C * Wo : 2 * C;
   for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
@@ -253,9 +253,6 @@ __global__ void pool2_kernel(const char* __restrict__ in, char* __restrict__ out
       *(uint4*)op = make_uint4(o[0], o[1], o[2], o[3]);
       if (!(FMT == 2 && skip_lo)) *(uint4*)(op + lo_out) = make_uint4(ol[0], ol[1], ol[2], ol[3]);   // (conv-only readers: hi + copies)
       if (FMT == 2) mx_store_copies(op - (c8 & 1) * 16 + 2 * lo_out, c8 & 1, m);
-    } else if (FMT == 3) {
-      const long long vlin = idx / c8n;
-      *(uint4*)(out + (vlin / Wo) * (2ll * C * Wo) + (long long)(c8 >> 1) * (Wo * 32) + x * 32 + (c8 & 1) * 16) = make_uint4(o[0], o[1], o[2], o[3]);
     } else {
       *(uint4*)(out + idx * 16) = make_uint4(o[0], o[1], o[2], o[3]);
     }
@@ -279,12 +276,6 @@ int conv_pick_q(int Cout, int W, int precision) {
   // 192 -> 64 @64^3 1664 -> 1264, 384 -> 128 @32^3 809 -> 631; Q = 1: 536 / 1479 / 733).  The single 16-bit and the bf16x2 / f16x2
   // kernels measured 0-7 % SLOWER with two (6 M forward 64 -> 64 @32^3 45.5 -> 46.9 us; strict 192 -> 64 @64^3 2045 -> 2197).
   if (precision == 4) q = 2;
-  // experiment switches (-DAMX_EXPERIMENT builds only): read ONCE -- the packing at create time and the launch must see the same Q --
-  // and only the values the kernels are instantiated for
-  static const int q_wide = [] { const char* e = exp_env("AMX_Q_WIDE"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2 || v == 4) ? v : 0; }();
-  static const int q_deep = [] { const char* e = exp_env("AMX_Q_DEEP"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2 || v == 4) ? v : 0; }();
-  if (W >= 32 && q_wide) q = q_wide;
-  if (W <= 8 && q_deep) q = q_deep;
   // (round 4, same box, batch 4: Q = 1 or 4 instead of 2 at the 8^3 level: 128 -> 256 22.2 -> 22.8 / 27.9 us, 256 -> 256 32.8 -> 34.7 / 44.9;
   //  at the 16^3 level Q = 1 / 4: 128 -> 128 28.1 -> 52.1 / 39.2 us -- more or fewer cout groups do not help: profiles/r04_deep_level_q.txt)
   while (Cout % (16 * q)) q >>= 1;   // 48 / 96 / 192 output channels (data gradients of the concat convs): 1 / 2 / 4
@@ -304,15 +295,12 @@ const char* last_conv_zm_kernel_name();
 
 // true when launch_conv runs the generic kernel for this layer -- the one whose epilogue can write InstanceNorm partial sums
 bool conv_fuses_stats(const ConvParams& p, int precision, int Q) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_FUSED_STATS") ? 1 : 0;
-  if (off || p.src0_f32c1 || p.out32) return false;
+  if (p.src0_f32c1 || p.out32) return false;
   return !((((precision < 2 && conv_zmarch_eligible(p)) || ((precision == 2 || precision == 3) && conv_zmarch_eligible_split(p))) && Q == p.Cout / 16));
 }
 int last_conv_stats_slots() { return last_conv_v2_stats_slots(); }
 
 hipError_t launch_conv(const ConvParams& p, int precision, int Q, hipStream_t st) {
-  const bool planar = p.out32 != nullptr;
   if (((precision < 2 && conv_zmarch_eligible(p)) || ((precision == 2 || precision == 3) && conv_zmarch_eligible_split(p))) && Q == p.Cout / 16) {
     // narrow full/half-resolution layers: z-marching ring kernel
     hipError_t e = launch_conv_zmarch(p, precision, st);
@@ -321,7 +309,6 @@ hipError_t launch_conv(const ConvParams& p, int precision, int Q, hipStream_t st
   }
   if (p.src0_f32c1) return hipErrorInvalidValue;   // the fp32 stem has its own kernel (amx_conv3d_stem.hip)
   if (p.raw_halo) return hipErrorInvalidValue;     // frame-reading sources: the z-march kernels only
-  (void)planar;
   if (conv_ks_eligible(p, precision, Q)) {           // deep levels: register-stationary weights, K split over the waves
     hipError_t e = launch_conv_ks(p, precision, Q, st);
     snprintf(g_kernel_name, sizeof g_kernel_name, "%s", last_conv_ks_kernel_name());
@@ -401,18 +388,14 @@ hipError_t launch_fold_norm(const float* gamma, const float* beta, const float* 
   return hipGetLastError();
 }
 
-// planar (precisions 0 / 1 only): input AND output are row-planar (layout FMT 3)
 hipError_t launch_pool2(const void* in, void* out, int N, int Do, int Ho, int Wo, int C, int avg,
-                        int precision, hipStream_t st, int skip_lo, int planar) {
-  if (planar && (precision > 1 || C % 16)) return hipErrorInvalidValue;
+                        int precision, hipStream_t st, int skip_lo) {
   const long long total = (long long)N * Do * Ho * Wo * (C / 8);
   const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
 #define AMX_POOL(T, A, S)                                                                            \
   hipLaunchKernelGGL((pool2_kernel<T, A, S>), dim3(blocks), dim3(256), 0, st, (const char*)in, (char*)out, \
                      N, Do, Ho, Wo, C, skip_lo)
-  switch (precision + (planar ? 10 : 0)) {
-    case 10: if (avg) AMX_POOL(f16, 1, 3); else AMX_POOL(f16, 0, 3); break;
-    case 11: if (avg) AMX_POOL(bf16, 1, 3); else AMX_POOL(bf16, 0, 3); break;
+  switch (precision) {
     case 0: if (avg) AMX_POOL(f16, 1, false); else AMX_POOL(f16, 0, false); break;
     case 1: if (avg) AMX_POOL(bf16, 1, false); else AMX_POOL(bf16, 0, false); break;
     case 2: if (avg) AMX_POOL(f16, 1, true); else AMX_POOL(f16, 0, true); break;

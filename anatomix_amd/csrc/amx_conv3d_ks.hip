@@ -185,22 +185,7 @@ __global__ __launch_bounds__(C::NWAVE * 64, C::NWAVE * C::WGS_PER_CU / 4) void c
     }
   };
 
-  // ablation switches and the optional cycle trace exist in -DAMX_EXPERIMENT builds only (AMX_DBG / AMX_TRACE=1: wave 0 of each
-  // workgroup stamps s_memtime per phase); the product kernel carries neither the branches nor their registers
-#ifdef AMX_EXPERIMENT
-  const int dbg = p.dbg;
-  unsigned long long* trace = (dbg & 8) ? (unsigned long long*)p.stats + (long long)blockIdx.x * 64 : nullptr;
-  int tcount = 0;
-#define AMX_STAMP()                                                                                      \
-  do {                                                                                                   \
-    if (trace && wave == 0 && lane == 0 && tcount < 64) trace[tcount] = __builtin_readcyclecounter();    \
-    ++tcount;                                                                                            \
-  } while (0)
-#else
-  constexpr int dbg = 0;
-#define AMX_STAMP() do {} while (0)
-#endif
-  AMX_STAMP();
+  constexpr int dbg = 0;                                    // ablation bits: compiled out, the kernel carries neither the branches nor their registers
 
   // ---- L2 warm-up of this workgroup's weights.  Every workgroup of a (cout group, slice) streams the SAME packed range, all of
   //      them at kernel start: each line is then a first touch (HBM / Infinity-Cache latency, ~1-2 us) for every CU at once, and a
@@ -248,7 +233,6 @@ __global__ __launch_bounds__(C::NWAVE * 64, C::NWAVE * C::WGS_PER_CU / 4) void c
   static_assert(NA <= 63, "vmcnt is a 6-bit counter");
   asm volatile("" ::"v"(sink));                             // (the touch is older than the halo DMA: returned by now)
   if (CW > 1) __syncthreads();                              // the other cout waves' share of the first halo has landed too
-  AMX_STAMP();
 
   f32x4 acc[NVTG][Q];
   int t = 0;                                                // stage counter of the brick's first chunk: chunk buffer (t + cp) & 1
@@ -280,7 +264,6 @@ __global__ __launch_bounds__(C::NWAVE * 64, C::NWAVE * C::WGS_PER_CU / 4) void c
             issue(nx, 0, (t + cp + 1) & 1);
           }
         }
-        AMX_STAMP();
         if (cp == 0) {
 #pragma unroll
           for (int c = 0; c < NVTG; ++c)
@@ -317,12 +300,10 @@ __global__ __launch_bounds__(C::NWAVE * 64, C::NWAVE * C::WGS_PER_CU / 4) void c
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-        AMX_STAMP();
         if (h == NH - 1) {
           // the next stage's halo (issued at least a whole sweep ago) and the previous stores have landed; the reads of this stage
           // have returned (their MFMAs were issued), so its buffer may be refilled by the stage after the next
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          AMX_STAMP();
         }
       }
 
@@ -411,13 +392,11 @@ __global__ __launch_bounds__(C::NWAVE * 64, C::NWAVE * C::WGS_PER_CU / 4) void c
         }
         __syncthreads();                                    // the scratch tiles may be overwritten (next round / group / brick)
       }
-      AMX_STAMP();
     }
     t += CPW;
     cu = nx;
     cu_valid = nx_valid;
   }
-#undef AMX_STAMP
 #undef AMX_DMA16
 }
 
@@ -504,36 +483,8 @@ static hipError_t launch_ks_cfg(ConvParams p, hipStream_t st) {
   if (wpc < 1) wpc = 1;
   const int runs = (nbricks + C::TEAMS - 1) / C::TEAMS;      // a workgroup needs at least one brick per team to be useful
   if (wpc > runs) wpc = runs;
-  static int dbg = -1;                                      // (always 0 in the product build: exp_env is a constant there)
-  static unsigned long long* trace_buf = nullptr;
-  if (dbg < 0) {
-    const char* e = exp_env("AMX_DBG");
-    dbg = e ? atoi(e) : 0;
-    if (exp_env("AMX_TRACE")) dbg |= 8;
-  }
-  p.dbg = dbg;
   const unsigned grid = (unsigned)(combos * wpc);
-  if (dbg & 8) {   // debug only: per-phase cycle stamps, printed after a sync
-    if (!trace_buf && hipMalloc((void**)&trace_buf, 1024 * 64 * 8) != hipSuccess) return hipErrorOutOfMemory;
-    (void)hipMemsetAsync(trace_buf, 0, 1024 * 64 * 8, st);
-    p.stats = (float*)trace_buf;
-  }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NWAVE * 64), C::LDS_BYTES, st, p);
-  if (dbg & 8) {
-    static int printed = 0;
-    (void)hipStreamSynchronize(st);
-    if (printed++ == 3) {
-      static unsigned long long hostbuf[1024 * 64];
-      (void)hipMemcpy(hostbuf, trace_buf, sizeof hostbuf, hipMemcpyDeviceToHost);
-      const int wgs[4] = {0, 1, (int)grid / 2, (int)grid - 1};
-      for (int wi = 0; wi < 4; ++wi) {
-        const unsigned long long* tr = hostbuf + (long long)wgs[wi] * 64;
-        fprintf(stderr, "[trace %s wg %d] start %llu :", g_kernel_name_ks, wgs[wi], tr[0]);
-        for (int k = 1; k < 64 && tr[k]; ++k) fprintf(stderr, " %llu", tr[k] - tr[k - 1]);
-        fprintf(stderr, "\n");
-      }
-    }
-  }
   return hipGetLastError();
 }
 
@@ -569,18 +520,14 @@ static KsPlan ks_plan(const ConvParams& p, int precision, int Q, bool can_split)
     // per SIMD -- 128 -> 128 @16^3 measured 24.9 us per launch against 21.3 for conv3d_k3_v2: profiles/r05_ks_shapes.txt; that
     // shape stays on the generic kernel.)
     const int s8 = nchunk / 8;                                // slices with CPW = 2
-    static const int thin = exp_env("AMX_KS_THIN") ? 1 : 0;  // experiment: always one chunk per wave (twice the slices)
     if ((long long)ncg * nbricks >= 192) return r;            // enough (cout group, brick) pairs without a split: partial tensors would only add traffic
-    if (!thin && s8 >= 2 && (long long)ncg * s8 * nbricks >= 192 && s8 <= 8) { r = {1, 4, 2, 1, s8, 1}; return r; }
+    if (s8 >= 2 && (long long)ncg * s8 * nbricks >= 192 && s8 <= 8) { r = {1, 4, 2, 1, s8, 1}; return r; }
     if (s8 * 2 <= 16) { r = {1, 4, 1, 1, s8 * 2, cw_of(s8 * 2)}; return r; }
   }
   return r;
 }
 
 bool conv_ks_eligible(const ConvParams& p, int precision, int Q) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_KS") ? 1 : 0;
-  if (off) return false;
   return ks_plan(p, precision, Q, p.part != nullptr).ok != 0;
 }
 

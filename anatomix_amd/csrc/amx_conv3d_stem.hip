@@ -552,8 +552,7 @@ const char* last_conv_stem_kernel_name() { return g_kernel_name4; }
 // z segments per (n, y, x) tile -- tiny LDS footprint: several workgroups per CU
 static void stem_segments(const ConvParams& p, int TY, int TX, int TZ, int* zseg_out, int* nseg_out) {
   const int tiles = ((p.H + TY - 1) / TY) * ((p.W + TX - 1) / TX) * p.N;
-  static int wgs = -1;
-  if (wgs < 0) wgs = exp_env("AMX_STEM_WGS") ? atoi(exp_env("AMX_STEM_WGS")) : 512;
+  const int wgs = 512;
   int nseg = (wgs + tiles - 1) / tiles;
   if (nseg < 1) nseg = 1;
   int zseg = (p.D + nseg - 1) / nseg;
@@ -566,9 +565,7 @@ static void stem_segments(const ConvParams& p, int TY, int TX, int TZ, int* zseg
 // InstanceNorm statistics in the epilogue (ConvParams::stats): the tap-gather kernel of the split precisions, whole tiles only.
 // Returns the slots per sample ([n][slot][Cout][2] partial sums), 0 when the layer must keep its separate statistics pass.
 int conv_stem_stats_slots(const ConvParams& p, int precision) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_FUSED_STATS") ? 1 : 0;
-  if (precision < 2 || off) return 0;
+  if (precision < 2) return 0;
   constexpr int TY = 8, TX = 32, TZ = 2, NC = 8;
   if (p.H % TY || p.W % TX || p.D % TZ) return 0;
   int zseg, nseg;
@@ -584,12 +581,6 @@ static hipError_t launch_stem_t(ConvParams p, hipStream_t st) {
   snprintf(g_kernel_name4, sizeof g_kernel_name4, "conv3d_stem<%s,q%d,%dx%dx%d,c%d+l1,r%d>",
            __is_same(T, f16) ? (SPLIT ? "f16x2" : "f16") : (SPLIT ? "bf16x2" : "bf16"), Q,
            TZ, TY, TX, NC, R);
-  static int dbg = -1;
-  if (dbg < 0) {
-    const char* e = exp_env("AMX_DBG");
-    dbg = e ? atoi(e) : 0;
-  }
-  p.dbg = dbg;
   p.nby = (p.H + TY - 1) / TY;
   p.nbx = (p.W + TX - 1) / TX;
   const int tiles = p.nby * p.nbx * p.N;
@@ -597,17 +588,16 @@ static hipError_t launch_stem_t(ConvParams p, hipStream_t st) {
   stem_segments(p, TY, TX, TZ, &zseg, &nseg);
   // The row-fragment kernel is the default where it measured faster: single 16-bit storage (6 M stem, batch 4 x 128^3, same box:
   // 135.3 -> 91.5 us).  In the split precisions the layer writes twice the bytes and is store-bound either way (tap-gather
-  // 220 / 145 us vs rows 235 / 152 us for 32 / 16 channels): those keep the tap-gather kernel.  AMX_STEM_GATHER=1 / =0 force one.
-  static int gather = -1;
-  if (gather < 0) gather = exp_env("AMX_STEM_GATHER") ? atoi(exp_env("AMX_STEM_GATHER")) : 2;
-  if (!p.stats && (gather == 0 || (gather == 2 && !SPLIT))) {
-    if (p.dbg & 2) p.dbg |= 4;
-    typedef Stem2Cfg<TY, TX, TZ, NC, R, SPLIT> C2;
-    snprintf(g_kernel_name4, sizeof g_kernel_name4, "conv3d_stem<%s,q%d,%dx%dx%d,c%d+cv1,r%d,rows>",
-             __is_same(T, f16) ? (SPLIT ? "f16x2" : "f16") : (SPLIT ? "bf16x2" : "bf16"), Q, TZ, TY, TX, NC, R);
-    hipLaunchKernelGGL((conv3d_stem2_kernel<T, Q, TY, TX, TZ, NC, R, SPLIT>), dim3((unsigned)(tiles * nseg)), dim3((NC + 1) * 64),
-                       C2::LDS_BYTES, st, p, zseg, nseg);
-    return hipGetLastError();
+  // 220 / 145 us vs rows 235 / 152 us for 32 / 16 channels): those keep the tap-gather kernel.
+  if constexpr (!SPLIT) {
+    if (!p.stats) {
+      typedef Stem2Cfg<TY, TX, TZ, NC, R, SPLIT> C2;
+      snprintf(g_kernel_name4, sizeof g_kernel_name4, "conv3d_stem<%s,q%d,%dx%dx%d,c%d+cv1,r%d,rows>",
+               __is_same(T, f16) ? "f16" : "bf16", Q, TZ, TY, TX, NC, R);
+      hipLaunchKernelGGL((conv3d_stem2_kernel<T, Q, TY, TX, TZ, NC, R, SPLIT>), dim3((unsigned)(tiles * nseg)), dim3((NC + 1) * 64),
+                         C2::LDS_BYTES, st, p, zseg, nseg);
+      return hipGetLastError();
+    }
   }
   hipLaunchKernelGGL((conv3d_stem_kernel<T, Q, TY, TX, TZ, NC, R, SPLIT>), dim3((unsigned)(tiles * nseg)), dim3((NC + 1) * 64),
                      C::LDS_BYTES, st, p, zseg, nseg);

@@ -371,9 +371,7 @@ const char* last_conv_upcat_kernel_name() { return g_kernel_name5; }
 size_t conv_upcat16_packed_bytes() { return (size_t)(kSteps + 64) * 1024; }
 
 bool conv_upcat16_eligible(const ConvParams& p) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_UPCAT") ? 1 : 0;
-  return !off && !p.src0_f32c1 && p.up_shift == 1 && p.C0 == 16 && p.C1 == 32 && p.Cout == 16 && p.W >= 32 && p.H >= 8 && p.D >= 4 &&
+  return !p.src0_f32c1 && p.up_shift == 1 && p.C0 == 16 && p.C1 == 32 && p.Cout == 16 && p.W >= 32 && p.H >= 8 && p.D >= 4 &&
          !(p.D & 1) && !(p.H & 1) && !(p.W & 1);
 }
 
@@ -389,12 +387,6 @@ static hipError_t launch_upcat_t(ConvParams p, hipStream_t st) {
     if (e != hipSuccess) return e;
     attr_once.set();
   }
-  static int dbg = -1;
-  if (dbg < 0) {
-    const char* e = exp_env("AMX_DBG");
-    dbg = e ? atoi(e) : 0;
-  }
-  p.dbg = dbg;
   p.nby = (p.H + C::TY - 1) / C::TY;
   p.nbx = (p.W + C::TX - 1) / C::TX;
   const int tiles = p.nby * p.nbx * p.N;

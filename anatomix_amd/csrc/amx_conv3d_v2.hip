@@ -399,7 +399,7 @@ __global__ __launch_bounds__((NWZ * NWY + NLW) * 64) void conv3d_k3_v2_kernel(co
   f32x4 kshift[Q];                 // InstanceNorm statistics: the conv bias of this lane's channels, reloaded only when the cout group changes
   int kshift_cg = -1;
 
-  // optional cycle trace (AMX_TRACE=1): wave 0 of each workgroup stamps s_memtime per phase
+  // optional cycle trace (dbg bit 8, never set by the launcher): wave 0 of each workgroup stamps s_memtime per phase
   unsigned long long* trace = (p.dbg & 8) ? (unsigned long long*)p.stats + (long long)blockIdx.x * 128 : nullptr;
   int tcount = 0;
 #define AMX_STAMP()                                                               \
@@ -734,39 +734,11 @@ static hipError_t launch_cfg2(ConvParams p, hipStream_t st) {
   p.nbx = (p.W + C::TX - 1) / C::TX;
   g_stats_slots = p.nbz * p.nby * p.nbx * C::NW;
   // the forward sizes its statistics scratch with conv_v2_stats_slots(): the two must agree, or the epilogue would write past it
-  if (p.stats && !(p.dbg & 8) && g_stats_slots != conv_v2_stats_slots(p.D, p.H, p.W, Q)) return hipErrorInvalidConfiguration;
-  static int dbg = -1;
-  static unsigned long long* trace_buf = nullptr;
-  if (dbg < 0) {
-    const char* e = exp_env("AMX_DBG");
-    dbg = e ? atoi(e) : 0;
-    if (exp_env("AMX_TRACE")) dbg |= 8;
-  }
-  p.dbg = dbg;
+  if (p.stats && g_stats_slots != conv_v2_stats_slots(p.D, p.H, p.W, Q)) return hipErrorInvalidConfiguration;
   const long long items = (long long)p.nbz * p.nby * p.nbx * p.N * (p.Cout / (16 * Q));
   const int per_cu = C::LDS_BYTES <= 80 * 1024 ? 2 : 1;
   long long grid = items < (long long)g_num_cus * per_cu ? items : (long long)g_num_cus * per_cu;
-  if (dbg & 8) {   // debug only: per-phase cycle stamps of a few workgroups, printed after a sync
-    if (!trace_buf && hipMalloc((void**)&trace_buf, 1024 * 128 * 8) != hipSuccess) return hipErrorOutOfMemory;
-    (void)hipMemsetAsync(trace_buf, 0, 1024 * 128 * 8, st);
-    p.stats = (float*)trace_buf;
-  }
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((C::NW + NLW) * 64), C::LDS_BYTES, st, p);
-  if (dbg & 8) {
-    static int printed = 0;
-    (void)hipStreamSynchronize(st);
-    if (printed++ == 3) {
-      static unsigned long long hostbuf[1024 * 128];
-      (void)hipMemcpy(hostbuf, trace_buf, sizeof hostbuf, hipMemcpyDeviceToHost);
-      const int wgs[4] = {0, 1, (int)grid / 2, (int)grid - 1};
-      for (int wi = 0; wi < 4; ++wi) {
-        const unsigned long long* tr = hostbuf + (long long)wgs[wi] * 128;
-        fprintf(stderr, "[trace %s wg %d] start %llu :", g_kernel_name2, wgs[wi], tr[0]);
-        for (int k = 1; k < 128 && tr[k]; ++k) fprintf(stderr, " %llu", tr[k] - tr[k - 1]);
-        fprintf(stderr, "\n");
-      }
-    }
-  }
   return hipGetLastError();
 }
 
@@ -775,26 +747,12 @@ static hipError_t launch_cfg2(ConvParams p, hipStream_t st) {
 // With only two buffers the loaders cannot run ahead and the classic barrier pipeline is faster (96 -> 32 @64^3: 202 vs 223 us).
 template <typename T, int SPLIT, int WZ, int WY, int WX, int NWZ, int NWY, int Q, int NCH, int OUTMODE>
 static hipError_t launch_pick(const ConvParams& p, hipStream_t st) {
-  static int classic = -1;
-  if (classic < 0) classic = exp_env("AMX_V2_CLASSIC") ? 1 : 0;
   typedef Conv2Cfg<T, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE> C0;
   constexpr bool can = 3 * C0::BUF + 64 <= 160 * 1024 && NWZ * NWY <= 8;
-  if constexpr (can) {
-    if (!classic) return launch_cfg2<T, SPLIT, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE, 4, 3>(p, st);
-  }
-  return launch_cfg2<T, SPLIT, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE>(p, st);
-}
-
-// environment switches of the brick choice, read once (the statistics-slot count below must see the same values as the dispatch)
-static bool v2_narrow() {
-  static int v = -1;
-  if (v < 0) v = exp_env("AMX_V2_NARROW") ? 1 : 0;
-  return v != 0;
-}
-static bool v2_half_brick() {
-  static int v = -1;
-  if (v < 0) v = exp_env("AMX_V2_NO_HALF_BRICK") ? 0 : 1;
-  return v != 0;
+  if constexpr (can)
+    return launch_cfg2<T, SPLIT, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE, 4, 3>(p, st);
+  else
+    return launch_cfg2<T, SPLIT, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE>(p, st);
 }
 
 template <typename T, int OUTMODE, int SPLIT>
@@ -803,10 +761,9 @@ static hipError_t launch_conv2_t(const ConvParams& p, int Q, hipStream_t st) {
   if (p.W >= 32) {
     if (Q == 1) return launch_pick<T, SPLIT, 1, 4, 32, 4, 2, 1, 1, OUTMODE>(p, st);       // brick 4x8x32, 8 waves
     if (Q == 2) {
-      // AMX_V2_NARROW: brick 4x4x16 instead -- three stage buffers fit the LDS, so the loader-wave pipeline applies.  Measured on
-      // 96 -> 32 @64^3, batch 4: 206 -> 197 us (+5 %); not the default: the same instantiation also serves the 16^3 layers, and one
-      // kernel name per layer class keeps the per-kernel tables of bench.py and rocprofv3 comparable.
-      if (OUTMODE == 0 && v2_narrow()) return launch_pick<T, SPLIT, 1, 2, 16, 4, 2, 2, 1, 0>(p, st);
+      // (brick 4x4x16 instead -- three stage buffers fit the LDS, so the loader-wave pipeline applies -- measured on 96 -> 32 @64^3,
+      //  batch 4: 206 -> 197 us (+5 %); not kept: the same instantiation also serves the 16^3 layers, and one kernel name per layer
+      //  class keeps the per-kernel tables of bench.py and rocprofv3 comparable)
       // (brick 4x8x16 instead -- 12 % less halo, 84 % instead of 53 % of the DMA lanes used -- measured on f16x2mx, batch 4: 64 -> 64 @64^3
       //  506 -> 508 us, 192 -> 64 @64^3 1337 -> 1377, 96 -> 32 @128^3 2815 -> 2854: these layers are not fill-bound)
       return launch_pick<T, SPLIT, 1, 2, 32, 4, 2, 2, 1, OUTMODE>(p, st);       // brick 4x4x32, 8 waves
@@ -826,7 +783,7 @@ static hipError_t launch_conv2_t(const ConvParams& p, int Q, hipStream_t st) {
   }
   // 4-wide levels: half bricks (4x2x8, 4 waves) -- twice the workgroups (1024 -> 1024 @4^3, batch 4: 128 -> 256 on 256 CUs) and half as
   // many waves streaming the same weight fragments from L2
-  if (Q == 2 && p.W <= 4 && v2_half_brick()) return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 2, 1, 0>(p, st);
+  if (Q == 2 && p.W <= 4) return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 2, 1, 0>(p, st);
   if (Q == 2) return launch_pick<T, SPLIT, 1, 2, 8, 4, 2, 2, 1, 0>(p, st);           // brick 4x4x8, 8 waves
   if (Q == 4) return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 4, 1, 0>(p, st);
   return hipErrorInvalidValue;
@@ -838,13 +795,13 @@ int conv_v2_stats_slots(int D, int H, int W, int Q) {
   int tz = 4, ty, tx, nw;
   if (W >= 32) {
     if (Q == 1) { ty = 8; tx = 32; nw = 8; }
-    else if (Q == 2) { ty = 4; tx = v2_narrow() ? 16 : 32; nw = 8; }
+    else if (Q == 2) { ty = 4; tx = 32; nw = 8; }
     else { ty = 4; tx = 16; nw = 8; }
   } else if (W >= 16) {
     if (Q == 1) { ty = 2; tx = 16; nw = 4; }
     else { ty = 4; tx = 16; nw = 8; }
   } else {
-    if (Q == 2 && !(W <= 4 && v2_half_brick())) { ty = 4; tx = 8; nw = 8; }
+    if (Q == 2 && W > 4) { ty = 4; tx = 8; nw = 8; }
     else { ty = 2; tx = 8; nw = 4; }
   }
   return ((D + tz - 1) / tz) * ((H + ty - 1) / ty) * ((W + tx - 1) / tx) * nw;

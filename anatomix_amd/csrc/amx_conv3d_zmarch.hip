@@ -261,14 +261,6 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
         };
         int next_issue = 0, next_pub = 0, seen_conv = 0;
         const unsigned a_landed = lds_addr(landed);
-#ifdef AMX_EXPERIMENT
-        unsigned long long* ltr = (p.dbg & 8) && lane == 0 && blockIdx.x == 0 ? (unsigned long long*)p.stats + 1001 * 128 : nullptr;   // trace slot (wg 500, half 1)
-        int lcount = 0;
-#define AMX_LSTAMP() do { if (ltr && lcount < 128) ltr[lcount] = __builtin_readcyclecounter(); ++lcount; } while (0)
-        AMX_LSTAMP();
-#else
-#define AMX_LSTAMP() do {} while (0)
-#endif
         while (next_pub < nin) {
           // staging slot k % RSTG held plane k - RSTG: every plane below k - RSTG + 1 must have been converted (min over the waves' inconv)
           while (next_issue < nin) {
@@ -281,11 +273,8 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
             __builtin_amdgcn_s_sleep(2);
             continue;
           }
-          AMX_LSTAMP();                                          // [issued what the staging ring allows]
           WaitVm<2, RSTG - 1>::run(next_issue - next_pub - 1);  // the oldest unpublished plane has landed
-          AMX_LSTAMP();                                          // [landed]
           flag_store_asm(a_landed, ++next_pub);
-          AMX_LSTAMP();                                          // [published]
         }
         return;
       }
@@ -375,14 +364,6 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
         asm volatile("" ::: "memory");                         // (LDS serves a wave's accesses in order: the flag lands behind the row copies)
         flag_store(inconv + w, k + NSW);
       };
-#ifdef AMX_EXPERIMENT
-      unsigned long long* str = (p.dbg & 8) && lane == 0 && blockIdx.x == 0 && w == 0 ? (unsigned long long*)p.stats + 1000 * 128 : nullptr;   // trace slot (wg 500, half 0)
-      int scount = 0;
-#define AMX_SSTAMP() do { if (str && scount < 128) str[scount] = __builtin_readcyclecounter(); ++scount; } while (0)
-      AMX_SSTAMP();
-#else
-#define AMX_SSTAMP() do {} while (0)
-#endif
       for (int q = w; q < nplanes; q += NSW) {
         const int z1 = reflect_clamp(zs - 1 + q, p.D);
         int zi[3];
@@ -406,10 +387,6 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
           if (q >= R + TZ * seen_done) __builtin_amdgcn_s_sleep(1);
         }
         asm volatile("" ::: "memory");
-        AMX_SSTAMP();                                            // [input landed, ring slot free]
-#ifdef AMX_EXPERIMENT
-        if (p.dbg & 64) { flag_store(ready + w, q + NSW); AMX_SSTAMP(); AMX_SSTAMP(); continue; }
-#endif
         int ib[3];
 #pragma unroll
         for (int kz = 0; kz < 3; ++kz) ib[kz] = INOFF + (zi[kz] % RC) * IPLSZ;
@@ -494,10 +471,8 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
           stage_c(bt);
           __builtin_amdgcn_sched_barrier(0);
         }
-        AMX_SSTAMP();                                            // [plane computed]
         asm volatile("" ::: "memory");                         // (LDS serves a wave's accesses in order: the flag lands behind the plane)
         flag_store(ready + w, q + NSW);
-        AMX_SSTAMP();                                            // [published]
       }
       for (; myk < nin; myk += NSW) convert_plane(myk);       // input planes that only other waves' last ring planes read
       if (RangeCheck<T>::on) raise_flag(p.oflow, ibad | !(vmax <= 65504.f));
@@ -586,7 +561,7 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
                                           : nullptr;
 
   bool bad = false;
-  // optional cycle trace (AMX_TRACE=1): consumer waves 0 and 4 of a few workgroups stamp s_memtime per phase
+  // optional cycle trace (dbg bit 8, never set by the launcher): consumer waves 0 and 4 of a few workgroups stamp s_memtime per phase
   unsigned long long* trace = (p.dbg & 8) && (wave == 0 || wave == 4) && lane == 0 && blockIdx.x < 500
                                   ? (unsigned long long*)p.stats + ((long long)blockIdx.x * 2 + (wave >> 2)) * 128 : nullptr;
   int tcount = 0;
@@ -610,11 +585,6 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
     }
 
     AMX_ZSTAMP();                                            // [planes landed]
-#ifdef AMX_EXPERIMENT
-    // (AMX_DBG bits 16..23 = n: the second consumer wave of every SIMD starts its first sweep n x 512 cycles late)
-    if (s == 0 && wave >= 4 && wave < 8)
-      for (int k = (p.dbg >> 16) & 255; k > 0; --k) __builtin_amdgcn_s_sleep(8);
-#endif
     // ring slots of the four input planes zs+2s-1 .. zs+2s+2  (q = 2s + pl)
     int b1[4], bx3[4];
 #pragma unroll
@@ -630,7 +600,7 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
 #pragma unroll
       for (int cy = 0; cy < 2; ++cy) acc[tz][cy] = bias;
 
-    // TIMING-ONLY experiment (AMX_DBG bits 10..12 = extra sweeps per step; results are garbage): what a layer costs when its matrix
+    // TIMING-ONLY experiment (dbg bits 10..12 = extra sweeps per step; results are garbage): what a layer costs when its matrix
     // work is doubled / tripled at unchanged traffic -- the lower bound of a conv -> conv chain through the ring
     for (int rep = (p.dbg >> 10) & 7; rep >= 0; --rep)
     if (!(p.dbg & 2)) {
@@ -936,60 +906,23 @@ static hipError_t launch_zm_ns(ConvParams p, hipStream_t st, const StemIn& si = 
     if (e != hipSuccess) return e;
     attr_once.set();
   }
-  static int dbg = -1;
-  if (dbg < 0) {
-    const char* e = exp_env("AMX_DBG");
-    dbg = e ? atoi(e) : 0;
-    if (exp_env("AMX_TRACE")) dbg |= 8;
-  }
-  p.dbg = dbg;
   p.nby = (p.H + TY - 1) / TY;
   p.nbx = (p.W + TX - 1) / TX;
   // z segments: enough workgroups to fill 256 CUs, each segment a multiple of TZ planes, >= 8 planes
   const int tiles = p.nby * p.nbx * p.N;
   int nseg, zseg;
   pick_z_segments(tiles, p.D, TZ, 256 * (LDS <= 80 * 1024 ? 2 : 1), &zseg, &nseg);
-  static unsigned long long* trace_buf = nullptr;
-  if (p.dbg & 8) {   // debug only: per-phase cycle stamps of consumer waves 0 and 4, printed after a sync
-    if (!trace_buf && hipMalloc((void**)&trace_buf, 1024 * 128 * 8) != hipSuccess) return hipErrorOutOfMemory;
-    (void)hipMemsetAsync(trace_buf, 0, 1024 * 128 * 8, st);
-    p.stats = (float*)trace_buf;
-  }
   hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * nseg)), dim3((8 + (STEM ? ZmStemCfg<TY, TX>::NSW + 1 : C::NL) + NS) * 64), LDS, st, p, zseg, nseg, si);
-  if (p.dbg & 8) {
-    static int printed = 0;
-    (void)hipStreamSynchronize(st);
-    if (printed++ == 3) {
-      static unsigned long long hostbuf[1024 * 128];
-      (void)hipMemcpy(hostbuf, trace_buf, sizeof hostbuf, hipMemcpyDeviceToHost);
-      const int wgs[4] = {0, 77, 255, 500};                     // (STEM: the slots of workgroup 500 hold stem wave 0 / the loader of workgroup 0)
-      for (int wi = 0; wi < (STEM ? 4 : 3); ++wi)
-        for (int half = 0; half < 2; ++half) {
-          const unsigned long long* tr = hostbuf + ((long long)wgs[wi] * 2 + half) * 128;
-          fprintf(stderr, "[trace %s wg %d wave %d] wait/sweep/epilogue:", g_kernel_name3, wgs[wi], half * 4);
-          for (int k = 1; k + 2 < 128 && tr[k + 2]; k += 3)
-            fprintf(stderr, " %llu/%llu/%llu", tr[k] - tr[k - 1], tr[k + 1] - tr[k], tr[k + 2] - tr[k + 1]);
-          fprintf(stderr, "\n");
-        }
-    }
-  }
   return hipGetLastError();
 }
 
-// Storer waves need full tiles and dense, 16-byte aligned outputs (whole rows are copied as 16-byte pieces).
-template <int QT, int TY, int OUTMODE>
+// Storer waves (fp32 planar output) need full tiles.  Planar rows move as float4 pieces; global dwordx4 accesses only need dword
+// alignment on gfx9, so a window that starts at an odd x of the accumulation volume (sliding-window starts 25, 75, 125 ...) is staged
+// too -- its pieces just straddle 16-byte boundaries.  (Unstaged, those windows took the scattered 4-byte read-modify-write path:
+// 197 vs 83 us.)
+template <int TY>
 static bool zm_can_stage(const ConvParams& p) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_STORERS") ? 1 : 0;
-  if (off || p.H % TY || p.W % 32) return false;
-  if (OUTMODE == 0)
-    return p.ox == 32 * QT && !((size_t)p.out & 15) && !(p.oy & 15) && !(p.oz & 15) && !(p.on & 15);
-  // fp32 planar rows move as float4 pieces; global dwordx4 accesses only need dword alignment on gfx9, so a window that
-  // starts at an odd x of the accumulation volume (sliding-window starts 25, 75, 125 ...) is staged too -- its pieces just
-  // straddle 16-byte boundaries.  (Unstaged, those windows took the scattered 4-byte read-modify-write path: 197 vs 83 us.)
-  static int aligned_only = -1;
-  if (aligned_only < 0) aligned_only = exp_env("AMX_STAGE_ALIGNED_ONLY") ? 1 : 0;
-  if (aligned_only) return !(p.py & 3) && !(p.pz & 3) && !(p.pc & 3) && !(p.pn & 3) && !((size_t)p.out32 & 15) && !((size_t)p.wmap & 15);
+  if (p.H % TY || p.W % 32) return false;
   return !((size_t)p.out32 & 3) && !((size_t)p.wmap & 3);
 }
 
@@ -999,19 +932,15 @@ static hipError_t launch_zm(const ConvParams& p, hipStream_t st) {
   // Measured (batch 4, 128^3, 16 -> 16): fp32 planar output 253 -> 177 us with storers (whole 128-byte lines, eight
   // rows per store instruction, instead of 64-byte pieces from the MFMA lanes); 16-bit NDHWC output 130 -> 155 us
   // (its direct stores are already 512-byte runs; the staging round trip only adds LDS traffic) -- so planar only.
-  static int stage16 = -1;
-  if (stage16 < 0) stage16 = exp_env("AMX_STAGE16") ? 1 : 0;
-  if constexpr (NCK == 1)
-    if ((OUTMODE == 1 || (stage16 && !p.out2)) && zm_can_stage<QT, TY, OUTMODE>(p)) return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, 2>(p, st);
+  if constexpr (NCK == 1 && OUTMODE == 1)
+    if (zm_can_stage<TY>(p)) return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, 2>(p, st);
   return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, 0>(p, st);
 }
 
 // Eligibility: one full-resolution input segment of 16 or 32 channels, 16 or 32 output channels
 // (not 32 -> 16), W >= 32; the packed weights must use Q = Cout/16 tiles per group (conv_pick_q does).
 bool conv_zmarch_eligible(const ConvParams& p) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_ZMARCH") ? 1 : 0;
-  if (off || p.src0_f32c1 || p.C1 != 0 || p.W < 32 || p.H < 8 || p.D < 8) return false;
+  if (p.src0_f32c1 || p.C1 != 0 || p.W < 32 || p.H < 8 || p.D < 8) return false;
   if (p.C0 == 16 && p.Cout == 16) return true;
   if (p.out32) return false;                                // planar epilogue only instantiated for 16 -> 16
   return (p.C0 == 16 || p.C0 == 32) && p.Cout == 32;
@@ -1019,25 +948,19 @@ bool conv_zmarch_eligible(const ConvParams& p) {
 
 // The fused max-pool needs even extents (every 2x2x2 window inside one wave's block).
 bool conv_zmarch_can_pool(const ConvParams& p) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_POOLFUSE") ? 1 : 0;
-  return !off && conv_zmarch_eligible(p) && !p.out32 && !(p.D & 1) && !(p.H & 1) && !(p.W & 1);
+  return conv_zmarch_eligible(p) && !p.out32 && !(p.D & 1) && !(p.H & 1) && !(p.W & 1);
 }
 
 // Strict precision: the 16 -> 16 layers (all of level 0 in the 6M network) have a z-march variant too.
 bool conv_zmarch_eligible_split(const ConvParams& p) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_ZMARCH_SPLIT") ? 1 : 0;
-  return !off && conv_zmarch_eligible(p) && p.C0 == 16 && p.Cout == 16;
+  return conv_zmarch_eligible(p) && p.C0 == 16 && p.Cout == 16;
 }
 bool conv_zmarch_can_pool_split(const ConvParams& p) { return conv_zmarch_can_pool(p) && conv_zmarch_eligible_split(p); }
 
 // Stem-fed 16 -> 16 layer (network.py modules 0..5 of the 6 M model as ONE launch): `p` describes the 16 -> 16 layer (its src0 is
 // ignored), the remaining arguments the stem in front of it.  Whole tiles only; single 16-bit precisions.
 bool conv_zmarch_stem_eligible(const ConvParams& p, int precision) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_STEMFUSE") ? 1 : 0;
-  return !off && precision < 2 && p.C0 == 16 && p.C1 == 0 && p.Cout == 16 && !p.out32 && !p.raw_halo && p.W >= 32 && !(p.W % 32) && !(p.H % 8) &&
+  return precision < 2 && p.C0 == 16 && p.C1 == 0 && p.Cout == 16 && !p.out32 && !p.raw_halo && p.W >= 32 && !(p.W % 32) && !(p.H % 8) &&
          !(p.D & 1) && p.D >= 8 && p.ox == 32 && (p.ocs == 0 || p.ocs == 32);
 }
 // x_offs (host array of p.N element offsets, or null; at most 16 samples then): sample i reads its volume at x + x_offs[i]

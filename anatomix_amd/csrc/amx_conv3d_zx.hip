@@ -50,7 +50,7 @@ typedef ZxCfgT<2, 32> ZxCfg;
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
-// Timing ablations (tools/zx_ablate.sh, env AMX_ZX_DBG) exist only in a build with -DAMX_ZX_ABLATE: even as never-taken run-time branches
+// Timing ablations (ConvParams::dbg bits) exist only in a build with -DAMX_ZX_ABLATE: even as never-taken run-time branches
 // they cost (two further switches of this kind slowed the kernel by 10 %: conditional loads are not scheduled ahead).
 #ifdef AMX_ZX_ABLATE
 #define ZX_DBG(bits) (p.dbg & (bits))
@@ -166,7 +166,7 @@ __global__ __launch_bounds__((ZxCfg::NC + ZxCfg::NCV) * 64) void conv3d_k3_zx_ke
         if (qq < nplanes) {
           // ring slot qq % R is free once every consumer is done with plane qq - R: planes < TZ * min(done) are dead
           while (qq >= R + TZ * __builtin_amdgcn_readfirstlane(flag_min8_asm(a_done))) __builtin_amdgcn_s_sleep(1);
-          if (!ZX_DBG(16) || qq < R) convert_plane(qq, h);      // (AMX_ZX_DBG 16: timing ablation, the ring is only filled once)
+          if (!ZX_DBG(16) || qq < R) convert_plane(qq, h);      // (dbg 16: timing ablation, the ring is only filled once)
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // LDS is in-order per CU: the flag lands after the plane's data
           flag_store(ready + cw, qq + 1);
         }
@@ -235,7 +235,7 @@ __global__ __launch_bounds__((ZxCfg::NC + ZxCfg::NCV) * 64) void conv3d_k3_zx_ke
         // the two x halves as a RUN-TIME loop: unrolled, hipcc kept the whole step's fragments and addresses alive (447 spilled
         // registers inside the 168 of three waves per SIMD; 97 registers, none spilled, this way)
 #pragma unroll 1
-        for (int xh = 0; xh < (ZX_DBG(2 | 32) ? 0 : 2); ++xh) {   // (AMX_ZX_DBG 2 / 32: timing ablation without the sweeps)
+        for (int xh = 0; xh < (ZX_DBG(2 | 32) ? 0 : 2); ++xh) {   // (dbg 2 / 32: timing ablation without the sweeps)
           const int lanebase = vbase + xh * C::HALF;
           f32x4 acc[2][2];
 #pragma unroll
@@ -515,10 +515,8 @@ hipError_t launch_pack_weights_zx(const float* w, const float* scale, void* wx, 
 // One full-resolution row-planar f16x2mx segment of 32 channels -> 32 channels, whole tiles; 16-bit row-planar output, or the network's
 // fp32 planar output (no importance map, no activation of its own)
 bool conv_zx_eligible(const ConvParams& p) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_ZX") ? 1 : 0;
   const bool out_ok = p.out32 ? (!p.wmap && p.act == ACT_NONE && !p.stats) : (p.out && p.ox == 32);
-  return !off && !p.src0_f32c1 && p.C0 == 32 && p.C1 == 0 && p.Cout == 32 && out_ok && p.mxs &&
+  return !p.src0_f32c1 && p.C0 == 32 && p.C1 == 0 && p.Cout == 32 && out_ok && p.mxs &&
          ((p.W % 32 == 0 && p.H % 2 == 0) || (p.W % 16 == 0 && p.H % 4 == 0)) && p.D % 2 == 0 && p.D >= 4 && p.s0x == 32;
 }
 int conv_zx_stats_slots(int H, int W) { return H * W / 32; }       // one per (tile, half tile), whichever tile shape runs
@@ -537,9 +535,6 @@ static hipError_t launch_conv_zx_t(ConvParams p, const float* in_ab, int in_act,
     if (e != hipSuccess) return e;
     attr_once.set();
   }
-  static int dbg = -1;
-  if (dbg < 0) dbg = exp_env("AMX_ZX_DBG") ? atoi(exp_env("AMX_ZX_DBG")) : 0;
-  p.dbg = dbg;
   p.nby = p.H / C::TY;
   p.nbx = p.W / C::TX;
   ZxExtra e;
@@ -549,12 +544,11 @@ static hipError_t launch_conv_zx_t(ConvParams p, const float* in_ab, int in_act,
 }
 
 hipError_t launch_conv_zx(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st) {
-  static int tile = -1;                 // AMX_ZX_TILE = 0: 2x32 tiles wherever they fit, 1 (default): 4x16 tiles wherever they fit
-  if (tile < 0) tile = exp_env("AMX_ZX_TILE") ? atoi(exp_env("AMX_ZX_TILE")) : 1;
-  const bool wide_ok = p.W % 32 == 0 && p.H % 2 == 0, tall_ok = p.W % 16 == 0 && p.H % 4 == 0;
+  // 4x16 tiles wherever they fit, 2x32 otherwise (conv_zx_eligible admits nothing else)
+  const bool tall_ok = p.W % 16 == 0 && p.H % 4 == 0;
   // (a ring of 8 planes instead of 6 for the 4x16 tiles: 1016 / 1067 -> 1015 / 1037 us, inside the noise -- not instantiated)
   // (two mailbox sets -- NBOX = 2, an mx wave one step ahead of its main waves: 1030 / 1014 -> 1036 / 1015 us, nothing -- not instantiated)
-  if (tall_ok && (tile == 1 || !wide_ok)) return launch_conv_zx_t<ZxCfgT<4, 16>>(p, in_ab, in_act, in_slope, wx, st);
+  if (tall_ok) return launch_conv_zx_t<ZxCfgT<4, 16>>(p, in_ab, in_act, in_slope, wx, st);
   return launch_conv_zx_t<ZxCfgT<2, 32>>(p, in_ab, in_act, in_slope, wx, st);
 }
 

@@ -458,11 +458,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
 // global memory and reads NT weight fragments from LDS for MT * NT MFMAs.  The row fragments of the next unit (row group x
 // K chunk of KC steps) are requested before the current unit is multiplied, so a wave always has KC * MT (x2 when split)
 // 1-KiB loads in flight; accumulators stay in registers across the chunks of a row group.
-static int gemm_env(const char* name, int dflt) {
-  const char* e = exp_env(name);
-  return e ? atoi(e) : dflt;
-}
-
 template <int V> using IC = std::integral_constant<int, V>;
 
 template <int MT, int NT, int KC, int EPI, bool SPLIT, int NW = 4>
@@ -601,9 +596,9 @@ static hipError_t launch_ws(const GemmParams& p, hipStream_t st) {
   nrb = nrb < 1 ? 1 : (nrb > G ? G : nrb);
   int rows_per_wg = (G + nrb - 1) / nrb * unit;
   // The planar-output stage moves exactly its algorithmic bytes (0.54 GB in, 1.07 GB out: profiles/r03_vit_pmc_traffic.json) yet
-  // runs at 2.7 TB/s.  Row blocks of 128 / 256 / 1024 / 5504 rows: 696 / 604 / 548 / 602 us -- 1024 it is (AMX_PLANAR_ROWS).
-  static const int planar_rows = gemm_env("AMX_PLANAR_ROWS", 1024);
-  if (EPI == EPI_PLANAR && planar_rows > 0 && rows_per_wg > planar_rows) rows_per_wg = (planar_rows + unit - 1) / unit * unit;
+  // runs at 2.7 TB/s.  Row blocks of 128 / 256 / 1024 / 5504 rows: 696 / 604 / 548 / 602 us -- 1024 it is.
+  constexpr int planar_rows = 1024;
+  if (EPI == EPI_PLANAR && rows_per_wg > planar_rows) rows_per_wg = (planar_rows + unit - 1) / unit * unit;
   nrb = (p.M + rows_per_wg - 1) / rows_per_wg;
   if (xcd_order) nrb = (nrb + 7) / 8 * 8;                          // whole groups of 8 row blocks (XCD-aware order in the kernel)
   hipLaunchKernelGGL((wsgemm_kernel<MT, NT, KC, EPI, SPLIT, NW>), dim3((unsigned)ncb * nrb), dim3(64 * nw), lds, st, p, rows_per_wg, xcd_order);
@@ -639,9 +634,9 @@ static hipError_t launch_ws_epi(const GemmParams& p, hipStream_t st) {
   }
   // measured in the ViT forward (tools/vit_gemm_sweep.sh): 4 row tiles per wave win for the wide fp32-output product (q | k | v),
   // 2 row tiles (3 waves per SIMD) for the residual / SwiGLU epilogues
-  static const int wsmt_env = gemm_env("AMX_GEMM_WSMT", 0);
-  const int wsmt = wsmt_env ? wsmt_env : (EPI == EPI_F32 ? 4 : 2);
-  if (wsmt == 2) {
+  // (a plain `if`: both row-tile variants stay instantiated for every epilogue -- dropping the unused ones changes how the shared
+  //  epilogue is inlined into the direct kernels of the same tile shape, i.e. their code)
+  if (EPI != EPI_F32) {
     if (five && 5 * per_tile <= 160 * 1024) return launch_ws<2, 5, 4, EPI, false>(p, st);
     if (!five && 4 * per_tile <= 160 * 1024) return launch_ws<2, 4, 4, EPI, false>(p, st);
     return hipErrorNotSupported;
@@ -653,21 +648,14 @@ static hipError_t launch_ws_epi(const GemmParams& p, hipStream_t st) {
 
 template <int EPI, bool SPLIT>
 static hipError_t launch_epi(const GemmParams& p, hipStream_t st) {
-  static const int use_ws = gemm_env("AMX_GEMM_WS", 1);
-  if (use_ws) {
+  {
     const hipError_t e = launch_ws_epi<EPI, SPLIT>(p, st);
     if (e != hipErrorNotSupported) return e;
   }
   // NT = 5 where the tile count is a multiple of 5 (396 -> 25 tiles, 3 x 396 -> 75): no idle column tiles.  SwiGLU pairs need an even NT.
   const bool five = EPI != EPI_SWIGLU && p.ntiles % 5 == 0;
-  static const int force_mt = gemm_env("AMX_GEMM_MT", 0), pf = gemm_env("AMX_GEMM_PF", 2);
-  bool small = (long long)((p.M + 255) / 256) * ((p.ntiles + (five ? 4 : 3)) / (five ? 5 : 4)) < 512;   // < 2 workgroups per CU: halve the row block
-  if (force_mt) small = force_mt == 2;
+  const bool small = (long long)((p.M + 255) / 256) * ((p.ntiles + (five ? 4 : 3)) / (five ? 5 : 4)) < 512;   // < 2 workgroups per CU: halve the row block
   if (SPLIT) return five ? launch_one<2, 5, EPI, true, 1>(p, st) : launch_one<2, 4, EPI, true, 1>(p, st);
-  if (pf == 1) {
-    if (five) return small ? launch_one<2, 5, EPI, false, 1>(p, st) : launch_one<4, 5, EPI, false, 1>(p, st);
-    return small ? launch_one<2, 4, EPI, false, 1>(p, st) : launch_one<4, 4, EPI, false, 1>(p, st);
-  }
   if (five) return small ? launch_one<2, 5, EPI, false, 2>(p, st) : launch_one<4, 5, EPI, false, 2>(p, st);
   return small ? launch_one<2, 4, EPI, false, 2>(p, st) : launch_one<4, 4, EPI, false, 2>(p, st);
 }

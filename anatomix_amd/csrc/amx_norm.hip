@@ -36,8 +36,7 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
 // of the voxel: xl8 at voxel + 4C + 32 (c8 >> 1) + 8 (c8 & 1), xh8 16 bytes behind it; nothing reads them but the conv kernels.
 template <int FMT> struct Fmt {
   static constexpr bool SPLIT = FMT == 1 || FMT == 2;
-  static constexpr int M = (FMT == 0 || FMT == 3) ? 1 : (FMT == 1 ? 2 : 3);      // voxel bytes = 2 C M
-  static constexpr bool PLANAR = FMT >= 2;                          // FMT 3: single values, row-planar (amx_common.h)
+  static constexpr int M = FMT == 0 ? 1 : (FMT == 1 ? 2 : 3);      // voxel bytes = 2 C M
   // byte offset of 8-channel group c8 (its hi half) of voxel v -- a linear index whose rows are W voxels long -- and the distance to
   // the lo half.  FMT 2 is row-planar (amx_common.h): plane c8 >> 1 of row v / W, 32 bytes per voxel.
   static __device__ __forceinline__ long long group(long long v, int C, int W, int c8) {
@@ -659,9 +658,7 @@ hipError_t launch_instnorm(void* x, const float* gamma, const float* beta, float
 
 // f16x2mx only: in-place norm apply + activation of x [N][D][H][W][C] (row-planar) and its 2x2x2 avg / max pooled copy
 bool in_apply_pool_eligible(int precision, int D, int H, int W, int C) {
-  static int off = -1;
-  if (off < 0) off = exp_env("AMX_NO_APPLY_POOL") ? 1 : 0;
-  return !off && precision == 4 && !(D & 1) && !(H & 1) && !(W & 1) && C % 16 == 0 && ((long long)W * (C / 8)) % 64 == 0;
+  return precision == 4 && !(D & 1) && !(H & 1) && !(W & 1) && C % 16 == 0 && ((long long)W * (C / 8)) % 64 == 0;
 }
 hipError_t launch_in_apply_pool(void* x, const float* ab, void* pooled, int N, int D, int H, int W, int C, int act, float slope, int avg,
                                 int skip_lo, int pool_skip_lo, int* oflow, hipStream_t st) {
@@ -716,10 +713,8 @@ hipError_t launch_affine_act(void* x, const float* scale, const float* shift, in
   return hipGetLastError();
 }
 
-// planar0 / planar1 (precisions 0 / 1): that segment is stored row-planar (layout FMT 3); both or neither when both are given
 hipError_t launch_export_ncdhw(const void* src0, int C0, const void* src1, int C1, int up_shift, int N, int D, int H, int W,
-                               float* out, int precision, hipStream_t st, int S0, int S1, int planar) {
-  if (planar && precision > 1) return hipErrorInvalidValue;
+                               float* out, int precision, hipStream_t st, int S0, int S1) {
   if (S0 <= 0) S0 = C0;
   if (S1 <= 0) S1 = C1;
   // a ragged channel count is only possible for a single segment whose storage is padded (the output conv of a network whose
@@ -728,9 +723,7 @@ hipError_t launch_export_ncdhw(const void* src0, int C0, const void* src1, int C
   const long long total = (long long)N * ((C0 + C1 + 7) / 8) * D * H * W;
   const int blocks = (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
 #define AMX_EX(T, S) hipLaunchKernelGGL((export_ncdhw_kernel<T, S>), dim3(blocks), dim3(256), 0, st, (const char*)src0, C0, (const char*)src1, C1, up_shift, N, D, H, W, out, S0, S1)
-  switch (precision + (planar ? 10 : 0)) {
-    case 10: AMX_EX(f16, 3); break;
-    case 11: AMX_EX(bf16, 3); break;
+  switch (precision) {
     case 0: AMX_EX(f16, false); break;
     case 1: AMX_EX(bf16, false); break;
     case 2: AMX_EX(f16, true); break;

@@ -446,11 +446,6 @@ int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_w
   const int E = h->E, Ep = h->Ep, T = h->T, V = h->V, hid = h->hidden, nreg = c.num_register_tokens;
   const int M = n * T;
   const int D0 = c.grid_d * 8, H0 = c.grid_h * 8, W0 = c.grid_w * 8;
-#ifdef AMX_VIT_DEBUG_STOP    // debugging aid of tools/vit_bisect.py (build with -DAMX_VIT_DEBUG_STOP): return after a stage.  Compiled OUT of the product.
-  static const int dbg_stop = exp_env("AMX_VIT_STOP") ? atoi(exp_env("AMX_VIT_STOP")) : 0;
-#else
-  constexpr int dbg_stop = 0;
-#endif
   h->dbg.clear();
   auto note = [&](const char* name, const void* p, size_t bytes) { h->dbg.push_back({name, (char*)p, bytes}); };
 
@@ -467,7 +462,6 @@ int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_w
     note("h0_hi", P.h_hi[0], (size_t)n * D0 * H0 * W0 * 32 * 2);
     note("p0_hi", P.p_hi[0], (size_t)n * D0 * H0 * W0 * 4 * 2);
   }
-  if (dbg_stop == 10) return AMX_OK;
   int Dk = D0, Hk = H0, Wk = W0;
   for (int k = 0; k < 3; ++k) {
     const Stage& s = h->st[k];
@@ -495,7 +489,6 @@ int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_w
                                     k < 2 ? P.p_hi[k + 1] : nullptr, k < 2 ? P.p_lo[k + 1] : nullptr, st));
     if (k == 0) { note("raw1_s0", P.raw1, (size_t)n * vo * s.cout * 4); }
     Dk = Do; Hk = Ho; Wk = Wo;
-    if (dbg_stop == 11 + k) return AMX_OK;
   }
   {
     amx::GemmParams g{};
@@ -503,11 +496,9 @@ int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_w
     g.w_hi = h->tokproj.hi; g.w_lo = h->tokproj.lo; g.ntiles = h->tokproj.ntiles; g.Nreal = E; g.bias = h->tokproj_b;
     g.out = P.tok; g.ldo = E; g.V = V; g.nreg = nreg; g.pos = h->pos;
     VIT_HIP(amx::launch_gemm(g, amx::EPI_TOKENS, st));
-    if (dbg_stop == 14) return AMX_OK;
     VIT_HIP(amx::launch_place_registers(h->regs, nreg, E, T, n, P.tok, st));
   }
   note("tokens", P.tok, (size_t)M * E * 4);
-  if (dbg_stop == 1) return AMX_OK;
 
   // ------------------------------------------------------------------ EVA blocks
   const int nb = n_blocks < 0 || n_blocks > c.depth ? c.depth : n_blocks;
@@ -547,7 +538,6 @@ int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_w
   // ------------------------------------------------------------------ final norm (drops the register tokens) + decoder
   const int Mv = n * V;
   VIT_HIP(amx::launch_ln_rows(P.tok, 0, E, E, h->fnw, h->fnb, 1e-6f, Mv, V, T, nreg, 0, P.Ad_hi[0], P.Ad_lo[0], Ep, st));
-  if (dbg_stop == 2) return AMX_OK;
   int gd = c.grid_d, gh = c.grid_h, gw = c.grid_w;
   long long rows = Mv;
   for (int k = 0; k < 3; ++k) {
@@ -572,7 +562,6 @@ int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_w
                                   P.Ad_lo[k + 1], up(d.cout, 32), st));
     }
     rows *= 8; gd *= 2; gh *= 2; gw *= 2;
-    if (dbg_stop == 3 + k) return AMX_OK;
   }
   return AMX_OK;
 }

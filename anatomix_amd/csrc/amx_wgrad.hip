@@ -76,11 +76,7 @@ __device__ __forceinline__ amx_u32x2 lds_read_tr16(unsigned addr) {
   return __builtin_bit_cast(amx_u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)addr));
 }
 
-#ifdef AMX_EXPERIMENT
-#define AMX_WT_DBG p.dbg
-#else
-#define AMX_WT_DBG 0
-#endif
+#define AMX_WT_DBG 0           // ablation bits of the kernel (1 = no MFMA sweep, 2 = no DMA): compiled out
 template <typename T, typename C>
 __global__ __launch_bounds__(640) void conv3d_wgrad_tr_kernel(const WgradParams p) {
   typedef typename Ops<T>::vec8 vec8;
@@ -511,9 +507,7 @@ static WtPlan wt_plan(int N, int D, int H, int W, int Cout, int CinPad) {
   q.nplanes = N * q.nyt * q.nxt * D;
   const int npairs = (Cout / 16) * (CinPad / 16);
   // one workgroup per compute unit (LDS), ONE round of at most 256 workgroups, every workgroup a contiguous run of planes
-  static int target = -1;
-  if (target < 0) target = exp_env("AMX_WGRAD_WGS") ? atoi(exp_env("AMX_WGRAD_WGS")) : 256;
-  int nc = target / npairs;
+  int nc = 256 / npairs;
   if (nc < 1) nc = 1;
   if (q.nplanes <= 4 * g) nc = 1;              // at most four items in all: one workgroup per pair writes dW itself (no partials, no reduce launch)
   int ppc = (q.nplanes + nc - 1) / nc;
@@ -548,7 +542,6 @@ hipError_t launch_wgrad(WgradParams p, int CinReal, float* dw, int accumulate, v
   p.partial = (float*)scratch;
   p.nchunk = q.nchunk; p.nyt = q.nyt; p.nxt = q.nxt; p.ppc = q.ppc; p.cpx = q.cpx; p.nplanes = q.nplanes;
   p.dw = dw; p.cin_real = CinReal; p.accumulate = accumulate;
-  p.dbg = exp_env("AMX_WGRAD_DBG") ? atoi(exp_env("AMX_WGRAD_DBG")) : 0;
   const int npairs = (p.Cout / 16) * (CinPad / 16);
   const int nwg = 8 * q.cpx;
   hipError_t e;

@@ -21,21 +21,14 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import _lib
 from . import train_ops as T
 
 _DT = {"f16": torch.float16, "fp16": torch.float16, "float16": torch.float16, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
 
 
-OVERLAP_WGRAD = _lib.exp_env("AMX_NO_OVERLAP_WGRAD", "0") != "1"   # weight gradients on a side stream, beside the data gradient of the same block
-OVERLAP_WGRAD_MIN_W = int(_lib.exp_env("AMX_OVERLAP_WGRAD_MIN_W", "32"))   # ... of blocks at least this wide (narrower: the two joins cost what the overlap returns; 6.41 -> 6.37 ms)
-RECOMPUTE_ACT = _lib.exp_env("AMX_BN_BWD_RECOMPUTE", "1") != "0"      # norm adjoint: sign of the activation's argument from x, y not read
-SPLIT_CONCAT_DGRAD = int(_lib.exp_env("AMX_SPLIT_CONCAT_DGRAD", "1"))      # 1: the 48 -> 16 layer's data gradient as two z-march launches; 2: every concat layer
-FUSED_FOLD_SPLIT = _lib.exp_env("AMX_FUSED_FOLD_SPLIT", "1") != "0"   # concat layers: pad_fold + channel split + child sum in one pass
-SPARSE_OUTPUT_TAP = _lib.exp_env("AMX_DENSE_OUTPUT_TAP", "0") != "1"   # output conv tapped at sampled voxels only: its backward from the rows
-DIRECT_DGRAD = _lib.exp_env("AMX_NO_DIRECT_DGRAD", "0") != "1"   # data gradient: interior launch + shell terms instead of the framed domain + pad_fold
-PACK_ASIDE = _lib.exp_env("AMX_NO_PACK_ASIDE", "0") != "1"     # A/B: both passes' weight packing on a side stream at the start of the forward
-BATCH_PACK = _lib.exp_env("AMX_NO_BATCH_PACK", "0") != "1"     # packed weights of a pass in one launch (T.pack_batch)
+# weight gradients go to a side stream, beside the data gradient of the same block, for blocks at least this wide (narrower: the two
+# joins cost what the overlap returns; 6.41 -> 6.37 ms per step)
+OVERLAP_WGRAD_MIN_W = 32
 _SIDE = {}
 
 
@@ -139,14 +132,14 @@ class _UnetTrainFn(torch.autograd.Function):
         # While a HIP graph is being captured both launches go to a side stream here, beside the input import -- the backward's packing
         # (the weights do not change in between) is then off the main stream altogether.
         pkey = (tuple(x.shape), dt)
-        plan = getattr(model, "_pack_plan", {}).get(pkey) if BATCH_PACK else None
-        bplan0 = getattr(model, "_pack_plan_bwd", {}).get(pkey) if BATCH_PACK else None
+        plan = getattr(model, "_pack_plan", {}).get(pkey)
+        bplan0 = getattr(model, "_pack_plan_bwd", {}).get(pkey)
         packs, rec = {}, {}
         ctx.bpacks_pre = None
         pack_side = None
         if plan:
             ids = sorted(plan)
-            if x.is_cuda and PACK_ASIDE and torch.cuda.is_current_stream_capturing():
+            if x.is_cuda and torch.cuda.is_current_stream_capturing():
                 pack_side = _side_stream(dev)
                 main_s = torch.cuda.current_stream(dev)
                 pack_side.wait_stream(main_s)
@@ -313,7 +306,7 @@ class _UnetTrainFn(torch.autograd.Function):
             else:
                 raise NotImplementedError(f"module {i} ({type(mods[i]).__name__}) in the HIP training path")
             i += 1
-        if BATCH_PACK and not plan:
+        if not plan:
             model.__dict__.setdefault("_pack_plan", {})[pkey] = rec
         ctx.pkey = pkey
         if tracked:
@@ -364,7 +357,7 @@ class _UnetTrainFn(torch.autograd.Function):
                 n_, d_, h_, w_, c_ = low.shape
                 add_grad(low_name, gu.reshape(n_, d_, 2, h_, 2, w_, 2, c_).float().sum((2, 4, 6)).to(dt))
         # data-gradient packings of the plain blocks in one launch (same record-and-replay as the forward)
-        bplan = getattr(model, "_pack_plan_bwd", {}).get(ctx.pkey) if BATCH_PACK else None
+        bplan = getattr(model, "_pack_plan_bwd", {}).get(ctx.pkey)
         bpacks, brec = {}, {}
         pre = getattr(ctx, "bpacks_pre", None)
         if bplan and pre is not None and pre[0] == bplan:            # packed beside the forward's input import (same weights)
@@ -413,7 +406,7 @@ class _UnetTrainFn(torch.autograd.Function):
                 rows = dtap.pop(idx, None) if idx in ctx.coords_of else None
                 if g is None and rows is None:
                     continue
-                if (g is None and SPARSE_OUTPUT_TAP and x1 is None and x0.is_cuda and blk["cout"] <= 16 and blk["cin"] <= 16
+                if (g is None and x1 is None and x0.is_cuda and blk["cout"] <= 16 and blk["cin"] <= 16
                         and rows.shape[1] <= 1024):
                     # the only cotangent of the output conv is 2 x 512 sampled rows: its weight and data gradient from those rows
                     # directly (amx_conv3d_backward_sampled) instead of a dense pass over a gradient volume of zeros
@@ -464,14 +457,14 @@ class _UnetTrainFn(torch.autograd.Function):
                     du.mul_(blk["a"].to(dt))
                 elif dy is not None and isinstance(bn, nn.BatchNorm3d):
                     _, dgamma, dbeta = T.bn_act_backward(dy, blk["Y"], blk["X"], blk["mean"], blk["rstd"], gam,
-                                                         blk["act"], 0.3, framed=fr, beta=bet, recompute=RECOMPUTE_ACT)
+                                                         blk["act"], 0.3, framed=fr, beta=bet, recompute=True)
                     pgrads[id(bn.weight)], pgrads[id(bn.bias)] = dgamma, dbeta
                 elif dy is not None:                                    # InstanceNorm3d: per sample
                     dgs, dbs = [], []
                     for s_ in range(n):
                         _, dg_, db_ = T.bn_act_backward(dy[s_:s_ + 1], blk["Y"][s_:s_ + 1], blk["X"][s_:s_ + 1], blk["mean"][s_],
                                                         blk["rstd"][s_], gam, blk["act"], 0.3, framed=fr[s_:s_ + 1], beta=bet,
-                                                        recompute=RECOMPUTE_ACT)
+                                                        recompute=True)
                         dgs.append(dg_)
                         dbs.append(db_)
                     if bn.weight is not None:
@@ -488,7 +481,7 @@ class _UnetTrainFn(torch.autograd.Function):
             # block touches a framed buffer (they are shared per shape).  Letting it also run beside the next block's BatchNorm
             # adjoint (second frame per shape + events) measured slower: 11.4 vs 10.7 ms per step in round 2, and again 9.04 vs 8.71 ms in
             # round 3 with the one-round weight-gradient launches (the two MFMA kernels contend; the adjoint passes lose more than the join costs).
-            if OVERLAP_WGRAD and x0.is_cuda and w >= OVERLAP_WGRAD_MIN_W:
+            if x0.is_cuda and w >= OVERLAP_WGRAD_MIN_W:
                 dw = torch.empty((blk["cout"], blk["cin"], 3, 3, 3), dtype=torch.float32, device=x0.device)
                 T.wgrad_scratch(x0, x1, blk["cout"])                   # make sure the cached scratch exists (allocated here)
                 side = _side_stream(x0.device)
@@ -505,9 +498,7 @@ class _UnetTrainFn(torch.autograd.Function):
                 if ctx.needs_input_grad[1]:                             # d loss / d image: the stem's data gradient (channel 0 of
                     dx_in = T.conv_dgrad(fr, conv.weight)[..., 0].float().unsqueeze(1)   # the 16-channel padded result)
                 continue
-            if (x1 is not None and blk.get("cat_parts") is None and SPLIT_CONCAT_DGRAD and FUSED_FOLD_SPLIT
-                    and ((blk["cout"] == 16 and c0 == 16 and x1.shape[-1] == 32) or
-                         (SPLIT_CONCAT_DGRAD > 1 and c0 % 16 == 0 and x1.shape[-1] % 16 == 0))
+            if (x1 is not None and blk.get("cat_parts") is None and blk["cout"] == 16 and c0 == 16 and x1.shape[-1] == 32
                     and tuple(conv.weight.shape[:2]) == (blk["cout"], c0 + x1.shape[-1])):
                 # the level-0 concat layer (48 -> 16): its data gradient is a 16 -> 48 convolution on the framed domain, which only the
                 # generic kernel takes as one launch (415 us at 128^3 x 2 views); as a 16 -> 16 (skip channels) and a 16 -> 32
@@ -515,20 +506,20 @@ class _UnetTrainFn(torch.autograd.Function):
                 w = conv.weight.detach()
                 w_skip = w[:, :c0].contiguous()
                 g_up = T.conv_dgrad_framed(fr, w[:, c0:].contiguous())
-                if DIRECT_DGRAD and T.dgrad_direct_supported(fr, w_skip):
+                if T.dgrad_direct_supported(fr, w_skip):
                     add_grad(blk["in0"], T.conv_dgrad_direct(fr, w_skip))
                 else:
                     grads[blk["in0"]] = T.pad_fold(T.conv_dgrad_framed(fr, w_skip), grads.get(blk["in0"]))
                 add_grad(blk["in1"], T.upcat_split_backward_framed(g_up, 0, x1.shape[-1])[1])
                 continue
-            if x1 is None and blk.get("cat_parts") is None and DIRECT_DGRAD and T.dgrad_direct_supported(fr, conv.weight):
+            if x1 is None and blk.get("cat_parts") is None and T.dgrad_direct_supported(fr, conv.weight):
                 # the forward kernel on the interior of the framed gradient + the folded shell terms: no (n + 4)^3 domain, no fold pass
                 g = T.conv_dgrad_direct(fr, conv.weight, wpk=bpacked(idx, fr.shape[-1], fr.shape[3] - 4))
                 add_grad(blk["in0"], g[..., : x0.shape[-1]] if g.shape[-1] != x0.shape[-1] else g)
                 continue
             g_fr = T.conv_dgrad_framed(fr, conv.weight, wpk=bpacked(idx, fr.shape[-1], fr.shape[3]))
             if (x1 is not None and blk.get("cat_parts") is None and g_fr.shape[-1] == c0 + x1.shape[-1] and c0 % 8 == 0
-                    and x1.shape[-1] % 8 == 0 and FUSED_FOLD_SPLIT):
+                    and x1.shape[-1] % 8 == 0):
                 # reflect-padding adjoint, channel split and the sum over the 8 children of every low-resolution voxel (adjoint of
                 # the nearest x2 upsample) in ONE pass over the framed result; the skip part accumulates in place when the skip
                 # already has a gradient
@@ -546,20 +537,12 @@ class _UnetTrainFn(torch.autograd.Function):
                 add_grad(blk["in0"], dcat[..., : x0.shape[-1]] if dcat.shape[-1] != x0.shape[-1] else dcat)
             else:
                 c1 = x1.shape[-1]
-                if dcat.shape[-1] == c0 + c1 and c0 % 8 == 0 and c1 % 8 == 0:
-                    # one pass: skip channels out (accumulated in place when the skip already has a gradient), the 8 children of
-                    # every low-resolution voxel summed (adjoint of the nearest x2 upsample)
-                    prev = grads.get(blk["in0"])
-                    dskip, dlow = T.upcat_split_backward(dcat, c0, c1, skip_into=prev)
-                    grads[blk["in0"]] = dskip
-                    add_grad(blk["in1"], dlow)
-                else:
-                    add_grad(blk["in0"], dcat[..., :c0].contiguous())
-                    up = dcat[..., c0:].reshape(n, d // 2, 2, h // 2, 2, w // 2, 2, c1)
-                    add_grad(blk["in1"], up.float().sum((2, 4, 6)).to(dt))
+                add_grad(blk["in0"], dcat[..., :c0].contiguous())
+                up = dcat[..., c0:].reshape(n, d // 2, 2, h // 2, 2, w // 2, 2, c1)
+                add_grad(blk["in1"], up.float().sum((2, 4, 6)).to(dt))
         if wgrad_pending is not None:
             torch.cuda.current_stream(tensors["x"].device).wait_stream(wgrad_pending)
-        if BATCH_PACK and not bplan:
+        if not bplan:
             model.__dict__.setdefault("_pack_plan_bwd", {})[ctx.pkey] = brec
         return (None, dx_in, None, None) + tuple(pgrads.get(pid) for pid in ctx.param_ids)
 

@@ -11,22 +11,12 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import _lib
 
-_PARALLEL_HEADS = _lib.exp_env("AMX_SERIAL_HEADS", "0") != "1"
-_SAMPLED_TAPS = _lib.exp_env("AMX_DENSE_TAPS", "0") != "1"      # 0: the dense-tap route (A/B; same values)
 _STREAMS = {}
 # Distinct side streams for the six per-layer head / loss chains.  One per layer (the first form) is NOT the fastest: HIP maps streams
 # onto four hardware queues and every cross-queue dependency of a replayed graph costs -- three streams (two layers each) measured
 # 7.45-7.50 ms per step against 7.74-7.77 with six, 7.53-7.55 with two, 7.68 with four (GPU_MAX_HW_QUEUES=8 instead: 14.4 ms).
-_HEAD_STREAMS = int(_lib.exp_env("AMX_HEAD_STREAMS", "3"))
-_PREDRAW = _lib.exp_env("AMX_NO_PREDRAW", "0") != "1"     # A/B: coordinates drawn up front on a side stream
-# A/B: the coordinate draws are enqueued behind the forward's first block instead of in front of it.  (Measured and dropped: the head +
-# loss chains started at their taps, beside the rest of the forward, on detached leaves of the rows with a second backward call for the
-# network -- 7.04 against 6.86 ms per step whether forked tap by tap or once in front of the 128^3 level: the forward's own chain changes
-# hardware queue at every fork of the replayed graph and its short deep-level kernels queue behind the heads'.)
-_LATE_DRAW = _lib.exp_env("AMX_DRAW_FIRST", "0") != "1"
-_BATCHED_HEADS = _lib.exp_env("AMX_HEAD_CHAINS", "0") != "1"   # A/B: 1 = the six per-layer chains on side streams (until round 6)
+_HEAD_STREAMS = 3
 _WEIGHTS = {}                                                # (device, nce weights, lambda, accumulation) -> weight vector on the device
 
 
@@ -40,7 +30,7 @@ def _layer_streams(device, n):
     """The side streams of the n per-layer chains (``_HEAD_STREAMS`` distinct ones, shared round-robin), created once per device."""
     key = (device.type, device.index)
     have = _STREAMS.setdefault(key, [])
-    nuniq = min(n, _HEAD_STREAMS) if _HEAD_STREAMS > 0 else n
+    nuniq = min(n, _HEAD_STREAMS)
     while len(have) < nuniq:
         have.append(torch.cuda.Stream(device=device))
     return [have[k % nuniq] for k in range(n)]
@@ -68,7 +58,7 @@ def _forward_backward(netG, netF, criterions, real_A, real_B, seg_A, nce_layers,
         shapes = tap_shapes.get(skey)
         pre = {}
         capturing = reals.is_cuda and torch.cuda.is_current_stream_capturing()
-        if shapes is not None and sample_ids is None and _PREDRAW and capturing:   # (eagerly the stream switches cost more than they return)
+        if shapes is not None and sample_ids is None and capturing:   # (eagerly the stream switches cost more than they return)
             side = _draw_stream(reals.device)
 
             def draw_all():
@@ -87,12 +77,13 @@ def _forward_backward(netG, netF, criterions, real_A, real_B, seg_A, nce_layers,
                 if tuple(shape) != tuple(shapes[i]):
                     raise RuntimeError("contrastive step: the tap shapes changed under a cached sampling plan")
                 return pre[i]
-            if _LATE_DRAW:
-                # a replayed graph hands its nodes to the device in capture order: six draw + filter launches in front of the forward
-                # kept the first convolution waiting for ~170 us of launch latency; behind the first block they cost nothing
-                sampler.on_start = draw_all
-            else:
-                draw_all()
+            # a replayed graph hands its nodes to the device in capture order: six draw + filter launches in front of the forward
+            # kept the first convolution waiting for ~170 us of launch latency; behind the first block they cost nothing.  (Measured and
+            # dropped: the head + loss chains started at their taps, beside the rest of the forward, on detached leaves of the rows with a
+            # second backward call for the network -- 7.04 against 6.86 ms per step whether forked tap by tap or once in front of the
+            # 128^3 level: the forward's own chain changes hardware queue at every fork of the replayed graph and its short deep-level
+            # kernels queue behind the heads'.)
+            sampler.on_start = draw_all
         else:
             seen = {}
 
@@ -117,7 +108,7 @@ def _forward_backward(netG, netF, criterions, real_A, real_B, seg_A, nce_layers,
     # three streams were 1.5 ms of a 7 ms step.
     stacked = None
     capturing_now = reals.is_cuda and torch.cuda.is_current_stream_capturing()
-    if sampled is not None and _BATCHED_HEADS and capturing_now:
+    if sampled is not None and capturing_now:
         from . import supcon as _supcon
         pooled, ids = netF.forward_rows(rows, coords, None, batched=True)
         stacked = _supcon.batched_losses(criterions, pooled, seg_A, ids, feat_sizes)
@@ -126,7 +117,7 @@ def _forward_backward(netG, netF, criterions, real_A, real_B, seg_A, nce_layers,
         layer_losses = list(stacked.detach().unbind(0))
         streams = None
     else:
-        streams = _layer_streams(reals.device, len(feat_sizes)) if (reals.is_cuda and _PARALLEL_HEADS and capturing_now) else None
+        streams = _layer_streams(reals.device, len(feat_sizes)) if (reals.is_cuda and capturing_now) else None
         ambient = torch.cuda.current_stream(reals.device) if streams is not None else None
         if sampled is not None:
             pooled, ids = netF.forward_rows(rows, coords, streams)
@@ -163,7 +154,7 @@ def _sampled_route(netG, netF, reals, nce_layers, num_patches):
     from ..model.network import Unet
     from .patch_sample import PatchSampleF
     layers = [int(l) for l in nce_layers]
-    if not (_SAMPLED_TAPS and isinstance(netG, Unet) and type(netF) is PatchSampleF and reals.is_cuda and num_patches > 0 and
+    if not (isinstance(netG, Unet) and type(netF) is PatchSampleF and reals.is_cuda and num_patches > 0 and
             torch.is_grad_enabled() and layers == sorted(set(layers)) and not getattr(netG, "allow_torch_path", False)):
         return None
     # the route calls the training Function directly: only where Unet.forward would have routed the call there itself (network.py

@@ -157,14 +157,13 @@ def test_engine_against_the_torch_composition_on_random_configurations(device, s
     assert e < 1e-3, (kw, batch, e)
 
 
-def test_single_f16_stem_output_is_an_opt_in_within_tolerance(device, monkeypatch):
-    """amx_vit_cfg.stem_split = 0 (env AMX_VIT_STEM_SPLIT=0): the stem's output without its lo plane -- faster, measured 3.7e-4 on
-    its own; the default keeps the plane (fp32-grade tokens, test_tokenizer_tokens_match_the_oracle)."""
-    monkeypatch.setenv("AMX_EXPERIMENT", "1")                   # the Python A/B switches are only read under this gate (_lib.exp_env)
-    monkeypatch.setenv("AMX_VIT_STEM_SPLIT", "0")
+def test_single_f16_stem_output_set_in_the_engine_config_is_within_tolerance(device):
+    """amx_vit_cfg.stem_split = 0: the stem's output without its lo plane -- faster, measured 3.7e-4 on its own; the default keeps
+    the plane (fp32-grade tokens, test_tokenizer_tokens_match_the_oracle)."""
     kw = dict(V.VIT_VARIANTS["anatomix-dev-vit"], input_shape=(64, 64, 64), eva_depth=2)
     m, sd = _model(kw, 8, device)
-    assert m._vit_cfg["stem_split"] == 0
+    assert m._vit_cfg["stem_split"] == 1
+    m._vit_cfg["stem_split"] = 0                                   # (read when the engine is created, at the first forward)
     x = V.synthetic_input(16, 1, (64, 64, 64))
     with torch.no_grad():
         y = m(x.to(device)).cpu()

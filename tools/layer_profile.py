@@ -10,7 +10,7 @@ batches = [int(a) for a in sys.argv[2:]] or [1, 2]
 kw = R.VARIANTS[variant]
 m = anatomix_amd.Unet(**kw); m.load_state_dict(R.synthetic_state_dict(kw, 0)); m = m.to(dev).eval()
 def call(f):
-    """Timing ablations (AMX_ZX_DBG ...) compute garbage: swallow the overflow guard's report of the previous forward and go on."""
+    """Timing ablations (kernel dbg bits) compute garbage: swallow the overflow guard's report of the previous forward and go on."""
     for _ in range(4):
         try:
             return f()

@@ -30,4 +30,4 @@ for _ in range(K): run()
 e1.record(); torch.cuda.synchronize()
 us = e0.elapsed_time(e1) / K * 1e3     # includes the tiny pack kernel (~3 us)
 fl = 2 * 27 * (c0 + c1) * cout * n * S ** 3
-print(f"AMX_DBG={os.environ.get('AMX_DBG','0')} {c0}+{c1}->{cout} @{S} n={n}: {us:.1f} us  {fl/us/1e6:.0f} TF")
+print(f"{c0}+{c1}->{cout} @{S} n={n}: {us:.1f} us  {fl/us/1e6:.0f} TF")

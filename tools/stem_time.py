@@ -11,4 +11,4 @@ with torch.no_grad():
     for _ in range(5):
         _, recs = m.profile_forward(x)
         for r in recs[:1]: tot[r["kernel"]] = tot.get(r["kernel"], 0) + r["ms"]
-print("AMX_DBG", os.environ.get("AMX_DBG", "0"), {k: round(v / 5 * 1e3, 1) for k, v in tot.items()})
+print({k: round(v / 5 * 1e3, 1) for k, v in tot.items()})
