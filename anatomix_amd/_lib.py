@@ -151,6 +151,15 @@ SYMBOLS = {
     "amx_box_filter3d": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "amx_correlate_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "amx_correlate_ssd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "amx_coupled_convex_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
+    "amx_coupled_convex": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, C.c_size_t, _P]),
+    "amx_coupled_convex_step_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
+    "amx_coupled_convex_step": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "amx_inverse_consistency_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
+    "amx_inverse_consistency": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "amx_resize_trilinear3d": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(C.c_float), _I, _P]),
+    "amx_stage1_registration_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "amx_stage1_registration": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -2,8 +2,9 @@
 model loading, min-max normalisation and sliding-window feature extraction (reference lines 16-78, 134-221), and the
 feature post-processing that runs on the extracted tensors before the convex optimisation -- ``MINDSSC`` (:311-406),
 ``apply_avg_pool3d`` (:105-131) and the SSD correlation volume ``correlate`` (:409-491) -- on the HIP kernels of
-``csrc/amx_regfeat.hip``.  The solver itself (coupled_convex, inverse_consistency, the Adam instance optimisation,
-Jacobian utilities) is downstream of the feature path and not part of this package.
+``csrc/amx_regfeat.hip``; and the discrete solver that follows them, ``coupled_convex`` (:494-552) and
+``inverse_consistency`` (:555-603), on the kernels of ``csrc/amx_regsolve.hip``.  The Adam instance optimisation and the
+Jacobian utilities (diffusion_regularizer, generate_grid, JacobianDet) are not part of this package.
 """
 from __future__ import annotations
 
@@ -150,6 +151,118 @@ def correlate(mind_fix, mind_mov, disp_hw, grid_sp, shape, ch=12):
         _lib.check(lib.amx_correlate_ssd(_lib.ptr(f), _lib.ptr(m), ch, h, w, d, int(disp_hw), _lib.ptr(ssd), _lib.ptr(amin),
                                          _lib.ptr(sc), nb, _stream(f.device)))
     return ssd, amin
+
+
+def _disp_hw_of(n_labels):
+    for hw in (1, 2, 3):
+        if (2 * hw + 1) ** 3 == n_labels:
+            return hw
+    raise ValueError(f"ssd has {n_labels} displacement labels; expected (2 disp_hw + 1)^3 with disp_hw in {{1, 2, 3}}")
+
+
+def _check_regular_mesh(disp_mesh_t, disp_hw):
+    """The kernels generate the mesh from the label index, so only the regular mesh of run_stage1_registration is
+    accepted: F.affine_grid(disp_hw * eye(3, 4), (1, 1, k, k, k), align_corners=True) as [3, k^3(, 1)], any float dtype.
+    Checked by shape and the two extreme rows."""
+    n = (2 * disp_hw + 1) ** 3
+    if disp_mesh_t is None or disp_mesh_t.numel() != 3 * n or disp_mesh_t.shape[0] != 3:
+        raise ValueError(f"coupled_convex: disp_mesh_t must be the regular [3, {n}] displacement mesh of "
+                         f"run_stage1_registration (got {None if disp_mesh_t is None else tuple(disp_mesh_t.shape)})")
+    m = disp_mesh_t.reshape(3, n)
+    ends = torch.stack([m[:, 0], m[:, n - 1]]).float().cpu().tolist()
+    if ends != [[-float(disp_hw)] * 3, [float(disp_hw)] * 3]:
+        raise ValueError("coupled_convex: only the regular integer mesh -disp_hw .. disp_hw of run_stage1_registration is "
+                         f"supported (the kernel generates it from the label index); got extreme rows {ends}")
+
+
+def coupled_convex(ssd, ssd_argmin, disp_mesh_t, grid_sp, shape):
+    """convex_adam_utils.py:494-552.  ssd [(2 disp_hw + 1)^3, h, w, d] and ssd_argmin [h, w, d] (or None: recomputed) as
+    ``correlate`` returns them, (h, w, d) = shape // grid_sp -> disp_soft [1, 3, h, w, d] in grid units.  ``disp_mesh_t``
+    is accepted for signature compatibility and must be the regular mesh (see _check_regular_mesh); ``disp_hw`` is inferred
+    from ``ssd.shape[0]``.  Two documented differences from the reference: ``ssd`` is NOT modified (the reference
+    accumulates the coupling penalty into it through a view -- the accumulation itself is reproduced), and the result is
+    fp32 whatever the mesh's dtype (the reference returns the mesh's dtype, half in its own caller)."""
+    hw = _disp_hw_of(int(ssd.shape[0]))
+    _check_regular_mesh(disp_mesh_t, hw)
+    s = _f32c(ssd, "coupled_convex")
+    h, w, d = int(shape[0]) // grid_sp, int(shape[1]) // grid_sp, int(shape[2]) // grid_sp
+    if tuple(s.shape[1:]) != (h, w, d):
+        raise ValueError(f"coupled_convex: ssd {tuple(s.shape)} does not match the grid ({h}, {w}, {d})")
+    amin = None
+    if ssd_argmin is not None:
+        if not ssd_argmin.is_cuda or ssd_argmin.numel() != h * w * d:
+            raise ValueError("coupled_convex: ssd_argmin must be a device tensor of h * w * d labels (or None)")
+        amin = ssd_argmin.to(torch.int64).contiguous()
+    lib = _lib.load()
+    out = torch.empty((1, 3, h, w, d), dtype=torch.float32, device=s.device)
+    with torch.cuda.device(s.device):
+        nb = lib.amx_coupled_convex_scratch_bytes(h, w, d)
+        sc = torch.empty(nb, dtype=torch.uint8, device=s.device)
+        _lib.check(lib.amx_coupled_convex(_lib.ptr(s), _lib.ptr(amin), h, w, d, hw, _lib.ptr(out), _lib.ptr(sc), nb,
+                                          _stream(s.device)))
+    return out
+
+
+def coupled_convex_step(ssd, soft_history):
+    """One iteration of ``coupled_convex`` from given state (extension of this package; ``coupled_convex`` is seven of
+    these on the device).  ``soft_history``: the soft fields s_0 .. s_{j-1} so far, each [1, 3, h, w, d] (empty: the plain
+    argmin).  Returns (labels int64 [h, w, d], s_j [1, 3, h, w, d])."""
+    hw = _disp_hw_of(int(ssd.shape[0]))
+    s = _f32c(ssd, "coupled_convex_step")
+    h, w, d = (int(v) for v in s.shape[1:])
+    j = len(soft_history)
+    hist = None
+    if j:
+        hist = torch.stack([_f32c(t, "coupled_convex_step").reshape(3, h, w, d) for t in soft_history]).contiguous()
+    lib = _lib.load()
+    out = torch.empty((1, 3, h, w, d), dtype=torch.float32, device=s.device)
+    lab = torch.empty((h, w, d), dtype=torch.int64, device=s.device)
+    with torch.cuda.device(s.device):
+        nb = lib.amx_coupled_convex_step_scratch_bytes(h, w, d)
+        sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=s.device)
+        _lib.check(lib.amx_coupled_convex_step(_lib.ptr(s), _lib.ptr(hist), j, h, w, d, hw, _lib.ptr(out), _lib.ptr(lab),
+                                               _lib.ptr(sc), nb, _stream(s.device)))
+    return lab, out
+
+
+def inverse_consistency(disp_field1s, disp_field2s, iterations=20):
+    """convex_adam_utils.py:555-603.  Two fields [1, 3, h, w, d] in normalised coordinates (channel 0 = last axis) ->
+    (disp_field1i, disp_field2i) after ``iterations`` Jacobi sweeps, one kernel launch per sweep; inputs untouched."""
+    a = _f32c(disp_field1s, "inverse_consistency")
+    b = _f32c(disp_field2s, "inverse_consistency")
+    if a.dim() != 5 or a.shape[0] != 1 or a.shape[1] != 3 or a.shape != b.shape:
+        raise ValueError(f"inverse_consistency expects two [1, 3, h, w, d] fields (got {tuple(a.shape)}, {tuple(b.shape)})")
+    _, _, h, w, d = a.shape
+    lib = _lib.load()
+    o1, o2 = torch.empty_like(a), torch.empty_like(b)
+    with torch.cuda.device(a.device):
+        nb = lib.amx_inverse_consistency_scratch_bytes(h, w, d)
+        sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=a.device)
+        _lib.check(lib.amx_inverse_consistency(_lib.ptr(a), _lib.ptr(b), h, w, d, int(iterations), _lib.ptr(o1), _lib.ptr(o2),
+                                               _lib.ptr(sc), nb, _stream(a.device)))
+    return o1, o2
+
+
+def resize_trilinear(x, size, scale=None, flip_channels=False):
+    """``F.interpolate(x.flip(1) * scale.view(1, -1, 1, 1, 1), size=size, mode="trilinear", align_corners=False)`` in one
+    pass (extension of this package; flip and scale optional): x [1, C, h, w, d] -> [1, C, *size].  ``scale``: C floats."""
+    t = _f32c(x, "resize_trilinear")
+    if t.dim() != 5 or t.shape[0] != 1:
+        raise ValueError(f"resize_trilinear expects [1, C, h, w, d] (got {tuple(t.shape)})")
+    _, c, h, w, d = t.shape
+    H, W, D = (int(v) for v in size)
+    sc = None
+    if scale is not None:
+        vals = [float(v) for v in scale]
+        if len(vals) != c:
+            raise ValueError(f"resize_trilinear: {len(vals)} scales for {c} channels")
+        sc = (ctypes.c_float * c)(*vals)
+    lib = _lib.load()
+    out = torch.empty((1, c, max(H, 0), max(W, 0), max(D, 0)), dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        _lib.check(lib.amx_resize_trilinear3d(_lib.ptr(t), c, h, w, d, _lib.ptr(out), H, W, D, sc, int(bool(flip_channels)),
+                                              _stream(t.device)))
+    return out
 
 
 def stage1_inputs(img_fixed, img_moving, model, grid_sp=2, disp_hw=1, downscale_feat_scalar=0.1, fixminclip=None,

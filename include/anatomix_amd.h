@@ -585,6 +585,49 @@ size_t amx_correlate_scratch_bytes(int h, int w, int d, int disp_hw);
 int amx_correlate_ssd(const float* d_fix, const float* d_mov, int c, int h, int w, int d, int disp_hw, float* d_ssd,
                       long long* d_argmin, void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- registration stage 1: the discrete solver downstream of amx_correlate_ssd (csrc/amx_regsolve.hip; fp32, planar
+ * [C][h][w][d], batch 1).  Every entry validates its arguments and returns an error without launching anything. ---- */
+
+/* coupled_convex (convex_adam_utils.py:494-552): d_ssd [(2 disp_hw + 1)^3][h][w][d] as amx_correlate_ssd leaves it,
+ * d_argmin int64 [h][w][d] (nullable: recomputed from d_ssd) -> d_disp_soft [3][h][w][d] in grid units; channel c is the
+ * mesh component (m % k, (m / k) % k, m / k^2)[c] - disp_hw of label m.  The penalty accumulates over the six iterations
+ * as in the reference, but d_ssd is NOT modified (the reference writes the coupled cost through a view into its ssd).
+ * Two launches per iteration.  d_scratch: amx_coupled_convex_scratch_bytes(h, w, d). */
+size_t amx_coupled_convex_scratch_bytes(int h, int w, int d);
+int amx_coupled_convex(const float* d_ssd, const long long* d_argmin, int h, int w, int d, int disp_hw, float* d_disp_soft,
+                       void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* One iteration j in [0, 6] of the above from given state: d_soft_hist [j][3][h][w][d] are the soft fields s_0 .. s_{j-1}
+ * (nullable for j == 0, the plain argmin of d_ssd) -> d_soft_out [3][h][w][d] = s_j and, if d_label is not NULL, the label
+ * int64 [h][w][d] each voxel picked.  amx_coupled_convex is seven of these. */
+size_t amx_coupled_convex_step_scratch_bytes(int h, int w, int d);
+int amx_coupled_convex_step(const float* d_ssd, const float* d_soft_hist, int j, int h, int w, int d, int disp_hw,
+                            float* d_soft_out, long long* d_label, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* inverse_consistency (convex_adam_utils.py:555-603): `iterations` Jacobi sweeps a' = (a - sample(b, id + a)) / 2,
+ * b' = (b - sample(a, id + b)) / 2 over two fields [3][h][w][d] in normalised coordinates (channel 0 = x = last axis;
+ * F.grid_sample / F.affine_grid defaults).  One launch per sweep; the inputs are not modified; the four output / input
+ * buffers must be distinct.  d_scratch: amx_inverse_consistency_scratch_bytes(h, w, d). */
+size_t amx_inverse_consistency_scratch_bytes(int h, int w, int d);
+int amx_inverse_consistency(const float* d_field1, const float* d_field2, int h, int w, int d, int iterations, float* d_out1,
+                            float* d_out2, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* F.interpolate(x, size=(H, W, D), mode="trilinear", align_corners=False) of d_in [c][h][w][d] -> d_out [c][H][W][D], any
+ * sizes, c <= 16.  Output channel k reads input channel (flip_channels ? c - 1 - k : k) multiplied by scale[k]; `scale` is
+ * a HOST array of c floats (copied at the call; NULL = 1). */
+int amx_resize_trilinear3d(const float* d_in, int c, int h, int w, int d, float* d_out, int H, int W, int D, const float* scale,
+                           int flip_channels, void* stream);
+
+/* run_stage1_registration (instance_optimization.py:122-222) from the pooled features d_feat_fix / d_feat_mov
+ * [n_ch][h][w][d]: correlate + coupled_convex, and with ic != 0 the reverse direction, 15 consistency sweeps and the
+ * upsampling, all enqueued on `stream` without host synchronisation.  ic == 0: d_disp_out [3][h][w][d] in grid units
+ * (the reference does not upsample in that branch; H, W, D are ignored).  ic != 0: d_disp_out [3][H][W][D] in voxels.
+ * d_scratch: amx_stage1_registration_scratch_bytes(h, w, d, disp_hw, ic). */
+size_t amx_stage1_registration_scratch_bytes(int h, int w, int d, int disp_hw, int ic);
+int amx_stage1_registration(const float* d_feat_fix, const float* d_feat_mov, int n_ch, int h, int w, int d, int disp_hw,
+                            int grid_sp, int ic, int H, int W, int D, float* d_disp_out, void* d_scratch, size_t scratch_bytes,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
