@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 
@@ -281,17 +282,6 @@ int conv_pick_q(int Cout, int W, int precision) {
   while (Cout % (16 * q)) q >>= 1;   // 48 / 96 / 192 output channels (data gradients of the concat convs): 1 / 2 / 4
   return q;
 }
-
-hipError_t launch_conv_v2(const ConvParams& p, int precision, int Q, hipStream_t st);
-const char* last_conv_v2_kernel_name();
-int last_conv_v2_stats_slots();
-bool conv_ks_eligible(const ConvParams& p, int precision, int Q);
-hipError_t launch_conv_ks(const ConvParams& p, int precision, int Q, hipStream_t st);
-const char* last_conv_ks_kernel_name();
-bool conv_zmarch_eligible(const ConvParams& p);
-bool conv_zmarch_eligible_split(const ConvParams& p);
-hipError_t launch_conv_zmarch(const ConvParams& p, int precision, hipStream_t st);
-const char* last_conv_zm_kernel_name();
 
 // true when launch_conv runs the generic kernel for this layer -- the one whose epilogue can write InstanceNorm partial sums
 bool conv_fuses_stats(const ConvParams& p, int precision, int Q) {

@@ -35,6 +35,7 @@
 #include <string.h>
 
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 

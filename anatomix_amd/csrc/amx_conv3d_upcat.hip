@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 

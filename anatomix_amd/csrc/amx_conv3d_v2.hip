@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 
@@ -700,7 +701,6 @@ static thread_local char g_kernel_name2[64] = "";
 const char* last_conv_v2_kernel_name() { return g_kernel_name2; }
 static thread_local int g_stats_slots = 0;
 int last_conv_v2_stats_slots() { return g_stats_slots; }       // partial-statistics slots per sample written by the last launch
-int conv_v2_stats_slots(int D, int H, int W, int Q);
 
 static int g_num_cus = 0;
 

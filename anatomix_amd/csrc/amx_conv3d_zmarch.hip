@@ -29,6 +29,7 @@
 #include <string.h>
 
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 

@@ -1,0 +1,215 @@
+// anatomix_amd -- host-side declarations shared between translation units: every amx:: function that one .hip file defines and
+// another calls, with its default arguments (stated here and nowhere else), plus the error helper of the C ABI entries.
+// Not part of the public C ABI (that is include/anatomix_amd.h).  The ViT engine's launchers and parameter structs are in amx_gemm.h.
+#pragma once
+#include "../../include/anatomix_amd.h"
+#include "amx_common.h"
+
+namespace amx {
+
+// amx_conv3d.hip
+hipError_t launch_conv(const ConvParams& p, int precision, int Q, hipStream_t st);
+hipError_t launch_pack_weights(const float* w, const float* scale, void* wpk, int CinReal, int CinPad,
+                               int Cout, int Q, int precision, hipStream_t st, int mode = 0, int CoutReal = 0, int CinStride = 0,
+                               int C0Real = 0, int C0Phys = 0);
+hipError_t launch_pack_weights_batch(int count, const float* const* w, void* const* wpk, const int* CinReal, const int* CinPad, const int* Cout,
+                                     const int* Q, const int* mode, const int* CoutReal, int precision, hipStream_t st);
+hipError_t launch_pack_weights_mx(const float* w, const float* scale, void* wpk, int* mxs, int CinReal, int CinPad, int Cout, int Q,
+                                  hipStream_t st, int CoutReal = 0, int CinStride = 0, int C0Real = 0, int C0Phys = 0);
+hipError_t launch_fold_norm(const float* gamma, const float* beta, const float* mean, const float* var,
+                            const float* conv_bias, float eps, int C, float* scale, float* shift,
+                            hipStream_t st);
+hipError_t launch_pool2(const void* in, void* out, int N, int Do, int Ho, int Wo, int C, int avg,
+                        int precision, hipStream_t st, int skip_lo = 0);
+int conv_pick_q(int Cout, int W, int precision);
+bool conv_fuses_stats(const ConvParams& p, int precision, int Q);
+int last_conv_stats_slots();
+const char* last_conv_kernel_name();
+
+// amx_conv3d_v2.hip
+int conv_v2_stats_slots(int D, int H, int W, int Q);
+hipError_t launch_conv_v2(const ConvParams& p, int precision, int Q, hipStream_t st);
+const char* last_conv_v2_kernel_name();
+int last_conv_v2_stats_slots();
+
+// amx_conv3d_ks.hip
+size_t conv_ks_part_bytes(int C0, int Cout, int N, int D, int H, int W, int precision, int Q);
+bool conv_ks_eligible(const ConvParams& p, int precision, int Q);
+hipError_t launch_conv_ks(const ConvParams& p, int precision, int Q, hipStream_t st);
+const char* last_conv_ks_kernel_name();
+
+// amx_conv3d_zmarch.hip
+bool conv_zmarch_can_pool(const ConvParams& p);
+bool conv_zmarch_can_pool_split(const ConvParams& p);
+bool conv_zmarch_eligible(const ConvParams& p);
+bool conv_zmarch_stem_eligible(const ConvParams& p, int precision);
+const char* last_conv_zm_kernel_name();
+hipError_t launch_conv_zmarch_stem(const ConvParams& p, const float* x, long long xs_n, long long xs_z, long long xs_y, const long long* x_offs,
+                                   const void* stem_wpk, const float* stem_bias, int stem_act, float stem_slope, int precision, hipStream_t st);
+bool conv_zmarch_eligible_split(const ConvParams& p);
+hipError_t launch_conv_zmarch(const ConvParams& p, int precision, hipStream_t st);
+
+// amx_conv3d_zx.hip
+bool conv_zx_eligible(const ConvParams& p);
+int conv_zx_stats_slots(int H, int W);
+size_t conv_zx_packed_bytes();
+hipError_t launch_pack_weights_zx(const float* w, const float* scale, void* wx, const int* mxs, int CoutReal, hipStream_t st);
+hipError_t launch_conv_zx(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st);
+const char* last_conv_zx_kernel_name();
+
+// amx_conv3d_stem.hip
+hipError_t launch_conv_stem(const ConvParams& p, int precision, hipStream_t st);
+hipError_t launch_pack_stem(const float* w, const float* scale, void* wpk, int Cout, int precision, hipStream_t st, int CoutReal = 0);
+const char* last_conv_stem_kernel_name();
+int conv_stem_stats_slots(const ConvParams& p, int precision);
+
+// amx_conv3d_upcat.hip
+size_t conv_upcat16_packed_bytes();
+bool conv_upcat16_eligible(const ConvParams& p);
+hipError_t launch_conv_upcat16(const ConvParams& p, int precision, hipStream_t st);
+hipError_t launch_pack_upcat16(const float* w, const float* scale, void* wpk, int precision, hipStream_t st);
+const char* last_conv_upcat_kernel_name();
+
+// amx_conv3d_upmerge.hip
+size_t conv_upmerge_packed_bytes(int C1, int Cout, int split);
+bool conv_upmerge_eligible(int C0, int C1, int Cout, int D, int H, int W, int up_shift, int split);
+hipError_t launch_conv_upmerge(const UpmergeParams& p, int precision, hipStream_t st);
+hipError_t launch_pack_upmerge(const float* w, const float* scale, void* wpk, int c_off, int CinTotal, int C1, int Cout, int precision,
+                               hipStream_t st);
+const char* last_conv_upmerge_kernel_name();
+
+// amx_norm.hip
+size_t instnorm_scratch_bytes(int N, int C, long long max_slots_x_C);
+bool in_apply_pool_eligible(int precision, int D, int H, int W, int C);
+hipError_t launch_in_apply_pool(void* x, const float* ab, void* pooled, int N, int D, int H, int W, int C, int act, float slope, int avg,
+                                int skip_lo, int pool_skip_lo, int* oflow, hipStream_t st);
+hipError_t launch_instnorm(void* x, const float* gamma, const float* beta, float eps, int N, long long vox, int C, int act,
+                           float slope, void* scratch, int precision, hipStream_t st, int* oflow = nullptr, int fused_slots = 0,
+                           const float* kshift = nullptr, int W = 0, int skip_lo = 0, int apply = 1, float* ab_out = nullptr);
+hipError_t launch_poison_if_flag(const int* flag, int* host_flag, float* y, long long count, hipStream_t st);
+hipError_t launch_upsample2_trilinear(const void* in, void* out, int N, int D, int H, int W, int C, int precision,
+                                      hipStream_t st, int skip_lo = 0, const float* ab = nullptr, int act = 0, float slope = 0.f,
+                                      int* oflow = nullptr);
+hipError_t launch_affine_act(void* x, const float* scale, const float* shift, int N, long long vox, int C, int act,
+                             float slope, int precision, hipStream_t st, int* oflow = nullptr);
+hipError_t launch_export_ncdhw(const void* src0, int C0, const void* src1, int C1, int up_shift, int N, int D, int H, int W,
+                               float* out, int precision, hipStream_t st, int S0 = 0, int S1 = 0);
+hipError_t launch_import_input(const float* src, void* dst, int N, int Cin, long long vox, int precision, hipStream_t st);
+hipError_t launch_import_ncdhw(const float* src, void* dst, int N, int C, int D, int H, int W, long long dn, long long dz,
+                               long long dy, long long dx, int accumulate, int precision, hipStream_t st);
+hipError_t launch_upsample2_trilinear_backward(const void* gout, void* gin, int N, int D, int H, int W, int C, int precision,
+                                               hipStream_t st);
+
+// amx_sw.hip
+hipError_t launch_sw_normalize(float* acc, const float* cnt, int channels, long long voxels, hipStream_t st);
+hipError_t launch_sw_count(float* cnt, int vd, int vh, int vw, int oz, int oy, int ox, int rd, int rh,
+                           int rw, const float* wmap, hipStream_t st);
+
+// amx_train.hip
+size_t train_scratch_bytes(int C);
+hipError_t launch_bn_train_forward(const void* x, void* y, const float* gamma, const float* beta, float eps, long long rows, int C,
+                                   int act, float slope, void* scratch, float* save_mean, float* save_rstd, float* running_mean,
+                                   float* running_var, float momentum, int precision, hipStream_t st);
+hipError_t launch_bn_act_backward(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
+                                  const float* gamma, const float* beta, float* dgamma, float* dbeta, void* dx_framed, int N, int D,
+                                  int H, int W, int C, int act, float slope, void* scratch, int precision, hipStream_t st);
+hipError_t launch_pad_fold(const void* g_framed, void* din, int N, int D, int H, int W, int C, int accumulate, int precision,
+                           hipStream_t st);
+hipError_t launch_dgrad_fold_shell(const void* dy, long long yn, long long yz, long long yy, long long yx, int cdy, const float* w,
+                                   int co_real, int ci_real, void* dx, int cdx, int N, int D, int H, int W, int precision, void* scratch,
+                                   hipStream_t st);
+size_t dgrad_shell_scratch_bytes();
+hipError_t launch_pool2_max_backward(const void* dp, const void* in, void* din, int N, int Do, int Ho, int Wo, int C,
+                                     int accumulate, int precision, hipStream_t st);
+hipError_t launch_upcat_split(const void* dcat, void* dskip, void* dlow, int N, int Dl, int Hl, int Wl, int c0, int c1,
+                              int acc_skip, int framed, int precision, hipStream_t st);
+
+// amx_wgrad.hip
+size_t wgrad_scratch_bytes(int N, int D, int H, int W, int Cout, int CinPad);
+hipError_t launch_wgrad(WgradParams p, int CinReal, float* dw, int accumulate, void* scratch, int precision, hipStream_t st);
+
+// amx_optim.hip
+hipError_t launch_adamw(const long long* table, int count, double lr, double b1, double b2, double eps, double wd, int maximize,
+                        hipStream_t st, const double* d_hyper = nullptr);
+
+// amx_supcon.hip
+size_t supcon_scratch_bytes(int N, int C);
+hipError_t launch_supcon(const float* feat, const int* labels, int N, int C, float temperature, int rarity, int balance,
+                         int sqrt_mode, float* loss, float* grad, void* scratch, hipStream_t st);
+hipError_t launch_supcon_batch(int nb, const float* const* feat, const int* const* labels, int N, int C, float temperature, int rarity,
+                               int balance, int sqrt_mode, float* const* loss, float* const* grad, void* scratch, hipStream_t st);
+
+// amx_mlp.hip
+hipError_t launch_mlp_layer_forward(const float* x, int n, int k, const float* w, int m, const float* gamma, const float* beta,
+                                    float eps, int act, float slope, float* z, float* y, float* mean, float* rstd, float* rmean,
+                                    float* rvar, float momentum, hipStream_t st);
+hipError_t launch_mlp_layer_backward(const float* dy, const float* y, const float* z, const float* mean, const float* rstd,
+                                     const float* gamma, int act, float slope, const float* x, const float* w, int n, int k,
+                                     int m, float* dz, float* dgamma, float* dbeta, float* dw, float* dx, float* wpart,
+                                     hipStream_t st);
+size_t mlp_backward_scratch_floats(int n, int cin, int width);
+hipError_t launch_mlp_heads_layer_forward(int nb, const float* const* x, int n, const int* k, const float* const* w, int m,
+                                          const float* const* gamma, const float* const* beta, float eps, int act, float slope,
+                                          float* const* z, float* const* y, float* const* mean, float* const* rstd,
+                                          float* const* rmean, float* const* rvar, float momentum, hipStream_t st);
+hipError_t launch_mlp_heads_layer_backward(int nb, const float* const* dy, const float* const* y, const float* const* z,
+                                           const float* const* mean, const float* const* rstd, const float* const* gamma, int act,
+                                           float slope, const float* const* x, const float* const* w, int n, const int* k, int m,
+                                           float* const* dz, float* const* dgamma, float* const* dbeta, float* const* dw,
+                                           float* const* dx, float* const* wpart, hipStream_t st);
+hipError_t launch_small_gemm_batch(int nb, bool ta, bool tb, const float* const* A, const float* const* B, float* const* Cm, int M,
+                                   int N, int R, int splits, float scale, hipStream_t st);
+
+// amx_sample.hip
+hipError_t launch_gather_labels_batch(const float* seg, int D, int H, int W, int nb, const long long* const* coords, int P, const int* dims,
+                                      int views, int* const* out, hipStream_t st);
+hipError_t launch_sample_coords(const long long* draws, int n, int num, int d0, int d1, int d2, long long* coords, hipStream_t st);
+hipError_t launch_sample_perm(const long long* keys, int nvox, int num, int d1, int d2, long long* coords, hipStream_t st);
+hipError_t launch_gather_labels(const float* seg, int D, int H, int W, const long long* coords, int P, int d, int h, int w, int views,
+                                int* out, hipStream_t st);
+hipError_t launch_gather_rows(const void* src, int dtype, long long sn, long long sz, long long sy, long long sx, long long sc,
+                              const long long* coords, int N, int P, int C, float* rows, hipStream_t st);
+hipError_t launch_sampled_conv_backward(const float* g, const long long* coords, const void* x, int xc, const float* w, int N, int P, int D,
+                                        int H, int W, int Cout, int Cin, float* dw, void* din, int dc, void* scratch, int precision,
+                                        hipStream_t st);
+size_t sampled_conv_backward_scratch_bytes(int P);
+hipError_t launch_scatter_rows(const float* rows, const long long* coords, void* dst, int dtype, long long dn, long long dz, long long dy,
+                               long long dx, int N, int P, int C, int accumulate, hipStream_t st);
+
+// amx_regfeat.hip
+size_t mindssc_scratch_bytes(int H, int W, int D);
+hipError_t launch_mindssc(const float* img, int H, int W, int D, int radius, int dilation, float* out, void* scratch,
+                          hipStream_t st);
+hipError_t launch_pool_cat(const float* a, int ca, float sa, const float* b, int cb, float sb, int H, int W, int D, int g,
+                           float* out, hipStream_t st);
+hipError_t launch_box_filter(const float* in, float* out, int C, int H, int W, int D, int k, hipStream_t st);
+size_t correlate_scratch_bytes(int h, int w, int d, int disp_hw);
+hipError_t launch_correlate(const float* fix, const float* mov, int C, int h, int w, int d, int disp_hw, float* ssd,
+                            long long* argmin, void* scratch, hipStream_t st);
+
+// amx_attention.hip
+size_t attention_scratch_bytes(int b, int heads, int n);
+void attention_operands(void* scratch, int b, int heads, int n, void** Qp, void** Kp, void** Vt, int* npad_out, int* nblk_pad_out);
+hipError_t launch_attention_fwd(const void* Qp, const void* Kp, const void* Vt, int b, int n, int heads, int hd, float* out, hipStream_t st);
+hipError_t launch_attention(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
+                            const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
+                            float* out, void* scratch, hipStream_t st);
+
+// amx_api.hip: stores the thread-local message that amx_last_error() returns, and gives `code` back
+int fail(int code, const char* fmt, ...);
+
+// precision helpers of the C ABI units (amx_api.hip, amx_unet.hip; kept here so that the two share one copy)
+// strict precision (AMX_PREC_F16X2 / AMX_PREC_BF16X2): every stored voxel holds [hi(C) | lo(C)] 16-bit channels
+// AMX_PREC_F16X2_MX: the pair plus 2 bytes of e4m3 copies per channel (amx_common.h, voxel layout FMT 2)
+inline bool is_split(int precision) { return precision >= AMX_PREC_F16X2; }
+inline bool is_mx(int precision) { return precision == AMX_PREC_F16X2_MX; }
+inline long long elem_bytes(int precision) { return fmt_elem_bytes(fmt_of_precision(precision)); }
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+}  // namespace amx
+
+#define AMX_HIP(expr)                                                                         \
+  do {                                                                                        \
+    hipError_t e_ = (expr);                                                                   \
+    if (e_ != hipSuccess) return amx::fail(AMX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)

@@ -11,6 +11,7 @@
 // and dX = dZ W.  (A first version fused the forward GEMM into the column-owned kernel: 32 blocks, each thread walking
 // its own rows -> 8x cache-line over-fetch and 50 us per layer; the split version is ~4x faster.)
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 

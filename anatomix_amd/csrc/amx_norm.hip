@@ -13,6 +13,7 @@
 //       neighbour index clamped (PyTorch's source-index clamp puts the whole weight on the edge voxel).
 // All tensors are channels-last 16-bit; one thread moves 8 channels (16 B) of one voxel.
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 
@@ -607,8 +608,8 @@ static size_t in_coeff_offset(int N, long long vox, int C, int fused_slots) {   
 // bias, or 0): only finalize + apply run here.
 // W: row length of the row-planar layout (precision 4 only; amx_common.h FMT 2)
 hipError_t launch_instnorm(void* x, const float* gamma, const float* beta, float eps, int N, long long vox, int C, int act,
-                           float slope, void* scratch, int precision, hipStream_t st, int* oflow, int fused_slots = 0,
-                           const float* kshift = nullptr, int W = 0, int skip_lo = 0, int apply = 1, float* ab_out = nullptr) {
+                           float slope, void* scratch, int precision, hipStream_t st, int* oflow, int fused_slots, const float* kshift,
+                           int W, int skip_lo, int apply, float* ab_out) {
   // apply = 0: statistics and finalize only -- the (a, b) pairs go to ab_out [N][C][2] and the CONSUMER normalises on the way in
   // (amx_conv3d_zx.hip); the tensor stays raw
   if (C % 8) return hipErrorInvalidValue;
@@ -668,8 +669,7 @@ hipError_t launch_in_apply_pool(void* x, const float* ab, void* pooled, int N, i
 }
 
 hipError_t launch_upsample2_trilinear(const void* in, void* out, int N, int D, int H, int W, int C, int precision,
-                                      hipStream_t st, int skip_lo = 0, const float* ab = nullptr, int act = 0, float slope = 0.f,
-                                      int* oflow = nullptr) {
+                                      hipStream_t st, int skip_lo, const float* ab, int act, float slope, int* oflow) {
   const unsigned blocks = (unsigned)((long long)N * (D + 1) * (H + 1));
 #define AMX_UP(T, S) hipLaunchKernelGGL((upsample2_trilinear_kernel<T, S>), dim3(blocks), dim3(256), 0, st, (const char*)in, (char*)out, N, D, H, W, C, skip_lo, ab, act, slope, oflow)
   switch (precision) {

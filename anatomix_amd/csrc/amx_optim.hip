@@ -7,7 +7,7 @@
 // with the step count t read from the device (one fp32 scalar per tensor, as torch's capturable state keeps it).
 #include <hip/hip_runtime.h>
 
-#include "amx_common.h"
+#include "amx_launch.h"
 
 namespace amx {
 

@@ -8,6 +8,7 @@
 // HBM/cache-bound stencil work on tensors that already sit in HBM; next to 343 UNet windows per volume they cost well
 // under 1 % of a registration, so they are written for coalesced streaming and fixed summation order, not for peak.
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 

@@ -7,21 +7,14 @@
 // fp32 throughout, batch 1, planar [C][h][w][d].  Streaming / stencil work, no MFMA.  The arithmetic follows the
 // reference's operation order (no fused multiply-add: see the pragma), so that the discrete choices of the solver are the
 // reference's wherever its own fp32 arithmetic decides them.
-#include <stdarg.h>
 #include <stdio.h>
 
-#include "../../include/anatomix_amd.h"
 #include "amx_device.h"
+#include "amx_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace amx {
-
-int set_error(int code, const char* msg);   // amx_api.hip (thread-local message)
-hipError_t launch_box_filter(const float* in, float* out, int C, int H, int W, int D, int k, hipStream_t st);
-size_t correlate_scratch_bytes(int h, int w, int d, int disp_hw);
-hipError_t launch_correlate(const float* fix, const float* mov, int C, int h, int w, int d, int disp_hw, float* ssd,
-                            long long* argmin, void* scratch, hipStream_t st);
 
 struct CoupledCoef {
   float c[6];
@@ -361,19 +354,7 @@ hipError_t launch_stage1(const float* fix, const float* mov, int n_ch, int h, in
 }  // namespace amx
 
 namespace {
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  return amx::set_error(code, buf);
-}
-#define AMX_HIP(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) return fail(AMX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
+using amx::fail;
 
 int grid_check(int h, int w, int d, int disp_hw) {
   if (h < 1 || w < 1 || d < 1) return fail(AMX_ERR_SHAPE, "non-positive shape (%d, %d, %d)", h, w, d);

@@ -6,6 +6,7 @@
 // without replacement) and needs only the draws (one torch.randint launch, so torch's generator still seeds it) and this
 // single-block kernel, which also does the unravelling.
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 

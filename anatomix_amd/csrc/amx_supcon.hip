@@ -13,6 +13,7 @@
 // The Gram matrix is 1024 x 1024 x 256 = 0.5 GFLOP -- negligible next to the UNet; the point of the kernel is to
 // replace ~40 small launches (and a 1024^2 autograd graph) per layer with six.
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 
@@ -298,9 +299,6 @@ __global__ __launch_bounds__(256) void sc_dnorm_kernel(const ScBatch bt, int C, 
 size_t supcon_scratch_bytes(int N, int C) {
   return ((size_t)(1 + SC_KSPLIT) * N * C + (size_t)N * N + (size_t)4 * N + 64) * sizeof(float);
 }
-
-hipError_t launch_small_gemm_batch(int nb, bool ta, bool tb, const float* const* A, const float* const* B, float* const* Cm, int M,
-                                   int N, int R, int splits, float scale, hipStream_t st);   // amx_mlp.hip
 
 // nb losses of one shape: feat[b] [N][C], labels[b] [N] -> loss[b], grad[b] (nullptr for every b: no gradients); scratch: nb slices of
 // supcon_scratch_bytes(N, C).

@@ -1,7 +1,7 @@
 // anatomix_amd -- bandwidth kernels around the sliding-window caller
 // (monai.inferers.sliding_window_inference as used by
 //  /root/reference/anatomix/registration/convex_adam_utils.py:202-219).
-#include "amx_common.h"
+#include "amx_launch.h"
 
 namespace amx {
 

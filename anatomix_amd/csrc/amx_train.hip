@@ -17,6 +17,7 @@
 //   pool2_max_backward: adjoint of nn.MaxPool3d(2): the gradient goes to the FIRST maximum of each window in (z,y,x)
 //                       order (torch's tie rule)
 #include "amx_device.h"
+#include "amx_launch.h"
 
 namespace amx {
 

@@ -147,7 +147,7 @@ def test_segmentation_validation_predictor_takes_the_fused_path(device):
 
 
 def test_output_widths_the_fused_step_cannot_accumulate_use_the_generic_loop(device):
-    """output_nc = 8 leaves the network through the export pass (amx_api.hip: final_via_export): the fused window entry would
+    """output_nc = 8 leaves the network through the export pass (amx_unet.hip: final_via_export): the fused window entry would
     return AMX_ERR_SHAPE, so the dispatcher must not pick it (advisor finding, round 3)."""
     kw = dict(dimension=3, input_nc=1, output_nc=8, num_downs=2, ngf=16)
     m = anatomix_amd.Unet(**kw)
