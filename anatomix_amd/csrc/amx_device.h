@@ -292,4 +292,14 @@ struct WaitVmDyn<0> {
 };
 __device__ __forceinline__ void wait_vmcnt_dyn(int n) { WaitVmDyn<63>::run(n); }
 
+
+// identity coordinate of voxel i of n as F.affine_grid(eye, align_corners=False) produces it:
+// linspace(-1, 1, n) * (n - 1) / n with torch.linspace's two-sided evaluation (each side one fused multiply-add)
+__device__ __forceinline__ float identity_coord(int i, int n) {
+  if (n <= 1) return 0.f;
+  const float step = 2.f / (float)(n - 1);
+  const float lin = i < n / 2 ? __fmaf_rn(step, (float)i, -1.f) : __fmaf_rn(-step, (float)(n - 1 - i), 1.f);
+  return __fdiv_rn(lin * (float)(n - 1), (float)n);
+}
+
 }  // namespace amx

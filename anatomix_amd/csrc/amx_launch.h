@@ -187,6 +187,24 @@ size_t correlate_scratch_bytes(int h, int w, int d, int disp_hw);
 hipError_t launch_correlate(const float* fix, const float* mov, int C, int h, int w, int d, int disp_hw, float* ssd,
                             long long* argmin, void* scratch, hipStream_t st);
 
+// amx_regsolve.hip
+hipError_t launch_resize_trilinear(const float* in, int C, int h, int w, int d, float* out, int H, int W, int D,
+                                   const float* scale, int flip, hipStream_t st);
+
+// amx_reginstopt.hip
+hipError_t launch_instopt_smooth3(const float* in, float* out, int h, int w, int d, hipStream_t st);
+size_t instopt_scratch_bytes(int h, int w, int d);
+hipError_t launch_instopt_grad(const float* weight, const float* fix, const float* mov, int c, int h, int w, int d, float lambda,
+                               float* grad_weight, float* disp_sample, float* loss2, void* scratch, hipStream_t st);
+hipError_t launch_instopt_adam(float* weight, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr, int t,
+                               hipStream_t st, bool zero_moments = false);
+hipError_t launch_instopt(float* weight, const float* fix, const float* mov, int c, int h, int w, int d, float lambda, double lr,
+                          int niter, float* fitted, void* scratch, hipStream_t st);
+size_t run_instopt_scratch_bytes(int c, int H, int W, int D, int g, int smooth);
+hipError_t launch_run_instopt(const float* disp_hr, const float* feat_fix, const float* feat_mov, int c, int H, int W, int D, int g,
+                              float lambda, int niter, int smooth, double lr, float* out, void* scratch, hipStream_t st);
+hipError_t launch_warp3d(const float* vol, int c, const float* disp, int H, int W, int D, int nearest, float* out, hipStream_t st);
+
 // amx_attention.hip
 size_t attention_scratch_bytes(int b, int heads, int n);
 void attention_operands(void* scratch, int b, int heads, int n, void** Qp, void** Kp, void** Vt, int* npad_out, int* nblk_pad_out);

@@ -103,15 +103,6 @@ __global__ __launch_bounds__(256) void coupled_argmin_kernel(const float* __rest
   }
 }
 
-// identity coordinate of voxel i of n as F.affine_grid(eye, align_corners=False) produces it:
-// linspace(-1, 1, n) * (n - 1) / n with torch.linspace's two-sided evaluation (each side one fused multiply-add)
-__device__ __forceinline__ float identity_coord(int i, int n) {
-  if (n <= 1) return 0.f;
-  const float step = 2.f / (float)(n - 1);
-  const float lin = i < n / 2 ? __fmaf_rn(step, (float)i, -1.f) : __fmaf_rn(-step, (float)(n - 1 - i), 1.f);
-  return __fdiv_rn(lin * (float)(n - 1), (float)n);
-}
-
 // One Jacobi sweep of inverse_consistency for both fields (blockIdx.y = field): out = 0.5 * (own - sample(other, id + own)),
 // F.grid_sample defaults (trilinear, zeros outside, align_corners=False); channel 0 is the x (last axis) coordinate.  One
 // voxel per thread, consecutive lanes along the row, all 24 corner loads issued before the blends.  (A run of four voxels

@@ -3,8 +3,9 @@ model loading, min-max normalisation and sliding-window feature extraction (refe
 feature post-processing that runs on the extracted tensors before the convex optimisation -- ``MINDSSC`` (:311-406),
 ``apply_avg_pool3d`` (:105-131) and the SSD correlation volume ``correlate`` (:409-491) -- on the HIP kernels of
 ``csrc/amx_regfeat.hip``; and the discrete solver that follows them, ``coupled_convex`` (:494-552) and
-``inverse_consistency`` (:555-603), on the kernels of ``csrc/amx_regsolve.hip``.  The Adam instance optimisation and the
-Jacobian utilities (diffusion_regularizer, generate_grid, JacobianDet) are not part of this package.
+``inverse_consistency`` (:555-603), on the kernels of ``csrc/amx_regsolve.hip``.  The Adam instance optimisation lives in
+``instance_optimization.py`` (its regulariser, ``diffusion_regularizer`` :81-102, is fused into the gradient kernel of
+``csrc/amx_reginstopt.hip``); the Jacobian utilities (generate_grid, JacobianDet) are not part of this package.
 """
 from __future__ import annotations
 
@@ -99,8 +100,8 @@ def MINDSSC(img, radius=2, dilation=2):
 
 def apply_avg_pool3d(disp_hr, kernel_size, num_repeats):
     """convex_adam_utils.py:105-131: ``num_repeats`` x F.avg_pool3d(kernel_size, padding=kernel_size // 2, stride=1).
-    disp_hr [1, C, H, W, D] (forward only: the instance optimisation's autograd use of this function is outside the
-    feature path)."""
+    disp_hr [1, C, H, W, D] (forward only: the instance optimisation does not differentiate through this function, its
+    smoothing and adjoint are ``instance_opt_smooth3``)."""
     if disp_hr.dim() != 5 or disp_hr.shape[0] != 1:
         raise ValueError(f"apply_avg_pool3d expects [1, C, H, W, D] (got {tuple(disp_hr.shape)})")
     if disp_hr.requires_grad and torch.is_grad_enabled():

@@ -628,6 +628,58 @@ int amx_stage1_registration(const float* d_feat_fix, const float* d_feat_mov, in
                             int grid_sp, int ic, int H, int W, int D, float* d_disp_out, void* d_scratch, size_t scratch_bytes,
                             void* stream);
 
+/* ---- registration stage 2: the Adam instance optimisation that follows stage 1, and the warp (csrc/amx_reginstopt.hip;
+ * fp32, planar [C][h][w][d], batch 1, on `stream` without host synchronisation).  Every entry validates its arguments and
+ * returns an error without launching anything.  The optimisation grid needs h, w, d >= 2 (the reference divides by n - 1 and
+ * takes means over n - 1 slices) and c >= 1. ---- */
+
+/* apply_avg_pool3d(x, 3, 3) of a 3-channel field (instance_optimization.py:332-334): three zero-padded box-3 passes in ONE
+ * launch, bit for bit what three amx_box_filter3d(k = 3) calls give.  Each pass is symmetric, so this is also the adjoint the
+ * backward needs.  d_in, d_out [3][h][w][d], distinct buffers. */
+int amx_instance_opt_smooth3(const float* d_in, float* d_out, int h, int w, int d, void* stream);
+
+/* One iteration's forward and backward from given state (instance_optimization.py:330-382 without the step): d_weight
+ * [3][h][w][d] (the Conv3d weight of create_warp, in grid cells; channel 0 moves along h), d_fix / d_mov [c][h][w][d] (the
+ * pooled features) -> d_grad_weight [3][h][w][d] = d(loss + reg) / d weight with
+ *   disp_sample = three box-3 passes of weight,
+ *   loss = mean_voxels(mean_c((grid_sample(mov, identity + disp_sample / ((n - 1) / 2)) - fix)^2) * 12)   (bilinear, zeros, align_corners=False),
+ *   reg  = lambda * diffusion_regularizer(disp_sample)                                                     (convex_adam_utils.py:81-102).
+ * d_disp_sample [3][h][w][d] (nullable) receives disp_sample; d_loss2 (nullable) two floats {loss, reg}, summed in a fixed
+ * order (run-to-run identical).  Three launches, four with d_loss2.  d_scratch: amx_instance_opt_scratch_bytes(c, h, w, d). */
+size_t amx_instance_opt_scratch_bytes(int c, int h, int w, int d);
+int amx_instance_opt_grad(const float* d_weight, const float* d_fix, const float* d_mov, int c, int h, int w, int d, float lambda,
+                          float* d_grad_weight, float* d_disp_sample, float* d_loss2, void* d_scratch, size_t scratch_bytes,
+                          void* stream);
+
+/* Step t >= 1 of torch.optim.Adam(lr, betas = (0.9, 0.999), eps = 1e-8, no weight decay; instance_optimization.py:324-326, :384)
+ * on n contiguous floats, in place -- the formula documented at amx_adamw_step with weight_decay = 0, with 1 - beta^t formed
+ * in double on the host and passed by value (no device step counter). */
+int amx_instance_opt_adam_step(float* d_weight, const float* d_grad, float* d_exp_avg, float* d_exp_avg_sq, long long n, double lr,
+                               int t, void* stream);
+
+/* The loop of run_instance_opt (instance_optimization.py:329-387): niter >= 1 iterations of Adam from d_weight_io (updated in
+ * place, niter - 1 times) -> d_fitted [3][h][w][d], the disp_sample of the LAST iteration's forward.  The reference's last
+ * backward and step do not reach its output and are not run; niter == 1 is gradient-free.  Four launches per iteration.
+ * d_scratch: amx_instance_opt_scratch_bytes(c, h, w, d). */
+int amx_instance_opt(float* d_weight_io, const float* d_fix, const float* d_mov, int c, int h, int w, int d, float lambda, double lr,
+                     int niter, float* d_fitted, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* run_instance_opt (instance_optimization.py:269-399) in one enqueue: avg_pool3d(grid_sp_adam) of both feature volumes
+ * d_feat_fix / d_feat_mov [c][H][W][D], create_warp's initial weight (:225-266: trilinear resize of d_disp_hr [3][H][W][D] to the
+ * grid, / grid_sp_adam), the loop above, the trilinear resize of disp_sample * grid_sp_adam back to (H, W, D) and, for
+ * selected_smooth in {3, 5}, three box passes of that size (any other value: none, as the reference's `in [3, 5]`) -> d_out
+ * [3][H][W][D] in voxels.  The inputs are not modified.  d_scratch: amx_run_instance_opt_scratch_bytes(same arguments). */
+size_t amx_run_instance_opt_scratch_bytes(int c, int H, int W, int D, int grid_sp_adam, int selected_smooth);
+int amx_run_instance_opt(const float* d_disp_hr, const float* d_feat_fix, const float* d_feat_mov, int c, int H, int W, int D,
+                         int grid_sp_adam, float lambda, int niter, int selected_smooth, double lr, float* d_out, void* d_scratch,
+                         size_t scratch_bytes, void* stream);
+
+/* The driver's warp (run_convex_adam_with_network_feats.py:238-266): d_out[c] = F.grid_sample(d_vol[c], identity + (d_disp /
+ * (n - 1) * 2).flip, padding zeros, align_corners=False); d_vol, d_out [c][H][W][D], d_disp [3][H][W][D] in voxels (channel 0
+ * along H).  AMX_WARP_NEAREST rounds half to even, as nearbyint.  H, W, D >= 2. */
+enum { AMX_WARP_BILINEAR = 0, AMX_WARP_NEAREST = 1 };
+int amx_warp3d(const float* d_vol, int c, const float* d_disp, int H, int W, int D, int mode, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
