@@ -16,6 +16,7 @@ ACT = {"none": 0, "relu": 1, "lrelu": 2}
 POOL = {"Max": 0, "Avg": 1}
 INTERP = {"nearest": 0, "trilinear": 1}
 WARP = {"bilinear": 0, "nearest": 1}
+SEG_LABEL = {"float32": 0, "int64": 1, "uint8": 2}
 # "strict" = bf16x2: split hi + lo operands, fp32-grade results with fp32's exponent range (include/anatomix_amd.h)
 # "f16x2mx" (alias "strict_mx") = f16 hi + lo pairs whose correction products run on the block-scaled fp8 MFMA (2 instead of 3 MFMA-
 # equivalents per product); implemented for the InstanceNorm configurations, where it is the default (Unet.precision)
@@ -169,6 +170,12 @@ SYMBOLS = {
     "amx_run_instance_opt_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I]),
     "amx_run_instance_opt": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, _I, C.c_double, _P, _P, C.c_size_t, _P]),
     "amx_warp3d": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "amx_seg_loss_scratch_bytes": (C.c_size_t, [_I, C.c_longlong, _I, _I]),
+    "amx_seg_loss_forward": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, C.c_longlong, _I, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P,
+                                  _P, _P, C.c_size_t, _P]),
+    "amx_seg_loss_backward": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, C.c_longlong, _I, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P,
+                                   _P, _P, _P, _P, C.c_size_t, _P]),
+    "amx_seg_argmax": (_I, [_P, _I, _P, _P, _I, _I, C.c_longlong, _P, _P]),
 }
 
 _lib = None

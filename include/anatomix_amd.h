@@ -680,6 +680,46 @@ int amx_run_instance_opt(const float* d_disp_hr, const float* d_feat_fix, const 
 enum { AMX_WARP_BILINEAR = 0, AMX_WARP_NEAREST = 1 };
 int amx_warp3d(const float* d_vol, int c, const float* d_disp, int H, int W, int D, int mode, float* d_out, void* stream);
 
+/* ---- segmentation finetuning: what follows the UNet in anatomix/segmentation/train_segmentation.py (csrc/amx_segloss.hip;
+ * fp32, planar NCDHW, on `stream` without host synchronisation or allocation; sums cross workgroups through a partial slab in
+ * d_scratch added in a fixed order, so results are bit-identical from run to run).  d_in is either the UNet's features
+ * x [n][feat][voxels] with the 1x1x1 head d_w [classes][feat], d_b [classes] (nullable) applied in registers (head mode,
+ * 1 <= feat <= 64: segmentation_utils.py:113-115), or the logits z [n][classes][voxels] themselves (feat == 0; d_w, d_b
+ * ignored).  2 <= classes <= 32.  d_labels [n][voxels] holds class indices as fp32 (truncated toward zero, as .long()), int64
+ * or uint8.  Every entry validates its arguments and returns an error without launching anything. ---- */
+enum { AMX_SEG_LABEL_F32 = 0, AMX_SEG_LABEL_I64 = 1, AMX_SEG_LABEL_U8 = 2 };
+
+/* bytes of d_scratch for the forward and the backward below (0 for arguments outside the envelope) */
+size_t amx_seg_loss_scratch_bytes(int n, long long voxels, int classes, int feat);
+
+/* monai DiceCELoss(softmax=True, to_onehot_y=True) as train_segmentation.py:105-107 builds it and :144-146 calls it, and with
+ * lambda_ce == 0 (the cross-entropy work is skipped) the DiceLoss of :109-111, :200.  With p = softmax(z, classes),
+ * t = one_hot(labels) and, per sample b and class c, I = sum_v p t, P = sum_v p, G = sum_v t:
+ *   dice = mean over (b, c in S) of 1 - (2 I + smooth_nr) / (G + P + smooth_dr),  S = all classes, without class 0 unless include_background
+ *   ce   = mean over all n * voxels voxels of -log p[label]   (every class: include_background only reaches the Dice term)
+ * d_loss [3] = {lambda_dice * dice + lambda_ce * ce, dice, ce}; d_stats [n][classes][3] = {I, P, G}, which the backward reads;
+ * d_bad_labels [1] = the number of labels outside [0, classes): when it is not 0 the three losses are NaN (a label is only ever
+ * compared with class indices, never used as an address).  Two launches. */
+int amx_seg_loss_forward(const float* d_in, int feat, const float* d_w, const float* d_b, const void* d_labels, int label_dtype, int n,
+                         int classes, long long voxels, int include_background, float smooth_nr, float smooth_dr, float lambda_dice,
+                         float lambda_ce, float* d_loss, float* d_stats, long long* d_bad_labels, void* d_scratch,
+                         size_t scratch_bytes, void* stream);
+
+/* The adjoint of the above (what loss.backward() computes at train_segmentation.py:147 through the loss and the head), from the
+ * same inputs, the forward's d_stats and the incoming gradient of the total loss d_gout [1], a DEVICE scalar (no host read).
+ * Logits mode: d_dx [n][classes][voxels] = d loss / d z; d_dw, d_db, d_scratch may be NULL.  Head mode: d_dx [n][feat][voxels]
+ * = W^T dz, d_dw [classes][feat] = sum_v dz x^T, d_db [classes] = sum_v dz; the logits and the softmax are recomputed from x.
+ * d_dx must not alias d_in.  One launch, two in head mode. */
+int amx_seg_loss_backward(const float* d_in, int feat, const float* d_w, const float* d_b, const void* d_labels, int label_dtype, int n,
+                          int classes, long long voxels, int include_background, float smooth_nr, float smooth_dr, float lambda_dice,
+                          float lambda_ce, const float* d_stats, const float* d_gout, float* d_dx, float* d_dw, float* d_db,
+                          void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* The post-transform of train_segmentation.py:84-86 (softmax, then argmax; the softmax does not change an arg-max): d_out
+ * uint8 [n][voxels] = the class of the largest logit, the lowest index on ties.  One launch. */
+int amx_seg_argmax(const float* d_in, int feat, const float* d_w, const float* d_b, int n, int classes, long long voxels,
+                   unsigned char* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
