@@ -205,6 +205,13 @@ hipError_t launch_run_instopt(const float* disp_hr, const float* feat_fix, const
                               float lambda, int niter, int smooth, double lr, float* out, void* scratch, hipStream_t st);
 hipError_t launch_warp3d(const float* vol, int c, const float* disp, int H, int W, int D, int nearest, float* out, hipStream_t st);
 
+// amx_regmetrics.hip
+hipError_t launch_label_overlap(const void* a, int lt_a, const void* b, int lt_b, long long voxels, int bins, long long* counts,
+                                long long* bad, hipStream_t st);
+size_t jacobian_det_scratch_bytes(int H, int W, int D);
+hipError_t launch_jacobian_det(const float* disp, int H, int W, int D, int add_identity, float* jdet, float* stats, void* scratch,
+                               hipStream_t st);
+
 // amx_attention.hip
 size_t attention_scratch_bytes(int b, int heads, int n);
 void attention_operands(void* scratch, int b, int heads, int n, void** Qp, void** Kp, void** Vt, int* npad_out, int* nblk_pad_out);

@@ -5,7 +5,9 @@ feature post-processing that runs on the extracted tensors before the convex opt
 ``csrc/amx_regfeat.hip``; and the discrete solver that follows them, ``coupled_convex`` (:494-552) and
 ``inverse_consistency`` (:555-603), on the kernels of ``csrc/amx_regsolve.hip``.  The Adam instance optimisation lives in
 ``instance_optimization.py`` (its regulariser, ``diffusion_regularizer`` :81-102, is fused into the gradient kernel of
-``csrc/amx_reginstopt.hip``); the Jacobian utilities (generate_grid, JacobianDet) are not part of this package.
+``csrc/amx_reginstopt.hip``).  The Jacobian utilities ``generate_grid`` and ``JacobianDet`` (:226-282) are here too, the
+determinant and its statistics on the kernel of ``csrc/amx_regmetrics.hip`` (``jacobian_determinant`` is the direct route
+from a displacement field); the label-overlap side of that file is in ``metrics.py``.
 """
 from __future__ import annotations
 
@@ -287,3 +289,72 @@ def stage1_inputs(img_fixed, img_moving, model, grid_sp=2, disp_hw=1, downscale_
     h, w, d = (int(v) for v in pred_f.shape[-3:])
     out["ssd"], out["ssd_argmin"] = correlate(smooth[0], smooth[1], disp_hw, grid_sp, (h, w, d), smooth[0].shape[1])
     return out
+
+
+# ---- Jacobian determinant (csrc/amx_regmetrics.hip) -------------------------------------------------------------------------
+
+JACOBIAN_STATS = ("folding_fraction", "min", "max", "mean", "log_mean", "log_std")
+
+
+def generate_grid(imgshape):
+    """convex_adam_utils.py:226-246: the integer coordinate grid [H, W, D, 3] of a volume, numpy int64.  Component c holds the
+    index along axis 2 - c (the last component is the index along the first axis), exactly as the reference builds it."""
+    h, w, d = (int(v) for v in imgshape[:3])
+    i, j, k = np.meshgrid(np.arange(h), np.arange(w), np.arange(d), indexing="ij")
+    return np.stack([k, j, i], axis=-1)
+
+
+def _jacobian_call(field, add_identity, want_field, want_stats):
+    """field: contiguous fp32 device tensor [3, H, W, D], channel a along axis a."""
+    lib = _lib.load()
+    _, h, w, d = (int(v) for v in field.shape)
+    jdet = torch.empty((h - 1, w - 1, d - 1), dtype=torch.float32, device=field.device) if want_field else None
+    stats = torch.empty(6, dtype=torch.float32, device=field.device) if want_stats else None
+    with torch.cuda.device(field.device):
+        nb = lib.amx_jacobian_det_scratch_bytes(h, w, d) if want_stats else 0
+        sc = torch.empty(max(nb, 8), dtype=torch.uint8, device=field.device) if want_stats else None
+        _lib.check(lib.amx_jacobian_det(_lib.ptr(field), h, w, d, int(add_identity), _lib.ptr(jdet), _lib.ptr(stats), _lib.ptr(sc),
+                                        nb, _stream(field.device)))
+    return jdet, stats
+
+
+def jacobian_determinant(disp_hr, return_stats=False):
+    """Jacobian determinant of the map x + disp_hr for a displacement field [1, 3, H, W, D] in voxels (channel a along axis a,
+    what ``run_instance_opt`` returns and ``warp_volume`` takes) -> [1, H-1, W-1, D-1] of forward differences, equal to the
+    reference's ``JacobianDet(disp_hr.permute(0, 2, 3, 4, 1).flip(-1), generate_grid((H, W, D)))`` without forming the grid.
+    With ``return_stats`` also a float32 device tensor of the six ``JACOBIAN_STATS`` taken over that field in the same pass."""
+    if disp_hr.dim() != 5 or disp_hr.shape[0] != 1 or disp_hr.shape[1] != 3 or min(disp_hr.shape[2:]) < 2:
+        raise ValueError(f"jacobian_determinant expects [1, 3, H, W, D] with H, W, D >= 2 (got {tuple(disp_hr.shape)})")
+    x = _f32c(disp_hr, "jacobian_determinant")
+    jdet, stats = _jacobian_call(x[0], 1, True, bool(return_stats))
+    return (jdet[None], stats) if return_stats else jdet[None]
+
+
+def jacobian_statistics(disp_hr):
+    """The six ``JACOBIAN_STATS`` of the map x + disp_hr ([1, 3, H, W, D], voxels) as a dict of floats, without writing the
+    determinant field (one pass over the displacement field; reads the result back, so it synchronises)."""
+    if disp_hr.dim() != 5 or disp_hr.shape[0] != 1 or disp_hr.shape[1] != 3 or min(disp_hr.shape[2:]) < 2:
+        raise ValueError(f"jacobian_statistics expects [1, 3, H, W, D] with H, W, D >= 2 (got {tuple(disp_hr.shape)})")
+    _, stats = _jacobian_call(_f32c(disp_hr, "jacobian_statistics")[0], 1, False, True)
+    return dict(zip(JACOBIAN_STATS, stats.tolist()))
+
+
+def JacobianDet(y_pred, sample_grid):
+    """convex_adam_utils.py:249-282.  y_pred [N, H, W, D, 3] (component c along axis 2 - c, as ``generate_grid``) and the grid
+    (tensor or numpy, broadcastable) -> [N, H-1, W-1, D-1].  On a device tensor the sum is formed as the reference forms it, its
+    components are put into axis order and the kernel differences that map (add_identity = 0), one call per sample; on a CPU
+    tensor this is the reference's arithmetic in plain torch."""
+    if not torch.is_tensor(sample_grid):
+        sample_grid = torch.from_numpy(np.ascontiguousarray(sample_grid)).to(y_pred.device)
+    if y_pred.dim() != 5 or y_pred.shape[-1] != 3 or min(y_pred.shape[1:4]) < 2:
+        raise ValueError(f"JacobianDet expects [N, H, W, D, 3] with H, W, D >= 2 (got {tuple(y_pred.shape)})")
+    J = y_pred + sample_grid
+    if not J.is_cuda:
+        base = J[:, :-1, :-1, :-1, :]
+        dy, dx, dz = J[:, 1:, :-1, :-1, :] - base, J[:, :-1, 1:, :-1, :] - base, J[:, :-1, :-1, 1:, :] - base
+        det0 = dx[..., 0] * (dy[..., 1] * dz[..., 2] - dy[..., 2] * dz[..., 1])
+        det1 = dx[..., 1] * (dy[..., 0] * dz[..., 2] - dy[..., 2] * dz[..., 0])
+        det2 = dx[..., 2] * (dy[..., 0] * dz[..., 1] - dy[..., 1] * dz[..., 0])
+        return det0 - det1 + det2
+    maps = J.float().flip(-1).permute(0, 4, 1, 2, 3).contiguous()
+    return torch.stack([_jacobian_call(m, 0, True, False)[0] for m in maps])

@@ -720,6 +720,33 @@ int amx_seg_loss_backward(const float* d_in, int feat, const float* d_w, const f
 int amx_seg_argmax(const float* d_in, int feat, const float* d_w, const float* d_b, int n, int classes, long long voxels,
                    unsigned char* d_out, void* stream);
 
+/* ---- registration metrics: the Dice score the reference's driver prints and the Jacobian determinant of the fitted map
+ * (csrc/amx_regmetrics.hip; fp32 or integer data, planar, batch 1, on `stream` without host synchronisation or allocation;
+ * bit-identical from run to run).  Every entry validates its arguments and returns an error without launching anything. ---- */
+
+/* What sklearn.metrics.f1_score needs from the two label maps (run_convex_adam_with_network_feats.py:283-295, which copies both
+ * maps to the host): d_a, d_b hold `voxels` labels each as fp32, int64 or uint8 (AMX_SEG_LABEL_*, one code per volume);
+ * d_counts [bins][3] = {#(a == l), #(b == l), #(a == l and b == l)} for l in [0, bins), 1 <= bins <= 1024; d_bad [1] = the number
+ * of voxels where either value is not an integer in [0, bins) (a fractional fp32 value, a negative one, NaN, one >= bins).  Such
+ * a voxel is left out of all three counts, in both volumes.  An fp32 label is compared, never truncated, and no label is used as an
+ * address before its range check.  The call zeroes both outputs first.  Per label the Dice (F1) score is
+ * 2 counts[l][2] / (counts[l][0] + counts[l][1]).  Two launches; integer atomics only, so the counts are exact. */
+int amx_label_overlap(const void* d_a, int dtype_a, const void* d_b, int dtype_b, long long voxels, int bins, long long* d_counts,
+                      long long* d_bad, void* stream);
+
+/* JacobianDet(y_pred, generate_grid((H, W, D))) (convex_adam_utils.py:226-282) for y_pred = disp.permute(1, 2, 3, 0).flip(-1):
+ * d_disp [3][H][W][D] in voxels, channel a along axis a (the layout of amx_warp3d and amx_run_instance_opt), H, W, D >= 2 ->
+ * d_jdet [H-1][W-1][D-1] (nullable), at (i, j, k) the determinant of the 3x3 matrix whose column a is the forward difference
+ * along axis a of the map x + u (add_identity != 0: u is differenced and 1 added on the diagonal) or of u itself
+ * (add_identity == 0, for a field that already holds the map); and d_stats [6] (nullable, not both) over that field =
+ * {share of determinants <= 0 (folding), min, max, mean, mean of log(det) over the positive ones (NaN when there is none),
+ * population standard deviation of that log (0 with fewer than two)}, accumulated in double.  d_jdet must not overlap d_disp.
+ * d_scratch: amx_jacobian_det_scratch_bytes(H, W, D), only read with d_stats (0 for arguments outside the envelope).  One launch,
+ * two with d_stats. */
+size_t amx_jacobian_det_scratch_bytes(int H, int W, int D);
+int amx_jacobian_det(const float* d_disp, int H, int W, int D, int add_identity, float* d_jdet, float* d_stats, void* d_scratch,
+                     size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
