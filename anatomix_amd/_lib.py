@@ -176,6 +176,14 @@ SYMBOLS = {
     "amx_seg_loss_backward": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, C.c_longlong, _I, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P,
                                    _P, _P, _P, _P, C.c_size_t, _P]),
     "amx_seg_argmax": (_I, [_P, _I, _P, _P, _I, _I, C.c_longlong, _P, _P]),
+    "amx_segaug_sample_bytes": (C.c_size_t, []),
+    "amx_segaug_scratch_bytes": (C.c_size_t, [_I, C.c_longlong]),
+    "amx_segaug_minmax": (_I, [_P, _I, C.c_longlong, _P, _P, C.c_size_t, _P]),
+    "amx_segaug_minmax_finalize": (_I, [_P, C.c_size_t, _I, C.c_longlong, _P, _P]),
+    "amx_segaug_pointwise": (_I, [_P, _P, _I, C.c_longlong, _P, _I, _P, _P, _P]),
+    "amx_segaug_crop": (_I, [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "amx_segaug_gaussian": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "amx_segaug_affine": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
     "amx_label_overlap": (_I, [_P, _I, _P, _I, C.c_longlong, _I, _P, _P, _P]),
     "amx_jacobian_det_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "amx_jacobian_det": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),

@@ -747,6 +747,85 @@ size_t amx_jacobian_det_scratch_bytes(int H, int W, int D);
 int amx_jacobian_det(const float* d_disp, int H, int W, int D, int add_identity, float* d_jdet, float* d_stats, void* d_scratch,
                      size_t scratch_bytes, void* stream);
 
+/* ---- segmentation finetuning: the augmentation chain of get_train_transforms (segmentation_utils.py:159-216) on a batch
+ * (csrc/amx_segaug.hip; fp32 NCDHW with one channel, labels fp32 or uint8 in and uint8 out, on `stream` without host
+ * synchronisation, read-back or allocation).  A batch is one launch per stage with the sample on grid.y, so the number of launches
+ * does not depend on n.  What differs per sample sits in a table of n amx_segaug_sample records that the caller fills on the
+ * host and copies to the device once per batch: every entry takes the host copy h_table (read for validation only) and the device
+ * copy d_table (read by the kernels).  A sample whose switch for a stage is off is copied through that stage bit for bit.
+ * Minimum and maximum go through per-workgroup partials in d_scratch and a finalize launch; no float atomics, so a batch is
+ * bit-identical from run to run.  16-byte accesses where voxels % 4 == 0 and the bases are 16-byte aligned, scalar ones
+ * otherwise.  MONAI is not a dependency: its documented algorithms are restated and parity with an
+ * installed MONAI is not pinned.  Every entry validates its arguments and returns an error without launching anything. ---- */
+enum {
+  AMX_SEGAUG_NOISE = 1,      /* RandGaussianNoise */
+  AMX_SEGAUG_BIAS = 2,       /* RandBiasField(degree=3) */
+  AMX_SEGAUG_GIBBS = 4,      /* RandGibbsNoise: the caller's FFTs; no kernel reads this bit */
+  AMX_SEGAUG_CONTRAST = 8,   /* RandAdjustContrast */
+  AMX_SEGAUG_SMOOTH = 16,    /* RandGaussianSmooth */
+  AMX_SEGAUG_SHARPEN = 32,   /* RandGaussianSharpen */
+  AMX_SEGAUG_AFFINE = 64,    /* RandAffine: the caller stores the identity in `affine` when it is off */
+  AMX_SEGAUG_RESCALE = 128   /* ScaleIntensity */
+};
+enum { AMX_SEGAUG_OP_SCALE = 0, AMX_SEGAUG_OP_CONTRAST = 1 };
+enum { AMX_SEGAUG_GAUSS_SMOOTH = 0, AMX_SEGAUG_GAUSS_SHARPEN = 1 };
+
+typedef struct amx_segaug_sample {
+  const float* vol;          /* the sample's resident volume [vol_dim[0]][vol_dim[1]][vol_dim[2]] (crop stage only) */
+  const void* lab;           /* its label map, same shape, fp32 or uint8 (crop stage only) */
+  int32_t flags;             /* AMX_SEGAUG_* switches */
+  int32_t vol_dim[3];
+  int32_t corner[3];         /* first voxel of the crop inside the volume */
+  float noise_std;
+  float bias[20];            /* c_ijk, i + j + k <= 3, (i, j, k) in lexicographic order; i runs along the first spatial axis */
+  float gibbs_r;             /* radius of the k-space mask (kept here so that one copy carries every parameter) */
+  float gamma;
+  int32_t radius[3][3];      /* Gaussian tail per [filter: smooth, sharpen sigma1, sharpen sigma2][axis], 0 <= radius <= 4 */
+  float taps[3][3][9];       /* its 2 radius + 1 taps, tap k (-radius <= k <= radius) at index k + radius */
+  float sharpen_alpha;
+  float affine[9];           /* A, row major: source = A (o - (size_out - 1) / 2) + (size_in - 1) / 2 */
+} amx_segaug_sample;
+
+/* sizeof(amx_segaug_sample), for a caller that lays the table out without this header */
+size_t amx_segaug_sample_bytes(void);
+/* bytes of d_scratch for the entries below that take it (0 for arguments outside the envelope) */
+size_t amx_segaug_scratch_bytes(int n, long long voxels);
+
+/* d_minmax [n][2] = {min, max} of each sample of d_x [n][voxels].  Two launches. */
+int amx_segaug_minmax(const float* d_x, int n, long long voxels, float* d_minmax, void* d_scratch, size_t scratch_bytes, void* stream);
+/* The same from the partials that amx_segaug_affine left in d_scratch for its image output (same n, voxels).  One launch. */
+int amx_segaug_minmax_finalize(const void* d_scratch, size_t scratch_bytes, int n, long long voxels, float* d_minmax, void* stream);
+
+/* One pointwise stage with the statistics d_minmax [n][2] of its own input, d_out may be d_in.  One launch.
+ *   AMX_SEGAUG_OP_SCALE (switch AMX_SEGAUG_RESCALE): (x - min) / (max - min); x * 0 when min == max
+ *   AMX_SEGAUG_OP_CONTRAST (switch AMX_SEGAUG_CONTRAST): ((x - min) / (range + 1e-7)) ^ gamma * range + min, range = max - min */
+int amx_segaug_pointwise(const float* d_in, float* d_out, int n, long long voxels, const float* d_minmax, int op,
+                         const amx_segaug_sample* h_table, const amx_segaug_sample* d_table, void* stream);
+
+/* Crop gather, noise and bias field in one pass: d_img [n][d][h][w] = (vol[corner + o] + noise_std * d_noise[o]) * exp(f(o)) with
+ * f the Legendre field over linspace(-1, 1, size) per axis of the crop, each factor under its switch (d_noise [n][d][h][w]
+ * standard normal, nullable when no sample has AMX_SEGAUG_NOISE); d_lab uint8 [n][d][h][w] = the label crop.  The crop must lie
+ * inside every sample's volume.  One launch. */
+int amx_segaug_crop(int n, int d, int h, int w, const float* d_noise, int label_dtype, float* d_img, unsigned char* d_lab,
+                    const amx_segaug_sample* h_table, const amx_segaug_sample* d_table, void* stream);
+
+/* Separable Gaussian with the table's taps, zero padding, taps not renormalised.  AMX_SEGAUG_GAUSS_SMOOTH (switch
+ * AMX_SEGAUG_SMOOTH): d_out = G_0(d_in), three launches.  AMX_SEGAUG_GAUSS_SHARPEN (switch AMX_SEGAUG_SHARPEN): b = G_1(d_in),
+ * d_out = b + sharpen_alpha (b - G_2(b)), six launches.  d_tmp holds 2 n d h w floats; d_in, d_out and d_tmp must not overlap.
+ * A radius above 4 (sigma > 1) in a sample whose switch is on is AMX_ERR_INVALID. */
+int amx_segaug_gaussian(const float* d_in, float* d_out, float* d_tmp, int n, int d, int h, int w, int mode,
+                        const amx_segaug_sample* h_table, const amx_segaug_sample* d_table, void* stream);
+
+/* Affine resample of image and label in one kernel: d_img_in, d_lab_in [n][di][hi][wi] -> d_img_out, d_lab_out [n][d][h][w].  For
+ * the output voxel o the source index is A (o - (size_out - 1) / 2) + (size_in - 1) / 2.  Image: trilinear, a corner outside the
+ * input contributes 0 (grid_sample's zeros padding).  Label: the voxel at the source index rounded half to even, 0 outside.
+ * A source index that is integral on all three axes copies the voxel bit for bit, so the identity at equal sizes returns both
+ * inputs.  The kernel also leaves the per-workgroup minimum and maximum of d_img_out in d_scratch for
+ * amx_segaug_minmax_finalize.  Inputs and outputs must not overlap.  One launch. */
+int amx_segaug_affine(const float* d_img_in, const unsigned char* d_lab_in, int n, int di, int hi, int wi, float* d_img_out,
+                      unsigned char* d_lab_out, int d, int h, int w, const amx_segaug_sample* h_table,
+                      const amx_segaug_sample* d_table, void* d_scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
