@@ -61,8 +61,6 @@ class LaunchRecord(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double)]
 
 
-_P = C.c_void_p
-_I = C.c_int
 SYMBOLS = {
     "amx_version": (_I, []),
     "amx_debug_fill_lds": (_I, [C.c_uint, _P]),
@@ -236,6 +234,32 @@ def check(status: int):
         raise cls(int(status), f"anatomix_amd error {status}: {load().amx_last_error().decode()}")
 
 
+def check_envelope(status: int):
+    """``check`` for the entries whose AMX_ERR_INVALID / AMX_ERR_SHAPE say that the call lies outside what they cover."""
+    if status in (AMX_ERR_INVALID, AMX_ERR_SHAPE):
+        raise AmxEnvelopeError(int(status), f"anatomix_amd error {status}: {load().amx_last_error().decode()}")
+    check(status)
+
+
 def ptr(t):
     """Device pointer of a torch tensor (or None)."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+# torch is imported inside the helpers below: importing this module stays torch-free
+def stream(dev):
+    """The current stream of ``dev`` as the ``void* stream`` argument of the C ABI."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def scratch(nbytes: int, dev):
+    """An uninitialised device buffer for a ``*_scratch_bytes`` answer (one byte when that is 0, so that it has a pointer)."""
+    import torch
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+
+
+def f32c(t):
+    """``t`` as a contiguous float32 tensor (itself when it already is one)."""
+    import torch
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()

@@ -429,8 +429,7 @@ int amx_supcon_loss(const float* d_feat, const int* d_labels, int n, int c, floa
                     size_t scratch_bytes, void* stream) {
   if (!d_feat || !d_labels || !d_loss || !d_scratch) return fail(AMX_ERR_INVALID, "null argument");
   if (n < 2 || n > 16384 || c < 1 || !(temperature > 0.f)) return fail(AMX_ERR_INVALID, "bad sizes (n=%d c=%d T=%g)", n, c, temperature);
-  if (scratch_bytes < amx::supcon_scratch_bytes(n, c))
-    return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", amx::supcon_scratch_bytes(n, c), scratch_bytes);
+  if (int rc = amx::need_scratch(amx::supcon_scratch_bytes(n, c), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_supcon(d_feat, d_labels, n, c, temperature, weigh_rarity, balance_denominator, sqrt_mode, d_loss,
                              d_grad, d_scratch, (hipStream_t)stream));
   return AMX_OK;
@@ -464,8 +463,7 @@ int amx_mindssc(const float* d_img, int H, int W, int D, int radius, int dilatio
   if (H < 1 || W < 1 || D < 1) return fail(AMX_ERR_SHAPE, "non-positive shape");
   if (radius < 1 || radius > 2 || dilation < 1 || dilation > 4)
     return fail(AMX_ERR_INVALID, "radius in {1, 2}, dilation in [1, 4] (got %d, %d)", radius, dilation);
-  if (scratch_bytes < amx::mindssc_scratch_bytes(H, W, D))
-    return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", amx::mindssc_scratch_bytes(H, W, D), scratch_bytes);
+  if (int rc = amx::need_scratch(amx::mindssc_scratch_bytes(H, W, D), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_mindssc(d_img, H, W, D, radius, dilation, d_out, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -493,8 +491,7 @@ int amx_correlate_ssd(const float* d_fix, const float* d_mov, int c, int h, int 
   if (!d_fix || !d_mov || !d_ssd || !d_scratch || c < 1) return fail(AMX_ERR_INVALID, "bad argument");
   if (h < 1 || w < 1 || d < 1) return fail(AMX_ERR_SHAPE, "non-positive shape");
   if (disp_hw < 1 || disp_hw > 3) return fail(AMX_ERR_INVALID, "disp_hw in {1, 2, 3} (got %d)", disp_hw);
-  if (scratch_bytes < amx::correlate_scratch_bytes(h, w, d, disp_hw))
-    return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", amx::correlate_scratch_bytes(h, w, d, disp_hw), scratch_bytes);
+  if (int rc = amx::need_scratch(amx::correlate_scratch_bytes(h, w, d, disp_hw), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_correlate(d_fix, d_mov, c, h, w, d, disp_hw, d_ssd, d_argmin, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -535,8 +532,7 @@ int amx_mlp_head_backward(const float* d_dy, const float* d_x, int n, int cin, i
   if (!d_dy || !d_x || !w || !gamma || !d_z || !d_y || !d_mean || !d_rstd || !dw || !dgamma || !dbeta || !d_scratch)
     return fail(AMX_ERR_INVALID, "null argument");
   if (int rc = mlp_check(n, cin, width, n_layers)) return rc;
-  if (scratch_bytes < amx_mlp_head_scratch_bytes(n, cin, width))
-    return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", amx_mlp_head_scratch_bytes(n, cin, width), scratch_bytes);
+  if (int rc = amx::need_scratch(amx_mlp_head_scratch_bytes(n, cin, width), scratch_bytes)) return rc;
   const size_t plane = (size_t)n * width;
   float* dz = (float*)d_scratch;
   float* dprev = dz + plane;
@@ -633,8 +629,7 @@ int amx_supcon_loss_batch(int n_losses, const float* const* d_feat, const int* c
   if (!d_feat || !d_labels || !d_loss || !d_scratch) return fail(AMX_ERR_INVALID, "null argument");
   if (n_losses < 1 || n_losses > amx::MLP_MAXB) return fail(AMX_ERR_INVALID, "1 <= losses <= %d (got %d)", amx::MLP_MAXB, n_losses);
   if (n < 2 || n > 16384 || c < 1 || !(temperature > 0.f)) return fail(AMX_ERR_INVALID, "bad sizes (n=%d c=%d T=%g)", n, c, temperature);
-  if (scratch_bytes < n_losses * amx::supcon_scratch_bytes(n, c))
-    return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", n_losses * amx::supcon_scratch_bytes(n, c), scratch_bytes);
+  if (int rc = amx::need_scratch(n_losses * amx::supcon_scratch_bytes(n, c), scratch_bytes)) return rc;
   for (int b = 0; b < n_losses; ++b) {
     if (!d_feat[b] || !d_labels[b] || !d_loss[b]) return fail(AMX_ERR_INVALID, "loss %d: null buffer", b);
     if (d_grad && (!d_grad[b] != !d_grad[0])) return fail(AMX_ERR_INVALID, "gradients for all losses or for none");

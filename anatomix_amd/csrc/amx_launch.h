@@ -222,6 +222,10 @@ hipError_t launch_attention(const float* q, const float* k, const float* v, cons
 
 // amx_api.hip: stores the thread-local message that amx_last_error() returns, and gives `code` back
 int fail(int code, const char* fmt, ...);
+// the scratch check of the C ABI entries: AMX_OK, or AMX_ERR_WORKSPACE when the caller's `got` bytes are fewer than `need`
+inline int need_scratch(size_t need, size_t got) {
+  return got < need ? fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, got) : AMX_OK;
+}
 
 // precision helpers of the C ABI units (amx_api.hip, amx_unet.hip; kept here so that the two share one copy)
 // strict precision (AMX_PREC_F16X2 / AMX_PREC_BF16X2): every stored voxel holds [hi(C) | lo(C)] 16-bit channels
@@ -230,6 +234,7 @@ inline bool is_split(int precision) { return precision >= AMX_PREC_F16X2; }
 inline bool is_mx(int precision) { return precision == AMX_PREC_F16X2_MX; }
 inline long long elem_bytes(int precision) { return fmt_elem_bytes(fmt_of_precision(precision)); }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace amx
 

@@ -272,17 +272,16 @@ static MindPairs make_pairs(int dilation) {
   return mp;
 }
 
-static inline int cdiv_i(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 size_t mindssc_scratch_bytes(int H, int W, int D) {
-  const size_t blocks = (size_t)cdiv_i(D, 16) * cdiv_i(W, 8) * cdiv_i(H, 8);
+  const size_t blocks = (size_t)cdiv(D, 16) * cdiv(W, 8) * cdiv(H, 8);
   return blocks * sizeof(double) + 256;
 }
 
 hipError_t launch_mindssc(const float* img, int H, int W, int D, int radius, int dilation, float* out, void* scratch,
                           hipStream_t st) {
   const MindPairs mp = make_pairs(dilation);
-  dim3 grid(cdiv_i(D, 16), cdiv_i(W, 8), cdiv_i(H, 8));
+  dim3 grid(cdiv(D, 16), cdiv(W, 8), cdiv(H, 8));
   const int nb = grid.x * grid.y * grid.z;
   double* partials = (double*)scratch;
   float* gm = (float*)((char*)scratch + (size_t)nb * sizeof(double));
@@ -295,18 +294,18 @@ hipError_t launch_mindssc(const float* img, int H, int W, int D, int radius, int
   kern<<<grid, 256, lds, st>>>(img, H, W, D, dilation, mp, out, partials);
   const long long plane = (long long)H * W * D;
   mind_mean_kernel<<<1, 256, 0, st>>>(partials, nb, 1.0 / (double)plane, gm);
-  mind_finish_kernel<<<cdiv_i(plane, 256), 256, 0, st>>>(out, plane, mp, gm);
+  mind_finish_kernel<<<cdiv(plane, 256), 256, 0, st>>>(out, plane, mp, gm);
   return hipGetLastError();
 }
 
 hipError_t launch_pool_cat(const float* a, int ca, float sa, const float* b, int cb, float sb, int H, int W, int D, int g,
                            float* out, hipStream_t st) {
   const long long oplane = (long long)(H / g) * (W / g) * (D / g);
-  pool_cat_kernel<<<cdiv_i(oplane, 256), 256, 0, st>>>(a, ca, sa, b, cb, sb, H, W, D, g, out);
+  pool_cat_kernel<<<cdiv(oplane, 256), 256, 0, st>>>(a, ca, sa, b, cb, sb, H, W, D, g, out);
   return hipGetLastError();
 }
 
-static inline dim3 box_grid(int C, int H, int W, int D) { return dim3(cdiv_i(D, 64) * cdiv_i(W, 8) * cdiv_i(H, 4), C); }
+static inline dim3 box_grid(int C, int H, int W, int D) { return dim3(cdiv(D, 64) * cdiv(W, 8) * cdiv(H, 4), C); }
 static inline size_t box_lds(int k) {
   const int r = k / 2;
   return (size_t)(4 + 2 * r) * (8 + 2 * r) * ((64 + 2 * r) | 1) * 4;
@@ -327,13 +326,13 @@ hipError_t launch_correlate(const float* fix, const float* mov, int C, int h, in
   const long long plane = (long long)h * w * d;
   const int k = 2 * disp_hw + 1, n = k * k * k;
   float* tmp = (float*)scratch;
-  dim3 grid(cdiv_i(plane, 256), k);
+  dim3 grid(cdiv(plane, 256), k);
   if (disp_hw == 1) ssd_raw_kernel<3><<<grid, 256, 0, st>>>(fix, mov, C, h, w, d, ssd);
   else if (disp_hw == 2) ssd_raw_kernel<5><<<grid, 256, 0, st>>>(fix, mov, C, h, w, d, ssd);
   else ssd_raw_kernel<7><<<grid, 256, 0, st>>>(fix, mov, C, h, w, d, ssd);
   box_filter_kernel<<<box_grid(n, h, w, d), 256, box_lds(3), st>>>(ssd, tmp, h, w, d, 3);
   box_filter_kernel<<<box_grid(n, h, w, d), 256, box_lds(3), st>>>(tmp, ssd, h, w, d, 3);
-  if (argmin) argmin_kernel<<<cdiv_i(plane, 256), 256, 0, st>>>(ssd, n, plane, argmin);
+  if (argmin) argmin_kernel<<<cdiv(plane, 256), 256, 0, st>>>(ssd, n, plane, argmin);
   return hipGetLastError();
 }
 

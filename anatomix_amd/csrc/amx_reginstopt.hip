@@ -11,6 +11,7 @@
 
 #include "amx_device.h"
 #include "amx_launch.h"
+#include "amx_stream.h"
 
 #pragma clang fp contract(off)
 
@@ -116,20 +117,6 @@ __device__ __forceinline__ void corners_of(float iz, float iy, float ix, int H, 
   }
 }
 
-// fixed-order sum of one value per thread over the 256 threads of a block (result valid in thread 0)
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // grad_sample = d (loss + reg) / d disp_sample for one voxel per thread, consecutive lanes along d:
 //   loss = mean_voxels(mean_c((grid_sample(mov, id + ds / half) - fix)^2) * 12),  reg = lambda * (three means of squared forward differences).
 // LOSS: also one partial {sum of squared residuals, three sums of squared differences} per block in partial[4][gridDim.x].
@@ -193,7 +180,7 @@ __global__ __launch_bounds__(256) void instopt_sample_grad_kernel(const float* _
     const float vals[4] = {sq, rsum[0], rsum[1], rsum[2]};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float r = block_sum_256(vals[q], red);
+      const float r = block_tree_sum<float, 256>(vals[q], red);
       if (threadIdx.x == 0) partial[(long long)q * gridDim.x + blockIdx.x] = r;
     }
   }
@@ -211,14 +198,7 @@ __global__ __launch_bounds__(256) void instopt_loss_kernel(const float* __restri
   for (int q = 0; q < 4; ++q) {
     double s = 0.0;
     for (int i = threadIdx.x; i < nblk; i += 256) s += (double)partial[(long long)q * nblk + i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-      if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-      __syncthreads();
-    }
-    tot[q] = red[0];
-    __syncthreads();
+    tot[q] = block_tree_sum<double, 256>(s, red);
   }
   if (threadIdx.x == 0) {
     loss2[0] = (float)(sc.data * tot[0]);
@@ -274,11 +254,8 @@ __global__ __launch_bounds__(256) void warp3d_kernel(const float* __restrict__ v
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------
-static inline int cdiv_o(long long a, long long b) { return (int)((a + b - 1) / b); }
-static inline size_t up256o(size_t v) { return (v + 255) & ~(size_t)255; }
-
 hipError_t launch_instopt_smooth3(const float* in, float* out, int h, int w, int d, hipStream_t st) {
-  const dim3 grid(cdiv_o(d, kSmX) * cdiv_o(w, kSmY) * cdiv_o(h, kSmZ), 3);
+  const dim3 grid(cdiv(d, kSmX) * cdiv(w, kSmY) * cdiv(h, kSmZ), 3);
   instopt_smooth3_kernel<<<grid, 256, 0, st>>>(in, out, h, w, d);
   return hipGetLastError();
 }
@@ -294,7 +271,7 @@ static hipError_t launch_sample_grad(const float* ds, const float* fix, const fl
     cf.data[a] = (float)(2.0 * 12.0 / ((double)c * plane) * (0.5 * n[a]) / (0.5 * (n[a] - 1)));
     cf.reg[a] = (float)(2.0 * (double)lambda / cnt[a]);
   }
-  const int nblk = cdiv_o((long long)plane, 256);
+  const int nblk = cdiv((long long)plane, 256);
   if (!loss2) {
     instopt_sample_grad_kernel<false><<<nblk, 256, 0, st>>>(ds, fix, mov, c, h, w, d, cf, grad, nullptr);
     return hipGetLastError();
@@ -310,7 +287,7 @@ struct InstoptLayout {
   size_t ds, gs, gw, m, v, part, total;
 };
 static InstoptLayout instopt_layout(int h, int w, int d) {
-  const size_t plane = (size_t)h * w * d, field = up256o(3 * plane * sizeof(float));
+  const size_t plane = (size_t)h * w * d, field = align_up(3 * plane * sizeof(float), 256);
   InstoptLayout L;
   size_t o = 0;
   L.ds = o, o += field;
@@ -318,7 +295,7 @@ static InstoptLayout instopt_layout(int h, int w, int d) {
   L.gw = o, o += field;
   L.m = o, o += field;
   L.v = o, o += field;
-  L.part = o, o += up256o((size_t)4 * cdiv_o((long long)plane, 256) * sizeof(float));
+  L.part = o, o += align_up((size_t)4 * cdiv((long long)plane, 256) * sizeof(float), 256);
   L.total = o;
   return L;
 }
@@ -345,7 +322,7 @@ hipError_t launch_instopt_adam(float* weight, const float* grad, float* exp_avg,
   const double b1 = 0.9, b2 = 0.999;
   const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
   const AdamStep a = {(float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(lr / bc1), (float)sqrt(bc2), 1e-8f, zero_moments ? 1 : 0};
-  instopt_adam_kernel<<<cdiv_o(n, 256), 256, 0, st>>>(weight, grad, exp_avg, exp_avg_sq, n, a);
+  instopt_adam_kernel<<<cdiv(n, 256), 256, 0, st>>>(weight, grad, exp_avg, exp_avg_sq, n, a);
   return hipGetLastError();
 }
 
@@ -374,8 +351,8 @@ struct RunLayout {
 };
 static RunLayout run_layout(int c, int H, int W, int D, int g, int smooth) {
   const int h = H / g, w = W / g, d = D / g;
-  const size_t plane = (size_t)h * w * d, field = up256o(3 * plane * sizeof(float)), feat = up256o((size_t)c * plane * sizeof(float));
-  const size_t full = (smooth == 3 || smooth == 5) ? up256o((size_t)3 * H * W * D * sizeof(float)) : 0;
+  const size_t plane = (size_t)h * w * d, field = align_up(3 * plane * sizeof(float), 256), feat = align_up((size_t)c * plane * sizeof(float), 256);
+  const size_t full = (smooth == 3 || smooth == 5) ? align_up((size_t)3 * H * W * D * sizeof(float), 256) : 0;
   RunLayout L;
   size_t o = 0;
   L.pf = o, o += feat;
@@ -413,7 +390,7 @@ hipError_t launch_run_instopt(const float* disp_hr, const float* feat_fix, const
 }
 
 hipError_t launch_warp3d(const float* vol, int c, const float* disp, int H, int W, int D, int nearest, float* out, hipStream_t st) {
-  const int grid = cdiv_o((long long)H * W * D, 256);
+  const int grid = cdiv((long long)H * W * D, 256);
   if (nearest) warp3d_kernel<true><<<grid, 256, 0, st>>>(vol, c, disp, H, W, D, out);
   else warp3d_kernel<false><<<grid, 256, 0, st>>>(vol, c, disp, H, W, D, out);
   return hipGetLastError();
@@ -455,8 +432,7 @@ int amx_instance_opt_grad(const float* d_weight, const float* d_fix, const float
     return fail(AMX_ERR_INVALID, "outputs must be distinct from the weight and from each other");
   if (int rc = instopt_grid_check(c, h, w, d)) return rc;
   if (!finite_f(lambda)) return fail(AMX_ERR_INVALID, "lambda is not finite");
-  const size_t need = amx::instopt_scratch_bytes(h, w, d);
-  if (scratch_bytes < need) return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, scratch_bytes);
+  if (int rc = amx::need_scratch(amx::instopt_scratch_bytes(h, w, d), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_instopt_grad(d_weight, d_fix, d_mov, c, h, w, d, lambda, d_grad_weight, d_disp_sample, d_loss2, d_scratch,
                                    (hipStream_t)stream));
   return AMX_OK;
@@ -480,8 +456,7 @@ int amx_instance_opt(float* d_weight_io, const float* d_fix, const float* d_mov,
   if (niter < 1 || niter > 100000) return fail(AMX_ERR_INVALID, "niter in [1, 100000] (got %d)", niter);
   if (!finite_f(lambda)) return fail(AMX_ERR_INVALID, "lambda is not finite");
   if (!(lr > 0.0) || lr - lr != 0.0) return fail(AMX_ERR_INVALID, "lr must be positive and finite");
-  const size_t need = amx::instopt_scratch_bytes(h, w, d);
-  if (scratch_bytes < need) return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, scratch_bytes);
+  if (int rc = amx::need_scratch(amx::instopt_scratch_bytes(h, w, d), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_instopt(d_weight_io, d_fix, d_mov, c, h, w, d, lambda, lr, niter, d_fitted, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -502,8 +477,7 @@ int amx_run_instance_opt(const float* d_disp_hr, const float* d_feat_fix, const 
   if (niter < 1 || niter > 100000) return fail(AMX_ERR_INVALID, "niter in [1, 100000] (got %d)", niter);
   if (!finite_f(lambda)) return fail(AMX_ERR_INVALID, "lambda is not finite");
   if (!(lr > 0.0) || lr - lr != 0.0) return fail(AMX_ERR_INVALID, "lr must be positive and finite");
-  const size_t need = amx::run_instopt_scratch_bytes(c, H, W, D, grid_sp_adam, selected_smooth);
-  if (scratch_bytes < need) return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, scratch_bytes);
+  if (int rc = amx::need_scratch(amx::run_instopt_scratch_bytes(c, H, W, D, grid_sp_adam, selected_smooth), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_run_instopt(d_disp_hr, d_feat_fix, d_feat_mov, c, H, W, D, grid_sp_adam, lambda, niter, selected_smooth, lr,
                                   d_out, d_scratch, (hipStream_t)stream));
   return AMX_OK;

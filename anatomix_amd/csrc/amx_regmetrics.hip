@@ -11,6 +11,7 @@
 
 #include "amx_device.h"
 #include "amx_launch.h"
+#include "amx_stream.h"
 
 // no fused multiply-add contraction: the determinant has the same bits whichever instantiation computes it (with or without the
 // statistics), and each product is rounded as the reference's fp32 arithmetic rounds it
@@ -19,7 +20,6 @@
 namespace amx {
 
 constexpr int kRmThreads = 256, kRmWaves = kRmThreads / 64;
-constexpr int kRmMaxBlocks = 2048;         // workgroups of the streaming launches (8 per CU): bounds the slab and a workgroup's share
 constexpr int kLovMaxBins = 1024;
 constexpr int kLovUnroll = 4;              // quads a thread loads before it counts any: the loads of a turn are all in flight together
 
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kRmThreads) void label_overlap_zero_kernel(unsigned
 }
 
 // Voxels [head, head + 4 nq) are read as quads (a + head and b + head are aligned for that), the `voxels - 4 nq` others one by
-// one.  The grid is min(what the work needs, kRmMaxBlocks), so a workgroup sees at most voxels / kRmMaxBlocks + 8192 voxels: with
+// one.  The grid is min(what the work needs, kStreamMaxBlocks), so a workgroup sees at most voxels / kStreamMaxBlocks + 8192 voxels: with
 // voxels < 2^40 that is below 2^30, and its 32-bit LDS counters cannot wrap before the one flush at the end.
 template <int LA, int LB>
 __global__ __launch_bounds__(kRmThreads) void label_overlap_kernel(const void* __restrict__ a, const void* __restrict__ b, long long head,
@@ -144,8 +144,7 @@ __global__ __launch_bounds__(kRmThreads) void label_overlap_kernel(const void* _
     if ((la | lb) < 0) ++bad;
     else lov_add(hist, la | (lb << 16), 1u);
   }
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) bad += __shfl_xor(bad, m, 64);
+  bad = wave_reduce_xor<SumOp>(bad);
   if (lane == 0) badred[wave] = bad;
   __syncthreads();
   if (tid == 0) {
@@ -194,7 +193,7 @@ hipError_t launch_label_overlap(const void* a, int lt_a, const void* b, int lt_b
   if (nq == 0) head = 0;
   const long long rest = voxels - 4 * nq, turns = (nq + kLovUnroll - 1) / kLovUnroll, units = turns > rest ? turns : rest;
   const long long need = (units + kRmThreads - 1) / kRmThreads;
-  const int grid = (int)(need < kRmMaxBlocks ? need : kRmMaxBlocks);
+  const int grid = (int)(need < kStreamMaxBlocks ? need : kStreamMaxBlocks);
   if (lt_a == RM_LABEL_F32) LOV_DISPATCH_B(RM_LABEL_F32);
   else if (lt_a == RM_LABEL_I64) LOV_DISPATCH_B(RM_LABEL_I64);
   else LOV_DISPATCH_B(RM_LABEL_U8);
@@ -362,11 +361,11 @@ static inline int jac_vpt(const float* u, int D) { return (D % 4 == 0 && ((uintp
 static inline int jac_blocks(const float* u, int H, int W, int D) {
   const int vpt = jac_vpt(u, D);
   const long long units = (long long)(H - 1) * (W - 1) * ((D - 1 + vpt - 1) / vpt), need = (units + kRmThreads - 1) / kRmThreads;
-  return (int)(need < kRmMaxBlocks ? need : kRmMaxBlocks);
+  return (int)(need < kStreamMaxBlocks ? need : kStreamMaxBlocks);
 }
 size_t jacobian_det_scratch_bytes(int H, int W, int D) {
   const long long need = ((long long)(H - 1) * (W - 1) * (D - 1) + kRmThreads - 1) / kRmThreads;       // covers both mappings
-  return (size_t)(need < kRmMaxBlocks ? need : kRmMaxBlocks) * kJacRec * sizeof(double);
+  return (size_t)(need < kStreamMaxBlocks ? need : kStreamMaxBlocks) * kJacRec * sizeof(double);
 }
 
 hipError_t launch_jacobian_det(const float* disp, int H, int W, int D, int add_identity, float* jdet, float* stats, void* scratch,

@@ -204,15 +204,13 @@ __global__ __launch_bounds__(256) void resize_trilinear_kernel(const float* __re
   }
 }
 
-static inline int cdiv_s(long long a, long long b) { return (int)((a + b - 1) / b); }
-static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static const CoupledCoef kCoef = {{0.003f, 0.01f, 0.03f, 0.1f, 0.3f, 1.f}};
 
 template <int V>
 static void launch_coupled_argmin_v(int J, const float* ssd, const float* hist, long long plane, int k, float* raw,
                                     long long* label, hipStream_t st) {
-  const int grid = cdiv_s(plane / V, 256);
+  const int grid = cdiv(plane / V, 256);
   switch (J) {
     case 0: coupled_argmin_kernel<0, V><<<grid, 256, 0, st>>>(ssd, hist, plane, k, kCoef, raw, label); break;
     case 1: coupled_argmin_kernel<1, V><<<grid, 256, 0, st>>>(ssd, hist, plane, k, kCoef, raw, label); break;
@@ -225,9 +223,9 @@ static void launch_coupled_argmin_v(int J, const float* ssd, const float* hist, 
 }
 
 // scratch of one step: the raw (pre-box) label field
-size_t coupled_step_scratch_bytes(int h, int w, int d) { return up256((size_t)3 * h * w * d * sizeof(float)); }
+size_t coupled_step_scratch_bytes(int h, int w, int d) { return align_up((size_t)3 * h * w * d * sizeof(float), 256); }
 // scratch of the whole solve: the raw field + the six soft fields s_0 .. s_5 that later iterations read
-size_t coupled_scratch_bytes(int h, int w, int d) { return coupled_step_scratch_bytes(h, w, d) + up256((size_t)18 * h * w * d * sizeof(float)); }
+size_t coupled_scratch_bytes(int h, int w, int d) { return coupled_step_scratch_bytes(h, w, d) + align_up((size_t)18 * h * w * d * sizeof(float), 256); }
 
 // iteration j (0 .. 6) from the j soft fields in hist: argmin + label gather, then box3 -> s_out.  Two launches.
 hipError_t launch_coupled_step(const float* ssd, const float* hist, int j, int h, int w, int d, int disp_hw, float* s_out,
@@ -248,7 +246,7 @@ hipError_t launch_coupled_convex(const float* ssd, const long long* argmin, int 
   float* hist = (float*)((char*)scratch + coupled_step_scratch_bytes(h, w, d));
   hipError_t e;
   if (argmin) {
-    mesh_gather_kernel<<<cdiv_s(plane, 256), 256, 0, st>>>(argmin, plane, k, raw);
+    mesh_gather_kernel<<<cdiv(plane, 256), 256, 0, st>>>(argmin, plane, k, raw);
     e = launch_box_filter(raw, hist, 3, h, w, d, 3, st);
   } else {
     e = launch_coupled_step(ssd, hist, 0, h, w, d, disp_hw, hist, nullptr, scratch, st);
@@ -258,7 +256,7 @@ hipError_t launch_coupled_convex(const float* ssd, const long long* argmin, int 
   return e;
 }
 
-size_t ic_scratch_bytes(int h, int w, int d) { return 2 * up256((size_t)3 * h * w * d * sizeof(float)); }
+size_t ic_scratch_bytes(int h, int w, int d) { return 2 * align_up((size_t)3 * h * w * d * sizeof(float), 256); }
 
 hipError_t launch_inverse_consistency(const float* f1, const float* f2, int h, int w, int d, int iterations, float* o1,
                                       float* o2, void* scratch, hipStream_t st) {
@@ -268,9 +266,9 @@ hipError_t launch_inverse_consistency(const float* f1, const float* f2, int h, i
     return e != hipSuccess ? e : hipMemcpyAsync(o2, f2, fb, hipMemcpyDeviceToDevice, st);
   }
   float* y1 = (float*)scratch;
-  float* y2 = (float*)((char*)scratch + up256(fb));
+  float* y2 = (float*)((char*)scratch + align_up(fb, 256));
   const float *a = f1, *b = f2;
-  const dim3 grid(cdiv_s((long long)h * w * d, 256), 2);
+  const dim3 grid(cdiv((long long)h * w * d, 256), 2);
   for (int t = 0; t < iterations; ++t) {
     const bool to_out = ((iterations - 1 - t) & 1) == 0;      // the last sweep lands in the outputs
     float* na = to_out ? o1 : y1;
@@ -286,7 +284,7 @@ hipError_t launch_resize_trilinear(const float* in, int C, int h, int w, int d, 
                                    const float* scale, int flip, hipStream_t st) {
   ResizeScale sc;
   for (int c = 0; c < kResizeMaxC; ++c) sc.v[c] = (scale && c < C) ? scale[c] : 1.f;
-  resize_trilinear_kernel<<<cdiv_s((long long)H * W * D, 256), 256, 0, st>>>(in, C, h, w, d, out, H, W, D, sc, flip);
+  resize_trilinear_kernel<<<cdiv((long long)H * W * D, 256), 256, 0, st>>>(in, C, h, w, d, out, H, W, D, sc, flip);
   return hipGetLastError();
 }
 
@@ -295,12 +293,12 @@ struct Stage1Layout {
   size_t ssd, corr, amin, coupled, s1, s2, n1, n2, i1, i2, ic, total;
 };
 static Stage1Layout stage1_layout(int h, int w, int d, int disp_hw, int ic) {
-  const size_t k = 2 * disp_hw + 1, plane = (size_t)h * w * d, field = up256(3 * plane * sizeof(float));
+  const size_t k = 2 * disp_hw + 1, plane = (size_t)h * w * d, field = align_up(3 * plane * sizeof(float), 256);
   Stage1Layout L;
   size_t o = 0;
-  L.ssd = o, o += up256(k * k * k * plane * sizeof(float));
-  L.corr = o, o += up256(correlate_scratch_bytes(h, w, d, disp_hw));
-  L.amin = o, o += up256(plane * sizeof(long long));
+  L.ssd = o, o += align_up(k * k * k * plane * sizeof(float), 256);
+  L.corr = o, o += align_up(correlate_scratch_bytes(h, w, d, disp_hw), 256);
+  L.amin = o, o += align_up(plane * sizeof(long long), 256);
   L.coupled = o, o += coupled_scratch_bytes(h, w, d);
   L.s1 = o, o += ic ? field : 0;
   L.s2 = o, o += ic ? field : 0;
@@ -334,8 +332,8 @@ hipError_t launch_stage1(const float* fix, const float* mov, int n_ch, int h, in
   // scale = (h - 1, w - 1, d - 1) / 2 per channel of disp_soft (instance_optimization.py:181-187)
   const Scale3 sc = {{(float)(h - 1) / 2.f, (float)(w - 1) / 2.f, (float)(d - 1) / 2.f}};
   float *n1 = (float*)(base + L.n1), *n2 = (float*)(base + L.n2), *i1 = (float*)(base + L.i1), *i2 = (float*)(base + L.i2);
-  field_normalize_kernel<<<cdiv_s(plane, 256), 256, 0, st>>>(s1, n1, plane, sc);
-  field_normalize_kernel<<<cdiv_s(plane, 256), 256, 0, st>>>(s2, n2, plane, sc);
+  field_normalize_kernel<<<cdiv(plane, 256), 256, 0, st>>>(s1, n1, plane, sc);
+  field_normalize_kernel<<<cdiv(plane, 256), 256, 0, st>>>(s2, n2, plane, sc);
   e = launch_inverse_consistency(n1, n2, h, w, d, 15, i1, i2, base + L.ic, st);
   if (e != hipSuccess) return e;
   const float up[3] = {sc.v[0] * (float)grid_sp, sc.v[1] * (float)grid_sp, sc.v[2] * (float)grid_sp};
@@ -365,8 +363,7 @@ int amx_coupled_convex(const float* d_ssd, const long long* d_argmin, int h, int
                        void* d_scratch, size_t scratch_bytes, void* stream) {
   if (!d_ssd || !d_disp_soft || !d_scratch) return fail(AMX_ERR_INVALID, "null argument");
   if (int rc = grid_check(h, w, d, disp_hw)) return rc;
-  if (scratch_bytes < amx::coupled_scratch_bytes(h, w, d))
-    return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", amx::coupled_scratch_bytes(h, w, d), scratch_bytes);
+  if (int rc = amx::need_scratch(amx::coupled_scratch_bytes(h, w, d), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_coupled_convex(d_ssd, d_argmin, h, w, d, disp_hw, d_disp_soft, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -380,8 +377,7 @@ int amx_coupled_convex_step(const float* d_ssd, const float* d_soft_hist, int j,
   if (!d_ssd || !d_soft_out || !d_scratch || (j > 0 && !d_soft_hist)) return fail(AMX_ERR_INVALID, "null argument");
   if (j < 0 || j > 6) return fail(AMX_ERR_INVALID, "iteration in [0, 6] (got %d)", j);
   if (int rc = grid_check(h, w, d, disp_hw)) return rc;
-  if (scratch_bytes < amx::coupled_step_scratch_bytes(h, w, d))
-    return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", amx::coupled_step_scratch_bytes(h, w, d), scratch_bytes);
+  if (int rc = amx::need_scratch(amx::coupled_step_scratch_bytes(h, w, d), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_coupled_step(d_ssd, d_soft_hist, j, h, w, d, disp_hw, d_soft_out, d_label, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -397,8 +393,7 @@ int amx_inverse_consistency(const float* d_field1, const float* d_field2, int h,
     return fail(AMX_ERR_INVALID, "outputs must be distinct from the inputs and from each other");
   if (h < 1 || w < 1 || d < 1) return fail(AMX_ERR_SHAPE, "non-positive shape (%d, %d, %d)", h, w, d);
   if (iterations < 0 || iterations > 10000) return fail(AMX_ERR_INVALID, "iterations in [0, 10000] (got %d)", iterations);
-  if (scratch_bytes < amx::ic_scratch_bytes(h, w, d))
-    return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", amx::ic_scratch_bytes(h, w, d), scratch_bytes);
+  if (int rc = amx::need_scratch(amx::ic_scratch_bytes(h, w, d), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_inverse_consistency(d_field1, d_field2, h, w, d, iterations, d_out1, d_out2, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -424,8 +419,7 @@ int amx_stage1_registration(const float* d_feat_fix, const float* d_feat_mov, in
   if (grid_sp < 1) return fail(AMX_ERR_INVALID, "grid_sp >= 1 (got %d)", grid_sp);
   if (ic && (H < 1 || W < 1 || D < 1)) return fail(AMX_ERR_SHAPE, "non-positive output shape (%d, %d, %d)", H, W, D);
   if (ic && (h < 2 || w < 2 || d < 2)) return fail(AMX_ERR_SHAPE, "inverse consistency needs a grid of at least 2 per axis");
-  const size_t need = amx::stage1_scratch_bytes(h, w, d, disp_hw, ic != 0);
-  if (scratch_bytes < need) return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, scratch_bytes);
+  if (int rc = amx::need_scratch(amx::stage1_scratch_bytes(h, w, d, disp_hw, ic != 0), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_stage1(d_feat_fix, d_feat_mov, n_ch, h, w, d, disp_hw, grid_sp, ic != 0, H, W, D, d_disp_out, d_scratch,
                              (hipStream_t)stream));
   return AMX_OK;

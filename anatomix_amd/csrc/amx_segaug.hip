@@ -13,124 +13,60 @@
 
 #include "amx_device.h"
 #include "amx_launch.h"
+#include "amx_stream.h"
 
 namespace amx {
 
-constexpr int kAugThreads = 256, kAugWaves = kAugThreads / 64, kAugVpt = 4, kAugTile = kAugThreads * kAugVpt;
-constexpr int kAugMaxBlocks = 2048;        // workgroups of a streaming launch (8 per CU): bounds the partial slab
+using Aug = StreamTile<>;                  // a thread owns four voxels of a tile of 1024 (amx_stream.h)
 constexpr int kAugMaxRadius = 4;
 using AugSample = amx_segaug_sample;
 
-template <bool VEC>
-__device__ __forceinline__ long long aug_voxel(int t, int j) {
-  return VEC ? (long long)t * kAugTile + threadIdx.x * kAugVpt + j : (long long)t * kAugTile + j * kAugThreads + threadIdx.x;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void aug_load4(const float* __restrict__ row, int t, long long V, float (&v)[kAugVpt]) {
-  if (VEC) {
-    const long long o = aug_voxel<true>(t, 0);
-    f32x4 q = {0.f, 0.f, 0.f, 0.f};
-    if (o < V) q = *(const f32x4*)(row + o);
-#pragma unroll
-    for (int j = 0; j < kAugVpt; ++j) v[j] = q[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < kAugVpt; ++j) {
-      const long long o = aug_voxel<false>(t, j);
-      v[j] = o < V ? row[o] : 0.f;
-    }
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void aug_store4(float* __restrict__ row, int t, long long V, const float (&v)[kAugVpt]) {
-  if (VEC) {
-    const long long o = aug_voxel<true>(t, 0);
-    if (o < V) *(f32x4*)(row + o) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-#pragma unroll
-    for (int j = 0; j < kAugVpt; ++j) {
-      const long long o = aug_voxel<false>(t, j);
-      if (o < V) row[o] = v[j];
-    }
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void aug_store4_u8(unsigned char* __restrict__ row, int t, long long V, const unsigned char (&v)[kAugVpt]) {
-  if (VEC) {
-    const long long o = aug_voxel<true>(t, 0);
-    if (o < V) *(uchar4*)(row + o) = make_uchar4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < kAugVpt; ++j) {
-      const long long o = aug_voxel<false>(t, j);
-      if (o < V) row[o] = v[j];
-    }
-  }
-}
-
 // ---- minimum and maximum --------------------------------------------------------------------------------------------------
-// {lo, hi} of the workgroup -> part[(n * gridDim.x + blockIdx.x) * 2]: per thread, wave (shuffles), workgroup (LDS).  Every
-// workgroup of a launch writes its pair, with (+inf, -inf) when it saw no voxel.
-__device__ __forceinline__ void aug_block_minmax(float lo, float hi, float* __restrict__ part) {
-  __shared__ float red[kAugWaves][2];
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) {
-    lo = fminf(lo, __shfl_xor(lo, m, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, m, 64));
-  }
+// {lo, hi} of the workgroup -> dst[2]: per thread, wave (shuffles), workgroup (LDS).  Every workgroup writes its pair, with
+// (+inf, -inf) when it saw no value.
+__device__ __forceinline__ void aug_block_minmax(float lo, float hi, float* __restrict__ dst) {
+  __shared__ float red[Aug::kWaves][2];
+  lo = wave_reduce_xor<MinOp>(lo);
+  hi = wave_reduce_xor<MaxOp>(hi);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (lane == 0) red[wave][0] = lo, red[wave][1] = hi;
   __syncthreads();
   if (threadIdx.x == 0) {
-    float* dst = part + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
     dst[0] = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
     dst[1] = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
   }
 }
+// the slab pair of this workgroup of a (chunks, B) grid
+__device__ __forceinline__ float* aug_part(float* __restrict__ part) { return part + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2; }
 
 template <bool VEC>
-__global__ __launch_bounds__(kAugThreads) void aug_minmax_kernel(const float* __restrict__ x, long long V, int ntiles, float* __restrict__ part) {
+__global__ __launch_bounds__(Aug::kThreads) void aug_minmax_kernel(const float* __restrict__ x, long long V, int ntiles, float* __restrict__ part) {
   const float* row = x + (long long)blockIdx.y * V;
   float lo = INFINITY, hi = -INFINITY;
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    float v[kAugVpt];
-    aug_load4<VEC>(row, t, V, v);
+    float v[Aug::kVpt];
+    Aug::load4<VEC>(row, t, V, v);
 #pragma unroll
-    for (int j = 0; j < kAugVpt; ++j)
-      if (aug_voxel<VEC>(t, j) < V) lo = fminf(lo, v[j]), hi = fmaxf(hi, v[j]);
+    for (int j = 0; j < Aug::kVpt; ++j)
+      if (Aug::voxel<VEC>(t, j) < V) lo = fminf(lo, v[j]), hi = fmaxf(hi, v[j]);
   }
-  aug_block_minmax(lo, hi, part);
+  aug_block_minmax(lo, hi, aug_part(part));
 }
 
 // grid (B): minmax[n] = {min, max} over the sample's nchunk partial pairs
-__global__ __launch_bounds__(kAugThreads) void aug_minmax_finalize_kernel(const float* __restrict__ part, int nchunk, float* __restrict__ minmax) {
-  __shared__ float red[kAugWaves][2];
+__global__ __launch_bounds__(Aug::kThreads) void aug_minmax_finalize_kernel(const float* __restrict__ part, int nchunk, float* __restrict__ minmax) {
   const int n = blockIdx.x;
   float lo = INFINITY, hi = -INFINITY;
-  for (int c = threadIdx.x; c < nchunk; c += kAugThreads) {
+  for (int c = threadIdx.x; c < nchunk; c += Aug::kThreads) {
     const float* p = part + ((long long)n * nchunk + c) * 2;
     lo = fminf(lo, p[0]), hi = fmaxf(hi, p[1]);
   }
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) {
-    lo = fminf(lo, __shfl_xor(lo, m, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, m, 64));
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) red[wave][0] = lo, red[wave][1] = hi;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    minmax[2 * n] = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
-    minmax[2 * n + 1] = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
-  }
+  aug_block_minmax(lo, hi, minmax + 2 * n);
 }
 
 // ---- ScaleIntensity / AdjustContrast ----------------------------------------------------------------------------------------
 template <bool VEC, int OP>
-__global__ __launch_bounds__(kAugThreads) void aug_pointwise_kernel(const float* in, float* out, long long V, int ntiles,
+__global__ __launch_bounds__(Aug::kThreads) void aug_pointwise_kernel(const float* in, float* out, long long V, int ntiles,
                                                                     const float* __restrict__ minmax, const AugSample* __restrict__ table) {
   const int n = blockIdx.y;
   const AugSample& s = table[n];
@@ -139,16 +75,16 @@ __global__ __launch_bounds__(kAugThreads) void aug_pointwise_kernel(const float*
   const float* src = in + (long long)n * V;
   float* dst = out + (long long)n * V;
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    float v[kAugVpt];
-    aug_load4<VEC>(src, t, V, v);
+    float v[Aug::kVpt];
+    Aug::load4<VEC>(src, t, V, v);
     if (on) {
 #pragma unroll
-      for (int j = 0; j < kAugVpt; ++j) {
+      for (int j = 0; j < Aug::kVpt; ++j) {
         if (OP == AMX_SEGAUG_OP_SCALE) v[j] = mn == mx ? v[j] * 0.f : (v[j] - mn) / range;
         else v[j] = powf((v[j] - mn) / (range + 1e-7f), gamma) * range + mn;
       }
     }
-    aug_store4<VEC>(dst, t, V, v);
+    Aug::store4<VEC>(dst, t, V, v);
   }
 }
 
@@ -166,7 +102,7 @@ __device__ __forceinline__ void aug_legendre(float x, float (&p)[4]) {
 }
 
 template <bool VEC, int LT>
-__global__ __launch_bounds__(kAugThreads) void aug_crop_kernel(AugDims g, const float* __restrict__ noise, float* __restrict__ img,
+__global__ __launch_bounds__(Aug::kThreads) void aug_crop_kernel(AugDims g, const float* __restrict__ noise, float* __restrict__ img,
                                                                unsigned char* __restrict__ lab, const AugSample* __restrict__ table) {
   const int n = blockIdx.y;
   const AugSample& s = table[n];
@@ -179,11 +115,11 @@ __global__ __launch_bounds__(kAugThreads) void aug_crop_kernel(AugDims g, const 
   for (int i = 0; i < 20; ++i) c[i] = s.bias[i];
   const long long base = (long long)n * g.V;
   for (int t = blockIdx.x; t < g.ntiles; t += gridDim.x) {
-    float v[kAugVpt];
-    unsigned char l[kAugVpt];
+    float v[Aug::kVpt];
+    unsigned char l[Aug::kVpt];
 #pragma unroll
-    for (int j = 0; j < kAugVpt; ++j) {
-      const long long o = aug_voxel<VEC>(t, j);
+    for (int j = 0; j < Aug::kVpt; ++j) {
+      const long long o = Aug::voxel<VEC>(t, j);
       v[j] = 0.f, l[j] = 0;
       if (o >= g.V) continue;
       const int x = (int)(o % g.w), y = (int)((o / g.w) % g.h), z = (int)(o / ((long long)g.w * g.h));
@@ -208,8 +144,8 @@ __global__ __launch_bounds__(kAugThreads) void aug_crop_kernel(AugDims g, const 
       }
       v[j] = a;
     }
-    aug_store4<VEC>(img + base, t, g.V, v);
-    aug_store4_u8<VEC>(lab + base, t, g.V, l);
+    Aug::store4<VEC>(img + base, t, g.V, v);
+    Aug::store4<VEC>(lab + base, t, g.V, l);
   }
 }
 
@@ -217,7 +153,7 @@ __global__ __launch_bounds__(kAugThreads) void aug_crop_kernel(AugDims g, const 
 // one axis of filter `filt` (0 smooth, 1 sharpen sigma1, 2 sharpen sigma2) for the samples with `bit` on, a copy for the others.
 // COMBINE (the last pass of the sharpening): out = b + alpha (b - pass).
 template <bool VEC, int AXIS, bool COMBINE>
-__global__ __launch_bounds__(kAugThreads) void aug_gauss_kernel(AugDims g, const float* __restrict__ in, float* __restrict__ out,
+__global__ __launch_bounds__(Aug::kThreads) void aug_gauss_kernel(AugDims g, const float* __restrict__ in, float* __restrict__ out,
                                                                 const float* __restrict__ b, int filt, int bit,
                                                                 const AugSample* __restrict__ table) {
   const int n = blockIdx.y;
@@ -234,13 +170,13 @@ __global__ __launch_bounds__(kAugThreads) void aug_gauss_kernel(AugDims g, const
   const long long stride = AXIS == 0 ? (long long)g.h * g.w : (AXIS == 1 ? g.w : 1);
   const float* src = in + base;
   for (int t = blockIdx.x; t < g.ntiles; t += gridDim.x) {
-    float v[kAugVpt];
+    float v[Aug::kVpt];
     if (!on) {
-      aug_load4<VEC>(src, t, g.V, v);
+      Aug::load4<VEC>(src, t, g.V, v);
     } else {
 #pragma unroll
-      for (int j = 0; j < kAugVpt; ++j) {
-        const long long o = aug_voxel<VEC>(t, j);
+      for (int j = 0; j < Aug::kVpt; ++j) {
+        const long long o = Aug::voxel<VEC>(t, j);
         v[j] = 0.f;
         if (o >= g.V) continue;
         const int cpos = (int)((o / stride) % len);
@@ -257,7 +193,7 @@ __global__ __launch_bounds__(kAugThreads) void aug_gauss_kernel(AugDims g, const
         v[j] = acc;
       }
     }
-    aug_store4<VEC>(out + base, t, g.V, v);
+    Aug::store4<VEC>(out + base, t, g.V, v);
   }
 }
 
@@ -268,7 +204,7 @@ struct AugAffineArgs {
 };
 
 template <bool VEC>
-__global__ __launch_bounds__(kAugThreads) void aug_affine_kernel(AugDims g, AugAffineArgs a, const float* __restrict__ img_in,
+__global__ __launch_bounds__(Aug::kThreads) void aug_affine_kernel(AugDims g, AugAffineArgs a, const float* __restrict__ img_in,
                                                                  const unsigned char* __restrict__ lab_in, float* __restrict__ img_out,
                                                                  unsigned char* __restrict__ lab_out, const AugSample* __restrict__ table,
                                                                  float* __restrict__ part) {
@@ -284,11 +220,11 @@ __global__ __launch_bounds__(kAugThreads) void aug_affine_kernel(AugDims g, AugA
   const long long base = (long long)n * g.V;
   float lo = INFINITY, hi = -INFINITY;
   for (int t = blockIdx.x; t < g.ntiles; t += gridDim.x) {
-    float v[kAugVpt];
-    unsigned char l[kAugVpt];
+    float v[Aug::kVpt];
+    unsigned char l[Aug::kVpt];
 #pragma unroll
-    for (int j = 0; j < kAugVpt; ++j) {
-      const long long o = aug_voxel<VEC>(t, j);
+    for (int j = 0; j < Aug::kVpt; ++j) {
+      const long long o = Aug::voxel<VEC>(t, j);
       v[j] = 0.f, l[j] = 0;
       if (o >= g.V) continue;
       const float px = (float)(int)(o % g.w) - ox, py = (float)(int)((o / g.w) % g.h) - oy, pz = (float)(int)(o / ((long long)g.w * g.h)) - oz;
@@ -317,37 +253,30 @@ __global__ __launch_bounds__(kAugThreads) void aug_affine_kernel(AugDims g, AugA
       }
       lo = fminf(lo, v[j]), hi = fmaxf(hi, v[j]);
     }
-    aug_store4<VEC>(img_out + base, t, g.V, v);
-    aug_store4_u8<VEC>(lab_out + base, t, g.V, l);
+    Aug::store4<VEC>(img_out + base, t, g.V, v);
+    Aug::store4<VEC>(lab_out + base, t, g.V, l);
   }
-  aug_block_minmax(lo, hi, part);
+  aug_block_minmax(lo, hi, aug_part(part));
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------
-static inline long long aug_tiles(long long V) { return (V + kAugTile - 1) / kAugTile; }
-static inline int aug_chunks(int n, long long V) {
-  const long long cap = kAugMaxBlocks / n > 1 ? kAugMaxBlocks / n : 1, t = aug_tiles(V);
-  return (int)(t < cap ? t : cap);
-}
-static inline bool aug_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static inline bool aug_al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 static AugDims aug_dims(int d, int h, int w) {
   AugDims g;
-  g.d = d, g.h = h, g.w = w, g.V = (long long)d * h * w, g.ntiles = (int)aug_tiles(g.V);
+  g.d = d, g.h = h, g.w = w, g.V = (long long)d * h * w, g.ntiles = (int)Aug::tiles(g.V);
   return g;
 }
 
-size_t segaug_scratch_bytes(int n, long long V) { return (size_t)n * aug_chunks(n, V) * 2 * sizeof(float); }
+size_t segaug_scratch_bytes(int n, long long V) { return (size_t)n * Aug::chunks(n, V) * 2 * sizeof(float); }
 
 hipError_t launch_segaug_minmax_finalize(const void* scratch, int n, long long V, float* minmax, hipStream_t st) {
-  aug_minmax_finalize_kernel<<<n, kAugThreads, 0, st>>>((const float*)scratch, aug_chunks(n, V), minmax);
+  aug_minmax_finalize_kernel<<<n, Aug::kThreads, 0, st>>>((const float*)scratch, Aug::chunks(n, V), minmax);
   return hipGetLastError();
 }
 
 hipError_t launch_segaug_minmax(const float* x, int n, long long V, float* minmax, void* scratch, hipStream_t st) {
-  const dim3 grid(aug_chunks(n, V), n);
-  if (V % 4 == 0 && aug_al16(x)) aug_minmax_kernel<true><<<grid, kAugThreads, 0, st>>>(x, V, (int)aug_tiles(V), (float*)scratch);
-  else aug_minmax_kernel<false><<<grid, kAugThreads, 0, st>>>(x, V, (int)aug_tiles(V), (float*)scratch);
+  const dim3 grid(Aug::chunks(n, V), n);
+  if (V % 4 == 0 && aligned16(x)) aug_minmax_kernel<true><<<grid, Aug::kThreads, 0, st>>>(x, V, (int)Aug::tiles(V), (float*)scratch);
+  else aug_minmax_kernel<false><<<grid, Aug::kThreads, 0, st>>>(x, V, (int)Aug::tiles(V), (float*)scratch);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return launch_segaug_minmax_finalize(scratch, n, V, minmax, st);
@@ -355,15 +284,15 @@ hipError_t launch_segaug_minmax(const float* x, int n, long long V, float* minma
 
 hipError_t launch_segaug_pointwise(const float* in, float* out, int n, long long V, const float* minmax, int op, const AugSample* table,
                                    hipStream_t st) {
-  const dim3 grid(aug_chunks(n, V), n);
-  const bool vec = V % 4 == 0 && aug_al16(in) && aug_al16(out);
-  const int nt = (int)aug_tiles(V);
+  const dim3 grid(Aug::chunks(n, V), n);
+  const bool vec = V % 4 == 0 && aligned16(in) && aligned16(out);
+  const int nt = (int)Aug::tiles(V);
   if (op == AMX_SEGAUG_OP_SCALE) {
-    if (vec) aug_pointwise_kernel<true, AMX_SEGAUG_OP_SCALE><<<grid, kAugThreads, 0, st>>>(in, out, V, nt, minmax, table);
-    else aug_pointwise_kernel<false, AMX_SEGAUG_OP_SCALE><<<grid, kAugThreads, 0, st>>>(in, out, V, nt, minmax, table);
+    if (vec) aug_pointwise_kernel<true, AMX_SEGAUG_OP_SCALE><<<grid, Aug::kThreads, 0, st>>>(in, out, V, nt, minmax, table);
+    else aug_pointwise_kernel<false, AMX_SEGAUG_OP_SCALE><<<grid, Aug::kThreads, 0, st>>>(in, out, V, nt, minmax, table);
   } else {
-    if (vec) aug_pointwise_kernel<true, AMX_SEGAUG_OP_CONTRAST><<<grid, kAugThreads, 0, st>>>(in, out, V, nt, minmax, table);
-    else aug_pointwise_kernel<false, AMX_SEGAUG_OP_CONTRAST><<<grid, kAugThreads, 0, st>>>(in, out, V, nt, minmax, table);
+    if (vec) aug_pointwise_kernel<true, AMX_SEGAUG_OP_CONTRAST><<<grid, Aug::kThreads, 0, st>>>(in, out, V, nt, minmax, table);
+    else aug_pointwise_kernel<false, AMX_SEGAUG_OP_CONTRAST><<<grid, Aug::kThreads, 0, st>>>(in, out, V, nt, minmax, table);
   }
   return hipGetLastError();
 }
@@ -371,14 +300,14 @@ hipError_t launch_segaug_pointwise(const float* in, float* out, int n, long long
 hipError_t launch_segaug_crop(int n, int d, int h, int w, const float* noise, int lt, float* img, unsigned char* lab, const AugSample* table,
                               hipStream_t st) {
   const AugDims g = aug_dims(d, h, w);
-  const dim3 grid(aug_chunks(n, g.V), n);
-  const bool vec = g.V % 4 == 0 && aug_al16(img) && aug_al4(lab);
+  const dim3 grid(Aug::chunks(n, g.V), n);
+  const bool vec = g.V % 4 == 0 && aligned16(img) && aligned4(lab);
   if (lt == AMX_SEG_LABEL_F32) {
-    if (vec) aug_crop_kernel<true, AMX_SEG_LABEL_F32><<<grid, kAugThreads, 0, st>>>(g, noise, img, lab, table);
-    else aug_crop_kernel<false, AMX_SEG_LABEL_F32><<<grid, kAugThreads, 0, st>>>(g, noise, img, lab, table);
+    if (vec) aug_crop_kernel<true, AMX_SEG_LABEL_F32><<<grid, Aug::kThreads, 0, st>>>(g, noise, img, lab, table);
+    else aug_crop_kernel<false, AMX_SEG_LABEL_F32><<<grid, Aug::kThreads, 0, st>>>(g, noise, img, lab, table);
   } else {
-    if (vec) aug_crop_kernel<true, AMX_SEG_LABEL_U8><<<grid, kAugThreads, 0, st>>>(g, noise, img, lab, table);
-    else aug_crop_kernel<false, AMX_SEG_LABEL_U8><<<grid, kAugThreads, 0, st>>>(g, noise, img, lab, table);
+    if (vec) aug_crop_kernel<true, AMX_SEG_LABEL_U8><<<grid, Aug::kThreads, 0, st>>>(g, noise, img, lab, table);
+    else aug_crop_kernel<false, AMX_SEG_LABEL_U8><<<grid, Aug::kThreads, 0, st>>>(g, noise, img, lab, table);
   }
   return hipGetLastError();
 }
@@ -386,10 +315,10 @@ hipError_t launch_segaug_crop(int n, int d, int h, int w, const float* noise, in
 template <int AXIS, bool COMBINE>
 static hipError_t aug_gauss_pass(const AugDims& g, int n, const float* in, float* out, const float* b, int filt, int bit,
                                  const AugSample* table, hipStream_t st) {
-  const dim3 grid(aug_chunks(n, g.V), n);
-  const bool vec = g.V % 4 == 0 && aug_al16(in) && aug_al16(out);
-  if (vec) aug_gauss_kernel<true, AXIS, COMBINE><<<grid, kAugThreads, 0, st>>>(g, in, out, b, filt, bit, table);
-  else aug_gauss_kernel<false, AXIS, COMBINE><<<grid, kAugThreads, 0, st>>>(g, in, out, b, filt, bit, table);
+  const dim3 grid(Aug::chunks(n, g.V), n);
+  const bool vec = g.V % 4 == 0 && aligned16(in) && aligned16(out);
+  if (vec) aug_gauss_kernel<true, AXIS, COMBINE><<<grid, Aug::kThreads, 0, st>>>(g, in, out, b, filt, bit, table);
+  else aug_gauss_kernel<false, AXIS, COMBINE><<<grid, Aug::kThreads, 0, st>>>(g, in, out, b, filt, bit, table);
   return hipGetLastError();
 }
 
@@ -417,10 +346,10 @@ hipError_t launch_segaug_affine(const float* img_in, const unsigned char* lab_in
   const AugDims g = aug_dims(d, h, w);
   AugAffineArgs a;
   a.di = di, a.hi = hi, a.wi = wi, a.Vi = (long long)di * hi * wi;
-  const dim3 grid(aug_chunks(n, g.V), n);
-  if (g.V % 4 == 0 && aug_al16(img_out) && aug_al4(lab_out))
-    aug_affine_kernel<true><<<grid, kAugThreads, 0, st>>>(g, a, img_in, lab_in, img_out, lab_out, table, (float*)scratch);
-  else aug_affine_kernel<false><<<grid, kAugThreads, 0, st>>>(g, a, img_in, lab_in, img_out, lab_out, table, (float*)scratch);
+  const dim3 grid(Aug::chunks(n, g.V), n);
+  if (g.V % 4 == 0 && aligned16(img_out) && aligned4(lab_out))
+    aug_affine_kernel<true><<<grid, Aug::kThreads, 0, st>>>(g, a, img_in, lab_in, img_out, lab_out, table, (float*)scratch);
+  else aug_affine_kernel<false><<<grid, Aug::kThreads, 0, st>>>(g, a, img_in, lab_in, img_out, lab_out, table, (float*)scratch);
   return hipGetLastError();
 }
 
@@ -462,8 +391,7 @@ size_t amx_segaug_scratch_bytes(int n, long long voxels) {
 int amx_segaug_minmax(const float* d_x, int n, long long voxels, float* d_minmax, void* d_scratch, size_t scratch_bytes, void* stream) {
   if (int rc = aug_check_batch(n, voxels)) return rc;
   if (!d_x || !d_minmax || !d_scratch) return fail(AMX_ERR_INVALID, "null input, output or scratch");
-  const size_t need = amx::segaug_scratch_bytes(n, voxels);
-  if (scratch_bytes < need) return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, scratch_bytes);
+  if (int rc = amx::need_scratch(amx::segaug_scratch_bytes(n, voxels), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_segaug_minmax(d_x, n, voxels, d_minmax, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -471,8 +399,7 @@ int amx_segaug_minmax(const float* d_x, int n, long long voxels, float* d_minmax
 int amx_segaug_minmax_finalize(const void* d_scratch, size_t scratch_bytes, int n, long long voxels, float* d_minmax, void* stream) {
   if (int rc = aug_check_batch(n, voxels)) return rc;
   if (!d_minmax || !d_scratch) return fail(AMX_ERR_INVALID, "null output or scratch");
-  const size_t need = amx::segaug_scratch_bytes(n, voxels);
-  if (scratch_bytes < need) return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, scratch_bytes);
+  if (int rc = amx::need_scratch(amx::segaug_scratch_bytes(n, voxels), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_segaug_minmax_finalize(d_scratch, n, voxels, d_minmax, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -554,8 +481,7 @@ int amx_segaug_affine(const float* d_img_in, const unsigned char* d_lab_in, int 
   const size_t vin = (size_t)n * di * hi * wi, vout = (size_t)n * d * h * w;
   if (aug_overlap(d_img_in, vin * 4, d_img_out, vout * 4) || aug_overlap(d_lab_in, vin, d_lab_out, vout))
     return fail(AMX_ERR_INVALID, "inputs and outputs must not overlap");
-  const size_t need = amx::segaug_scratch_bytes(n, (long long)d * h * w);
-  if (scratch_bytes < need) return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, scratch_bytes);
+  if (int rc = amx::need_scratch(amx::segaug_scratch_bytes(n, (long long)d * h * w), scratch_bytes)) return rc;
   for (int i = 0; i < n; ++i)
     for (int q = 0; q < 9; ++q)
       if (!aug_finite(h_table[i].affine[q])) return fail(AMX_ERR_INVALID, "sample %d: affine entry %d is not finite", i, q);

@@ -12,12 +12,12 @@
 
 #include "amx_device.h"
 #include "amx_launch.h"
+#include "amx_stream.h"
 
 namespace amx {
 
-constexpr int kSegThreads = 256, kSegWaves = kSegThreads / 64, kSegVpt = 4, kSegTile = kSegThreads * kSegVpt;
+using Seg = StreamTile<>;                  // a thread owns four voxels of a tile of 1024 (amx_stream.h)
 constexpr int kSegMaxF = 64, kSegMaxC = 32;
-constexpr int kSegMaxBlocks = 2048;        // workgroups of the streaming launches (8 per CU): bounds the slabs
 
 enum { SEG_LABEL_F32 = 0, SEG_LABEL_I64 = 1, SEG_LABEL_U8 = 2 };
 
@@ -43,90 +43,52 @@ struct SegArgs {
   const void* labels;     // [B][V]
   int F, C;
   long long V;
-  int ntiles;             // ceil(V / kSegTile)
+  int ntiles;             // ceil(V / Seg::kTile)
 };
-
-// voxel j of this thread in tile t: four consecutive voxels behind one 16-byte access (VEC: V % 4 == 0 and 16-byte aligned bases,
-// so a quad is inside the row or outside it as a whole), otherwise four voxels 256 apart read one by one (coalesced across lanes)
-template <bool VEC>
-__device__ __forceinline__ long long seg_voxel(int t, int j) {
-  return VEC ? (long long)t * kSegTile + threadIdx.x * kSegVpt + j : (long long)t * kSegTile + j * kSegThreads + threadIdx.x;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void seg_load4(const float* __restrict__ row, int t, long long V, float (&v)[kSegVpt]) {
-  if (VEC) {
-    const long long o = seg_voxel<true>(t, 0);
-    f32x4 q = {0.f, 0.f, 0.f, 0.f};
-    if (o < V) q = *(const f32x4*)(row + o);
-#pragma unroll
-    for (int j = 0; j < kSegVpt; ++j) v[j] = q[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < kSegVpt; ++j) {
-      const long long o = seg_voxel<false>(t, j);
-      v[j] = o < V ? row[o] : 0.f;
-    }
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void seg_store4(float* __restrict__ row, int t, long long V, const float (&v)[kSegVpt]) {
-  if (VEC) {
-    const long long o = seg_voxel<true>(t, 0);
-    if (o < V) *(f32x4*)(row + o) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-#pragma unroll
-    for (int j = 0; j < kSegVpt; ++j) {
-      const long long o = seg_voxel<false>(t, j);
-      if (o < V) row[o] = v[j];
-    }
-  }
-}
 
 // head weights transposed and padded into LDS: wT[f][CP] (rows of padded classes zero), bias[CP]
 template <int CP>
 __device__ __forceinline__ void seg_stage_head(const SegArgs& a, float* __restrict__ wT, float* __restrict__ bias) {
-  for (int i = threadIdx.x; i < a.F * CP; i += kSegThreads) {
+  for (int i = threadIdx.x; i < a.F * CP; i += Seg::kThreads) {
     const int f = i / CP, c = i % CP;
     wT[i] = c < a.C ? a.w[c * a.F + f] : 0.f;
   }
-  for (int c = threadIdx.x; c < CP; c += kSegThreads) bias[c] = (c < a.C && a.b) ? a.b[c] : 0.f;
+  for (int c = threadIdx.x; c < CP; c += Seg::kThreads) bias[c] = (c < a.C && a.b) ? a.b[c] : 0.f;
 }
 
 // logits of the thread's four voxels of sample n, tile t; padded classes get -inf (softmax 0)
 template <int CP, bool HEAD, bool VEC>
 __device__ __forceinline__ void seg_logits(const SegArgs& a, int n, int t, const float* __restrict__ wT, const float* __restrict__ bias,
-                                           float (&z)[CP][kSegVpt]) {
+                                           float (&z)[CP][Seg::kVpt]) {
   if (HEAD) {
 #pragma unroll
     for (int c = 0; c < CP; ++c)
 #pragma unroll
-      for (int j = 0; j < kSegVpt; ++j) z[c][j] = bias[c];
+      for (int j = 0; j < Seg::kVpt; ++j) z[c][j] = bias[c];
     const float* row = a.in + (long long)n * a.F * a.V;
     for (int f = 0; f < a.F; ++f, row += a.V) {
-      float x[kSegVpt];
-      seg_load4<VEC>(row, t, a.V, x);
+      float x[Seg::kVpt];
+      Seg::load4<VEC>(row, t, a.V, x);
 #pragma unroll
       for (int c = 0; c < CP; ++c) {
         const float wc = wT[f * CP + c];
 #pragma unroll
-        for (int j = 0; j < kSegVpt; ++j) z[c][j] += wc * x[j];
+        for (int j = 0; j < Seg::kVpt; ++j) z[c][j] += wc * x[j];
       }
     }
 #pragma unroll
     for (int c = 0; c < CP; ++c)
       if (c >= a.C)
 #pragma unroll
-        for (int j = 0; j < kSegVpt; ++j) z[c][j] = -INFINITY;
+        for (int j = 0; j < Seg::kVpt; ++j) z[c][j] = -INFINITY;
   } else {
 #pragma unroll
     for (int c = 0; c < CP; ++c) {
       if (c < a.C) {
-        seg_load4<VEC>(a.in + ((long long)n * a.C + c) * a.V, t, a.V, z[c]);
+        Seg::load4<VEC>(a.in + ((long long)n * a.C + c) * a.V, t, a.V, z[c]);
       } else {
 #pragma unroll
-        for (int j = 0; j < kSegVpt; ++j) z[c][j] = -INFINITY;
+        for (int j = 0; j < Seg::kVpt; ++j) z[c][j] = -INFINITY;
       }
     }
   }
@@ -134,7 +96,7 @@ __device__ __forceinline__ void seg_logits(const SegArgs& a, int n, int t, const
 
 // softmax over the classes of one voxel, the maximum subtracted; returns log(sum exp(z - max)) and the maximum
 template <int CP>
-__device__ __forceinline__ void seg_softmax(const float (&z)[CP][kSegVpt], int j, float (&p)[CP], float& m, float& s) {
+__device__ __forceinline__ void seg_softmax(const float (&z)[CP][Seg::kVpt], int j, float (&p)[CP], float& m, float& s) {
   m = z[0][j];
 #pragma unroll
   for (int c = 1; c < CP; ++c) m = fmaxf(m, z[c][j]);
@@ -147,13 +109,6 @@ __device__ __forceinline__ void seg_softmax(const float (&z)[CP][kSegVpt], int j
   const float inv = 1.f / s;
 #pragma unroll
   for (int c = 0; c < CP; ++c) p[c] *= inv;
-}
-
-// sum over the 64 lanes of a wave in a fixed order (every lane gets the result)
-__device__ __forceinline__ float seg_wave_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
 }
 
 // Wave sums of N values per lane with about N + 6 shuffles instead of 6 N: step k halves the array, a lane keeping the half its
@@ -188,10 +143,10 @@ __device__ __forceinline__ int seg_rs_index(int lane) {
 // grid (nchunk, B).  One partial row per workgroup: part[(n * nchunk + chunk) * (3 C + 1)] = {I_c, P_c, G_c} per class, then the
 // cross-entropy sum; badpart[n * nchunk + chunk] = labels outside [0, C).
 template <int CP, bool HEAD, int LT, bool VEC>
-__global__ __launch_bounds__(kSegThreads) void seg_stats_kernel(SegArgs a, int do_ce, float* __restrict__ part, int* __restrict__ badpart) {
+__global__ __launch_bounds__(Seg::kThreads) void seg_stats_kernel(SegArgs a, int do_ce, float* __restrict__ part, int* __restrict__ badpart) {
   __shared__ float wT[HEAD ? kSegMaxF * CP : 1], bias[CP];
-  __shared__ float red[kSegWaves][3 * CP + 1];
-  __shared__ int redbad[kSegWaves];
+  __shared__ float red[Seg::kWaves][3 * CP + 1];
+  __shared__ int redbad[Seg::kWaves];
   if (HEAD) {
     seg_stage_head<CP>(a, wT, bias);
     __syncthreads();
@@ -202,11 +157,11 @@ __global__ __launch_bounds__(kSegThreads) void seg_stats_kernel(SegArgs a, int d
 #pragma unroll
   for (int c = 0; c < CP; ++c) aI[c] = aP[c] = aG[c] = 0.f;
   for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
-    float z[CP][kSegVpt];
+    float z[CP][Seg::kVpt];
     seg_logits<CP, HEAD, VEC>(a, n, t, wT, bias, z);
 #pragma unroll
-    for (int j = 0; j < kSegVpt; ++j) {
-      const long long o = seg_voxel<VEC>(t, j);
+    for (int j = 0; j < Seg::kVpt; ++j) {
+      const long long o = Seg::voxel<VEC>(t, j);
       if (o >= a.V) continue;
       const int lab = seg_label<LT>(a.labels, (long long)n * a.V + o, a.C);
       float p[CP], m, s;
@@ -227,16 +182,15 @@ __global__ __launch_bounds__(kSegThreads) void seg_stats_kernel(SegArgs a, int d
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int c = 0; c < CP; ++c) {
-    const float i = seg_wave_sum(aI[c]), p = seg_wave_sum(aP[c]), g = seg_wave_sum(aG[c]);
+    const float i = wave_reduce_xor<SumOp>(aI[c]), p = wave_reduce_xor<SumOp>(aP[c]), g = wave_reduce_xor<SumOp>(aG[c]);
     if (lane == 0) red[wave][3 * c] = i, red[wave][3 * c + 1] = p, red[wave][3 * c + 2] = g;
   }
-  ce = seg_wave_sum(ce);
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) bad += __shfl_xor(bad, m, 64);
+  ce = wave_reduce_xor<SumOp>(ce);
+  bad = wave_reduce_xor<SumOp>(bad);
   if (lane == 0) red[wave][3 * CP] = ce, redbad[wave] = bad;
   __syncthreads();
   const long long blk = (long long)n * gridDim.x + blockIdx.x;
-  for (int k = threadIdx.x; k <= 3 * a.C; k += kSegThreads) {
+  for (int k = threadIdx.x; k <= 3 * a.C; k += Seg::kThreads) {
     const int src = k == 3 * a.C ? 3 * CP : k;
     part[blk * (3 * a.C + 1) + k] = ((red[0][src] + red[1][src]) + red[2][src]) + red[3][src];
   }
@@ -247,25 +201,6 @@ struct SegLossCoef {
   int B, C, nchunk, first_class;          // first_class: 1 when the background is excluded from the Dice term
   double smooth_nr, smooth_dr, lambda_dice, lambda_ce, inv_bv;
 };
-
-template <int T>
-__device__ __forceinline__ double seg_block_sum_f64(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ double seg_wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // one workgroup of 16 waves: stats[B][C][3] = the slab's rows added in a fixed order in double (a wave per value, lane l taking
 // chunks l, l + 64, ...), then loss[3] = {total, dice, ce} from the stored (fp32) statistics, which are what the backward reads;
@@ -281,22 +216,22 @@ __global__ __launch_bounds__(kSegFinThreads) void seg_loss_finalize_kernel(const
     const int n = o / row, q = o % row;
     double s = 0.0;
     for (int ch = lane; ch < k.nchunk; ch += 64) s += (double)part[((long long)n * k.nchunk + ch) * row + q];
-    s = seg_wave_sum_f64(s);
+    s = wave_reduce_xor<SumOp>(s);
     if (lane == 0) {
       if (q == 3 * k.C) ce += s;
       else stats[(long long)n * 3 * k.C + q] = (float)s;
     }
   }
   for (int o = threadIdx.x; o < k.B * k.nchunk; o += kSegFinThreads) bad += (double)badpart[o];
-  ce = seg_block_sum_f64<kSegFinThreads>(ce, red);
-  bad = seg_block_sum_f64<kSegFinThreads>(bad, red);      // (its barriers also order the stats stores above before the reads below)
+  ce = block_tree_sum<double, kSegFinThreads>(ce, red);
+  bad = block_tree_sum<double, kSegFinThreads>(bad, red);      // (its barriers also order the stats stores above before the reads below)
   double dice = 0.0;
   for (int o = threadIdx.x; o < k.B * k.C; o += kSegFinThreads) {
     if (o % k.C < k.first_class) continue;
     const double I = stats[3LL * o], P = stats[3LL * o + 1], G = stats[3LL * o + 2];
     dice += 1.0 - (2.0 * I + k.smooth_nr) / (G + P + k.smooth_dr);
   }
-  dice = seg_block_sum_f64<kSegFinThreads>(dice, red);
+  dice = block_tree_sum<double, kSegFinThreads>(dice, red);
   if (threadIdx.x == 0) {
     const double dm = dice / ((double)k.B * (k.C - k.first_class)), cm = ce * k.inv_bv;
     const float nanv = __int_as_float(0x7fc00000);
@@ -321,17 +256,17 @@ struct SegBwdCoef {
 };
 
 template <int CP, bool HEAD, int LT, bool VEC>
-__global__ __launch_bounds__(kSegThreads) void seg_backward_kernel(SegArgs a, SegBwdCoef k, const float* __restrict__ stats,
+__global__ __launch_bounds__(Seg::kThreads) void seg_backward_kernel(SegArgs a, SegBwdCoef k, const float* __restrict__ stats,
                                                                    const float* __restrict__ gout, float* __restrict__ dout,
                                                                    float* __restrict__ part) {
   __shared__ float wT[HEAD ? kSegMaxF * CP : 1], bias[CP], alpha[CP], beta[CP];
-  __shared__ float accW[HEAD ? kSegWaves * kSegMaxF * CP : 1], accB[HEAD ? kSegWaves * CP : 1];
+  __shared__ float accW[HEAD ? Seg::kWaves * kSegMaxF * CP : 1], accB[HEAD ? Seg::kWaves * CP : 1];
   const int n = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float g0 = *gout;
   if (HEAD) {
     seg_stage_head<CP>(a, wT, bias);
-    for (int i = threadIdx.x; i < kSegWaves * a.F * CP; i += kSegThreads) accW[i] = 0.f;
-    for (int i = threadIdx.x; i < kSegWaves * CP; i += kSegThreads) accB[i] = 0.f;
+    for (int i = threadIdx.x; i < Seg::kWaves * a.F * CP; i += Seg::kThreads) accW[i] = 0.f;
+    for (int i = threadIdx.x; i < Seg::kWaves * CP; i += Seg::kThreads) accB[i] = 0.f;
   }
   if ((int)threadIdx.x < CP) {
     const int c = threadIdx.x;
@@ -348,11 +283,11 @@ __global__ __launch_bounds__(kSegThreads) void seg_backward_kernel(SegArgs a, Se
   __syncthreads();
   const float cs = g0 * k.ce_scale;
   for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
-    float z[CP][kSegVpt];                 // logits, then d loss / d logits in place
+    float z[CP][Seg::kVpt];                 // logits, then d loss / d logits in place
     seg_logits<CP, HEAD, VEC>(a, n, t, wT, bias, z);
 #pragma unroll
-    for (int j = 0; j < kSegVpt; ++j) {
-      const long long o = seg_voxel<VEC>(t, j);
+    for (int j = 0; j < Seg::kVpt; ++j) {
+      const long long o = Seg::voxel<VEC>(t, j);
       if (o >= a.V) {
 #pragma unroll
         for (int c = 0; c < CP; ++c) z[c][j] = 0.f;
@@ -373,7 +308,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_backward_kernel(SegArgs a, Se
     if (!HEAD) {
 #pragma unroll
       for (int c = 0; c < CP; ++c)
-        if (c < a.C) seg_store4<VEC>(dout + ((long long)n * a.C + c) * a.V, t, a.V, z[c]);
+        if (c < a.C) Seg::store4<VEC>(dout + ((long long)n * a.C + c) * a.V, t, a.V, z[c]);
       continue;
     }
     {
@@ -386,16 +321,16 @@ __global__ __launch_bounds__(kSegThreads) void seg_backward_kernel(SegArgs a, Se
     const float* row = a.in + (long long)n * a.F * a.V;
     float* drow = dout + (long long)n * a.F * a.V;
     for (int f = 0; f < a.F; ++f, row += a.V, drow += a.V) {
-      float x[kSegVpt], dx[kSegVpt] = {0.f, 0.f, 0.f, 0.f}, v[CP];
-      seg_load4<VEC>(row, t, a.V, x);
+      float x[Seg::kVpt], dx[Seg::kVpt] = {0.f, 0.f, 0.f, 0.f}, v[CP];
+      Seg::load4<VEC>(row, t, a.V, x);
 #pragma unroll
       for (int c = 0; c < CP; ++c) {
         const float wc = wT[f * CP + c];
 #pragma unroll
-        for (int j = 0; j < kSegVpt; ++j) dx[j] += wc * z[c][j];
+        for (int j = 0; j < Seg::kVpt; ++j) dx[j] += wc * z[c][j];
         v[c] = (z[c][0] * x[0] + z[c][1] * x[1]) + (z[c][2] * x[2] + z[c][3] * x[3]);
       }
-      seg_store4<VEC>(drow, t, a.V, dx);
+      Seg::store4<VEC>(drow, t, a.V, dx);
       const float r = seg_reduce_scatter<CP>(v);
       if (lane < CP) accW[(wave * a.F + f) * CP + seg_rs_index<CP>(lane)] += r;
     }
@@ -404,7 +339,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_backward_kernel(SegArgs a, Se
   __syncthreads();
   const int row = a.C * a.F + a.C;
   float* dst = part + ((long long)n * gridDim.x + blockIdx.x) * row;
-  for (int i = threadIdx.x; i < row; i += kSegThreads) {
+  for (int i = threadIdx.x; i < row; i += Seg::kThreads) {
     float s;
     if (i < a.C * a.F) {
       const int c = i / a.F, f = i % a.F;
@@ -420,13 +355,13 @@ __global__ __launch_bounds__(kSegThreads) void seg_backward_kernel(SegArgs a, Se
 }
 
 // grid (C F + C): value o of every partial row added in row order (double) -> dW [C][F] then db [C]
-__global__ __launch_bounds__(kSegThreads) void seg_backward_finalize_kernel(const float* __restrict__ part, int nrows, int row, int cf,
+__global__ __launch_bounds__(Seg::kThreads) void seg_backward_finalize_kernel(const float* __restrict__ part, int nrows, int row, int cf,
                                                                             float* __restrict__ dw, float* __restrict__ db) {
-  __shared__ double red[kSegThreads];
+  __shared__ double red[Seg::kThreads];
   const int o = blockIdx.x;
   double s = 0.0;
-  for (int r = threadIdx.x; r < nrows; r += kSegThreads) s += (double)part[(long long)r * row + o];
-  s = seg_block_sum_f64<kSegThreads>(s, red);
+  for (int r = threadIdx.x; r < nrows; r += Seg::kThreads) s += (double)part[(long long)r * row + o];
+  s = block_tree_sum<double, Seg::kThreads>(s, red);
   if (threadIdx.x == 0) {
     if (o < cf) dw[o] = (float)s;
     else db[o - cf] = (float)s;
@@ -436,7 +371,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_backward_finalize_kernel(cons
 // ---- prediction -----------------------------------------------------------------------------------------------------------
 // arg-max of the logits, the first maximum winning (torch.argmax on ties picks the lowest index too); uint8 [B][V]
 template <int CP, bool HEAD, bool VEC>
-__global__ __launch_bounds__(kSegThreads) void seg_argmax_kernel(SegArgs a, unsigned char* __restrict__ out) {
+__global__ __launch_bounds__(Seg::kThreads) void seg_argmax_kernel(SegArgs a, unsigned char* __restrict__ out) {
   __shared__ float wT[HEAD ? kSegMaxF * CP : 1], bias[CP];
   if (HEAD) {
     seg_stage_head<CP>(a, wT, bias);
@@ -444,11 +379,11 @@ __global__ __launch_bounds__(kSegThreads) void seg_argmax_kernel(SegArgs a, unsi
   }
   const int n = blockIdx.y;
   for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
-    float z[CP][kSegVpt];
+    float z[CP][Seg::kVpt];
     seg_logits<CP, HEAD, VEC>(a, n, t, wT, bias, z);
-    unsigned char best[kSegVpt];
+    unsigned char best[Seg::kVpt];
 #pragma unroll
-    for (int j = 0; j < kSegVpt; ++j) {
+    for (int j = 0; j < Seg::kVpt; ++j) {
       float m = z[0][j];
       int bi = 0;
 #pragma unroll
@@ -457,55 +392,38 @@ __global__ __launch_bounds__(kSegThreads) void seg_argmax_kernel(SegArgs a, unsi
       best[j] = (unsigned char)bi;
     }
     unsigned char* dst = out + (long long)n * a.V;
-    if (VEC) {
-      const long long o = seg_voxel<true>(t, 0);
-      if (o < a.V) *(uchar4*)(dst + o) = make_uchar4(best[0], best[1], best[2], best[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < kSegVpt; ++j) {
-        const long long o = seg_voxel<false>(t, j);
-        if (o < a.V) dst[o] = best[j];
-      }
-    }
+    Seg::store4<VEC>(dst, t, a.V, best);
   }
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------
-static inline size_t up256s(size_t v) { return (v + 255) & ~(size_t)255; }
-static inline long long seg_tiles(long long V) { return (V + kSegTile - 1) / kSegTile; }
-static inline int seg_chunks(int n, long long V) {
-  const long long cap = kSegMaxBlocks / n > 1 ? kSegMaxBlocks / n : 1, t = seg_tiles(V);
-  return (int)(t < cap ? t : cap);
-}
 static inline int seg_cp(int C) { return C <= 4 ? 4 : (C <= 8 ? 8 : (C <= 16 ? 16 : 32)); }
-static inline bool seg_vec(long long V, const void* p0, const void* p1) {
-  return V % 4 == 0 && ((uintptr_t)p0 & 15) == 0 && ((uintptr_t)p1 & 15) == 0;
-}
+static inline bool seg_vec(long long V, const void* p0, const void* p1) { return V % 4 == 0 && aligned16(p0) && aligned16(p1); }
 
 struct SegLayout {
   size_t part, bad, total;
 };
 static SegLayout seg_layout(int n, long long V, int C, int F) {
-  const size_t rows = (size_t)n * seg_chunks(n, V);
+  const size_t rows = (size_t)n * Seg::chunks(n, V);
   const size_t fwd = rows * (3 * C + 1), bwd = F > 0 ? rows * ((size_t)C * F + C) : 0;
   SegLayout L;
   L.part = 0;
-  L.bad = up256s((fwd > bwd ? fwd : bwd) * sizeof(float));
-  L.total = L.bad + up256s(rows * sizeof(int));
+  L.bad = align_up((fwd > bwd ? fwd : bwd) * sizeof(float), 256);
+  L.total = L.bad + align_up(rows * sizeof(int), 256);
   return L;
 }
 size_t seg_loss_scratch_bytes(int n, long long V, int C, int F) { return seg_layout(n, V, C, F).total; }
 
 static SegArgs seg_args(const float* in, int F, const float* w, const float* b, const void* labels, int C, long long V) {
   SegArgs a;
-  a.in = in, a.w = w, a.b = b, a.labels = labels, a.F = F, a.C = C, a.V = V, a.ntiles = (int)seg_tiles(V);
+  a.in = in, a.w = w, a.b = b, a.labels = labels, a.F = F, a.C = C, a.V = V, a.ntiles = (int)Seg::tiles(V);
   return a;
 }
 
 #define SEG_DISPATCH_VEC(KERNEL, CP, HEAD, LT, ...)                                                          \
   do {                                                                                                        \
-    if (vec) KERNEL<CP, HEAD, LT, true><<<grid, kSegThreads, 0, st>>>(__VA_ARGS__);                            \
-    else KERNEL<CP, HEAD, LT, false><<<grid, kSegThreads, 0, st>>>(__VA_ARGS__);                               \
+    if (vec) KERNEL<CP, HEAD, LT, true><<<grid, Seg::kThreads, 0, st>>>(__VA_ARGS__);                            \
+    else KERNEL<CP, HEAD, LT, false><<<grid, Seg::kThreads, 0, st>>>(__VA_ARGS__);                               \
   } while (0)
 #define SEG_DISPATCH_LT(KERNEL, CP, HEAD, ...)                                                                \
   do {                                                                                                        \
@@ -535,7 +453,7 @@ hipError_t launch_seg_loss_forward(const float* in, int F, const float* w, const
   float* part = (float*)((char*)scratch + L.part);
   int* badpart = (int*)((char*)scratch + L.bad);
   const SegArgs a = seg_args(in, F, w, b, labels, C, V);
-  const int nchunk = seg_chunks(n, V), cp = seg_cp(C), do_ce = lambda_ce != 0.f;
+  const int nchunk = Seg::chunks(n, V), cp = seg_cp(C), do_ce = lambda_ce != 0.f;
   const bool head = F > 0, vec = seg_vec(V, in, in);
   const dim3 grid(nchunk, n);
   SEG_DISPATCH(seg_stats_kernel, a, do_ce, part, badpart);
@@ -554,7 +472,7 @@ hipError_t launch_seg_loss_backward(const float* in, int F, const float* w, cons
   const SegLayout L = seg_layout(n, V, C, F);
   float* part = scratch ? (float*)((char*)scratch + L.part) : nullptr;
   const SegArgs a = seg_args(in, F, w, b, labels, C, V);
-  const int nchunk = seg_chunks(n, V), cp = seg_cp(C), first = include_background ? 0 : 1;
+  const int nchunk = Seg::chunks(n, V), cp = seg_cp(C), first = include_background ? 0 : 1;
   const bool head = F > 0, vec = seg_vec(V, in, dx);
   const SegBwdCoef k = {first, smooth_nr, smooth_dr, lambda_dice, (float)((double)lambda_ce / ((double)n * (double)V)),
                         1.0 / ((double)n * (C - first))};
@@ -562,23 +480,23 @@ hipError_t launch_seg_loss_backward(const float* in, int F, const float* w, cons
   SEG_DISPATCH(seg_backward_kernel, a, k, stats, gout, dx, part);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !head) return e;
-  seg_backward_finalize_kernel<<<C * F + C, kSegThreads, 0, st>>>(part, n * nchunk, C * F + C, C * F, dw, db);
+  seg_backward_finalize_kernel<<<C * F + C, Seg::kThreads, 0, st>>>(part, n * nchunk, C * F + C, C * F, dw, db);
   return hipGetLastError();
 }
 
 #undef SEG_DISPATCH_LT
 #define SEG_DISPATCH_LT(KERNEL, CP, HEAD, ...)                                                                \
   do {                                                                                                        \
-    if (vec) KERNEL<CP, HEAD, true><<<grid, kSegThreads, 0, st>>>(__VA_ARGS__);                                \
-    else KERNEL<CP, HEAD, false><<<grid, kSegThreads, 0, st>>>(__VA_ARGS__);                                   \
+    if (vec) KERNEL<CP, HEAD, true><<<grid, Seg::kThreads, 0, st>>>(__VA_ARGS__);                                \
+    else KERNEL<CP, HEAD, false><<<grid, Seg::kThreads, 0, st>>>(__VA_ARGS__);                                   \
   } while (0)
 
 hipError_t launch_seg_argmax(const float* in, int F, const float* w, const float* b, int n, int C, long long V, unsigned char* out,
                              hipStream_t st) {
   const SegArgs a = seg_args(in, F, w, b, nullptr, C, V);
   const int cp = seg_cp(C);
-  const bool head = F > 0, vec = V % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 3) == 0;
-  const dim3 grid(seg_chunks(n, V), n);
+  const bool head = F > 0, vec = V % 4 == 0 && aligned16(in) && aligned4(out);
+  const dim3 grid(Seg::chunks(n, V), n);
   SEG_DISPATCH(seg_argmax_kernel, a, out);
   return hipGetLastError();
 }
@@ -624,8 +542,7 @@ int amx_seg_loss_forward(const float* d_in, int feat, const float* d_w, const fl
   if (int rc = seg_check(d_in, feat, d_w, n, classes, voxels)) return rc;
   if (int rc = seg_loss_check(d_labels, label_dtype, smooth_nr, smooth_dr, lambda_dice, lambda_ce)) return rc;
   if (!d_loss || !d_stats || !d_bad_labels || !d_scratch) return fail(AMX_ERR_INVALID, "null output or scratch");
-  const size_t need = amx::seg_loss_scratch_bytes(n, voxels, classes, feat);
-  if (scratch_bytes < need) return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, scratch_bytes);
+  if (int rc = amx::need_scratch(amx::seg_loss_scratch_bytes(n, voxels, classes, feat), scratch_bytes)) return rc;
   AMX_HIP(amx::launch_seg_loss_forward(d_in, feat, d_w, d_b, d_labels, label_dtype, n, classes, voxels, include_background, smooth_nr,
                                        smooth_dr, lambda_dice, lambda_ce, d_loss, d_stats, d_bad_labels, d_scratch,
                                        (hipStream_t)stream));
@@ -641,8 +558,7 @@ int amx_seg_loss_backward(const float* d_in, int feat, const float* d_w, const f
   if (!d_stats || !d_gout || !d_dx || d_dx == d_in) return fail(AMX_ERR_INVALID, "null argument, or d_dx aliases the input");
   if (feat > 0) {
     if (!d_dw || !d_db || !d_scratch) return fail(AMX_ERR_INVALID, "head mode needs d_dw, d_db and scratch");
-    const size_t need = amx::seg_loss_scratch_bytes(n, voxels, classes, feat);
-    if (scratch_bytes < need) return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, scratch_bytes);
+    if (int rc = amx::need_scratch(amx::seg_loss_scratch_bytes(n, voxels, classes, feat), scratch_bytes)) return rc;
   }
   AMX_HIP(amx::launch_seg_loss_backward(d_in, feat, d_w, d_b, d_labels, label_dtype, n, classes, voxels, include_background, smooth_nr,
                                         smooth_dr, lambda_dice, lambda_ce, d_stats, d_gout, d_dx, d_dw, d_db, d_scratch,

@@ -1,0 +1,128 @@
+// anatomix_amd -- what the streaming units (amx_segloss.hip, amx_segaug.hip, amx_regmetrics.hip, amx_reginstopt.hip) share:
+// the four-voxel tile access, the ascending xor butterfly over a wave and the LDS tree sum over a workgroup.  Each reduction
+// here has ONE order; a reduction in another order (amx_mlp.hip's wave_sum, amx_supcon.hip's block_sum, ...) is another function
+// and stays in its unit, since merging them would change results in the last bit.
+#pragma once
+#include <stdint.h>
+
+#include "amx_common.h"
+
+namespace amx {
+
+constexpr int kStreamMaxBlocks = 2048;     // workgroups of a streaming launch (8 per CU): bounds the partial slabs
+
+// ---- streaming tile ---------------------------------------------------------------------------------------------------------
+// A workgroup of THREADS threads covers tile t = VPT * THREADS voxels of a row of V, a thread owning VPT of them: VPT consecutive
+// voxels behind one 16-byte access (VEC: V % 4 == 0 and aligned bases, so a quad is inside the row or outside it as a whole),
+// otherwise VPT voxels THREADS apart accessed one by one (coalesced across lanes).
+template <int THREADS = 256, int VPT = 4>
+struct StreamTile {
+  static_assert(VPT == 4, "the vector path is one 16-byte access of four floats");
+  static constexpr int kThreads = THREADS, kWaves = THREADS / 64, kVpt = VPT, kTile = THREADS * VPT;
+
+  // voxel j of this thread in tile t
+  template <bool VEC>
+  static __device__ __forceinline__ long long voxel(int t, int j) {
+    return VEC ? (long long)t * kTile + threadIdx.x * VPT + j : (long long)t * kTile + j * THREADS + threadIdx.x;
+  }
+
+  // voxels past V read as 0
+  template <bool VEC>
+  static __device__ __forceinline__ void load4(const float* __restrict__ row, int t, long long V, float (&v)[VPT]) {
+    if (VEC) {
+      const long long o = voxel<true>(t, 0);
+      f32x4 q = {0.f, 0.f, 0.f, 0.f};
+      if (o < V) q = *(const f32x4*)(row + o);
+#pragma unroll
+      for (int j = 0; j < VPT; ++j) v[j] = q[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < VPT; ++j) {
+        const long long o = voxel<false>(t, j);
+        v[j] = o < V ? row[o] : 0.f;
+      }
+    }
+  }
+
+  template <bool VEC>
+  static __device__ __forceinline__ void store4(float* __restrict__ row, int t, long long V, const float (&v)[VPT]) {
+    if (VEC) {
+      const long long o = voxel<true>(t, 0);
+      if (o < V) *(f32x4*)(row + o) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < VPT; ++j) {
+        const long long o = voxel<false>(t, j);
+        if (o < V) row[o] = v[j];
+      }
+    }
+  }
+
+  // VEC: one 4-byte store (a 4-byte aligned base)
+  template <bool VEC>
+  static __device__ __forceinline__ void store4(unsigned char* __restrict__ row, int t, long long V, const unsigned char (&v)[VPT]) {
+    if (VEC) {
+      const long long o = voxel<true>(t, 0);
+      if (o < V) *(uchar4*)(row + o) = make_uchar4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < VPT; ++j) {
+        const long long o = voxel<false>(t, j);
+        if (o < V) row[o] = v[j];
+      }
+    }
+  }
+
+  // host side: tiles of a row, and the grid.x of a launch over n rows (grid.y): all the tiles, or the share of the cap
+  static inline long long tiles(long long V) { return (V + kTile - 1) / kTile; }
+  static inline int chunks(int n, long long V) {
+    const long long cap = kStreamMaxBlocks / n > 1 ? kStreamMaxBlocks / n : 1, t = tiles(V);
+    return (int)(t < cap ? t : cap);
+  }
+};
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
+// ---- butterfly reduce -------------------------------------------------------------------------------------------------------
+struct SumOp {
+  template <typename T>
+  static __device__ __forceinline__ T apply(T a, T b) { return a + b; }
+};
+struct MinOp {
+  static __device__ __forceinline__ float apply(float a, float b) { return fminf(a, b); }
+  static __device__ __forceinline__ double apply(double a, double b) { return fmin(a, b); }
+  static __device__ __forceinline__ int apply(int a, int b) { return a < b ? a : b; }
+};
+struct MaxOp {
+  static __device__ __forceinline__ float apply(float a, float b) { return fmaxf(a, b); }
+  static __device__ __forceinline__ double apply(double a, double b) { return fmax(a, b); }
+  static __device__ __forceinline__ int apply(int a, int b) { return a > b ? a : b; }
+};
+
+// Op over the 64 lanes of a wave, partner masks 1, 2, 4, 8, 16, 32 in that order; every lane gets the result
+template <typename Op, typename T>
+__device__ __forceinline__ T wave_reduce_xor(T v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v = Op::apply(v, __shfl_xor(v, m, 64));
+  return v;
+}
+
+// ---- tree sum ---------------------------------------------------------------------------------------------------------------
+// fixed-order sum of one value per thread over the NT threads of a workgroup through red[NT] (LDS): halving tree, every thread
+// gets the result.  The trailing barrier frees red for the next call (and orders the caller's earlier stores like any barrier).
+template <typename T, int NT>
+__device__ __forceinline__ T block_tree_sum(T v, T* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+#pragma unroll
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const T r = red[0];
+  __syncthreads();
+  return r;
+}
+
+}  // namespace amx

@@ -319,7 +319,7 @@ class Unet(nn.Module):
         return lib
 
     def _upload_weights(self, lib, device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        stream = _lib.stream(device)
         keep = []   # fp32 staging copies must outlive the enqueued pack kernels (same stream => safe)
         nconv = lib.amx_unet_num_convs(self._handle)
         mi, ci, co, ni = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
@@ -370,7 +370,7 @@ class Unet(nn.Module):
                 self._forward_chunks(lib, xin, y, device)
             else:
                 ws, need = self._get_workspace(lib, n, d, h, w, device)
-                stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+                stream = _lib.stream(device)
                 _lib.check(lib.amx_unet_forward(self._handle, _lib.ptr(xin), _lib.ptr(y), n, d, h, w, _lib.ptr(ws),
                                                 need, stream))
         return y if x.dtype == torch.float32 else y.to(x.dtype)
@@ -411,7 +411,7 @@ class Unet(nn.Module):
             return
         dev = torch.device("cuda", self._handle_key[0]) if self._handle_key[0] is not None else torch.device("cuda")
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _lib.stream(dev)
             _lib.check(_lib.load().amx_unet_numerics_status(self._handle, int(bool(synchronize)), stream))
 
     def forward_hip_taps(self, x, layers, encode_only=False):
@@ -439,7 +439,7 @@ class Unet(nn.Module):
                                          device=device))
             mods = (ctypes.c_int * max(len(want), 1))(*want)
             outs = (ctypes.c_void_p * max(len(want), 1))(*[f.data_ptr() for f in feats])
-            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            stream = _lib.stream(device)
             _lib.check(lib.amx_unet_forward_taps(self._handle, _lib.ptr(xin), _lib.ptr(y), n, d, h, w, _lib.ptr(ws), need,
                                                  mods, len(want), outs, stop, stream))
         if x.dtype != torch.float32:
@@ -461,7 +461,7 @@ class Unet(nn.Module):
             n, _, d, h, w = xin.shape
             ws, need = self._get_workspace(lib, n, d, h, w, device)
             y = torch.empty((n, self._cfg["output_nc"], d, h, w), dtype=torch.float32, device=device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            stream = _lib.stream(device)
             recs = (_lib.LaunchRecord * 256)()
             cnt = ctypes.c_int(0)
             _lib.check(lib.amx_unet_forward_profiled(self._handle, _lib.ptr(xin), _lib.ptr(y), n, d, h, w,

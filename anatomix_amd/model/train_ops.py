@@ -14,10 +14,6 @@ _PREC = {torch.float16: 0, torch.bfloat16: 1}
 ACT = _lib.ACT
 
 
-def _st(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 _CACHE = {}
 
 
@@ -65,7 +61,7 @@ def pack_batch(reqs, dtype, device):
         arr[i].cout_real, arr[i].cout, arr[i].w = cout_real, cout, width
         off += nb
     with torch.cuda.device(device):
-        _lib.check(lib.amx_conv3d_pack_batch(arr, len(reqs), _PREC[dtype], _st(device)))
+        _lib.check(lib.amx_conv3d_pack_batch(arr, len(reqs), _PREC[dtype], _lib.stream(device)))
     return views
 
 
@@ -99,7 +95,7 @@ def conv_forward(x0, x1, weight, act="none", slope=0.3, out32=False, shift=None,
             o16, o32 = out, None
         _lib.check(lib.amx_conv3d_k3_reflect_ex(_lib.ptr(x0), c0, _lib.ptr(x1), c1, _lib.ptr(wt), weight_mode, cin_real, cout_real,
                                                 None, _lib.ptr(shift), cout, n, d, h, w, ACT[act], slope, _PREC[x0.dtype],
-                                                _lib.ptr(wpk), _lib.ptr(o16), _lib.ptr(o32), _st(dev)))
+                                                _lib.ptr(wpk), _lib.ptr(o16), _lib.ptr(o32), _lib.stream(dev)))
     return out
 
 
@@ -116,7 +112,7 @@ def bn_train_forward(x, gamma, beta, eps, act="relu", slope=0.3, running_mean=No
         sc = _scratch(lib, dev, c)
         _lib.check(lib.amx_bn_train_forward(_lib.ptr(x), _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), float(eps), n, vox, c,
                                             ACT[act], slope, _lib.ptr(sc), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(running_mean),
-                                            _lib.ptr(running_var), float(momentum), _PREC[x.dtype], _st(dev)))
+                                            _lib.ptr(running_var), float(momentum), _PREC[x.dtype], _lib.stream(dev)))
     return y, mean, rstd
 
 
@@ -153,11 +149,11 @@ def bn_act_backward(dy, y, x, mean, rstd, gamma, act="relu", slope=0.3, framed=N
         if recompute and mean is not None:
             _lib.check(lib.amx_bn_act_backward_recompute(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gamma),
                                                          _lib.ptr(beta), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(framed), n, d, h, w,
-                                                         c, ACT[act], slope, _lib.ptr(sc), _PREC[dy.dtype], _st(dev)))
+                                                         c, ACT[act], slope, _lib.ptr(sc), _PREC[dy.dtype], _lib.stream(dev)))
         else:
             _lib.check(lib.amx_bn_act_backward(_lib.ptr(dy), _lib.ptr(y), _lib.ptr(x), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gamma),
                                                _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(framed), n, d, h, w, c, ACT[act], slope,
-                                               _lib.ptr(sc), _PREC[dy.dtype], _st(dev)))
+                                               _lib.ptr(sc), _PREC[dy.dtype], _lib.stream(dev)))
     return framed, dgamma, dbeta
 
 
@@ -203,11 +199,11 @@ def conv_dgrad_direct(dx_framed, weight, wpk=None):
             wpk = _cached(("wpk", dev, nb), lambda: torch.empty(nb, dtype=torch.uint8, device=dev))
         prec = _PREC[dx_framed.dtype]
         _lib.check(lib.amx_conv3d_dgrad_interior(_lib.ptr(dx_framed), c, _lib.ptr(wt), flags, co_f, ci_f, cout, n, d, h, w, prec,
-                                                 _lib.ptr(wpk), _lib.ptr(out), _st(dev)))
+                                                 _lib.ptr(wpk), _lib.ptr(out), _lib.stream(dev)))
         # (one fragment table per call site would be needed if calls of DIFFERENT layers could overlap: they are stream-ordered)
         tab = _cached(("shell_tab", dev), lambda: torch.empty(lib.amx_conv3d_dgrad_shell_scratch_bytes(), dtype=torch.uint8, device=dev))
         _lib.check(lib.amx_conv3d_dgrad_fold_shell(_lib.ptr(dx_framed), c, _lib.ptr(wt), co_f, ci_f, _lib.ptr(out), cout, n, d, h, w, prec,
-                                                   _lib.ptr(tab), _st(dev)))
+                                                   _lib.ptr(tab), _lib.stream(dev)))
     return out
 
 
@@ -220,7 +216,7 @@ def pad_fold(g, accumulate_into=None):
     din = accumulate_into if accumulate_into is not None else torch.empty((n, d, h, w, cin_pad), dtype=g.dtype, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.amx_pad_fold(_lib.ptr(g), _lib.ptr(din), n, d, h, w, cin_pad, int(accumulate_into is not None),
-                                    _PREC[g.dtype], _st(dev)))
+                                    _PREC[g.dtype], _lib.stream(dev)))
     return din
 
 
@@ -250,7 +246,7 @@ def conv_wgrad(dx_framed, x0, x1, cin_real, cout, out=None, accumulate=False):
         sc = _cached(("wgrad", dev, nbytes), lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
         _lib.check(lib.amx_conv3d_wgrad(ctypes.c_void_p(view.data_ptr()), sn, sz, sy, sx, _lib.ptr(x0), c0, _lib.ptr(x1), c1,
                                         cin_real, cout, n, d, h, w, _lib.ptr(dw), 1 if accumulate else 0, _lib.ptr(sc), nbytes, _PREC[x0.dtype],
-                                        _st(dev)))
+                                        _lib.stream(dev)))
     return dw
 
 
@@ -260,7 +256,8 @@ def pool2(x, mode):
     n, d, h, w, c = x.shape
     out = torch.empty((n, d // 2, h // 2, w // 2, c), dtype=x.dtype, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.amx_pool2(_lib.ptr(x), _lib.ptr(out), n, d // 2, h // 2, w // 2, c, int(mode), _PREC[x.dtype], _st(x.device)))
+        _lib.check(lib.amx_pool2(_lib.ptr(x), _lib.ptr(out), n, d // 2, h // 2, w // 2, c, int(mode), _PREC[x.dtype],
+                   _lib.stream(x.device)))
     return out
 
 
@@ -274,7 +271,7 @@ def upsample2_trilinear(x):
     n, d, h, w, c = x.shape
     out = torch.empty((n, 2 * d, 2 * h, 2 * w, c), dtype=x.dtype, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.amx_upsample2_trilinear(_lib.ptr(x), _lib.ptr(out), n, d, h, w, c, _PREC[x.dtype], _st(x.device)))
+        _lib.check(lib.amx_upsample2_trilinear(_lib.ptr(x), _lib.ptr(out), n, d, h, w, c, _PREC[x.dtype], _lib.stream(x.device)))
     return out
 
 
@@ -286,7 +283,7 @@ def upsample2_trilinear_backward(g):
     out = torch.empty((n, d2 // 2, h2 // 2, w2 // 2, c), dtype=g.dtype, device=g.device)
     with torch.cuda.device(g.device):
         _lib.check(lib.amx_upsample2_trilinear_backward(_lib.ptr(g), _lib.ptr(out), n, d2 // 2, h2 // 2, w2 // 2, c,
-                                                        _PREC[g.dtype], _st(g.device)))
+                                                        _PREC[g.dtype], _lib.stream(g.device)))
     return out
 
 
@@ -296,7 +293,7 @@ def pool2_max_backward(dp, inp, accumulate_into=None):
     din = accumulate_into if accumulate_into is not None else torch.empty_like(inp)
     with torch.cuda.device(dp.device):
         _lib.check(lib.amx_pool2_max_backward(_lib.ptr(dp), _lib.ptr(inp), _lib.ptr(din), n, do, ho, wo, c,
-                                              int(accumulate_into is not None), _PREC[dp.dtype], _st(dp.device)))
+                                              int(accumulate_into is not None), _PREC[dp.dtype], _lib.stream(dp.device)))
     return din
 
 
@@ -307,7 +304,7 @@ def export_ncdhw(x):
     x = x.contiguous()
     out = torch.empty((n, c, d, h, w), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.amx_export_ncdhw(_lib.ptr(x), c, n, d, h, w, _lib.ptr(out), _PREC[x.dtype], _st(x.device)))
+        _lib.check(lib.amx_export_ncdhw(_lib.ptr(x), c, n, d, h, w, _lib.ptr(out), _PREC[x.dtype], _lib.stream(x.device)))
     return out
 
 
@@ -329,7 +326,7 @@ def gather_rows(x, coords, channels_last=True):
     rows = torch.empty((n, p, c), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.amx_gather_rows(ctypes.c_void_p(x.data_ptr()), dtype, sn, sz, sy, sx, sc, _lib.ptr(coords), n, p, c, _lib.ptr(rows),
-                                       _st(x.device)))
+                                       _lib.stream(x.device)))
     return rows
 
 
@@ -345,7 +342,7 @@ def scatter_rows(rows, coords, dst, accumulate=False):
     assert sc == es and dst.shape[0] == n and dst.shape[4] >= c and coords.shape == (p, 3)
     with torch.cuda.device(rows.device):
         _lib.check(lib.amx_scatter_rows(_lib.ptr(rows), _lib.ptr(coords), ctypes.c_void_p(dst.data_ptr()), _PREC[dst.dtype], sn, sz, sy, sx,
-                                        n, p, c, int(accumulate), _st(rows.device)))
+                                        n, p, c, int(accumulate), _lib.stream(rows.device)))
     return dst
 
 
@@ -366,7 +363,7 @@ def conv_backward_sampled(grows, coords, x0, weight, cin_real, need_din=True):
         sc = torch.empty(nb, dtype=torch.uint8, device=x0.device)
         _lib.check(lib.amx_conv3d_backward_sampled(_lib.ptr(grows), _lib.ptr(coords), _lib.ptr(x0), xc, _lib.ptr(wt), n, p, d, h, w, cout,
                                                    cin_real, _lib.ptr(dw), _lib.ptr(din), xc, _lib.ptr(sc), nb, _PREC[x0.dtype],
-                                                   _st(x0.device)))
+                                                   _lib.stream(x0.device)))
     return dw, din
 
 
@@ -377,7 +374,7 @@ def import_input(x, dtype):
     xs = x.detach().contiguous().float()
     out = torch.empty((n, d, h, w, 16), dtype=dtype, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.amx_import_input(_lib.ptr(xs), _lib.ptr(out), n, cin, d, h, w, _PREC[dtype], _st(x.device)))
+        _lib.check(lib.amx_import_input(_lib.ptr(xs), _lib.ptr(out), n, cin, d, h, w, _PREC[dtype], _lib.stream(x.device)))
     return out
 
 
@@ -392,7 +389,7 @@ def import_ncdhw(g, dst, accumulate=False):
     assert sc == es and tuple(dst.shape[:4]) == (n, d, h, w) and dst.shape[4] >= c
     with torch.cuda.device(g.device):
         _lib.check(lib.amx_import_ncdhw(_lib.ptr(g), ctypes.c_void_p(dst.data_ptr()), n, c, d, h, w, sn, sz, sy, sx,
-                                        int(accumulate), _PREC[dst.dtype], _st(g.device)))
+                                        int(accumulate), _PREC[dst.dtype], _lib.stream(g.device)))
     return dst
 
 
@@ -406,7 +403,7 @@ def upcat_split_backward_framed(g, c0, c1, skip_into=None):
     dlow = torch.empty((n, d // 2, h // 2, w // 2, c1), dtype=g.dtype, device=g.device)
     with torch.cuda.device(g.device):
         _lib.check(lib.amx_upcat_split_backward_framed(_lib.ptr(g), _lib.ptr(dskip), _lib.ptr(dlow), n, d // 2, h // 2, w // 2, c0, c1,
-                                                       int(skip_into is not None), _PREC[g.dtype], _st(g.device)))
+                                                       int(skip_into is not None), _PREC[g.dtype], _lib.stream(g.device)))
     return dskip, dlow
 
 
@@ -420,5 +417,5 @@ def upcat_split_backward(dcat, c0, c1, skip_into=None):
     dlow = torch.empty((n, d // 2, h // 2, w // 2, c1), dtype=dcat.dtype, device=dcat.device)
     with torch.cuda.device(dcat.device):
         _lib.check(lib.amx_upcat_split_backward(_lib.ptr(dcat), _lib.ptr(dskip), _lib.ptr(dlow), n, d // 2, h // 2, w // 2, c0, c1,
-                                                int(skip_into is not None), _PREC[dcat.dtype], _st(dcat.device)))
+                                                int(skip_into is not None), _PREC[dcat.dtype], _lib.stream(dcat.device)))
     return dskip, dlow

@@ -205,7 +205,7 @@ class EvaAttention(nn.Module):
             if self._scratch is None or self._scratch.numel() < nb or self._scratch.device != dev:
                 self._scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
             qn = self.q_norm
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _lib.stream(dev)
             _lib.check(lib.amx_attention_qknorm_rope(
                 _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(qn.weight if qn else None), _lib.ptr(qn.bias if qn else None),
                 _lib.ptr(self.k_norm.weight if qn else None), _lib.ptr(self.k_norm.bias if qn else None),
@@ -331,7 +331,7 @@ class PrimusV2(nn.Module):
         if tuple(x.shape[2:]) != tuple(8 * g for g in self.grid) or x.shape[1] != self._vit_cfg["input_channels"]:
             raise ValueError(f"PrimusV2 was built for inputs of {tuple(8 * g for g in self.grid)} (got {tuple(x.shape[1:])})")
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _lib.stream(dev)
             if self._handle is None:
                 cfg = _lib.VitCfg(**self._vit_cfg)
                 hnd = ctypes.c_void_p()
@@ -372,7 +372,7 @@ class PrimusV2(nn.Module):
         out = torch.empty(nbytes.value, dtype=torch.uint8, device=self._engine_ws.device)
         with torch.cuda.device(out.device):
             _lib.check(lib.amx_vit_debug_read(self._handle, name.encode(), _lib.ptr(out), nbytes.value, None,
-                                              ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)))
+                                              _lib.stream(out.device)))
         return out.view(dtype)
 
     def _drop_engine(self):

@@ -99,7 +99,7 @@ class _MlpHeadFn(torch.autograd.Function):
         rstd = torch.empty((L, width), dtype=torch.float32, device=dev)
         bn0 = layers[0][1]
         with torch.cuda.device(dev):
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _lib.stream(dev)
             _lib.check(lib.amx_mlp_head_forward(_lib.ptr(xc), n, cin, width, L, _ptr_array(ws), _ptr_array(gs), _ptr_array(bs),
                                                 _ptr_array(rms), _ptr_array(rvs), float(bn0.eps), float(bn0.momentum),
                                                 _lib.ACT[act], float(slope), _lib.ptr(z), _lib.ptr(y), _lib.ptr(mean),
@@ -128,7 +128,7 @@ class _MlpHeadFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             nb = lib.amx_mlp_head_scratch_bytes(n, cin, width)
             sc = torch.empty(nb, dtype=torch.uint8, device=dev)
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _lib.stream(dev)
             _lib.check(lib.amx_mlp_head_backward(_lib.ptr(dyc), _lib.ptr(xc), n, cin, width, L, _ptr_array(ws), _ptr_array(gs),
                                                  _lib.ACT[act], float(slope), _lib.ptr(z), _lib.ptr(y), _lib.ptr(mean),
                                                  _lib.ptr(rstd), _ptr_array(dws), _ptr_array(dgs), _ptr_array(dbs), _lib.ptr(dx),
@@ -173,7 +173,7 @@ class _MlpHeadsFn(torch.autograd.Function):
         bn0 = layers0[0][1]
         cin_arr = (ctypes.c_int * nb)(*cins)
         with torch.cuda.device(dev):
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _lib.stream(dev)
             _lib.check(lib.amx_mlp_heads_forward(nb, _ptr_array(xcs), n, cin_arr, width, L, _ptr_array(ws), _ptr_array(gs), _ptr_array(bs),
                                                  _ptr_array(rms), _ptr_array(rvs), float(bn0.eps), float(bn0.momentum), _lib.ACT[act],
                                                  float(slope), _ptr_array(list(z)), _ptr_array(list(y)), _ptr_array(list(mean)),
@@ -206,7 +206,7 @@ class _MlpHeadsFn(torch.autograd.Function):
             nbytes = max(lib.amx_mlp_head_scratch_bytes(n, c, width) for c in cins)
             nbytes = (nbytes + 255) // 256 * 256
             sc = torch.empty((nb, nbytes), dtype=torch.uint8, device=dev)
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _lib.stream(dev)
             _lib.check(lib.amx_mlp_heads_backward(nb, _ptr_array(dycs), _ptr_array(xcs), n, cin_arr, width, L, _ptr_array(ws), _ptr_array(gs),
                                                   _lib.ACT[act], float(slope), _ptr_array(list(z)), _ptr_array(list(y)),
                                                   _ptr_array(list(mean)), _ptr_array(list(rstd)), _ptr_array(dws), _ptr_array(dgs),

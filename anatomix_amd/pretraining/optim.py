@@ -124,5 +124,5 @@ class FusedAdamW(torch.optim.Optimizer):
                     table = np.asarray(rows, dtype=np.int64)
                     _lib.check(lib.amx_adamw_step_dev(table.ctypes.data_as(ctypes.c_void_p), len(rows), _lib.ptr(dbuf),
                                                       int(bool(group["maximize"])),
-                                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                                      _lib.stream(dev)))
         return loss

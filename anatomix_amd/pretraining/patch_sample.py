@@ -75,7 +75,7 @@ class PatchSampleF(nn.Module):
         keys = torch.randint(1 << 62, (d[0] * d[1] * d[2],), device=device, dtype=torch.int64)
         coords = torch.empty((num, 3), dtype=torch.int64, device=device)
         with torch.cuda.device(device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            st = _lib.stream(device)
             _lib.check(lib.amx_sample_perm(_lib.ptr(keys), d[0], d[1], d[2], num, _lib.ptr(coords), st))
         return coords[:, 3 - len(dims):]
 
@@ -90,7 +90,7 @@ class PatchSampleF(nn.Module):
         d = [1] * (3 - len(dims)) + [int(v) for v in dims]
         coords = torch.empty((num, 3), dtype=torch.int64, device=device)
         with torch.cuda.device(device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            st = _lib.stream(device)
             _lib.check(lib.amx_sample_coords(_lib.ptr(draws), 2 * num, num, d[0], d[1], d[2], _lib.ptr(coords), st))
         return coords[:, 3 - len(dims):]
 

@@ -24,7 +24,7 @@ class _SupConHip(torch.autograd.Function):
         with torch.cuda.device(dev):
             nbytes = lib.amx_supcon_scratch_bytes(n, c)
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _lib.stream(dev)
             _lib.check(lib.amx_supcon_loss(_lib.ptr(x), _lib.ptr(labels), n, c, float(temperature), int(rarity), int(balance),
                                            int(sqrt_mode), _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(scratch), nbytes, st))
         ctx.save_for_backward(grad)
@@ -53,7 +53,7 @@ class _SupConBatchHip(torch.autograd.Function):
         with torch.cuda.device(dev):
             per = lib.amx_supcon_scratch_bytes(n, c)
             scratch = torch.empty(nb * per, dtype=torch.uint8, device=dev)
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _lib.stream(dev)
             arr = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
             _lib.check(lib.amx_supcon_loss_batch(nb, arr(xs), arr(list(labels)), n, c, float(temperature), int(rarity), int(balance),
                                                  int(sqrt_mode), arr(list(loss)), None if grad is None else arr(list(grad)),
@@ -98,7 +98,7 @@ def batched_losses(criterions, features, labels_seg, coords, ranges):
     lab = torch.empty((nb, ntps * num_patches), dtype=torch.int32, device=f0.device)
     dims = (ctypes.c_int * (3 * nb))(*[int(v) for r in ranges for v in r])
     with torch.cuda.device(f0.device):
-        st = ctypes.c_void_p(torch.cuda.current_stream(f0.device).cuda_stream)
+        st = _lib.stream(f0.device)
         arr = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         _lib.check(lib.amx_gather_labels_batch(_lib.ptr(seg), seg.shape[2], seg.shape[3], seg.shape[4], nb, arr(cs), num_patches, dims, ntps,
                                                arr(list(lab)), st))
@@ -149,7 +149,7 @@ class SupPatchNCELoss(nn.Module):
             coords = labels_coords.contiguous()
             lab = torch.empty(ntps * num_patches, dtype=torch.int32, device=features.device)
             with torch.cuda.device(features.device):
-                st = ctypes.c_void_p(torch.cuda.current_stream(features.device).cuda_stream)
+                st = _lib.stream(features.device)
                 _lib.check(lib.amx_gather_labels(_lib.ptr(seg), seg.shape[2], seg.shape[3], seg.shape[4], _lib.ptr(coords), num_patches,
                                                  int(coords_range[0]), int(coords_range[1]), int(coords_range[2]), ntps, _lib.ptr(lab), st))
             return _SupConHip.apply(features.reshape(ntps * num_patches, nc), lab, self.temperature, self.weigh_rarity,

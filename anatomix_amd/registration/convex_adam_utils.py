@@ -73,14 +73,10 @@ def extract_features(img_fixed, img_moving, model, fixminclip=None, fixmaxclip=N
 
 # ---- feature post-processing on the HIP kernels (fp32, batch 1, like the reference's tensors) -------------------------
 
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _f32c(t, what):
     if not t.is_cuda:
         raise RuntimeError(f"{what}: the registration feature kernels run on the GPU (got a {t.device} tensor); there is no CPU path")
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+    return _lib.f32c(t)
 
 
 def MINDSSC(img, radius=2, dilation=2):
@@ -96,7 +92,7 @@ def MINDSSC(img, radius=2, dilation=2):
         nb = lib.amx_mindssc_scratch_bytes(h, w, d)
         sc = torch.empty(nb, dtype=torch.uint8, device=x.device)
         _lib.check(lib.amx_mindssc(_lib.ptr(x), h, w, d, int(radius), int(dilation), _lib.ptr(out), _lib.ptr(sc), nb,
-                                   _stream(x.device)))
+                                   _lib.stream(x.device)))
     return out
 
 
@@ -114,7 +110,7 @@ def apply_avg_pool3d(disp_hr, kernel_size, num_repeats):
     with torch.cuda.device(x.device):
         for _ in range(int(num_repeats)):
             y = torch.empty_like(x)
-            _lib.check(lib.amx_box_filter3d(_lib.ptr(x), _lib.ptr(y), c, h, w, d, int(kernel_size), _stream(x.device)))
+            _lib.check(lib.amx_box_filter3d(_lib.ptr(x), _lib.ptr(y), c, h, w, d, int(kernel_size), _lib.stream(x.device)))
             x = y
     return x
 
@@ -132,7 +128,7 @@ def smooth_merged_features(mind, pred, grid_sp, downscale_feat_scalar=0.1):
     out = torch.empty((1, ca + cb, h // g, w // g, d // g), dtype=torch.float32, device=b.device)
     with torch.cuda.device(b.device):
         _lib.check(lib.amx_avg_pool3d_cat(_lib.ptr(a), ca, 1.0, _lib.ptr(b), cb, float(downscale_feat_scalar), h, w, d, g,
-                                          _lib.ptr(out), _stream(b.device)))
+                                          _lib.ptr(out), _lib.stream(b.device)))
     return out
 
 
@@ -152,7 +148,7 @@ def correlate(mind_fix, mind_mov, disp_hw, grid_sp, shape, ch=12):
         nb = lib.amx_correlate_scratch_bytes(h, w, d, int(disp_hw))
         sc = torch.empty(nb, dtype=torch.uint8, device=f.device)
         _lib.check(lib.amx_correlate_ssd(_lib.ptr(f), _lib.ptr(m), ch, h, w, d, int(disp_hw), _lib.ptr(ssd), _lib.ptr(amin),
-                                         _lib.ptr(sc), nb, _stream(f.device)))
+                                         _lib.ptr(sc), nb, _lib.stream(f.device)))
     return ssd, amin
 
 
@@ -202,7 +198,7 @@ def coupled_convex(ssd, ssd_argmin, disp_mesh_t, grid_sp, shape):
         nb = lib.amx_coupled_convex_scratch_bytes(h, w, d)
         sc = torch.empty(nb, dtype=torch.uint8, device=s.device)
         _lib.check(lib.amx_coupled_convex(_lib.ptr(s), _lib.ptr(amin), h, w, d, hw, _lib.ptr(out), _lib.ptr(sc), nb,
-                                          _stream(s.device)))
+                                          _lib.stream(s.device)))
     return out
 
 
@@ -222,9 +218,9 @@ def coupled_convex_step(ssd, soft_history):
     lab = torch.empty((h, w, d), dtype=torch.int64, device=s.device)
     with torch.cuda.device(s.device):
         nb = lib.amx_coupled_convex_step_scratch_bytes(h, w, d)
-        sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=s.device)
+        sc = _lib.scratch(nb, s.device)
         _lib.check(lib.amx_coupled_convex_step(_lib.ptr(s), _lib.ptr(hist), j, h, w, d, hw, _lib.ptr(out), _lib.ptr(lab),
-                                               _lib.ptr(sc), nb, _stream(s.device)))
+                                               _lib.ptr(sc), nb, _lib.stream(s.device)))
     return lab, out
 
 
@@ -240,9 +236,9 @@ def inverse_consistency(disp_field1s, disp_field2s, iterations=20):
     o1, o2 = torch.empty_like(a), torch.empty_like(b)
     with torch.cuda.device(a.device):
         nb = lib.amx_inverse_consistency_scratch_bytes(h, w, d)
-        sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=a.device)
+        sc = _lib.scratch(nb, a.device)
         _lib.check(lib.amx_inverse_consistency(_lib.ptr(a), _lib.ptr(b), h, w, d, int(iterations), _lib.ptr(o1), _lib.ptr(o2),
-                                               _lib.ptr(sc), nb, _stream(a.device)))
+                                               _lib.ptr(sc), nb, _lib.stream(a.device)))
     return o1, o2
 
 
@@ -264,7 +260,7 @@ def resize_trilinear(x, size, scale=None, flip_channels=False):
     out = torch.empty((1, c, max(H, 0), max(W, 0), max(D, 0)), dtype=torch.float32, device=t.device)
     with torch.cuda.device(t.device):
         _lib.check(lib.amx_resize_trilinear3d(_lib.ptr(t), c, h, w, d, _lib.ptr(out), H, W, D, sc, int(bool(flip_channels)),
-                                              _stream(t.device)))
+                                              _lib.stream(t.device)))
     return out
 
 
@@ -314,7 +310,7 @@ def _jacobian_call(field, add_identity, want_field, want_stats):
         nb = lib.amx_jacobian_det_scratch_bytes(h, w, d) if want_stats else 0
         sc = torch.empty(max(nb, 8), dtype=torch.uint8, device=field.device) if want_stats else None
         _lib.check(lib.amx_jacobian_det(_lib.ptr(field), h, w, d, int(add_identity), _lib.ptr(jdet), _lib.ptr(stats), _lib.ptr(sc),
-                                        nb, _stream(field.device)))
+                                        nb, _lib.stream(field.device)))
     return jdet, stats
 
 

@@ -14,7 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
-from .convex_adam_utils import MINDSSC, _f32c, _stream, resize_trilinear
+from .convex_adam_utils import MINDSSC, _f32c, resize_trilinear
 
 
 def _fill_outside_mask(img, mask_vol):
@@ -70,9 +70,9 @@ def run_stage1_registration(features_fix_smooth, features_mov_smooth, disp_hw, g
     out = torch.empty((1, 3, H, W, D) if ic else (1, 3, h, w, d), dtype=torch.float32, device=f.device)
     with torch.cuda.device(f.device):
         nb = lib.amx_stage1_registration_scratch_bytes(h, w, d, int(disp_hw), int(ic))
-        sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=f.device)
+        sc = _lib.scratch(nb, f.device)
         _lib.check(lib.amx_stage1_registration(_lib.ptr(f), _lib.ptr(m), int(n_ch), h, w, d, int(disp_hw), g, int(ic), H, W, D,
-                                               _lib.ptr(out), _lib.ptr(sc), nb, _stream(f.device)))
+                                               _lib.ptr(out), _lib.ptr(sc), nb, _lib.stream(f.device)))
     return out
 
 
@@ -124,10 +124,10 @@ def run_instance_opt(disp_hr, features_fix, features_mov, grid_sp_adam, lambda_w
     out = torch.empty((1, 3, H, W, D), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         nb = lib.amx_run_instance_opt_scratch_bytes(c, H, W, D, g, smooth)
-        sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+        sc = _lib.scratch(nb, x.device)
         _lib.check(lib.amx_run_instance_opt(_lib.ptr(x), _lib.ptr(f), _lib.ptr(m), c, H, W, D, g, float(lambda_weight),
                                             int(selected_niter), smooth, float(lr), _lib.ptr(out), _lib.ptr(sc), nb,
-                                            _stream(x.device)))
+                                            _lib.stream(x.device)))
     return out
 
 
@@ -157,9 +157,9 @@ def instance_opt_grad(weight, patch_fix, patch_mov, lambda_weight):
     loss2 = torch.empty(2, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         nb = lib.amx_instance_opt_scratch_bytes(c, h, w, d)
-        sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+        sc = _lib.scratch(nb, x.device)
         _lib.check(lib.amx_instance_opt_grad(_lib.ptr(x), _lib.ptr(f), _lib.ptr(m), c, h, w, d, float(lambda_weight),
-                                             _lib.ptr(grad), _lib.ptr(ds), _lib.ptr(loss2), _lib.ptr(sc), nb, _stream(x.device)))
+                                             _lib.ptr(grad), _lib.ptr(ds), _lib.ptr(loss2), _lib.ptr(sc), nb, _lib.stream(x.device)))
     return grad, ds, loss2[0], loss2[1]
 
 
@@ -177,9 +177,9 @@ def instance_opt(weight, patch_fix, patch_mov, lambda_weight, niter, lr=1):
     fitted = torch.empty_like(x)
     with torch.cuda.device(x.device):
         nb = lib.amx_instance_opt_scratch_bytes(c, h, w, d)
-        sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+        sc = _lib.scratch(nb, x.device)
         _lib.check(lib.amx_instance_opt(_lib.ptr(x), _lib.ptr(f), _lib.ptr(m), c, h, w, d, float(lambda_weight), float(lr),
-                                        int(niter), _lib.ptr(fitted), _lib.ptr(sc), nb, _stream(x.device)))
+                                        int(niter), _lib.ptr(fitted), _lib.ptr(sc), nb, _lib.stream(x.device)))
     return fitted, x
 
 
@@ -192,7 +192,7 @@ def instance_opt_smooth3(field):
     h, w, d = (int(v) for v in x.shape[2:])
     out = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().amx_instance_opt_smooth3(_lib.ptr(x), _lib.ptr(out), h, w, d, _stream(x.device)))
+        _lib.check(_lib.load().amx_instance_opt_smooth3(_lib.ptr(x), _lib.ptr(out), h, w, d, _lib.stream(x.device)))
     return out
 
 
@@ -203,7 +203,7 @@ def instance_opt_adam_step(weight, grad, exp_avg, exp_avg_sq, t, lr=1):
             raise ValueError(f"instance_opt_adam_step: {nm} must be a contiguous fp32 device tensor of the weight's size")
     with torch.cuda.device(weight.device):
         _lib.check(_lib.load().amx_instance_opt_adam_step(_lib.ptr(weight), _lib.ptr(grad), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq),
-                                                          weight.numel(), float(lr), int(t), _stream(weight.device)))
+                                                          weight.numel(), float(lr), int(t), _lib.stream(weight.device)))
     return weight
 
 
@@ -223,5 +223,5 @@ def warp_volume(vol, disp_hr, mode="bilinear"):
     c, (H, W, D) = v.shape[1], (int(n) for n in v.shape[2:])
     out = torch.empty_like(v)
     with torch.cuda.device(v.device):
-        _lib.check(_lib.load().amx_warp3d(_lib.ptr(v), c, _lib.ptr(x), H, W, D, _lib.WARP[mode], _lib.ptr(out), _stream(v.device)))
+        _lib.check(_lib.load().amx_warp3d(_lib.ptr(v), c, _lib.ptr(x), H, W, D, _lib.WARP[mode], _lib.ptr(out), _lib.stream(v.device)))
     return out

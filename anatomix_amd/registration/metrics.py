@@ -6,7 +6,6 @@ from __future__ import annotations
 import torch
 
 from .. import _lib
-from .convex_adam_utils import _stream
 
 _DTYPES = {torch.float32: "float32", torch.int64: "int64", torch.uint8: "uint8"}
 
@@ -30,7 +29,7 @@ def _overlap(a, b, bins):
     with torch.cuda.device(a.device):
         _lib.check(_lib.load().amx_label_overlap(_lib.ptr(a), _lib.SEG_LABEL[_DTYPES[a.dtype]], _lib.ptr(b),
                                                  _lib.SEG_LABEL[_DTYPES[b.dtype]], a.numel(), bins, _lib.ptr(out),
-                                                 _lib.ptr(out[3 * bins:]), _stream(a.device)))
+                                                 _lib.ptr(out[3 * bins:]), _lib.stream(a.device)))
     return out[:3 * bins].view(bins, 3), out[3 * bins:]
 
 

@@ -291,7 +291,7 @@ def _normalize(acc, cnt):
     """acc[b, c] /= cnt in place (acc [B,C,d,H,W] contiguous, cnt [d,H,W] contiguous)."""
     if acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous() and cnt.is_contiguous() and acc.numel():
         lib = _lib.load()
-        st = ctypes.c_void_p(torch.cuda.current_stream(acc.device).cuda_stream)
+        st = _lib.stream(acc.device)
         vox = cnt.numel()
         with torch.cuda.device(acc.device):
             for b in range(acc.shape[0]):

@@ -33,16 +33,6 @@ SAMPLE_DTYPE = np.dtype([("vol", "<u8"), ("lab", "<u8"), ("flags", "<i4"), ("vol
 _GIBBS_R_WORD = SAMPLE_DTYPE.fields["gibbs_r"][1] // 4
 
 
-def _check(status):
-    if status in (_lib.AMX_ERR_INVALID, _lib.AMX_ERR_SHAPE):
-        raise _lib.AmxEnvelopeError(int(status), f"anatomix_amd error {status}: {_lib.load().amx_last_error().decode()}")
-    _lib.check(status)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _image(x, name="image"):
     """A contiguous float32 [B, 1, D, H, W] device tensor, or an error: there is no host path and no conversion."""
     if not isinstance(x, torch.Tensor):
@@ -195,22 +185,22 @@ def _minmax(x, scratch=None):
     lib = _lib.load()
     mm = torch.empty((B, 2), dtype=torch.float32, device=x.device)
     nb = lib.amx_segaug_scratch_bytes(B, V)
-    sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device) if scratch is None else scratch
-    _check(lib.amx_segaug_minmax(_lib.ptr(x), B, V, _lib.ptr(mm), _lib.ptr(sc), nb, _stream(x.device)))
+    sc = _lib.scratch(nb, x.device) if scratch is None else scratch
+    _lib.check_envelope(lib.amx_segaug_minmax(_lib.ptr(x), B, V, _lib.ptr(mm), _lib.ptr(sc), nb, _lib.stream(x.device)))
     return mm
 
 
 def _pointwise(x, out, mm, op, table):
-    _check(_lib.load().amx_segaug_pointwise(_lib.ptr(x), _lib.ptr(out), x.shape[0], x[0].numel(), _lib.ptr(mm), op, *table.args,
-                                            _stream(x.device)))
+    _lib.check_envelope(_lib.load().amx_segaug_pointwise(_lib.ptr(x), _lib.ptr(out), x.shape[0], x[0].numel(), _lib.ptr(mm), op,
+                        *table.args, _lib.stream(x.device)))
     return out
 
 
 def _crop(table, B, size, noise, label_dtype, dev):
     img = torch.empty((B, 1) + tuple(size), dtype=torch.float32, device=dev)
     lab = torch.empty((B, 1) + tuple(size), dtype=torch.uint8, device=dev)
-    _check(_lib.load().amx_segaug_crop(B, *size, _lib.ptr(noise), _lib.SEG_LABEL[str(label_dtype).split(".")[1]], _lib.ptr(img),
-                                       _lib.ptr(lab), *table.args, _stream(dev)))
+    _lib.check_envelope(_lib.load().amx_segaug_crop(B, *size, _lib.ptr(noise), _lib.SEG_LABEL[str(label_dtype).split(".")[1]],
+                        _lib.ptr(img), _lib.ptr(lab), *table.args, _lib.stream(dev)))
     return img, lab
 
 
@@ -218,7 +208,8 @@ def _gaussian(x, mode, table):
     B, _, d, h, w = x.shape
     out = torch.empty_like(x)
     tmp = torch.empty((2,) + tuple(x.shape), dtype=torch.float32, device=x.device)
-    _check(_lib.load().amx_segaug_gaussian(_lib.ptr(x), _lib.ptr(out), _lib.ptr(tmp), B, d, h, w, mode, *table.args, _stream(x.device)))
+    _lib.check_envelope(_lib.load().amx_segaug_gaussian(_lib.ptr(x), _lib.ptr(out), _lib.ptr(tmp), B, d, h, w, mode, *table.args,
+                        _lib.stream(x.device)))
     return out
 
 
@@ -253,9 +244,9 @@ def _affine(img, lab, size, table):
     out = torch.empty((B, 1) + tuple(size), dtype=torch.float32, device=img.device)
     olab = torch.empty((B, 1) + tuple(size), dtype=torch.uint8, device=img.device)
     nb = lib.amx_segaug_scratch_bytes(B, out[0].numel())
-    sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=img.device)
-    _check(lib.amx_segaug_affine(_lib.ptr(img), _lib.ptr(lab), B, *img.shape[2:], _lib.ptr(out), _lib.ptr(olab), *size, *table.args,
-                                 _lib.ptr(sc), nb, _stream(img.device)))
+    sc = _lib.scratch(nb, img.device)
+    _lib.check_envelope(lib.amx_segaug_affine(_lib.ptr(img), _lib.ptr(lab), B, *img.shape[2:], _lib.ptr(out), _lib.ptr(olab), *size,
+                        *table.args, _lib.ptr(sc), nb, _lib.stream(img.device)))
     return out, olab, sc, nb
 
 
@@ -471,6 +462,6 @@ def augment_batch(volumes, labels, params, noise=None):
             x = _gaussian(x, _GAUSS_SHARPEN, table)
         out, olab, sc, nb = _affine(x, lab, crop, table)
         mm = torch.empty((B, 2), dtype=torch.float32, device=dev)
-        _check(_lib.load().amx_segaug_minmax_finalize(_lib.ptr(sc), nb, B, out[0].numel(), _lib.ptr(mm), _stream(dev)))
+        _lib.check_envelope(_lib.load().amx_segaug_minmax_finalize(_lib.ptr(sc), nb, B, out[0].numel(), _lib.ptr(mm), _lib.stream(dev)))
         _pointwise(out, out, mm, _OP_SCALE, table)
     return out, olab

@@ -11,7 +11,6 @@ t = one_hot(labels), per sample b and class c  I = sum_v p t, P = sum_v p, G = s
 A label outside [0, C) makes the loss NaN and is counted in ``last_bad_labels``."""
 from __future__ import annotations
 
-import ctypes
 
 import torch
 import torch.nn as nn
@@ -49,20 +48,6 @@ def _envelope(classes, feat):
                                     f"segmentation loss kernels: 1 <= head input channels <= {MAX_HEAD_CHANNELS} (got {feat})")
 
 
-def _check(status):
-    if status in (_lib.AMX_ERR_INVALID, _lib.AMX_ERR_SHAPE):
-        raise _lib.AmxEnvelopeError(int(status), f"anatomix_amd error {status}: {_lib.load().amx_last_error().decode()}")
-    _lib.check(status)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _f32c(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-
 def _labels_arg(labels, B, V):
     """Contiguous labels [B * V] in one of the dtypes the kernels read directly, and its dtype code."""
     if labels.numel() != B * V or labels.shape[0] != B:
@@ -95,9 +80,9 @@ class _SegLossFn(torch.autograd.Function):
         F = x.shape[1] if head else 0
         _envelope(C, F if head else None)
         V = x[0, 0].numel()
-        xc = _f32c(x.detach())
-        w = _f32c(weight.detach()).reshape(C, F) if head else None
-        b = _f32c(bias.detach()) if (head and bias is not None) else None
+        xc = _lib.f32c(x.detach())
+        w = _lib.f32c(weight.detach()).reshape(C, F) if head else None
+        b = _lib.f32c(bias.detach()) if (head and bias is not None) else None
         lab, lt = _labels_arg(labels, B, V)
         lib = _lib.load()
         dev = xc.device
@@ -106,9 +91,9 @@ class _SegLossFn(torch.autograd.Function):
         bad = torch.empty(1, dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             nb = lib.amx_seg_loss_scratch_bytes(B, V, C, F)
-            sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-            _check(lib.amx_seg_loss_forward(_lib.ptr(xc), F, _lib.ptr(w), _lib.ptr(b), _lib.ptr(lab), lt, B, C, V, *cfg.tail(),
-                                            _lib.ptr(loss3), _lib.ptr(stats), _lib.ptr(bad), _lib.ptr(sc), nb, _stream(dev)))
+            sc = _lib.scratch(nb, dev)
+            _lib.check_envelope(lib.amx_seg_loss_forward(_lib.ptr(xc), F, _lib.ptr(w), _lib.ptr(b), _lib.ptr(lab), lt, B, C, V, *cfg.tail(),
+                                _lib.ptr(loss3), _lib.ptr(stats), _lib.ptr(bad), _lib.ptr(sc), nb, _lib.stream(dev)))
         CALLS["head" if head else "logits"] += 1
         ctx.save_for_backward(xc, w, b, lab, stats)
         ctx.cfg, ctx.lt, ctx.dims = cfg, lt, (B, C, F, V)
@@ -125,16 +110,16 @@ class _SegLossFn(torch.autograd.Function):
         head = F > 0
         lib = _lib.load()
         dev = xc.device
-        g = _f32c(gout.detach())           # d / d {total, dice, ce}: the kernel reads element 0; the components are handed out detached
+        g = _lib.f32c(gout.detach())           # d / d {total, dice, ce}: the kernel reads element 0; the components are handed out detached
         dx = torch.empty_like(xc)
         dw = torch.empty((C, F), dtype=torch.float32, device=dev) if head else None
         db = torch.empty(C, dtype=torch.float32, device=dev) if head else None
         with torch.cuda.device(dev):
             nb = lib.amx_seg_loss_scratch_bytes(B, V, C, F) if head else 0
-            sc = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev) if head else None
-            _check(lib.amx_seg_loss_backward(_lib.ptr(xc), F, _lib.ptr(w), _lib.ptr(b), _lib.ptr(lab), ctx.lt, B, C, V, *ctx.cfg.tail(),
-                                             _lib.ptr(stats), _lib.ptr(g), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(sc), nb,
-                                             _stream(dev)))
+            sc = _lib.scratch(nb, dev) if head else None
+            _lib.check_envelope(lib.amx_seg_loss_backward(_lib.ptr(xc), F, _lib.ptr(w), _lib.ptr(b), _lib.ptr(lab), ctx.lt, B, C, V,
+                                *ctx.cfg.tail(), _lib.ptr(stats), _lib.ptr(g), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(sc), nb,
+                                _lib.stream(dev)))
         gx = dx.view(ctx.x_meta[0]).to(ctx.x_meta[1]) if ctx.needs_input_grad[0] else None
         gw = dw.view(ctx.w_meta[0]).to(ctx.w_meta[1]) if (head and ctx.needs_input_grad[1]) else None
         gb = db.to(ctx.b_dtype) if (ctx.b_dtype is not None and ctx.needs_input_grad[2]) else None
@@ -282,11 +267,11 @@ def predict_labels(features_or_logits, head=None):
     if conv is not None and F != conv.in_channels:
         raise ValueError(f"predict_labels: features [B, {conv.in_channels}, ...] (got {tuple(x.shape)})")
     _envelope(C, F if conv is not None else None)
-    xc = _f32c(x.detach())
-    w = _f32c(conv.weight.detach()).reshape(C, F) if conv is not None else None
-    b = _f32c(conv.bias.detach()) if (conv is not None and conv.bias is not None) else None
+    xc = _lib.f32c(x.detach())
+    w = _lib.f32c(conv.weight.detach()).reshape(C, F) if conv is not None else None
+    b = _lib.f32c(conv.bias.detach()) if (conv is not None and conv.bias is not None) else None
     out = torch.empty(out_shape, dtype=torch.uint8, device=xc.device)
     with torch.cuda.device(xc.device):
-        _check(_lib.load().amx_seg_argmax(_lib.ptr(xc), F, _lib.ptr(w), _lib.ptr(b), x.shape[0], C, xc[0, 0].numel(), _lib.ptr(out),
-                                          _stream(xc.device)))
+        _lib.check_envelope(_lib.load().amx_seg_argmax(_lib.ptr(xc), F, _lib.ptr(w), _lib.ptr(b), x.shape[0], C, xc[0, 0].numel(),
+                            _lib.ptr(out), _lib.stream(xc.device)))
     return out

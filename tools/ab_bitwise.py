@@ -1,0 +1,209 @@
+"""Bitwise A/B of two builds of libanatomix_amd.so over the entries of the streaming units (segmentation loss, augmentation,
+registration metrics, instance optimisation, MIND-SSC / correlation): the proof that a refactor of their shared helpers changed no
+summation order and no contraction.
+
+    python tools/ab_bitwise.py --old PATH/libanatomix_amd.so [--new PATH/libanatomix_amd.so]
+
+One process uses one library (anatomix_amd/_lib.py reads AMX_LIB_PATH at import), so each side runs in a fresh child process of
+its own (``--child``), one after the other and each under its own time limit.  A child runs every entry on seeded inputs and
+prints one SHA-256 per output tensor; the two listings are compared here and THAT comparison sets the exit status: 0 identical,
+1 different, 2 a child failed (the second one is then not started)."""
+import argparse
+import hashlib
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- child: one listing --------------------------------------------------------------------------------------------------
+
+def child():
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from anatomix_amd import _lib
+    from anatomix_amd.registration import convex_adam_utils as CU, instance_optimization as IO, metrics as RM
+    from anatomix_amd.segmentation import augment as G
+
+    dev = torch.device("cuda:0")
+    lib = _lib.load()
+    gen = torch.Generator().manual_seed(20240607)
+    count = [0]
+
+    def emit(name, t):
+        h = hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+        count[0] += 1
+        print(f"{name} {tuple(t.shape)} {str(t.dtype).split('.')[1]} {h}", flush=True)
+
+    def rand(*shape, offset=0):
+        """Seeded standard-normal device tensor; offset = 1 puts its base one float past an aligned allocation."""
+        buf = torch.empty(int(np.prod(shape)) + offset, dtype=torch.float32, device=dev)
+        buf[offset:] = torch.randn(int(np.prod(shape)), generator=gen).to(dev)
+        return buf[offset:].view(*shape)
+
+    def empty(*shape, offset=0):
+        return torch.empty(int(np.prod(shape)) + offset, dtype=torch.float32, device=dev)[offset:].view(*shape)
+
+    # ---- amx_seg_loss_forward / _backward / amx_seg_argmax, head mode and logits mode
+    LABEL = (torch.float32, torch.int64, torch.uint8)
+    seg_cases = [("V1", 1, 2, (1, 1, 1), 0), ("c5_17x16x19", 3, 5, (17, 16, 19), 0), ("c5_odd_17x15x19", 3, 5, (17, 15, 19), 0),
+                 ("V4096", 2, 3, (16, 16, 16), 0), ("V4096_off1", 2, 3, (16, 16, 16), 1), ("96cubed", 4, 5, (96, 96, 96), 0)]
+    for ci, (tag, B, C, size, off) in enumerate(seg_cases):
+        V = int(np.prod(size))
+        for F in (16, 0):
+            mode = "head" if F else "logits"
+            ldt = LABEL[(ci + (1 if F else 0)) % 3]
+            x = rand(B, F or C, V, offset=off)
+            w = rand(C, F) * 0.3 if F else None
+            b = rand(C) if F else None
+            lab = torch.randint(0, C, (B, V), generator=gen).to(ldt).to(dev)
+            loss, stats = torch.empty(3, dtype=torch.float32, device=dev), torch.empty(B, C, 3, dtype=torch.float32, device=dev)
+            bad = torch.empty(1, dtype=torch.int64, device=dev)
+            lt = _lib.SEG_LABEL[str(ldt).split(".")[1]]
+            tail = (0, 1e-5, 1e-5, 1.0, 1.0)        # include_background, smooth_nr, smooth_dr, lambda_dice, lambda_ce
+            nb = lib.amx_seg_loss_scratch_bytes(B, V, C, F)
+            sc = _lib.scratch(nb, dev)
+            _lib.check(lib.amx_seg_loss_forward(_lib.ptr(x), F, _lib.ptr(w), _lib.ptr(b), _lib.ptr(lab), lt, B, C, V, *tail,
+                                                _lib.ptr(loss), _lib.ptr(stats), _lib.ptr(bad), _lib.ptr(sc), nb, _lib.stream(dev)))
+            for n, t in (("loss", loss), ("stats", stats), ("bad", bad)):
+                emit(f"seg_loss_forward/{mode}/{tag}/{n}", t)
+            gout = torch.tensor([0.7, 0.0, 0.0], dtype=torch.float32, device=dev)
+            dx = empty(B, F or C, V, offset=off)
+            dw = torch.empty(C, F, dtype=torch.float32, device=dev) if F else None
+            db = torch.empty(C, dtype=torch.float32, device=dev) if F else None
+            _lib.check(lib.amx_seg_loss_backward(_lib.ptr(x), F, _lib.ptr(w), _lib.ptr(b), _lib.ptr(lab), lt, B, C, V, *tail,
+                                                 _lib.ptr(stats), _lib.ptr(gout), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
+                                                 _lib.ptr(sc) if F else None, nb, _lib.stream(dev)))
+            for n, t in (("dx", dx), ("dw", dw), ("db", db)):
+                if t is not None:
+                    emit(f"seg_loss_backward/{mode}/{tag}/{n}", t)
+            pred = torch.empty(B, V, dtype=torch.uint8, device=dev)
+            _lib.check(lib.amx_seg_argmax(_lib.ptr(x), F, _lib.ptr(w), _lib.ptr(b), B, C, V, _lib.ptr(pred), _lib.stream(dev)))
+            emit(f"seg_argmax/{mode}/{tag}/labels", pred)
+            del x, dx, lab, pred, sc
+
+    # ---- segaug: minmax (+ finalize), pointwise x 2, crop, gaussian x 2, affine, minmax_finalize of the affine's partials
+    B = 4
+    for s in (15, 16, 96):
+        size, tag = (s, s, s), f"{s}cubed"
+        vols = [rand(s + 3, s + 2, s + 1) for _ in range(B)]
+        labs = [torch.randint(0, 5, (s + 3, s + 2, s + 1), generator=gen).to(torch.uint8).to(dev) for _ in range(B)]
+        t = G._Table(B)
+        for i in range(B):
+            t.host["vol"][i], t.host["lab"][i] = vols[i].data_ptr(), labs[i].data_ptr()
+            t.host["vol_dim"][i] = vols[i].shape
+            t.host["corner"][i] = (i % 4, i % 3, i % 2)
+            t.host["flags"][i] = (G.RESCALE | G.CONTRAST | G.AFFINE | (G.NOISE if i != 1 else 0) | (G.BIAS if i != 2 else 0)
+                                  | (G.SMOOTH | G.SHARPEN if i != 3 else 0))
+            t.host["noise_std"][i] = 0.05 + 0.01 * i
+            t.host["bias"][i] = np.linspace(0.0, 0.05, 20) * (1 + i)
+            t.host["gamma"][i] = 0.6 + 0.9 * i
+            t.host["sharpen_alpha"][i] = 10.0 + 5.0 * i
+            t.host["affine"][i] = G.affine_matrix((0.1 * i, -0.2, 0.3), (0.05, -0.1, 0.02 * i), (1.1, 0.9, 1.0 + 0.05 * i)).reshape(9)
+        G._set_taps(t, 0, np.array([[0.5 + 0.1 * i, 0.6, 0.85] for i in range(B)]))
+        G._set_taps(t, 1, np.array([[0.8, 0.5 + 0.1 * i, 0.7] for i in range(B)]))
+        G._set_taps(t, 2, np.array([[0.5, 0.6, 0.5 + 0.05 * i] for i in range(B)]))
+        t.device(dev)
+        img, lab = G._crop(t, B, size, rand(B, 1, *size), torch.uint8, dev)
+        emit(f"segaug_crop/{tag}/img", img)
+        emit(f"segaug_crop/{tag}/lab", lab)
+        mm = G._minmax(img)
+        emit(f"segaug_minmax/{tag}/minmax", mm)
+        emit(f"segaug_pointwise/scale/{tag}/out", G._pointwise(img, torch.empty_like(img), mm, G._OP_SCALE, t))
+        pos = img.abs() + 0.1
+        emit(f"segaug_pointwise/contrast/{tag}/out", G._pointwise(pos, torch.empty_like(pos), G._minmax(pos), G._OP_CONTRAST, t))
+        emit(f"segaug_gaussian/smooth/{tag}/out", G._gaussian(img, G._GAUSS_SMOOTH, t))
+        emit(f"segaug_gaussian/sharpen/{tag}/out", G._gaussian(img, G._GAUSS_SHARPEN, t))
+        out, olab, sc, nb = G._affine(img, lab, size, t)
+        emit(f"segaug_affine/{tag}/img", out)
+        emit(f"segaug_affine/{tag}/lab", olab)
+        mm2 = torch.empty((B, 2), dtype=torch.float32, device=dev)
+        _lib.check(lib.amx_segaug_minmax_finalize(_lib.ptr(sc), nb, B, out[0].numel(), _lib.ptr(mm2), _lib.stream(dev)))
+        emit(f"segaug_minmax_finalize/{tag}/minmax", mm2)
+        del vols, labs, img, lab, out, olab, pos
+
+    # ---- registration metrics
+    for shape in ((7, 9, 11), (32, 32, 32)):
+        tag = "x".join(map(str, shape))
+        a = torch.randint(0, 14, shape, generator=gen)
+        bb = torch.where(torch.rand(shape, generator=gen) < 0.8, a, torch.randint(0, 20, shape, generator=gen))     # some >= bins: bad
+        for da, db_ in ((torch.uint8, torch.int64), (torch.float32, torch.uint8)):
+            counts, nbad = RM._overlap(a.to(da).to(dev), bb.to(db_).to(dev), 16)
+            pair = f"{str(da).split('.')[1]}_{str(db_).split('.')[1]}"
+            emit(f"label_overlap/{tag}/{pair}/counts", counts)
+            emit(f"label_overlap/{tag}/{pair}/bad", nbad)
+        jdet, stats = CU._jacobian_call(rand(3, *shape) * 0.3, 1, True, True)
+        emit(f"jacobian_det/{tag}/jdet", jdet)
+        emit(f"jacobian_det/{tag}/stats", stats)
+
+    # ---- instance optimisation (12 x 10 x 14, c = 3, g = 1) and the stage-1 features (5 x 8 x 16; 7 channels on 6 x 9 x 11)
+    h, w, d, c = 12, 10, 14, 3
+    wgt, fix, mov = rand(1, 3, h, w, d) * 0.5, rand(1, c, h, w, d), rand(1, c, h, w, d)
+    for n, tns in zip(("grad", "disp_sample", "loss", "reg"), IO.instance_opt_grad(wgt, fix, mov, 0.75)):
+        emit(f"instance_opt_grad/{h}x{w}x{d}/{n}", tns)
+    emit(f"run_instance_opt/{h}x{w}x{d}/niter5/out", IO.run_instance_opt(wgt * 2, fix, mov, 1, 0.75, (h, w, d), 5, 0))
+    emit(f"run_instance_opt/{h}x{w}x{d}/niter5_smooth3/out", IO.run_instance_opt(wgt * 2, fix, mov, 1, 0.75, (h, w, d), 5, 3))
+    emit("mindssc/5x8x16/r1d2/out", CU.MINDSSC(rand(1, 1, 5, 8, 16).abs(), 1, 2))
+    emit("mindssc/5x8x16/r2d2/out", CU.MINDSSC(rand(1, 1, 5, 8, 16).abs(), 2, 2))
+    ssd, amin = CU.correlate(rand(1, 7, 6, 9, 11), rand(1, 7, 6, 9, 11), 1, 1, (6, 9, 11), 7)
+    emit("correlate_ssd/6x9x11/hw1/ssd", ssd)
+    emit("correlate_ssd/6x9x11/hw1/argmin", amin)
+    torch.cuda.synchronize()
+    print(f"# {count[0]} tensors from {_lib.LIB_PATH}", flush=True)
+
+
+# ---- parent: two children, one comparison -----------------------------------------------------------------------------------
+
+def run_side(name, lib_path, timeout):
+    env = dict(os.environ, AMX_LIB_PATH=os.path.abspath(lib_path))
+    try:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True, timeout=timeout)
+    except subprocess.TimeoutExpired:
+        print(f"{name}: no listing within {timeout} s")
+        return None
+    if r.returncode != 0:
+        print(f"{name}: child exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}")
+        return None
+    return [ln for ln in r.stdout.splitlines() if ln and not ln.startswith("#")]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--child", action="store_true", help="print this process's listing (AMX_LIB_PATH selects the library)")
+    ap.add_argument("--old", help="the library to compare against (e.g. the parent commit's build)")
+    ap.add_argument("--new", default=os.path.join(ROOT, "anatomix_amd", "csrc", "libanatomix_amd.so"))
+    ap.add_argument("--timeout", type=float, default=240.0, help="seconds per child")
+    ap.add_argument("--print-listings", action="store_true")
+    a = ap.parse_args()
+    if a.child:
+        return child()
+    if not a.old:
+        ap.error("--old is required")
+    listings = {}
+    for name, path in (("old", a.old), ("new", a.new)):
+        if not os.path.exists(path):
+            print(f"{name}: {path} does not exist")
+            return 2
+        listings[name] = run_side(name, path, a.timeout)
+        if listings[name] is None:
+            return 2
+    old, new = listings["old"], listings["new"]
+    if a.print_listings:
+        print("\n".join(new))
+    key = lambda ln: ln.split(" (")[0]
+    do, dn = {key(ln): ln for ln in old}, {key(ln): ln for ln in new}
+    diff = [k for k in do if do[k] != dn.get(k)] + [k for k in dn if k not in do]
+    for k in diff:
+        print(f"DIFFERENT {k}\n  old {do.get(k)}\n  new {dn.get(k)}")
+    if diff or len(old) != len(new) or not old:
+        print(f"ab_bitwise: {len(diff)} of {len(old)} tensors differ between {a.old} and {a.new}")
+        return 1
+    print(f"ab_bitwise: identical, {len(old)} tensors, {a.old} against {a.new}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

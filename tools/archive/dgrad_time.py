@@ -20,11 +20,10 @@ def timeit(f, k=20):
     return e0.elapsed_time(e1) / k * 1e3
 print(f"{cout}->{cin} dgrad @{S}^3 x{n}: framed conv {timeit(lambda: T.conv_dgrad_framed(fr, w)):.1f} us, + pad_fold {timeit(lambda: T.pad_fold(T.conv_dgrad_framed(fr, w))):.1f} us; "
       f"direct {timeit(lambda: T.conv_dgrad_direct(fr, w)):.1f} us")
-import ctypes
 from anatomix_amd import _lib
 lib = _lib.load()
 out = T.conv_dgrad_direct(fr, w)
 tab = torch.empty(lib.amx_conv3d_dgrad_shell_scratch_bytes(), dtype=torch.uint8, device=dev)
 def shell():
-    _lib.check(lib.amx_conv3d_dgrad_fold_shell(_lib.ptr(fr), cout, _lib.ptr(w), cout, cin, _lib.ptr(out), out.shape[-1], n, S, S, S, 1, _lib.ptr(tab), T._st(dev)))
+    _lib.check(lib.amx_conv3d_dgrad_fold_shell(_lib.ptr(fr), cout, _lib.ptr(w), cout, cin, _lib.ptr(out), out.shape[-1], n, S, S, S, 1, _lib.ptr(tab), _lib.stream(dev)))
 print(f"shell kernel alone {timeit(shell):.1f} us")

@@ -134,7 +134,8 @@ class HipStages:
     def rescale(self, x):
         _, _, sc, nb = self.aff
         mm = torch.empty((B, 2), dtype=torch.float32, device=self.dev)
-        G._check(G._lib.load().amx_segaug_minmax_finalize(G._lib.ptr(sc), nb, B, x[0].numel(), G._lib.ptr(mm), G._stream(self.dev)))
+        G._lib.check_envelope(G._lib.load().amx_segaug_minmax_finalize(G._lib.ptr(sc), nb, B, x[0].numel(), G._lib.ptr(mm),
+                              G._lib.stream(self.dev)))
         return G._pointwise(x, torch.empty_like(x), mm, G._OP_SCALE, self.t)
 
 
