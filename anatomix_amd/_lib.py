@@ -182,6 +182,10 @@ SYMBOLS = {
     "amx_segaug_crop": (_I, [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "amx_segaug_gaussian": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "amx_segaug_affine": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "amx_preaug_view_bytes": (C.c_size_t, []),
+    "amx_preaug_spatial": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "amx_preaug_blur": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "amx_preaug_intensity": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "amx_label_overlap": (_I, [_P, _I, _P, _I, C.c_longlong, _I, _P, _P, _P]),
     "amx_jacobian_det_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "amx_jacobian_det": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),

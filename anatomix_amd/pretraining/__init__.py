@@ -6,6 +6,9 @@
   contrastive_step .. the per-batch body of SupCLModel.optimize_parameters / forward / calculate_NCE_loss
                       (supcl_model.py:603-661, 723-843) without the option parsing / logging around it.
   FusedAdamW ........ torch.optim.AdamW as built at supcl_model.py:510-516, 584-590: one HIP launch per optimizer (amx_adamw_step)
+  augment ........... the TorchIO branch of H5SupCLDataset (pretraining/data/h5supcl_dataset.py:122-178, 260-303) on the device:
+                      flip + affine, blur, noise, bias field, gamma, motion (HIP kernels of csrc/amx_preaug.hip; torch.fft for motion)
+  AugmentedTwoViewLoader  the loader that feeds the step: H5SupCLDataset + augment_pair + the crop, collated device batches
 The UNet inside the step runs forward and backward on the HIP kernels (anatomix_amd.model.train).
 """
 from .supcon import SupPatchNCELoss
@@ -14,5 +17,9 @@ from .step import contrastive_step, GraphedContrastiveStep, StepRecord
 from .data_parallel import GradientBuckets
 from .optim import FusedAdamW
 from .data import H5SupCLDataset, random_crop
+from . import augment, loader
+from .augment import augment_pair, draw_params
+from .loader import AugmentedTwoViewLoader
 
-__all__ = ["SupPatchNCELoss", "PatchSampleF", "contrastive_step", "GraphedContrastiveStep", "StepRecord", "GradientBuckets", "FusedAdamW", "H5SupCLDataset", "random_crop"]
+__all__ = ["SupPatchNCELoss", "PatchSampleF", "contrastive_step", "GraphedContrastiveStep", "StepRecord", "GradientBuckets", "FusedAdamW", "H5SupCLDataset", "random_crop",
+           "augment", "loader", "augment_pair", "draw_params", "AugmentedTwoViewLoader"]

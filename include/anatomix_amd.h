@@ -826,6 +826,60 @@ int amx_segaug_affine(const float* d_img_in, const unsigned char* d_lab_in, int 
                       unsigned char* d_lab_out, int d, int h, int w, const amx_segaug_sample* h_table,
                       const amx_segaug_sample* d_table, void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- contrastive pretraining: the two-view augmentation of H5SupCLDataset (pretraining/data/h5supcl_dataset.py:122-178,
+ * 260-303) on one pair (csrc/amx_preaug.hip; fp32 [views][d][h][w] with w contiguous, labels uint8, on `stream` without host
+ * synchronisation, read-back or allocation).  One launch per stage with the view on grid.y.  What differs per view sits in a
+ * table of `views` amx_preaug_view records that the caller fills on the host and copies to the device once per pair: every entry
+ * takes the host copy h_table (read for validation only) and the device copy d_table (read by the kernels).  A view whose switch
+ * for a stage is off is copied through that stage bit for bit.  Nothing is accumulated across threads and there are no float
+ * atomics, so a pair is bit-identical from run to run.  16-byte accesses where the sizes divide by 4 and the bases are 16-byte
+ * aligned, scalar ones otherwise.  TorchIO is not a dependency: its documented algorithms are restated
+ * and parity with an installed TorchIO is not pinned.  Every entry validates its arguments (axes <= 2^29, fewer than 2^31 voxels
+ * per view) and returns an error without launching anything. ---- */
+enum {
+  AMX_PREAUG_SPATIAL = 1,    /* RandomFlip and / or RandomAffine, folded into `map` (h5supcl_dataset.py:149-178, 279-290) */
+  AMX_PREAUG_BLUR = 2,       /* RandomBlur (h5supcl_dataset.py:130-132) */
+  AMX_PREAUG_NOISE = 4,      /* RandomNoise (h5supcl_dataset.py:133-135) */
+  AMX_PREAUG_BIAS = 8,       /* RandomBiasField (h5supcl_dataset.py:136-138) */
+  AMX_PREAUG_GAMMA = 16      /* RandomGamma (h5supcl_dataset.py:139-143) */
+};
+enum { AMX_PREAUG_MAX_RADIUS = 8 };
+
+typedef struct amx_preaug_view {
+  int32_t flags;             /* AMX_PREAUG_* switches */
+  float map[12];             /* 3 x 4, row major: source index on axis a of output voxel (z, y, x) = map[4a] z + map[4a+1] y + map[4a+2] x + map[4a+3] */
+  int32_t radius[3];         /* Gaussian radius per axis (d, h, w), 0 <= radius <= 8; 0 skips the axis */
+  float taps[3][17];         /* its 2 radius + 1 taps, tap k (-radius <= k <= radius) at index k + radius */
+  float noise_std;
+  float bias[20];            /* c_ijk of the monomials z^i y^j x^k, i + j + k <= 3, (i, j, k) in lexicographic order */
+  float gamma;
+} amx_preaug_view;
+
+/* sizeof(amx_preaug_view), for a caller that lays the table out without this header */
+size_t amx_preaug_view_bytes(void);
+
+/* RandomFlip + RandomAffine of the views and their shared label map in one gather launch (h5supcl_dataset.py:279-290, where the
+ * transform of view A is replayed on view B; also the rigid moves of RandomMotion, h5supcl_dataset.py:144-146, with one view and no
+ * label): d_in [views][d][h][w] -> d_out, d_lab_in [d][h][w] -> d_lab_out (both null, or neither; the label follows view 0's map).
+ * Image: trilinear, a corner outside the input contributes the view's pad value d_minmax[2 view] (amx_segaug_minmax's output, the
+ * minimum first).  Label: the voxel at the source index rounded half to even, 0 outside.  A source index that is integral on all
+ * three axes copies the voxel bit for bit, so flips and the identity are exact.  Inputs and outputs must not overlap. */
+int amx_preaug_spatial(const float* d_in, const unsigned char* d_lab_in, int views, int d, int h, int w, const float* d_minmax, float* d_out,
+                       unsigned char* d_lab_out, const amx_preaug_view* h_table, const amx_preaug_view* d_table, void* stream);
+
+/* RandomBlur (h5supcl_dataset.py:130-132): the separable Gaussian of scipy.ndimage.gaussian_filter with the table's taps,
+ * mode='reflect' (the reflection repeats where the radius exceeds the axis).  Two launches, both served from LDS tiles: w and h
+ * fused over a plane tile into d_tmp, then a march along d through a ring of planes.  d_tmp holds views d h w floats; d_in, d_out
+ * and d_tmp must not overlap.  A radius above 8 (sigma > 2) in a view whose switch is on is AMX_ERR_INVALID. */
+int amx_preaug_blur(const float* d_in, float* d_out, float* d_tmp, int views, int d, int h, int w, const amx_preaug_view* h_table,
+                    const amx_preaug_view* d_table, void* stream);
+
+/* RandomNoise, RandomBiasField and RandomGamma (h5supcl_dataset.py:133-143) in one pointwise launch:
+ * y = x + noise_std d_noise; y *= exp(f), f the cubic polynomial of `bias` over linspace(-1, 1, size) per axis; y = sign(y) |y|^gamma,
+ * each under its switch.  d_noise [views][d][h][w] standard normal, nullable when no view has AMX_PREAUG_NOISE.  d_out may be d_in. */
+int amx_preaug_intensity(const float* d_in, const float* d_noise, float* d_out, int views, int d, int h, int w, const amx_preaug_view* h_table,
+                         const amx_preaug_view* d_table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
