@@ -186,6 +186,15 @@ SYMBOLS = {
     "amx_preaug_spatial": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "amx_preaug_blur": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "amx_preaug_intensity": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "amx_synth_view_bytes": (C.c_size_t, []),
+    "amx_synth_scratch_bytes": (C.c_size_t, [_I, C.c_longlong]),
+    "amx_synth_gmm_minmax": (_I, [_P, _P, _I, C.c_longlong, _P, _P, _P, C.c_size_t, _P]),
+    "amx_synth_appearance": (_I, [_P, _P, C.POINTER(_P), C.POINTER(_I), _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "amx_synth_logk_mean": (_I, [_P, _I, C.c_longlong, _P, _P, C.c_size_t, _P]),
+    "amx_synth_spike": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "amx_synth_lowres": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "amx_synth_clip_minmax": (_I, [_P, _I, C.c_longlong, _P, C.c_size_t, _P]),
+    "amx_synth_finish": (_I, [_P, _P, _I, C.c_longlong, _P, _I, _P]),
     "amx_label_overlap": (_I, [_P, _I, _P, _I, C.c_longlong, _I, _P, _P, _P]),
     "amx_jacobian_det_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "amx_jacobian_det": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),

@@ -880,6 +880,90 @@ int amx_preaug_blur(const float* d_in, float* d_out, float* d_tmp, int views, in
 int amx_preaug_intensity(const float* d_in, const float* d_noise, float* d_out, int views, int d, int h, int w, const amx_preaug_view* h_table,
                          const amx_preaug_view* d_table, void* stream);
 
+/* ---- synthetic data generation, step 2: two views per label map (synthetic-data-generation/step2_generate_views.py with
+ * datagen_utils.py:475-646) on a batch (csrc/amx_synth.hip; fp32 rows [n][d][h][w] with n = 2 batch and row = 2 sample + view,
+ * labels uint8 [batch][d][h][w], on `stream` without host synchronisation, read-back or allocation).  One launch per stage with
+ * the row on grid.y.  What differs per row sits in a table of n amx_synth_view records that the caller fills on the host and
+ * copies to the device once per batch: every entry that takes it takes the host copy h_table (read for validation only) and the
+ * device copy d_table (read by the kernels).  A row whose switch for a stage is off passes that stage bit for bit.  Minimum and
+ * maximum leave per-workgroup partials in d_scratch in the layout of amx_segaug_minmax_finalize (same rows, voxels), which turns
+ * them into [n][2]; sums are two-level in a fixed order; no float atomics, so a batch is bit-identical from run to run.  16-byte
+ * accesses where voxels % 4 == 0 and the bases are aligned, scalar ones otherwise.  The stages the segmentation chain already has
+ * (ScaleIntensity, bias field, AdjustContrast, Gaussian smooth and sharpen) are the amx_segaug_* entries.  MONAI is not a
+ * dependency: KSpaceSpikeNoise and SimulateLowResolution are restated from their documented algorithms
+ * and parity with an installed MONAI is not pinned.  Every entry validates its arguments and returns an error without launching
+ * anything. ---- */
+enum {
+  AMX_SYNTH_ZERO_BACKGROUND = 1, /* sample_gmm skipped the first label: rank 0 is exactly 0 */
+  AMX_SYNTH_SPIKE = 2,           /* RandKSpaceSpikeNoise */
+  AMX_SYNTH_SPIKE_FIXED = 4,     /* the spike's log-magnitude is spike_intensity, not spike_factor * 2.5 * mean(log(|k| + 1e-10)) */
+  AMX_SYNTH_LOWRES = 8           /* RandSimulateLowResolution */
+};
+enum { AMX_SYNTH_MAX_SCALES = 8 };
+
+typedef struct amx_synth_view {
+  int32_t flags;             /* AMX_SYNTH_* switches */
+  int32_t nlabels;           /* number of distinct labels of the sample, 1 .. 256 */
+  uint8_t rank[256];         /* label -> its position among the sample's sorted distinct labels (labels not present: anything < nlabels) */
+  float mean[256];           /* per rank */
+  float std[256];
+  float perl_mult;           /* view = s * (1 + perl_mult * P) */
+  int32_t spike_loc[3];      /* index of the spike in the SHIFTED k-space (fftshift), 0 <= loc < size */
+  int32_t spike_slot;        /* row of d_k (and of d_logk_mean) that holds this row's transform */
+  float spike_factor;        /* u of k_intensity = u * 2.5 * mean(log(|k| + 1e-10)) */
+  float spike_intensity;     /* k_intensity itself under AMX_SYNTH_SPIKE_FIXED */
+  int32_t lowres[3];         /* size of the low-resolution grid, 1 <= lowres <= size */
+} amx_synth_view;
+
+/* sizeof(amx_synth_view), for a caller that lays the table out without this header */
+size_t amx_synth_view_bytes(void);
+/* bytes of d_scratch for the entries below that take it, for `rows` rows (0 for arguments outside the envelope); never less than
+ * amx_segaug_scratch_bytes(rows, voxels) */
+size_t amx_synth_scratch_bytes(int rows, long long voxels);
+
+/* Appearance pass 1: g = max(std[rank(label)] * noise + mean[rank(label)], 0), exactly 0 at rank 0 under
+ * AMX_SYNTH_ZERO_BACKGROUND, is evaluated and not stored; d_scratch receives the min / max partials of g for the 2 batch rows.
+ * d_labels [batch][voxels] is shared by a sample's two views, d_noise [2 batch][voxels] is standard normal.  A row with one label
+ * and a zero background (a constant volume) is AMX_ERR_INVALID.  One launch. */
+int amx_synth_gmm_minmax(const unsigned char* d_labels, const float* d_noise, int batch, long long voxels, const amx_synth_view* h_table,
+                         const amx_synth_view* d_table, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* Appearance pass 2: d_out [2 batch][d][h][w] = (g - min) / (max - min) * (1 + perl_mult * P) with {min, max} = d_gmm_minmax
+ * [2 batch][2] (pass 1 finalized) and P = sum over the nscales scales of the trilinear upsample (align_corners=False, source
+ * coordinate max((o + 0.5) / scale - 0.5, 0), upper neighbour clamped) of d_grids[s] [2 batch][d / scale][h / scale][w / scale];
+ * d_grids and scales are HOST arrays of nscales entries.  g and P are evaluated on the fly; the coarse values a workgroup's tile
+ * needs are interpolated along d and h into LDS first.  Every scale must divide d, h and w (AMX_ERR_SHAPE otherwise, as for a w
+ * whose collapsed rows exceed 48 KiB of LDS).  d_scratch receives the min / max partials of d_out.  One launch. */
+int amx_synth_appearance(const unsigned char* d_labels, const float* d_noise, const float* const* d_grids, const int* scales, int nscales,
+                         const float* d_gmm_minmax, float* d_out, int batch, int d, int h, int w, const amx_synth_view* h_table,
+                         const amx_synth_view* d_table, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* d_mean [rows] = mean over a row of log(|k| + 1e-10), d_k [rows][voxels] complex64 (interleaved, 8-byte aligned; fftn's
+ * output, shifted or not).  Per-thread double sums, a tree per workgroup, a second level over the partials.  Two launches. */
+int amx_synth_logk_mean(const float* d_k, int rows, long long voxels, float* d_mean, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* KSpaceSpikeNoise without the inverse transform, in place on the rows with AMX_SYNTH_SPIKE (the others are not touched):
+ * setting log|k| at spike_loc of the shifted k-space to k_intensity with the phase kept adds one plane wave,
+ *   x(r) += Re(delta / N * exp(2 pi i sum_a f_a r_a / n_a)),  f_a = (loc_a - n_a / 2) mod n_a,  delta = exp(k_intensity) k[f] / |k[f]| - k[f]
+ * (phase 0 where k[f] = 0).  d_k [k_rows][d][h][w] complex64 is the UNSHIFTED fftn of the rows, row spike_slot for each of
+ * them; d_logk_mean [k_rows] is amx_synth_logk_mean's output (nullable when every spike is AMX_SYNTH_SPIKE_FIXED).  The phase
+ * is reduced modulo n_a in integers before the sine and cosine.  One launch. */
+int amx_synth_spike(float* d_x, const float* d_k, int k_rows, const float* d_logk_mean, int n, int d, int h, int w, const amx_synth_view* h_table,
+                    const amx_synth_view* d_table, void* stream);
+
+/* SimulateLowResolution(downsample_mode="nearest-exact", upsample_mode="trilinear", align_corners=False) as one gather: each
+ * output voxel blends the 8 low-resolution neighbours of its source coordinate, each of them read at its nearest-exact source
+ * voxel of d_in; float32 index arithmetic as torch's.  Rows without AMX_SYNTH_LOWRES are copied.  d_in and d_out must not
+ * overlap.  One launch. */
+int amx_synth_lowres(const float* d_in, float* d_out, int n, int d, int h, int w, const amx_synth_view* h_table, const amx_synth_view* d_table,
+                     void* stream);
+
+/* The tail.  amx_synth_clip_minmax: the min / max partials of max(x, 0) (ThresholdIntensity(above=True, threshold=0) folded into
+ * the statistics pass) into d_scratch.  amx_synth_finish: ScaleIntensity of max(x, 0) with d_minmax [n][2] ((c - min) / (max - min);
+ * c * 0 when min == max) as float32, or with out_u8 != 0 as uint8 trunc(255 * y); d_out may be d_in for float32.  One launch each. */
+int amx_synth_clip_minmax(const float* d_x, int n, long long voxels, void* d_scratch, size_t scratch_bytes, void* stream);
+int amx_synth_finish(const float* d_in, void* d_out, int n, long long voxels, const float* d_minmax, int out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
