@@ -212,6 +212,12 @@ size_t jacobian_det_scratch_bytes(int H, int W, int D);
 hipError_t launch_jacobian_det(const float* disp, int H, int W, int D, int add_identity, float* jdet, float* stats, void* scratch,
                                hipStream_t st);
 
+// amx_segaug.hip: the min / max of n rows of V floats (CLIP: of max(x, 0)) as per-workgroup partial pairs in `scratch`
+// (minmax_bytes), and their reduction to minmax[n][2]
+size_t minmax_bytes(int n, long long V);
+hipError_t launch_minmax_partials(const float* x, int n, long long V, bool clip, void* scratch, hipStream_t st);
+hipError_t launch_minmax_finalize(const void* scratch, int n, long long V, float* minmax, hipStream_t st);
+
 // amx_attention.hip
 size_t attention_scratch_bytes(int b, int heads, int n);
 void attention_operands(void* scratch, int b, int heads, int n, void** Qp, void** Kp, void** Vt, int* npad_out, int* nblk_pad_out);
@@ -225,6 +231,31 @@ int fail(int code, const char* fmt, ...);
 // the scratch check of the C ABI entries: AMX_OK, or AMX_ERR_WORKSPACE when the caller's `got` bytes are fewer than `need`
 inline int need_scratch(size_t need, size_t got) {
   return got < need ? fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, got) : AMX_OK;
+}
+
+// the checks of the row-streaming C ABI units (amx_segaug.hip, amx_preaug.hip, amx_synth.hip).  A unit names its rows: `count` is
+// the argument ("n", "views", "rows"), `one` a single row ("sample", "view", "row").
+constexpr long long kMaxRowVoxels = 1LL << 31;      // per row: keeps every tile count inside an int
+inline bool row_count_ok(int n) { return n >= 1 && n <= 65535; }      // rows are grid.y
+inline bool row_voxels_ok(long long voxels) { return voxels >= 1 && voxels < kMaxRowVoxels; }
+inline bool rows_ok(int n, long long voxels) { return row_count_ok(n) && row_voxels_ok(voxels); }
+inline int check_rows(int n, long long voxels, const char* count, const char* one) {
+  if (!row_count_ok(n)) return fail(AMX_ERR_SHAPE, "1 <= %s <= 65535 (got %d)", count, n);
+  if (!row_voxels_ok(voxels)) return fail(AMX_ERR_SHAPE, "1 <= voxels < 2^31 per %s (got %lld)", one, voxels);
+  return AMX_OK;
+}
+inline int check_rows_dims(int n, int d, int h, int w, const char* count, const char* one) {
+  if (d < 1 || h < 1 || w < 1) return fail(AMX_ERR_SHAPE, "spatial sizes must be positive (got %d x %d x %d)", d, h, w);
+  return check_rows(n, (long long)d * h * w, count, one);
+}
+inline int check_tables(const void* h_table, const void* d_table) {
+  if (!h_table || !d_table) return fail(AMX_ERR_INVALID, "null parameter table (host copy and device copy are both needed)");
+  return AMX_OK;
+}
+inline bool is_finite(float v) { return v == v && v - v == 0.f; }
+inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
 }
 
 // precision helpers of the C ABI units (amx_api.hip, amx_unet.hip; kept here so that the two share one copy)

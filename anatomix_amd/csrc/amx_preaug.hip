@@ -19,17 +19,11 @@ using Pre = StreamTile<>;                  // a thread owns four voxels of a til
 using PreView = amx_preaug_view;
 constexpr int kPreMaxRadius = AMX_PREAUG_MAX_RADIUS, kPreTaps = 2 * kPreMaxRadius + 1;
 
-struct PreDims {
-  int d, h, w;
-  long long V;
-  int ntiles;
-};
-
 // ---- flip + affine (and the rigid moves of the motion artefact) ---------------------------------------------------------------
 // source index of output voxel o = M (z, y, x, 1); image: trilinear with `pad` for a corner outside, label: nearest (half to even)
 // with 0 outside.  The label follows view 0's map and is written by the workgroups of view 0.
 template <bool VEC>
-__global__ __launch_bounds__(Pre::kThreads) void pre_spatial_kernel(PreDims g, const float* __restrict__ in, const unsigned char* __restrict__ lab_in,
+__global__ __launch_bounds__(Pre::kThreads) void pre_spatial_kernel(StreamDims g, const float* __restrict__ in, const unsigned char* __restrict__ lab_in,
                                                                   const float* __restrict__ minmax, float* __restrict__ out,
                                                                   unsigned char* __restrict__ lab_out, const PreView* __restrict__ table) {
   const int n = blockIdx.y;
@@ -96,12 +90,6 @@ __device__ __forceinline__ int pre_reflect(int i, int n) {
   return m < n ? m : 2 * n - 1 - m;
 }
 
-// the taps of one axis centred in registers: tap[k + kPreMaxRadius], 0 outside the radius (uniform, so scalar loads)
-__device__ __forceinline__ void pre_load_taps(const PreView& s, int axis, int r, float (&tap)[kPreTaps]) {
-#pragma unroll
-  for (int k = -kPreMaxRadius; k <= kPreMaxRadius; ++k) tap[k + kPreMaxRadius] = (k >= -r && k <= r) ? s.taps[axis][k + r] : 0.f;
-}
-
 // W and H in one kernel over a plane tile of kBlurTH x kBlurTW outputs.  The tile and a halo of 8 on every side are staged in LDS
 // once, reflected while staging (the reflected row and column of every staged position are computed once per workgroup); the W pass
 // reads the stage and writes the rows the H pass needs; the H pass reads those.  A lane owns a column, a wave a row of 64: every
@@ -114,7 +102,7 @@ struct PreBlurGrid {
   int tiles_x, tiles_y;
 };
 
-__global__ __launch_bounds__(Pre::kThreads) void pre_blur_wh_kernel(PreDims g, PreBlurGrid bg, const float* __restrict__ in, float* __restrict__ out,
+__global__ __launch_bounds__(Pre::kThreads) void pre_blur_wh_kernel(StreamDims g, PreBlurGrid bg, const float* __restrict__ in, float* __restrict__ out,
                                                                   const PreView* __restrict__ table) {
   __shared__ float stage[kBlurSH][kBlurSW];
   __shared__ float mid[kBlurSH][kBlurTW];
@@ -146,7 +134,7 @@ __global__ __launch_bounds__(Pre::kThreads) void pre_blur_wh_kernel(PreDims g, P
   }
   __syncthreads();
   float tap[kPreTaps];
-  pre_load_taps(s, 2, rw, tap);
+  load_centred_taps<kPreMaxRadius>(s.taps[2], rw, tap);
   for (int row = lo + ly0; row < hi; row += kRowsPerPass) {
     float acc = stage[row][lx + kPreMaxRadius];
     if (rw > 0) {
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(Pre::kThreads) void pre_blur_wh_kernel(PreDims g, P
     mid[row][lx] = acc;
   }
   __syncthreads();
-  pre_load_taps(s, 1, rh, tap);
+  load_centred_taps<kPreMaxRadius>(s.taps[1], rh, tap);
   for (int y = ly0; y < kBlurTH; y += kRowsPerPass) {
     float acc = mid[y + kPreMaxRadius][lx];
     if (rh > 0) {
@@ -179,7 +167,7 @@ __global__ __launch_bounds__(Pre::kThreads) void pre_blur_wh_kernel(PreDims g, P
 constexpr int kBlurZChunk = 32;
 
 template <bool VEC>
-__global__ __launch_bounds__(Pre::kThreads) void pre_blur_d_kernel(PreDims g, int plane_tiles, const float* __restrict__ in, float* __restrict__ out,
+__global__ __launch_bounds__(Pre::kThreads) void pre_blur_d_kernel(StreamDims g, int plane_tiles, const float* __restrict__ in, float* __restrict__ out,
                                                                  const PreView* __restrict__ table) {
   __shared__ __attribute__((aligned(16))) float ring[kPreTaps][Pre::kTile];
   const int n = blockIdx.y;
@@ -248,11 +236,8 @@ __global__ __launch_bounds__(Pre::kThreads) void pre_blur_d_kernel(PreDims g, in
 }
 
 // ---- noise + bias field + gamma ---------------------------------------------------------------------------------------------
-// coordinate i of linspace(-1, 1, n)
-__device__ __forceinline__ float pre_lin(int i, int n) { return n > 1 ? -1.f + 2.f * (float)i / (float)(n - 1) : -1.f; }
-
 template <bool VEC>
-__global__ __launch_bounds__(Pre::kThreads) void pre_intensity_kernel(PreDims g, const float* in, const float* __restrict__ noise, float* out,
+__global__ __launch_bounds__(Pre::kThreads) void pre_intensity_kernel(StreamDims g, const float* in, const float* __restrict__ noise, float* out,
                                                                     const PreView* __restrict__ table) {
   const int n = blockIdx.y;
   const PreView& s = table[n];
@@ -273,17 +258,11 @@ __global__ __launch_bounds__(Pre::kThreads) void pre_intensity_kernel(PreDims g,
       float a = v[j];
       if (do_noise) a += std * nz[j];
       if (do_bias) {
-        const float x = pre_lin((int)(o % g.w), g.w), y = pre_lin((int)((o / g.w) % g.h), g.h), z = pre_lin((int)(o / ((long long)g.w * g.h)), g.d);
+        int iz, iy, ix;
+        g.split(o, iz, iy, ix);
+        const float x = lin_coord(ix, g.w), y = lin_coord(iy, g.h), z = lin_coord(iz, g.d);
         const float pz[4] = {1.f, z, z * z, z * z * z}, py[4] = {1.f, y, y * y, y * y * y}, px[4] = {1.f, x, x * x, x * x * x};
-        float f = 0.f;
-        int q = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4 - i; ++jj)
-#pragma unroll
-            for (int k = 0; k < 4 - i - jj; ++k) f += c[q++] * (pz[i] * py[jj] * px[k]);
-        a *= expf(f);
+        a *= expf(poly3_sum(c, pz, py, px));
       }
       if (do_gamma) a = copysignf(powf(fabsf(a), gamma), a);
       v[j] = a;
@@ -293,15 +272,9 @@ __global__ __launch_bounds__(Pre::kThreads) void pre_intensity_kernel(PreDims g,
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------
-static PreDims pre_dims(int d, int h, int w) {
-  PreDims g;
-  g.d = d, g.h = h, g.w = w, g.V = (long long)d * h * w, g.ntiles = (int)Pre::tiles(g.V);
-  return g;
-}
-
 static hipError_t launch_preaug_spatial(const float* in, const unsigned char* lab_in, int views, int d, int h, int w, const float* minmax, float* out,
                                         unsigned char* lab_out, const PreView* table, hipStream_t st) {
-  const PreDims g = pre_dims(d, h, w);
+  const StreamDims g = StreamDims::make(d, h, w);
   const dim3 grid(Pre::chunks(views, g.V), views);
   if (g.V % 4 == 0 && aligned16(out) && (!lab_out || aligned4(lab_out)))
     pre_spatial_kernel<true><<<grid, Pre::kThreads, 0, st>>>(g, in, lab_in, minmax, out, lab_out, table);
@@ -313,7 +286,7 @@ static long long preaug_blur_wh_blocks(int d, int h, int w) { return (long long)
 static long long preaug_blur_d_blocks(int d, int h, int w) { return Pre::tiles((long long)h * w) * cdiv(d, kBlurZChunk); }
 
 static hipError_t launch_preaug_blur(const float* in, float* out, float* tmp, int views, int d, int h, int w, const PreView* table, hipStream_t st) {
-  const PreDims g = pre_dims(d, h, w);
+  const StreamDims g = StreamDims::make(d, h, w);
   PreBlurGrid bg;
   bg.tiles_x = cdiv(w, kBlurTW), bg.tiles_y = cdiv(h, kBlurTH);
   pre_blur_wh_kernel<<<dim3((unsigned)preaug_blur_wh_blocks(d, h, w), views), Pre::kThreads, 0, st>>>(g, bg, in, tmp, table);
@@ -329,7 +302,7 @@ static hipError_t launch_preaug_blur(const float* in, float* out, float* tmp, in
 
 static hipError_t launch_preaug_intensity(const float* in, const float* noise, float* out, int views, int d, int h, int w, const PreView* table,
                                           hipStream_t st) {
-  const PreDims g = pre_dims(d, h, w);
+  const StreamDims g = StreamDims::make(d, h, w);
   const dim3 grid(Pre::chunks(views, g.V), views);
   if (g.V % 4 == 0 && aligned16(in) && aligned16(out) && (!noise || aligned16(noise)))
     pre_intensity_kernel<true><<<grid, Pre::kThreads, 0, st>>>(g, in, noise, out, table);
@@ -341,22 +314,12 @@ static hipError_t launch_preaug_intensity(const float* in, const float* noise, f
 
 namespace {
 using amx::fail;
-constexpr long long kPreMaxVoxels = 1LL << 31;      // per view: keeps every tile count inside an int
 constexpr int kPreMaxAxis = 1 << 29;                // keeps 2 * axis + halo inside an int (the reflection)
 
 int pre_check(int views, int d, int h, int w, const void* h_table, const void* d_table) {
-  if (views < 1 || views > 65535) return fail(AMX_ERR_SHAPE, "1 <= views <= 65535 (got %d)", views);
-  if (d < 1 || h < 1 || w < 1) return fail(AMX_ERR_SHAPE, "spatial sizes must be positive (got %d x %d x %d)", d, h, w);
   if (d > kPreMaxAxis || h > kPreMaxAxis || w > kPreMaxAxis) return fail(AMX_ERR_SHAPE, "an axis above 2^29 (got %d x %d x %d)", d, h, w);
-  const long long voxels = (long long)d * h * w;
-  if (voxels >= kPreMaxVoxels) return fail(AMX_ERR_SHAPE, "1 <= voxels < 2^31 per view (got %lld)", voxels);
-  if (!h_table || !d_table) return fail(AMX_ERR_INVALID, "null parameter table (host copy and device copy are both needed)");
-  return AMX_OK;
-}
-bool pre_finite(float v) { return v == v && v - v == 0.f; }
-bool pre_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
+  if (int rc = amx::check_rows_dims(views, d, h, w, "views", "view")) return rc;
+  return amx::check_tables(h_table, d_table);
 }
 }  // namespace
 
@@ -370,12 +333,12 @@ int amx_preaug_spatial(const float* d_in, const unsigned char* d_lab_in, int vie
   if (!d_in || !d_out || !d_minmax) return fail(AMX_ERR_INVALID, "null input, output or statistics");
   if ((d_lab_in == nullptr) != (d_lab_out == nullptr)) return fail(AMX_ERR_INVALID, "d_lab_in and d_lab_out: both or neither");
   const size_t vox = (size_t)d * h * w;
-  if (pre_overlap(d_in, views * vox * 4, d_out, views * vox * 4) || (d_lab_in && pre_overlap(d_lab_in, vox, d_lab_out, vox)))
+  if (amx::overlap(d_in, views * vox * 4, d_out, views * vox * 4) || (d_lab_in && amx::overlap(d_lab_in, vox, d_lab_out, vox)))
     return fail(AMX_ERR_INVALID, "inputs and outputs must not overlap");
   for (int i = 0; i < views; ++i)
     if (h_table[i].flags & AMX_PREAUG_SPATIAL)
       for (int q = 0; q < 12; ++q)
-        if (!pre_finite(h_table[i].map[q])) return fail(AMX_ERR_INVALID, "view %d: map entry %d is not finite", i, q);
+        if (!amx::is_finite(h_table[i].map[q])) return fail(AMX_ERR_INVALID, "view %d: map entry %d is not finite", i, q);
   AMX_HIP(amx::launch_preaug_spatial(d_in, d_lab_in, views, d, h, w, d_minmax, d_out, d_lab_out, d_table, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -385,7 +348,7 @@ int amx_preaug_blur(const float* d_in, float* d_out, float* d_tmp, int views, in
   if (int rc = pre_check(views, d, h, w, h_table, d_table)) return rc;
   if (!d_in || !d_out || !d_tmp) return fail(AMX_ERR_INVALID, "null input, output or temporary");
   const size_t bytes = (size_t)views * d * h * w * sizeof(float);
-  if (pre_overlap(d_in, bytes, d_out, bytes) || pre_overlap(d_in, bytes, d_tmp, bytes) || pre_overlap(d_out, bytes, d_tmp, bytes))
+  if (amx::overlap(d_in, bytes, d_out, bytes) || amx::overlap(d_in, bytes, d_tmp, bytes) || amx::overlap(d_out, bytes, d_tmp, bytes))
     return fail(AMX_ERR_INVALID, "d_in, d_out and d_tmp must not overlap");
   if (amx::preaug_blur_wh_blocks(d, h, w) > 0x7fffffffLL || amx::preaug_blur_d_blocks(d, h, w) > 0x7fffffffLL)
     return fail(AMX_ERR_SHAPE, "%d x %d x %d needs more workgroups than a launch has", d, h, w);
@@ -396,7 +359,7 @@ int amx_preaug_blur(const float* d_in, float* d_out, float* d_tmp, int views, in
       if (r < 0 || r > AMX_PREAUG_MAX_RADIUS)
         return fail(AMX_ERR_INVALID, "view %d axis %d: radius %d is outside 0 .. %d (sigma <= 2)", i, a, r, AMX_PREAUG_MAX_RADIUS);
       for (int k = 0; k <= 2 * r; ++k)
-        if (!pre_finite(h_table[i].taps[a][k])) return fail(AMX_ERR_INVALID, "view %d axis %d: tap %d is not finite", i, a, k);
+        if (!amx::is_finite(h_table[i].taps[a][k])) return fail(AMX_ERR_INVALID, "view %d axis %d: tap %d is not finite", i, a, k);
     }
   }
   AMX_HIP(amx::launch_preaug_blur(d_in, d_out, d_tmp, views, d, h, w, d_table, (hipStream_t)stream));
@@ -408,16 +371,16 @@ int amx_preaug_intensity(const float* d_in, const float* d_noise, float* d_out, 
   if (int rc = pre_check(views, d, h, w, h_table, d_table)) return rc;
   if (!d_in || !d_out) return fail(AMX_ERR_INVALID, "null input or output");
   const size_t bytes = (size_t)views * d * h * w * sizeof(float);
-  if (d_in != d_out && pre_overlap(d_in, bytes, d_out, bytes)) return fail(AMX_ERR_INVALID, "d_out is d_in or does not overlap it");
-  if (d_noise && pre_overlap(d_noise, bytes, d_out, bytes)) return fail(AMX_ERR_INVALID, "d_noise must not overlap d_out");
+  if (d_in != d_out && amx::overlap(d_in, bytes, d_out, bytes)) return fail(AMX_ERR_INVALID, "d_out is d_in or does not overlap it");
+  if (d_noise && amx::overlap(d_noise, bytes, d_out, bytes)) return fail(AMX_ERR_INVALID, "d_noise must not overlap d_out");
   for (int i = 0; i < views; ++i) {
     const amx_preaug_view& s = h_table[i];
     if ((s.flags & AMX_PREAUG_NOISE) && !d_noise) return fail(AMX_ERR_INVALID, "view %d has AMX_PREAUG_NOISE but d_noise is null", i);
-    if ((s.flags & AMX_PREAUG_NOISE) && !pre_finite(s.noise_std)) return fail(AMX_ERR_INVALID, "view %d: noise_std is not finite", i);
+    if ((s.flags & AMX_PREAUG_NOISE) && !amx::is_finite(s.noise_std)) return fail(AMX_ERR_INVALID, "view %d: noise_std is not finite", i);
     if (s.flags & AMX_PREAUG_BIAS)
       for (int q = 0; q < 20; ++q)
-        if (!pre_finite(s.bias[q])) return fail(AMX_ERR_INVALID, "view %d: bias coefficient %d is not finite", i, q);
-    if ((s.flags & AMX_PREAUG_GAMMA) && !(pre_finite(s.gamma) && s.gamma > 0.f))
+        if (!amx::is_finite(s.bias[q])) return fail(AMX_ERR_INVALID, "view %d: bias coefficient %d is not finite", i, q);
+    if ((s.flags & AMX_PREAUG_GAMMA) && !(amx::is_finite(s.gamma) && s.gamma > 0.f))
       return fail(AMX_ERR_INVALID, "view %d: gamma must be positive and finite (got %g)", i, (double)s.gamma);
   }
   AMX_HIP(amx::launch_preaug_intensity(d_in, d_noise, d_out, views, d, h, w, d_table, (hipStream_t)stream));

@@ -22,25 +22,9 @@ constexpr int kAugMaxRadius = 4;
 using AugSample = amx_segaug_sample;
 
 // ---- minimum and maximum --------------------------------------------------------------------------------------------------
-// {lo, hi} of the workgroup -> dst[2]: per thread, wave (shuffles), workgroup (LDS).  Every workgroup writes its pair, with
-// (+inf, -inf) when it saw no value.
-__device__ __forceinline__ void aug_block_minmax(float lo, float hi, float* __restrict__ dst) {
-  __shared__ float red[Aug::kWaves][2];
-  lo = wave_reduce_xor<MinOp>(lo);
-  hi = wave_reduce_xor<MaxOp>(hi);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) red[wave][0] = lo, red[wave][1] = hi;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    dst[0] = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
-    dst[1] = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
-  }
-}
-// the slab pair of this workgroup of a (chunks, B) grid
-__device__ __forceinline__ float* aug_part(float* __restrict__ part) { return part + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2; }
-
-template <bool VEC>
-__global__ __launch_bounds__(Aug::kThreads) void aug_minmax_kernel(const float* __restrict__ x, long long V, int ntiles, float* __restrict__ part) {
+// partial pairs of n rows of V floats; CLIP: of max(x, 0) (datagen's ThresholdIntensity folded in, amx_synth.hip)
+template <bool VEC, bool CLIP>
+__global__ __launch_bounds__(Aug::kThreads) void minmax_kernel(const float* __restrict__ x, long long V, int ntiles, float* __restrict__ part) {
   const float* row = x + (long long)blockIdx.y * V;
   float lo = INFINITY, hi = -INFINITY;
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -48,20 +32,23 @@ __global__ __launch_bounds__(Aug::kThreads) void aug_minmax_kernel(const float* 
     Aug::load4<VEC>(row, t, V, v);
 #pragma unroll
     for (int j = 0; j < Aug::kVpt; ++j)
-      if (Aug::voxel<VEC>(t, j) < V) lo = fminf(lo, v[j]), hi = fmaxf(hi, v[j]);
+      if (Aug::voxel<VEC>(t, j) < V) {
+        const float c = CLIP ? fmaxf(v[j], 0.f) : v[j];
+        lo = fminf(lo, c), hi = fmaxf(hi, c);
+      }
   }
-  aug_block_minmax(lo, hi, aug_part(part));
+  block_minmax(lo, hi, minmax_slab(part));
 }
 
 // grid (B): minmax[n] = {min, max} over the sample's nchunk partial pairs
-__global__ __launch_bounds__(Aug::kThreads) void aug_minmax_finalize_kernel(const float* __restrict__ part, int nchunk, float* __restrict__ minmax) {
+__global__ __launch_bounds__(Aug::kThreads) void minmax_finalize_kernel(const float* __restrict__ part, int nchunk, float* __restrict__ minmax) {
   const int n = blockIdx.x;
   float lo = INFINITY, hi = -INFINITY;
   for (int c = threadIdx.x; c < nchunk; c += Aug::kThreads) {
     const float* p = part + ((long long)n * nchunk + c) * 2;
     lo = fminf(lo, p[0]), hi = fmaxf(hi, p[1]);
   }
-  aug_block_minmax(lo, hi, minmax + 2 * n);
+  block_minmax(lo, hi, minmax + 2 * n);
 }
 
 // ---- ScaleIntensity / AdjustContrast ----------------------------------------------------------------------------------------
@@ -89,20 +76,12 @@ __global__ __launch_bounds__(Aug::kThreads) void aug_pointwise_kernel(const floa
 }
 
 // ---- crop gather + noise + bias field ----------------------------------------------------------------------------------------
-struct AugDims {
-  int d, h, w;
-  long long V;
-  int ntiles;
-};
-
-// coordinate i of linspace(-1, 1, n)
-__device__ __forceinline__ float aug_lin(int i, int n) { return n > 1 ? -1.f + 2.f * (float)i / (float)(n - 1) : -1.f; }
 __device__ __forceinline__ void aug_legendre(float x, float (&p)[4]) {
   p[0] = 1.f, p[1] = x, p[2] = 0.5f * (3.f * x * x - 1.f), p[3] = 0.5f * (5.f * x * x * x - 3.f * x);
 }
 
 template <bool VEC, int LT>
-__global__ __launch_bounds__(Aug::kThreads) void aug_crop_kernel(AugDims g, const float* __restrict__ noise, float* __restrict__ img,
+__global__ __launch_bounds__(Aug::kThreads) void aug_crop_kernel(StreamDims g, const float* __restrict__ noise, float* __restrict__ img,
                                                                unsigned char* __restrict__ lab, const AugSample* __restrict__ table) {
   const int n = blockIdx.y;
   const AugSample& s = table[n];
@@ -122,25 +101,18 @@ __global__ __launch_bounds__(Aug::kThreads) void aug_crop_kernel(AugDims g, cons
       const long long o = Aug::voxel<VEC>(t, j);
       v[j] = 0.f, l[j] = 0;
       if (o >= g.V) continue;
-      const int x = (int)(o % g.w), y = (int)((o / g.w) % g.h), z = (int)(o / ((long long)g.w * g.h));
+      int z, y, x;
+      g.split(o, z, y, x);
       const long long src = ((long long)(cz + z) * H + (cy + y)) * W + (cx + x);
       float a = vol[src];
       l[j] = LT == AMX_SEG_LABEL_F32 ? (unsigned char)(int)((const float*)s.lab)[src] : ((const unsigned char*)s.lab)[src];
       if (do_noise) a += std * noise[base + o];
       if (do_bias) {
         float pz[4], py[4], px[4];
-        aug_legendre(aug_lin(z, g.d), pz);
-        aug_legendre(aug_lin(y, g.h), py);
-        aug_legendre(aug_lin(x, g.w), px);
-        float f = 0.f;
-        int q = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4 - i; ++jj)
-#pragma unroll
-            for (int k = 0; k < 4 - i - jj; ++k) f += c[q++] * (pz[i] * py[jj] * px[k]);
-        a *= expf(f);
+        aug_legendre(lin_coord(z, g.d), pz);
+        aug_legendre(lin_coord(y, g.h), py);
+        aug_legendre(lin_coord(x, g.w), px);
+        a *= expf(poly3_sum(c, pz, py, px));
       }
       v[j] = a;
     }
@@ -153,7 +125,7 @@ __global__ __launch_bounds__(Aug::kThreads) void aug_crop_kernel(AugDims g, cons
 // one axis of filter `filt` (0 smooth, 1 sharpen sigma1, 2 sharpen sigma2) for the samples with `bit` on, a copy for the others.
 // COMBINE (the last pass of the sharpening): out = b + alpha (b - pass).
 template <bool VEC, int AXIS, bool COMBINE>
-__global__ __launch_bounds__(Aug::kThreads) void aug_gauss_kernel(AugDims g, const float* __restrict__ in, float* __restrict__ out,
+__global__ __launch_bounds__(Aug::kThreads) void aug_gauss_kernel(StreamDims g, const float* __restrict__ in, float* __restrict__ out,
                                                                 const float* __restrict__ b, int filt, int bit,
                                                                 const AugSample* __restrict__ table) {
   const int n = blockIdx.y;
@@ -161,9 +133,7 @@ __global__ __launch_bounds__(Aug::kThreads) void aug_gauss_kernel(AugDims g, con
   const bool on = s.flags & bit;
   const int r = min(max(s.radius[filt][AXIS], 0), kAugMaxRadius);      // the entry refuses more where the switch is on
   float tap[2 * kAugMaxRadius + 1];
-#pragma unroll
-  for (int k = -kAugMaxRadius; k <= kAugMaxRadius; ++k)      // centred, so that the unrolled loop below indexes registers statically
-    tap[k + kAugMaxRadius] = (k >= -r && k <= r) ? s.taps[filt][AXIS][k + r] : 0.f;
+  load_centred_taps<kAugMaxRadius>(s.taps[filt][AXIS], r, tap);
   const float alpha = s.sharpen_alpha;
   const long long base = (long long)n * g.V;
   const int len = AXIS == 0 ? g.d : (AXIS == 1 ? g.h : g.w);
@@ -198,13 +168,9 @@ __global__ __launch_bounds__(Aug::kThreads) void aug_gauss_kernel(AugDims g, con
 }
 
 // ---- affine resample of image and label --------------------------------------------------------------------------------------
-struct AugAffineArgs {
-  int di, hi, wi;       // input size
-  long long Vi;
-};
-
+// g: the output, in: the input
 template <bool VEC>
-__global__ __launch_bounds__(Aug::kThreads) void aug_affine_kernel(AugDims g, AugAffineArgs a, const float* __restrict__ img_in,
+__global__ __launch_bounds__(Aug::kThreads) void aug_affine_kernel(StreamDims g, StreamDims in, const float* __restrict__ img_in,
                                                                  const unsigned char* __restrict__ lab_in, float* __restrict__ img_out,
                                                                  unsigned char* __restrict__ lab_out, const AugSample* __restrict__ table,
                                                                  float* __restrict__ part) {
@@ -214,9 +180,9 @@ __global__ __launch_bounds__(Aug::kThreads) void aug_affine_kernel(AugDims g, Au
 #pragma unroll
   for (int i = 0; i < 9; ++i) A[i] = s.affine[i];
   const float oz = 0.5f * (g.d - 1), oy = 0.5f * (g.h - 1), ox = 0.5f * (g.w - 1);
-  const float iz = 0.5f * (a.di - 1), iy = 0.5f * (a.hi - 1), ix = 0.5f * (a.wi - 1);
-  const float* src = img_in + (long long)n * a.Vi;
-  const unsigned char* lsrc = lab_in + (long long)n * a.Vi;
+  const float iz = 0.5f * (in.d - 1), iy = 0.5f * (in.h - 1), ix = 0.5f * (in.w - 1);
+  const float* src = img_in + (long long)n * in.V;
+  const unsigned char* lsrc = lab_in + (long long)n * in.V;
   const long long base = (long long)n * g.V;
   float lo = INFINITY, hi = -INFINITY;
   for (int t = blockIdx.x; t < g.ntiles; t += gridDim.x) {
@@ -232,54 +198,53 @@ __global__ __launch_bounds__(Aug::kThreads) void aug_affine_kernel(AugDims g, Au
       const float sy = A[3] * pz + A[4] * py + A[5] * px + iy;
       const float sx = A[6] * pz + A[7] * py + A[8] * px + ix;
       // anything at least one voxel outside the input (NaN included) has no corner and no nearest voxel inside
-      if (sz > -1.f && sz < (float)a.di && sy > -1.f && sy < (float)a.hi && sx > -1.f && sx < (float)a.wi) {
+      if (sz > -1.f && sz < (float)in.d && sy > -1.f && sy < (float)in.h && sx > -1.f && sx < (float)in.w) {
         const float fz0 = floorf(sz), fy0 = floorf(sy), fx0 = floorf(sx);
         const int z0 = (int)fz0, y0 = (int)fy0, x0 = (int)fx0;
         const float fz = sz - fz0, fy = sy - fy0, fx = sx - fx0;
         if (fz == 0.f && fy == 0.f && fx == 0.f) {
-          v[j] = src[((long long)z0 * a.hi + y0) * a.wi + x0];      // z0, y0, x0 >= 0 here: an integral index above -1
+          v[j] = src[((long long)z0 * in.h + y0) * in.w + x0];      // z0, y0, x0 >= 0 here: an integral index above -1
         } else {
           float acc = 0.f;
 #pragma unroll
           for (int c = 0; c < 8; ++c) {
             const int zz = z0 + (c >> 2), yy = y0 + ((c >> 1) & 1), xx = x0 + (c & 1);
             const float wgt = ((c >> 2) ? fz : 1.f - fz) * (((c >> 1) & 1) ? fy : 1.f - fy) * ((c & 1) ? fx : 1.f - fx);
-            if (zz >= 0 && zz < a.di && yy >= 0 && yy < a.hi && xx >= 0 && xx < a.wi) acc += wgt * src[((long long)zz * a.hi + yy) * a.wi + xx];
+            if (zz >= 0 && zz < in.d && yy >= 0 && yy < in.h && xx >= 0 && xx < in.w) acc += wgt * src[((long long)zz * in.h + yy) * in.w + xx];
           }
           v[j] = acc;
         }
         const int nz = (int)rintf(sz), ny = (int)rintf(sy), nx = (int)rintf(sx);
-        if (nz >= 0 && nz < a.di && ny >= 0 && ny < a.hi && nx >= 0 && nx < a.wi) l[j] = lsrc[((long long)nz * a.hi + ny) * a.wi + nx];
+        if (nz >= 0 && nz < in.d && ny >= 0 && ny < in.h && nx >= 0 && nx < in.w) l[j] = lsrc[((long long)nz * in.h + ny) * in.w + nx];
       }
       lo = fminf(lo, v[j]), hi = fmaxf(hi, v[j]);
     }
     Aug::store4<VEC>(img_out + base, t, g.V, v);
     Aug::store4<VEC>(lab_out + base, t, g.V, l);
   }
-  aug_block_minmax(lo, hi, aug_part(part));
+  block_minmax(lo, hi, minmax_slab(part));
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------
-static AugDims aug_dims(int d, int h, int w) {
-  AugDims g;
-  g.d = d, g.h = h, g.w = w, g.V = (long long)d * h * w, g.ntiles = (int)Aug::tiles(g.V);
-  return g;
-}
+size_t minmax_bytes(int n, long long V) { return (size_t)n * Aug::chunks(n, V) * 2 * sizeof(float); }
 
-size_t segaug_scratch_bytes(int n, long long V) { return (size_t)n * Aug::chunks(n, V) * 2 * sizeof(float); }
-
-hipError_t launch_segaug_minmax_finalize(const void* scratch, int n, long long V, float* minmax, hipStream_t st) {
-  aug_minmax_finalize_kernel<<<n, Aug::kThreads, 0, st>>>((const float*)scratch, Aug::chunks(n, V), minmax);
+hipError_t launch_minmax_partials(const float* x, int n, long long V, bool clip, void* scratch, hipStream_t st) {
+  const dim3 grid(Aug::chunks(n, V), n);
+  const int nt = (int)Aug::tiles(V);
+  const bool vec = V % 4 == 0 && aligned16(x);
+  if (clip) {
+    if (vec) minmax_kernel<true, true><<<grid, Aug::kThreads, 0, st>>>(x, V, nt, (float*)scratch);
+    else minmax_kernel<false, true><<<grid, Aug::kThreads, 0, st>>>(x, V, nt, (float*)scratch);
+  } else {
+    if (vec) minmax_kernel<true, false><<<grid, Aug::kThreads, 0, st>>>(x, V, nt, (float*)scratch);
+    else minmax_kernel<false, false><<<grid, Aug::kThreads, 0, st>>>(x, V, nt, (float*)scratch);
+  }
   return hipGetLastError();
 }
 
-hipError_t launch_segaug_minmax(const float* x, int n, long long V, float* minmax, void* scratch, hipStream_t st) {
-  const dim3 grid(Aug::chunks(n, V), n);
-  if (V % 4 == 0 && aligned16(x)) aug_minmax_kernel<true><<<grid, Aug::kThreads, 0, st>>>(x, V, (int)Aug::tiles(V), (float*)scratch);
-  else aug_minmax_kernel<false><<<grid, Aug::kThreads, 0, st>>>(x, V, (int)Aug::tiles(V), (float*)scratch);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return launch_segaug_minmax_finalize(scratch, n, V, minmax, st);
+hipError_t launch_minmax_finalize(const void* scratch, int n, long long V, float* minmax, hipStream_t st) {
+  minmax_finalize_kernel<<<n, Aug::kThreads, 0, st>>>((const float*)scratch, Aug::chunks(n, V), minmax);
+  return hipGetLastError();
 }
 
 hipError_t launch_segaug_pointwise(const float* in, float* out, int n, long long V, const float* minmax, int op, const AugSample* table,
@@ -299,7 +264,7 @@ hipError_t launch_segaug_pointwise(const float* in, float* out, int n, long long
 
 hipError_t launch_segaug_crop(int n, int d, int h, int w, const float* noise, int lt, float* img, unsigned char* lab, const AugSample* table,
                               hipStream_t st) {
-  const AugDims g = aug_dims(d, h, w);
+  const StreamDims g = StreamDims::make(d, h, w);
   const dim3 grid(Aug::chunks(n, g.V), n);
   const bool vec = g.V % 4 == 0 && aligned16(img) && aligned4(lab);
   if (lt == AMX_SEG_LABEL_F32) {
@@ -313,7 +278,7 @@ hipError_t launch_segaug_crop(int n, int d, int h, int w, const float* noise, in
 }
 
 template <int AXIS, bool COMBINE>
-static hipError_t aug_gauss_pass(const AugDims& g, int n, const float* in, float* out, const float* b, int filt, int bit,
+static hipError_t aug_gauss_pass(const StreamDims& g, int n, const float* in, float* out, const float* b, int filt, int bit,
                                  const AugSample* table, hipStream_t st) {
   const dim3 grid(Aug::chunks(n, g.V), n);
   const bool vec = g.V % 4 == 0 && aligned16(in) && aligned16(out);
@@ -324,7 +289,7 @@ static hipError_t aug_gauss_pass(const AugDims& g, int n, const float* in, float
 
 hipError_t launch_segaug_gaussian(const float* in, float* out, float* tmp, int n, int d, int h, int w, int mode, const AugSample* table,
                                   hipStream_t st) {
-  const AugDims g = aug_dims(d, h, w);
+  const StreamDims g = StreamDims::make(d, h, w);
   float *t0 = tmp, *t1 = tmp + (long long)n * g.V;
   hipError_t e;
   if (mode == AMX_SEGAUG_GAUSS_SMOOTH) {
@@ -343,13 +308,12 @@ hipError_t launch_segaug_gaussian(const float* in, float* out, float* tmp, int n
 
 hipError_t launch_segaug_affine(const float* img_in, const unsigned char* lab_in, int n, int di, int hi, int wi, float* img_out,
                                 unsigned char* lab_out, int d, int h, int w, const AugSample* table, void* scratch, hipStream_t st) {
-  const AugDims g = aug_dims(d, h, w);
-  AugAffineArgs a;
-  a.di = di, a.hi = hi, a.wi = wi, a.Vi = (long long)di * hi * wi;
+  const StreamDims g = StreamDims::make(d, h, w);
+  const StreamDims in = StreamDims::make(di, hi, wi);
   const dim3 grid(Aug::chunks(n, g.V), n);
   if (g.V % 4 == 0 && aligned16(img_out) && aligned4(lab_out))
-    aug_affine_kernel<true><<<grid, Aug::kThreads, 0, st>>>(g, a, img_in, lab_in, img_out, lab_out, table, (float*)scratch);
-  else aug_affine_kernel<false><<<grid, Aug::kThreads, 0, st>>>(g, a, img_in, lab_in, img_out, lab_out, table, (float*)scratch);
+    aug_affine_kernel<true><<<grid, Aug::kThreads, 0, st>>>(g, in, img_in, lab_in, img_out, lab_out, table, (float*)scratch);
+  else aug_affine_kernel<false><<<grid, Aug::kThreads, 0, st>>>(g, in, img_in, lab_in, img_out, lab_out, table, (float*)scratch);
   return hipGetLastError();
 }
 
@@ -357,26 +321,8 @@ hipError_t launch_segaug_affine(const float* img_in, const unsigned char* lab_in
 
 namespace {
 using amx::fail;
-constexpr long long kAugMaxVoxels = 1LL << 31;      // per sample: keeps every tile count inside an int
-
-int aug_check_batch(int n, long long voxels) {
-  if (n < 1 || n > 65535) return fail(AMX_ERR_SHAPE, "1 <= n <= 65535 (got %d)", n);
-  if (voxels < 1 || voxels >= kAugMaxVoxels) return fail(AMX_ERR_SHAPE, "1 <= voxels < 2^31 per sample (got %lld)", voxels);
-  return AMX_OK;
-}
-int aug_check_dims(int n, int d, int h, int w) {
-  if (d < 1 || h < 1 || w < 1) return fail(AMX_ERR_SHAPE, "spatial sizes must be positive (got %d x %d x %d)", d, h, w);
-  return aug_check_batch(n, (long long)d * h * w);
-}
-int aug_check_tables(const void* h_table, const void* d_table) {
-  if (!h_table || !d_table) return fail(AMX_ERR_INVALID, "null parameter table (host copy and device copy are both needed)");
-  return AMX_OK;
-}
-bool aug_finite(float v) { return v == v && v - v == 0.f; }
-bool aug_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
+int aug_check_batch(int n, long long voxels) { return amx::check_rows(n, voxels, "n", "sample"); }
+int aug_check_dims(int n, int d, int h, int w) { return amx::check_rows_dims(n, d, h, w, "n", "sample"); }
 }  // namespace
 
 extern "C" {
@@ -384,35 +330,35 @@ extern "C" {
 size_t amx_segaug_sample_bytes(void) { return sizeof(amx_segaug_sample); }
 
 size_t amx_segaug_scratch_bytes(int n, long long voxels) {
-  if (n < 1 || n > 65535 || voxels < 1 || voxels >= kAugMaxVoxels) return 0;
-  return amx::segaug_scratch_bytes(n, voxels);
+  return amx::rows_ok(n, voxels) ? amx::minmax_bytes(n, voxels) : 0;
 }
 
 int amx_segaug_minmax(const float* d_x, int n, long long voxels, float* d_minmax, void* d_scratch, size_t scratch_bytes, void* stream) {
   if (int rc = aug_check_batch(n, voxels)) return rc;
   if (!d_x || !d_minmax || !d_scratch) return fail(AMX_ERR_INVALID, "null input, output or scratch");
-  if (int rc = amx::need_scratch(amx::segaug_scratch_bytes(n, voxels), scratch_bytes)) return rc;
-  AMX_HIP(amx::launch_segaug_minmax(d_x, n, voxels, d_minmax, d_scratch, (hipStream_t)stream));
+  if (int rc = amx::need_scratch(amx::minmax_bytes(n, voxels), scratch_bytes)) return rc;
+  AMX_HIP(amx::launch_minmax_partials(d_x, n, voxels, false, d_scratch, (hipStream_t)stream));
+  AMX_HIP(amx::launch_minmax_finalize(d_scratch, n, voxels, d_minmax, (hipStream_t)stream));
   return AMX_OK;
 }
 
 int amx_segaug_minmax_finalize(const void* d_scratch, size_t scratch_bytes, int n, long long voxels, float* d_minmax, void* stream) {
   if (int rc = aug_check_batch(n, voxels)) return rc;
   if (!d_minmax || !d_scratch) return fail(AMX_ERR_INVALID, "null output or scratch");
-  if (int rc = amx::need_scratch(amx::segaug_scratch_bytes(n, voxels), scratch_bytes)) return rc;
-  AMX_HIP(amx::launch_segaug_minmax_finalize(d_scratch, n, voxels, d_minmax, (hipStream_t)stream));
+  if (int rc = amx::need_scratch(amx::minmax_bytes(n, voxels), scratch_bytes)) return rc;
+  AMX_HIP(amx::launch_minmax_finalize(d_scratch, n, voxels, d_minmax, (hipStream_t)stream));
   return AMX_OK;
 }
 
 int amx_segaug_pointwise(const float* d_in, float* d_out, int n, long long voxels, const float* d_minmax, int op,
                          const amx_segaug_sample* h_table, const amx_segaug_sample* d_table, void* stream) {
   if (int rc = aug_check_batch(n, voxels)) return rc;
-  if (int rc = aug_check_tables(h_table, d_table)) return rc;
+  if (int rc = amx::check_tables(h_table, d_table)) return rc;
   if (!d_in || !d_out || !d_minmax) return fail(AMX_ERR_INVALID, "null input, output or statistics");
   if (op != AMX_SEGAUG_OP_SCALE && op != AMX_SEGAUG_OP_CONTRAST) return fail(AMX_ERR_INVALID, "op: AMX_SEGAUG_OP_SCALE or _CONTRAST (got %d)", op);
   if (op == AMX_SEGAUG_OP_CONTRAST)
     for (int i = 0; i < n; ++i)
-      if ((h_table[i].flags & AMX_SEGAUG_CONTRAST) && !(aug_finite(h_table[i].gamma) && h_table[i].gamma > 0.f))
+      if ((h_table[i].flags & AMX_SEGAUG_CONTRAST) && !(amx::is_finite(h_table[i].gamma) && h_table[i].gamma > 0.f))
         return fail(AMX_ERR_INVALID, "sample %d: gamma must be positive and finite (got %g)", i, (double)h_table[i].gamma);
   AMX_HIP(amx::launch_segaug_pointwise(d_in, d_out, n, voxels, d_minmax, op, d_table, (hipStream_t)stream));
   return AMX_OK;
@@ -421,7 +367,7 @@ int amx_segaug_pointwise(const float* d_in, float* d_out, int n, long long voxel
 int amx_segaug_crop(int n, int d, int h, int w, const float* d_noise, int label_dtype, float* d_img, unsigned char* d_lab,
                     const amx_segaug_sample* h_table, const amx_segaug_sample* d_table, void* stream) {
   if (int rc = aug_check_dims(n, d, h, w)) return rc;
-  if (int rc = aug_check_tables(h_table, d_table)) return rc;
+  if (int rc = amx::check_tables(h_table, d_table)) return rc;
   if (!d_img || !d_lab) return fail(AMX_ERR_INVALID, "null output");
   if (label_dtype != AMX_SEG_LABEL_F32 && label_dtype != AMX_SEG_LABEL_U8)
     return fail(AMX_ERR_INVALID, "label_dtype: AMX_SEG_LABEL_F32 or AMX_SEG_LABEL_U8 (got %d)", label_dtype);
@@ -433,12 +379,12 @@ int amx_segaug_crop(int n, int d, int h, int w, const float* d_noise, int label_
       if (s.vol_dim[a] < 1 || s.corner[a] < 0 || (long long)s.corner[a] + size[a] > s.vol_dim[a])
         return fail(AMX_ERR_SHAPE, "sample %d axis %d: crop [%d, %d + %d) leaves the volume of %d", i, a, s.corner[a], s.corner[a], size[a],
                     s.vol_dim[a]);
-    if ((long long)s.vol_dim[0] * s.vol_dim[1] * s.vol_dim[2] >= kAugMaxVoxels) return fail(AMX_ERR_SHAPE, "sample %d: volume of 2^31 voxels or more", i);
+    if ((long long)s.vol_dim[0] * s.vol_dim[1] * s.vol_dim[2] >= amx::kMaxRowVoxels) return fail(AMX_ERR_SHAPE, "sample %d: volume of 2^31 voxels or more", i);
     if ((s.flags & AMX_SEGAUG_NOISE) && !d_noise) return fail(AMX_ERR_INVALID, "sample %d has AMX_SEGAUG_NOISE but d_noise is null", i);
-    if ((s.flags & AMX_SEGAUG_NOISE) && !aug_finite(s.noise_std)) return fail(AMX_ERR_INVALID, "sample %d: noise_std is not finite", i);
+    if ((s.flags & AMX_SEGAUG_NOISE) && !amx::is_finite(s.noise_std)) return fail(AMX_ERR_INVALID, "sample %d: noise_std is not finite", i);
     if (s.flags & AMX_SEGAUG_BIAS)
       for (int q = 0; q < 20; ++q)
-        if (!aug_finite(s.bias[q])) return fail(AMX_ERR_INVALID, "sample %d: bias coefficient %d is not finite", i, q);
+        if (!amx::is_finite(s.bias[q])) return fail(AMX_ERR_INVALID, "sample %d: bias coefficient %d is not finite", i, q);
   }
   AMX_HIP(amx::launch_segaug_crop(n, d, h, w, d_noise, label_dtype, d_img, d_lab, d_table, (hipStream_t)stream));
   return AMX_OK;
@@ -447,12 +393,12 @@ int amx_segaug_crop(int n, int d, int h, int w, const float* d_noise, int label_
 int amx_segaug_gaussian(const float* d_in, float* d_out, float* d_tmp, int n, int d, int h, int w, int mode,
                         const amx_segaug_sample* h_table, const amx_segaug_sample* d_table, void* stream) {
   if (int rc = aug_check_dims(n, d, h, w)) return rc;
-  if (int rc = aug_check_tables(h_table, d_table)) return rc;
+  if (int rc = amx::check_tables(h_table, d_table)) return rc;
   if (!d_in || !d_out || !d_tmp) return fail(AMX_ERR_INVALID, "null input, output or temporary");
   if (mode != AMX_SEGAUG_GAUSS_SMOOTH && mode != AMX_SEGAUG_GAUSS_SHARPEN)
     return fail(AMX_ERR_INVALID, "mode: AMX_SEGAUG_GAUSS_SMOOTH or _SHARPEN (got %d)", mode);
   const size_t bytes = (size_t)n * d * h * w * sizeof(float);
-  if (aug_overlap(d_in, bytes, d_out, bytes) || aug_overlap(d_in, bytes, d_tmp, 2 * bytes) || aug_overlap(d_out, bytes, d_tmp, 2 * bytes))
+  if (amx::overlap(d_in, bytes, d_out, bytes) || amx::overlap(d_in, bytes, d_tmp, 2 * bytes) || amx::overlap(d_out, bytes, d_tmp, 2 * bytes))
     return fail(AMX_ERR_INVALID, "d_in, d_out and d_tmp must not overlap");
   const int bit = mode == AMX_SEGAUG_GAUSS_SMOOTH ? AMX_SEGAUG_SMOOTH : AMX_SEGAUG_SHARPEN;
   const int f0 = mode == AMX_SEGAUG_GAUSS_SMOOTH ? 0 : 1, f1 = mode == AMX_SEGAUG_GAUSS_SMOOTH ? 0 : 2;
@@ -464,7 +410,7 @@ int amx_segaug_gaussian(const float* d_in, float* d_out, float* d_tmp, int n, in
         if (r < 0 || r > amx::kAugMaxRadius)
           return fail(AMX_ERR_INVALID, "sample %d filter %d axis %d: radius %d is outside 0 .. %d (sigma <= 1)", i, f, a, r, amx::kAugMaxRadius);
       }
-    if (mode == AMX_SEGAUG_GAUSS_SHARPEN && !aug_finite(h_table[i].sharpen_alpha))
+    if (mode == AMX_SEGAUG_GAUSS_SHARPEN && !amx::is_finite(h_table[i].sharpen_alpha))
       return fail(AMX_ERR_INVALID, "sample %d: sharpen_alpha is not finite", i);
   }
   AMX_HIP(amx::launch_segaug_gaussian(d_in, d_out, d_tmp, n, d, h, w, mode, d_table, (hipStream_t)stream));
@@ -476,15 +422,15 @@ int amx_segaug_affine(const float* d_img_in, const unsigned char* d_lab_in, int 
                       const amx_segaug_sample* d_table, void* d_scratch, size_t scratch_bytes, void* stream) {
   if (int rc = aug_check_dims(n, d, h, w)) return rc;
   if (int rc = aug_check_dims(n, di, hi, wi)) return rc;
-  if (int rc = aug_check_tables(h_table, d_table)) return rc;
+  if (int rc = amx::check_tables(h_table, d_table)) return rc;
   if (!d_img_in || !d_lab_in || !d_img_out || !d_lab_out || !d_scratch) return fail(AMX_ERR_INVALID, "null input, output or scratch");
   const size_t vin = (size_t)n * di * hi * wi, vout = (size_t)n * d * h * w;
-  if (aug_overlap(d_img_in, vin * 4, d_img_out, vout * 4) || aug_overlap(d_lab_in, vin, d_lab_out, vout))
+  if (amx::overlap(d_img_in, vin * 4, d_img_out, vout * 4) || amx::overlap(d_lab_in, vin, d_lab_out, vout))
     return fail(AMX_ERR_INVALID, "inputs and outputs must not overlap");
-  if (int rc = amx::need_scratch(amx::segaug_scratch_bytes(n, (long long)d * h * w), scratch_bytes)) return rc;
+  if (int rc = amx::need_scratch(amx::minmax_bytes(n, (long long)d * h * w), scratch_bytes)) return rc;
   for (int i = 0; i < n; ++i)
     for (int q = 0; q < 9; ++q)
-      if (!aug_finite(h_table[i].affine[q])) return fail(AMX_ERR_INVALID, "sample %d: affine entry %d is not finite", i, q);
+      if (!amx::is_finite(h_table[i].affine[q])) return fail(AMX_ERR_INVALID, "sample %d: affine entry %d is not finite", i, q);
   AMX_HIP(amx::launch_segaug_affine(d_img_in, d_lab_in, n, di, hi, wi, d_img_out, d_lab_out, d, h, w, d_table, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }

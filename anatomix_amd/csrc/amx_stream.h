@@ -1,7 +1,9 @@
-// anatomix_amd -- what the streaming units (amx_segloss.hip, amx_segaug.hip, amx_regmetrics.hip, amx_reginstopt.hip) share:
-// the four-voxel tile access, the ascending xor butterfly over a wave and the LDS tree sum over a workgroup.  Each reduction
-// here has ONE order; a reduction in another order (amx_mlp.hip's wave_sum, amx_supcon.hip's block_sum, ...) is another function
-// and stays in its unit, since merging them would change results in the last bit.
+// anatomix_amd -- what the streaming units (amx_segloss.hip, amx_segaug.hip, amx_preaug.hip, amx_synth.hip, amx_regmetrics.hip,
+// amx_reginstopt.hip) share: the four-voxel tile access, the ascending xor butterfly over a wave and the LDS tree sum over a
+// workgroup, and for the three augmentation units the volume dims, the workgroup min / max with its partial slab, the
+// degree-3 polynomial sum and the centred taps.  Each reduction here has ONE order; a reduction in another order
+// (amx_mlp.hip's wave_sum, amx_supcon.hip's block_sum, ...) is another function and stays in its unit, since merging them would
+// change results in the last bit.
 #pragma once
 #include <stdint.h>
 
@@ -81,6 +83,24 @@ struct StreamTile {
   }
 };
 
+// ---- volume dims ------------------------------------------------------------------------------------------------------------
+// a [d][h][w] volume streamed as one row of V voxels in ntiles tiles (the base of a kernel argument that needs more: SynApp)
+struct StreamDims {
+  int d, h, w;
+  long long V;
+  int ntiles;
+
+  static inline StreamDims make(int d, int h, int w) {
+    StreamDims g;
+    g.d = d, g.h = h, g.w = w, g.V = (long long)d * h * w, g.ntiles = (int)StreamTile<>::tiles(g.V);
+    return g;
+  }
+  // (z, y, x) of voxel o
+  __device__ __forceinline__ void split(long long o, int& z, int& y, int& x) const {
+    x = (int)(o % w), y = (int)((o / w) % h), z = (int)(o / ((long long)w * h));
+  }
+};
+
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 
@@ -106,6 +126,50 @@ __device__ __forceinline__ T wave_reduce_xor(T v) {
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) v = Op::apply(v, __shfl_xor(v, m, 64));
   return v;
+}
+
+// ---- minimum and maximum ----------------------------------------------------------------------------------------------------
+// {lo, hi} of the workgroup (a StreamTile<> one: four waves) -> dst[2]: per thread, wave (shuffles), workgroup (LDS).  Every
+// workgroup writes its pair, with (+inf, -inf) when it saw no value.
+__device__ __forceinline__ void block_minmax(float lo, float hi, float* __restrict__ dst) {
+  static_assert(StreamTile<>::kWaves == 4, "the last step combines four waves");
+  __shared__ float red[StreamTile<>::kWaves][2];
+  lo = wave_reduce_xor<MinOp>(lo);
+  hi = wave_reduce_xor<MaxOp>(hi);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) red[wave][0] = lo, red[wave][1] = hi;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    dst[0] = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
+    dst[1] = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
+  }
+}
+// the slab pair of this workgroup of a (chunks, rows) grid: pair [row][chunk], what the finalize kernel of amx_segaug.hip reads
+__device__ __forceinline__ float* minmax_slab(float* __restrict__ part) { return part + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2; }
+
+// ---- bias field and taps ----------------------------------------------------------------------------------------------------
+// coordinate i of linspace(-1, 1, n)
+__device__ __forceinline__ float lin_coord(int i, int n) { return n > 1 ? -1.f + 2.f * (float)i / (float)(n - 1) : -1.f; }
+
+// sum of c[q] pz[i] py[j] px[k] over i + j + k <= 3, (i, j, k) lexicographic: the 20 terms in that order
+__device__ __forceinline__ float poly3_sum(const float (&c)[20], const float (&pz)[4], const float (&py)[4], const float (&px)[4]) {
+  float f = 0.f;
+  int q = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4 - i; ++j)
+#pragma unroll
+      for (int k = 0; k < 4 - i - j; ++k) f += c[q++] * (pz[i] * py[j] * px[k]);
+  return f;
+}
+
+// the 2 r + 1 taps of one axis (r <= R) centred in registers: tap[k + R], 0 outside the radius, so that an unrolled loop over
+// -R .. R indexes registers statically (uniform, so scalar loads)
+template <int R>
+__device__ __forceinline__ void load_centred_taps(const float* __restrict__ taps, int r, float (&tap)[2 * R + 1]) {
+#pragma unroll
+  for (int k = -R; k <= R; ++k) tap[k + R] = (k >= -r && k <= r) ? taps[k + r] : 0.f;
 }
 
 // ---- tree sum ---------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 // fp32 planar rows [n][V] with n = 2 batch (row = 2 sample + view), labels uint8 [batch][V].  One launch per stage with the row on
 // grid.y; what differs per row is read from a device table of amx_synth_view records.  A thread owns four voxels of a tile of
 // 1024 (amx_stream.h): one 16-byte access where V % 4 == 0 and the bases are aligned, four voxels 256 apart otherwise.  Minimum and
-// maximum leave per-workgroup partials in the layout amx_segaug_minmax_finalize reads.  No float atomics: two runs agree bit for bit.
+// maximum leave per-workgroup partials in the one layout of amx_stream.h, which amx_segaug_minmax_finalize reads.  No float atomics: two runs agree bit for bit.
 #include <math.h>
 #include <stdio.h>
 
@@ -22,21 +22,6 @@ namespace amx {
 using Syn = StreamTile<>;
 using SynView = amx_synth_view;
 constexpr int kSynMaxLdsFloats = 12288;      // 48 KiB of collapsed coarse rows per workgroup, the two label tables besides
-
-// ---- minimum and maximum (the partial layout of amx_segaug.hip: pair [row][chunk]) -------------------------------------------
-__device__ __forceinline__ void syn_block_minmax(float lo, float hi, float* __restrict__ part) {
-  __shared__ float red[Syn::kWaves][2];
-  lo = wave_reduce_xor<MinOp>(lo);
-  hi = wave_reduce_xor<MaxOp>(hi);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) red[wave][0] = lo, red[wave][1] = hi;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float* dst = part + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
-    dst[0] = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
-    dst[1] = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
-  }
-}
 
 // labels of this thread's four voxels; voxels past V read as 0
 template <bool VEC>
@@ -94,14 +79,13 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_gmm_minmax_kernel(const uns
         lo = fminf(lo, g), hi = fmaxf(hi, g);
       }
   }
-  syn_block_minmax(lo, hi, part);
+  block_minmax(lo, hi, minmax_slab(part));
 }
 
 // ---- appearance pass 2 -------------------------------------------------------------------------------------------------------
-struct SynApp {
-  int d, h, w;
-  long long V;
-  int ntiles, nscales, sumcw, maxrows;
+struct SynApp : StreamDims {
+  explicit SynApp(const StreamDims& g) : StreamDims(g) {}
+  int nscales, sumcw, maxrows;
   float rs[AMX_SYNTH_MAX_SCALES];                // 1 / scale
   int cd[AMX_SYNTH_MAX_SCALES], ch[AMX_SYNTH_MAX_SCALES], cw[AMX_SYNTH_MAX_SCALES], off[AMX_SYNTH_MAX_SCALES + 1];
   const float* grid[AMX_SYNTH_MAX_SCALES];       // [n][cd][ch][cw], already multiplied by its std
@@ -180,7 +164,7 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_appearance_kernel(SynApp a,
     Syn::store4<VEC>(dst, t, a.V, v);
     __syncthreads();      // the rows of this tile are read: the next tile may overwrite them
   }
-  syn_block_minmax(lo, hi, part);
+  block_minmax(lo, hi, minmax_slab(part));
 }
 
 // ---- k-space spike ---------------------------------------------------------------------------------------------------------
@@ -221,15 +205,9 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_logk_finalize_kernel(const 
   if (threadIdx.x == 0) mean[blockIdx.x] = (float)(sum / (double)V);
 }
 
-struct SynDims {
-  int d, h, w;
-  long long V;
-  int ntiles;
-};
-
 // x += Re(delta / N exp(2 pi i sum_a f_a r_a / n_a)) for the rows with AMX_SYNTH_SPIKE; the others are not touched
 template <bool VEC>
-__global__ __launch_bounds__(Syn::kThreads) void syn_spike_kernel(SynDims g, float* __restrict__ x, const float* __restrict__ k,
+__global__ __launch_bounds__(Syn::kThreads) void syn_spike_kernel(StreamDims g, float* __restrict__ x, const float* __restrict__ k,
                                                                 const float* __restrict__ logk_mean, const SynView* __restrict__ table) {
   const int row = blockIdx.y;
   const SynView& s = table[row];
@@ -250,7 +228,8 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_spike_kernel(SynDims g, flo
     for (int j = 0; j < Syn::kVpt; ++j) {
       const long long o = Syn::voxel<VEC>(t, j);
       if (o >= g.V) continue;
-      const int vx = (int)(o % g.w), vy = (int)((o / g.w) % g.h), vz = (int)(o / ((long long)g.w * g.h));
+      int vz, vy, vx;
+      g.split(o, vz, vy, vx);
       // the phase in turns: every term reduced modulo its axis in integers first
       float turns = (float)(int)(((long long)fz * vz) % g.d) * iz + (float)(int)(((long long)fy * vy) % g.h) * iy +
                     (float)(int)(((long long)fx * vx) % g.w) * ix;
@@ -275,7 +254,7 @@ __device__ __forceinline__ void syn_lowres_axis(int o, int n, int t, int& s0, in
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(Syn::kThreads) void syn_lowres_kernel(SynDims g, const float* __restrict__ in, float* __restrict__ out,
+__global__ __launch_bounds__(Syn::kThreads) void syn_lowres_kernel(StreamDims g, const float* __restrict__ in, float* __restrict__ out,
                                                                  const SynView* __restrict__ table) {
   const int row = blockIdx.y;
   const SynView& s = table[row];
@@ -293,7 +272,8 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_lowres_kernel(SynDims g, co
         const long long o = Syn::voxel<VEC>(t, j);
         v[j] = 0.f;
         if (o >= g.V) continue;
-        const int vx = (int)(o % g.w), vy = (int)((o / g.w) % g.h), vz = (int)(o / ((long long)g.w * g.h));
+        int vz, vy, vx;
+        g.split(o, vz, vy, vx);
         int z0, z1, y0, y1, x0, x1;
         float lz, ly, lx;
         syn_lowres_axis(vz, g.d, td, z0, z1, lz);
@@ -313,23 +293,6 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_lowres_kernel(SynDims g, co
 }
 
 // ---- tail: ThresholdIntensity(above, 0) + ScaleIntensity (+ uint8) -------------------------------------------------------------
-template <bool VEC>
-__global__ __launch_bounds__(Syn::kThreads) void syn_clip_minmax_kernel(const float* __restrict__ x, long long V, int ntiles, float* __restrict__ part) {
-  const float* row = x + (long long)blockIdx.y * V;
-  float lo = INFINITY, hi = -INFINITY;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    float v[Syn::kVpt];
-    Syn::load4<VEC>(row, t, V, v);
-#pragma unroll
-    for (int j = 0; j < Syn::kVpt; ++j)
-      if (Syn::voxel<VEC>(t, j) < V) {
-        const float c = fmaxf(v[j], 0.f);
-        lo = fminf(lo, c), hi = fmaxf(hi, c);
-      }
-  }
-  syn_block_minmax(lo, hi, part);
-}
-
 template <bool VEC, bool U8>
 __global__ __launch_bounds__(Syn::kThreads) void syn_finish_kernel(const float* in, void* out, long long V, int ntiles, const float* __restrict__ minmax) {
   const int row = blockIdx.y;
@@ -359,29 +322,14 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_finish_kernel(const float* 
 namespace {
 using amx::fail;
 using amx::Syn;
-constexpr long long kSynMaxVoxels = 1LL << 31;      // per row: keeps every tile count inside an int
-
-size_t syn_minmax_bytes(int n, long long V) { return (size_t)n * Syn::chunks(n, V) * 2 * sizeof(float); }
 size_t syn_logk_bytes(int n, long long V) { return (size_t)n * Syn::chunks(n, V) * sizeof(double); }
 
-int syn_check_rows(int n, long long voxels) {
-  if (n < 1 || n > 65535) return fail(AMX_ERR_SHAPE, "1 <= rows <= 65535 (got %d)", n);
-  if (voxels < 1 || voxels >= kSynMaxVoxels) return fail(AMX_ERR_SHAPE, "1 <= voxels < 2^31 per row (got %lld)", voxels);
-  return AMX_OK;
-}
-int syn_check_dims(int n, int d, int h, int w) {
-  if (d < 1 || h < 1 || w < 1) return fail(AMX_ERR_SHAPE, "spatial sizes must be positive (got %d x %d x %d)", d, h, w);
-  return syn_check_rows(n, (long long)d * h * w);
-}
+int syn_check_rows(int n, long long voxels) { return amx::check_rows(n, voxels, "rows", "row"); }
+int syn_check_dims(int n, int d, int h, int w) { return amx::check_rows_dims(n, d, h, w, "rows", "row"); }
 int syn_check_batch(int batch) {
   if (batch < 1 || batch > 32767) return fail(AMX_ERR_SHAPE, "1 <= batch <= 32767 (got %d)", batch);
   return AMX_OK;
 }
-int syn_check_tables(const void* h_table, const void* d_table) {
-  if (!h_table || !d_table) return fail(AMX_ERR_INVALID, "null parameter table (host copy and device copy are both needed)");
-  return AMX_OK;
-}
-bool syn_finite(float v) { return v == v && v - v == 0.f; }
 
 // the appearance model's part of the records of 2 batch rows
 int syn_check_gmm(const amx_synth_view* t, int rows) {
@@ -393,8 +341,8 @@ int syn_check_gmm(const amx_synth_view* t, int rows) {
     for (int l = 0; l < 256; ++l)
       if (s.rank[l] >= s.nlabels) return fail(AMX_ERR_INVALID, "row %d: rank[%d] = %d is not below nlabels = %d", i, l, s.rank[l], s.nlabels);
     for (int r = 0; r < s.nlabels; ++r)
-      if (!syn_finite(s.mean[r]) || !syn_finite(s.std[r])) return fail(AMX_ERR_INVALID, "row %d: mean or std of rank %d is not finite", i, r);
-    if (!syn_finite(s.perl_mult)) return fail(AMX_ERR_INVALID, "row %d: perl_mult is not finite", i);
+      if (!amx::is_finite(s.mean[r]) || !amx::is_finite(s.std[r])) return fail(AMX_ERR_INVALID, "row %d: mean or std of rank %d is not finite", i, r);
+    if (!amx::is_finite(s.perl_mult)) return fail(AMX_ERR_INVALID, "row %d: perl_mult is not finite", i);
   }
   return AMX_OK;
 }
@@ -405,8 +353,8 @@ extern "C" {
 size_t amx_synth_view_bytes(void) { return sizeof(amx_synth_view); }
 
 size_t amx_synth_scratch_bytes(int rows, long long voxels) {
-  if (rows < 1 || rows > 65535 || voxels < 1 || voxels >= kSynMaxVoxels) return 0;
-  const size_t a = syn_minmax_bytes(rows, voxels), b = syn_logk_bytes(rows, voxels);
+  if (!amx::rows_ok(rows, voxels)) return 0;
+  const size_t a = amx::minmax_bytes(rows, voxels), b = syn_logk_bytes(rows, voxels);
   return a > b ? a : b;
 }
 
@@ -415,9 +363,9 @@ int amx_synth_gmm_minmax(const unsigned char* d_labels, const float* d_noise, in
   if (int rc = syn_check_batch(batch)) return rc;
   const int n = 2 * batch;
   if (int rc = syn_check_rows(n, voxels)) return rc;
-  if (int rc = syn_check_tables(h_table, d_table)) return rc;
+  if (int rc = amx::check_tables(h_table, d_table)) return rc;
   if (!d_labels || !d_noise || !d_scratch) return fail(AMX_ERR_INVALID, "null labels, noise or scratch");
-  if (int rc = amx::need_scratch(syn_minmax_bytes(n, voxels), scratch_bytes)) return rc;
+  if (int rc = amx::need_scratch(amx::minmax_bytes(n, voxels), scratch_bytes)) return rc;
   if (int rc = syn_check_gmm(h_table, n)) return rc;
   const dim3 grid(Syn::chunks(n, voxels), n);
   const int nt = (int)Syn::tiles(voxels);
@@ -435,15 +383,15 @@ int amx_synth_appearance(const unsigned char* d_labels, const float* d_noise, co
   if (int rc = syn_check_batch(batch)) return rc;
   const int n = 2 * batch;
   if (int rc = syn_check_dims(n, d, h, w)) return rc;
-  if (int rc = syn_check_tables(h_table, d_table)) return rc;
+  if (int rc = amx::check_tables(h_table, d_table)) return rc;
   if (!d_labels || !d_noise || !d_gmm_minmax || !d_out || !d_scratch) return fail(AMX_ERR_INVALID, "null labels, noise, statistics, output or scratch");
   if (nscales < 1 || nscales > AMX_SYNTH_MAX_SCALES || !scales || !d_grids)
     return fail(AMX_ERR_INVALID, "1 <= nscales <= %d with their sizes and grids (got %d)", AMX_SYNTH_MAX_SCALES, nscales);
   const long long V = (long long)d * h * w;
-  if (int rc = amx::need_scratch(syn_minmax_bytes(n, V), scratch_bytes)) return rc;
+  if (int rc = amx::need_scratch(amx::minmax_bytes(n, V), scratch_bytes)) return rc;
   if (int rc = syn_check_gmm(h_table, n)) return rc;
-  amx::SynApp a;
-  a.d = d, a.h = h, a.w = w, a.V = V, a.ntiles = (int)Syn::tiles(V), a.nscales = nscales, a.off[0] = 0;
+  amx::SynApp a(amx::StreamDims::make(d, h, w));
+  a.nscales = nscales, a.off[0] = 0;
   for (int s = 0; s < AMX_SYNTH_MAX_SCALES; ++s) a.rs[s] = 0.f, a.cd[s] = a.ch[s] = a.cw[s] = 1, a.off[s + 1] = 0, a.grid[s] = nullptr;
   for (int s = 0; s < nscales; ++s) {
     const int sc = scales[s];
@@ -487,7 +435,7 @@ int amx_synth_logk_mean(const float* d_k, int rows, long long voxels, float* d_m
 int amx_synth_spike(float* d_x, const float* d_k, int k_rows, const float* d_logk_mean, int n, int d, int h, int w, const amx_synth_view* h_table,
                     const amx_synth_view* d_table, void* stream) {
   if (int rc = syn_check_dims(n, d, h, w)) return rc;
-  if (int rc = syn_check_tables(h_table, d_table)) return rc;
+  if (int rc = amx::check_tables(h_table, d_table)) return rc;
   if (!d_x || !d_k) return fail(AMX_ERR_INVALID, "null image or k-space");
   const int size[3] = {d, h, w};
   for (int i = 0; i < n; ++i) {
@@ -498,14 +446,13 @@ int amx_synth_spike(float* d_x, const float* d_k, int k_rows, const float* d_log
       if (s.spike_loc[a] < 0 || s.spike_loc[a] >= size[a])
         return fail(AMX_ERR_INVALID, "row %d axis %d: spike location %d is outside 0 .. %d", i, a, s.spike_loc[a], size[a] - 1);
     if (s.flags & AMX_SYNTH_SPIKE_FIXED) {
-      if (!syn_finite(s.spike_intensity)) return fail(AMX_ERR_INVALID, "row %d: spike_intensity is not finite", i);
+      if (!amx::is_finite(s.spike_intensity)) return fail(AMX_ERR_INVALID, "row %d: spike_intensity is not finite", i);
     } else {
       if (!d_logk_mean) return fail(AMX_ERR_INVALID, "row %d takes its intensity from the mean of log|k| but d_logk_mean is null", i);
-      if (!syn_finite(s.spike_factor)) return fail(AMX_ERR_INVALID, "row %d: spike_factor is not finite", i);
+      if (!amx::is_finite(s.spike_factor)) return fail(AMX_ERR_INVALID, "row %d: spike_factor is not finite", i);
     }
   }
-  amx::SynDims g;
-  g.d = d, g.h = h, g.w = w, g.V = (long long)d * h * w, g.ntiles = (int)Syn::tiles(g.V);
+  const amx::StreamDims g = amx::StreamDims::make(d, h, w);
   const dim3 grid(Syn::chunks(n, g.V), n);
   if (g.V % 4 == 0 && amx::aligned16(d_x)) amx::syn_spike_kernel<true><<<grid, Syn::kThreads, 0, (hipStream_t)stream>>>(g, d_x, d_k, d_logk_mean, d_table);
   else amx::syn_spike_kernel<false><<<grid, Syn::kThreads, 0, (hipStream_t)stream>>>(g, d_x, d_k, d_logk_mean, d_table);
@@ -516,18 +463,17 @@ int amx_synth_spike(float* d_x, const float* d_k, int k_rows, const float* d_log
 int amx_synth_lowres(const float* d_in, float* d_out, int n, int d, int h, int w, const amx_synth_view* h_table, const amx_synth_view* d_table,
                      void* stream) {
   if (int rc = syn_check_dims(n, d, h, w)) return rc;
-  if (int rc = syn_check_tables(h_table, d_table)) return rc;
+  if (int rc = amx::check_tables(h_table, d_table)) return rc;
   if (!d_in || !d_out) return fail(AMX_ERR_INVALID, "null input or output");
   const size_t bytes = (size_t)n * d * h * w * sizeof(float);
-  if ((uintptr_t)d_in < (uintptr_t)d_out + bytes && (uintptr_t)d_out < (uintptr_t)d_in + bytes) return fail(AMX_ERR_INVALID, "d_in and d_out must not overlap");
+  if (amx::overlap(d_in, bytes, d_out, bytes)) return fail(AMX_ERR_INVALID, "d_in and d_out must not overlap");
   const int size[3] = {d, h, w};
   for (int i = 0; i < n; ++i)
     if (h_table[i].flags & AMX_SYNTH_LOWRES)
       for (int a = 0; a < 3; ++a)
         if (h_table[i].lowres[a] < 1 || h_table[i].lowres[a] > size[a])
           return fail(AMX_ERR_INVALID, "row %d axis %d: low-resolution size %d is outside 1 .. %d", i, a, h_table[i].lowres[a], size[a]);
-  amx::SynDims g;
-  g.d = d, g.h = h, g.w = w, g.V = (long long)d * h * w, g.ntiles = (int)Syn::tiles(g.V);
+  const amx::StreamDims g = amx::StreamDims::make(d, h, w);
   const dim3 grid(Syn::chunks(n, g.V), n);
   if (g.V % 4 == 0 && amx::aligned16(d_in) && amx::aligned16(d_out))
     amx::syn_lowres_kernel<true><<<grid, Syn::kThreads, 0, (hipStream_t)stream>>>(g, d_in, d_out, d_table);
@@ -539,12 +485,8 @@ int amx_synth_lowres(const float* d_in, float* d_out, int n, int d, int h, int w
 int amx_synth_clip_minmax(const float* d_x, int n, long long voxels, void* d_scratch, size_t scratch_bytes, void* stream) {
   if (int rc = syn_check_rows(n, voxels)) return rc;
   if (!d_x || !d_scratch) return fail(AMX_ERR_INVALID, "null input or scratch");
-  if (int rc = amx::need_scratch(syn_minmax_bytes(n, voxels), scratch_bytes)) return rc;
-  const dim3 grid(Syn::chunks(n, voxels), n);
-  const int nt = (int)Syn::tiles(voxels);
-  if (voxels % 4 == 0 && amx::aligned16(d_x)) amx::syn_clip_minmax_kernel<true><<<grid, Syn::kThreads, 0, (hipStream_t)stream>>>(d_x, voxels, nt, (float*)d_scratch);
-  else amx::syn_clip_minmax_kernel<false><<<grid, Syn::kThreads, 0, (hipStream_t)stream>>>(d_x, voxels, nt, (float*)d_scratch);
-  AMX_HIP(hipGetLastError());
+  if (int rc = amx::need_scratch(amx::minmax_bytes(n, voxels), scratch_bytes)) return rc;
+  AMX_HIP(amx::launch_minmax_partials(d_x, n, voxels, true, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }
 

@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, _stream
 from ..segmentation import augment as SA
 
 ZERO_BACKGROUND, SPIKE, SPIKE_FIXED, LOWRES = 1, 2, 4, 8
@@ -35,59 +35,30 @@ VIEW_DTYPE = np.dtype([("flags", "<i4"), ("nlabels", "<i4"), ("rank", "u1", (256
                        ("spike_intensity", "<f4"), ("lowres", "<i4", (3,))])
 
 
-class _Table:
-    """The per-row records of one batch: filled on the host, copied to the device once (``device()``)."""
-
-    def __init__(self, n):
-        lib = _lib.load()
-        if lib.amx_synth_view_bytes() != VIEW_DTYPE.itemsize:
-            raise _lib.AmxError(f"amx_synth_view is {lib.amx_synth_view_bytes()} bytes in the library and {VIEW_DTYPE.itemsize} here")
-        self.host = np.zeros(n, VIEW_DTYPE)
-        self.host["nlabels"] = 1
-        self.host["lowres"] = 1
-        self.dev = None
-
-    def device(self, dev):
-        self.dev = torch.from_numpy(self.host.view(np.uint8).reshape(-1)).to(dev)
-        return self
-
-    @property
-    def args(self):
-        return ctypes.c_void_p(self.host.ctypes.data), _lib.ptr(self.dev)
+class _Table(_stream.RecordTable):
+    """The per-row records of one batch."""
+    DTYPE, STRUCT, SIZE_SYMBOL = VIEW_DTYPE, "amx_synth_view", "amx_synth_view_bytes"
+    DEFAULTS = {"nlabels": 1, "lowres": 1}
 
 
 def _rows(x, name="image"):
     """A contiguous float32 device tensor [B, C, D, H, W] as rows [B C, 1, D, H, W], or an error."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name}: a torch tensor (got {type(x).__name__})")
-    if not x.is_cuda:
-        raise RuntimeError(f"{name}: the data generation runs on the GPU and has no host path (got a {x.device} tensor)")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{name}: float32 (got {x.dtype})")
+    x = _stream.device_tensor(x, name, (torch.float32,), "data generation")
     if x.dim() != 5:
         raise ValueError(f"{name}: [B, C, D, H, W] (got {tuple(x.shape)})")
     return x.contiguous().view((x.shape[0] * x.shape[1], 1) + tuple(x.shape[2:]))
 
 
 def _labels(y):
-    if not isinstance(y, torch.Tensor):
-        raise TypeError(f"labels: a torch tensor (got {type(y).__name__})")
-    if not y.is_cuda:
-        raise RuntimeError(f"labels: the data generation runs on the GPU and has no host path (got a {y.device} tensor)")
-    if y.dtype != torch.uint8:
-        raise TypeError(f"labels: uint8 (got {y.dtype})")
+    y = _stream.device_tensor(y, "labels", (torch.uint8,), "data generation")
     if y.dim() != 5 or y.shape[1] != 1:
         raise ValueError(f"labels: [B, 1, D, H, W] (got {tuple(y.shape)})")
     return y.contiguous()
 
 
 def _per_row(v, n, width=None, name="parameter", dtype=np.float64):
-    a = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=dtype)
-    shape = (n,) if width is None else (n, width)
-    try:
-        return np.ascontiguousarray(np.broadcast_to(a, shape))
-    except ValueError:
-        raise ValueError(f"{name}: a scalar, {'' if width is None else f'{width} values, '}or one per view ({n}) (got shape {a.shape})") from None
+    return _stream.per_row(v, (n,) if width is None else (n, width), name,
+                           f"a scalar, {'' if width is None else f'{width} values, '}or one per view ({n})", dtype=dtype)
 
 
 def coarse_shapes(shape, scales):
@@ -226,9 +197,7 @@ def _scratch(n, V, dev):
 
 
 def _finalize(sc, nb, n, V, dev):
-    mm = torch.empty((n, 2), dtype=torch.float32, device=dev)
-    _lib.check_envelope(_lib.load().amx_segaug_minmax_finalize(_lib.ptr(sc), nb, n, V, _lib.ptr(mm), _lib.stream(dev)))
-    return mm
+    return _stream.minmax_finalize(sc, nb, n, V, dev)
 
 
 def _appearance_table(params, B):

@@ -12,13 +12,12 @@ There is no host path: CPU tensors, other dtypes than float32 and more than one 
 from __future__ import annotations
 
 import copy
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, _stream
 
 SPATIAL, BLUR, NOISE, BIAS, GAMMA = 1, 2, 4, 8, 16
 MAX_RADIUS = 8
@@ -35,12 +34,7 @@ _IDENTITY_MAP = np.hstack([np.eye(3), np.zeros((3, 1))])
 
 def _views(x, name="image"):
     """A contiguous float32 [views, D, H, W] device tensor (a [D, H, W] volume is one view), or an error: no host path, no conversion."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name}: a torch tensor (got {type(x).__name__})")
-    if not x.is_cuda:
-        raise RuntimeError(f"{name}: the augmentation runs on the GPU and has no host path (got a {x.device} tensor)")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{name}: float32 (got {x.dtype})")
+    x = _stream.device_tensor(x, name, (torch.float32,), "augmentation")
     if x.dim() == 3:
         x = x[None]
     if x.dim() != 4:
@@ -50,44 +44,20 @@ def _views(x, name="image"):
 
 def _volume(x, name, dtypes=(torch.float32,)):
     """One volume of a sample, [D, H, W] or [1, D, H, W], as a contiguous [D, H, W] device tensor."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name}: a torch tensor (got {type(x).__name__})")
-    if not x.is_cuda:
-        raise RuntimeError(f"{name}: the augmentation runs on the GPU and has no host path (got a {x.device} tensor)")
-    if x.dtype not in dtypes:
-        raise TypeError(f"{name}: {' or '.join(str(d).split('.')[1] for d in dtypes)} (got {x.dtype})")
+    x = _stream.device_tensor(x, name, dtypes, "augmentation")
     if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1):
         raise ValueError(f"{name}: [D, H, W] or [1, D, H, W] with one channel (got {tuple(x.shape)})")
     return x.reshape(x.shape[-3:]).contiguous()
 
 
 def _per_view(v, n, shape, name):
-    a = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
-    try:
-        return np.ascontiguousarray(np.broadcast_to(a, (n,) + tuple(shape)))
-    except ValueError:
-        raise ValueError(f"{name}: shape {tuple(shape)} or one per view of the {n} (got {a.shape})") from None
+    return _stream.per_row(v, (n,) + tuple(shape), name, f"shape {tuple(shape)} or one per view of the {n}", got="got")
 
 
-class _Table:
-    """The per-view records of one pair: filled on the host, copied to the device once (``device()``)."""
-
-    def __init__(self, n):
-        lib = _lib.load()
-        if lib.amx_preaug_view_bytes() != VIEW_DTYPE.itemsize:
-            raise _lib.AmxError(f"amx_preaug_view is {lib.amx_preaug_view_bytes()} bytes in the library and {VIEW_DTYPE.itemsize} here")
-        self.host = np.zeros(n, VIEW_DTYPE)
-        self.host["map"] = _IDENTITY_MAP.reshape(12)
-        self.host["gamma"] = 1.0
-        self.dev = None
-
-    def device(self, dev):
-        self.dev = torch.from_numpy(self.host.view(np.uint8).reshape(-1)).to(dev)
-        return self
-
-    @property
-    def args(self):
-        return ctypes.c_void_p(self.host.ctypes.data), _lib.ptr(self.dev)
+class _Table(_stream.RecordTable):
+    """The per-view records of one pair."""
+    DTYPE, STRUCT, SIZE_SYMBOL = VIEW_DTYPE, "amx_preaug_view", "amx_preaug_view_bytes"
+    DEFAULTS = {"map": _IDENTITY_MAP.reshape(12), "gamma": 1.0}
 
 
 # ---- parameters -----------------------------------------------------------------------------------------------------------------
@@ -203,8 +173,7 @@ def draw_params(rng, shape, opt):
 # ---- the stages on the stacked views --------------------------------------------------------------------------------------------
 
 def _minmax(x):
-    from ..segmentation.augment import _minmax as seg_minmax       # amx_segaug_minmax as it stands: one row per view
-    return seg_minmax(x[:, None])
+    return _stream.minmax(x)       # amx_segaug_minmax as it stands: one row per view
 
 
 def _spatial(x, lab, table, mm):

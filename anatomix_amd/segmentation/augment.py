@@ -11,13 +11,12 @@ its version and is not reproduced: ``draw_params`` has one documented order of i
 There is no host path: CPU tensors, other dtypes than float32 and more than one channel raise."""
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, _stream
 
 NOISE, BIAS, GIBBS, CONTRAST, SMOOTH, SHARPEN, AFFINE, RESCALE = 1, 2, 4, 8, 16, 32, 64, 128
 SWITCHES = (("noise", NOISE, 0.33), ("bias", BIAS, 0.33), ("gibbs", GIBBS, 0.33), ("contrast", CONTRAST, 0.33),
@@ -35,12 +34,7 @@ _GIBBS_R_WORD = SAMPLE_DTYPE.fields["gibbs_r"][1] // 4
 
 def _image(x, name="image"):
     """A contiguous float32 [B, 1, D, H, W] device tensor, or an error: there is no host path and no conversion."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name}: a torch tensor (got {type(x).__name__})")
-    if not x.is_cuda:
-        raise RuntimeError(f"{name}: the augmentation runs on the GPU and has no host path (got a {x.device} tensor)")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{name}: float32 (got {x.dtype})")
+    x = _stream.device_tensor(x, name, (torch.float32,), "augmentation")
     if x.dim() != 5 or x.shape[1] != 1:
         raise ValueError(f"{name}: [B, 1, D, H, W] with one channel (got {tuple(x.shape)})")
     return x.contiguous()
@@ -58,34 +52,14 @@ def _label(y, like, name="label"):
 
 def _per_sample(v, B, width=None, name="parameter"):
     """A float64 array [B] (or [B, width]) from a scalar, one row, or one entry per sample."""
-    a = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
-    shape = (B,) if width is None else (B, width)
-    try:
-        return np.ascontiguousarray(np.broadcast_to(a, shape))
-    except ValueError:
-        raise ValueError(f"{name}: a scalar, {'' if width is None else f'{width} values, '}or one per sample of the batch of {B} "
-                         f"(got shape {a.shape})") from None
+    return _stream.per_row(v, (B,) if width is None else (B, width), name,
+                           f"a scalar, {'' if width is None else f'{width} values, '}or one per sample of the batch of {B}")
 
 
-class _Table:
-    """The per-sample records of one batch: filled on the host, copied to the device once (``device()``)."""
-
-    def __init__(self, B):
-        lib = _lib.load()
-        if lib.amx_segaug_sample_bytes() != SAMPLE_DTYPE.itemsize:
-            raise _lib.AmxError(f"amx_segaug_sample is {lib.amx_segaug_sample_bytes()} bytes in the library and {SAMPLE_DTYPE.itemsize} here")
-        self.host = np.zeros(B, SAMPLE_DTYPE)
-        self.host["affine"] = np.eye(3, dtype=np.float32).reshape(9)
-        self.host["gamma"] = 1.0
-        self.dev = None
-
-    def device(self, dev):
-        self.dev = torch.from_numpy(self.host.view(np.uint8).reshape(-1)).to(dev)
-        return self
-
-    @property
-    def args(self):
-        return ctypes.c_void_p(self.host.ctypes.data), _lib.ptr(self.dev)
+class _Table(_stream.RecordTable):
+    """The per-sample records of one batch."""
+    DTYPE, STRUCT, SIZE_SYMBOL = SAMPLE_DTYPE, "amx_segaug_sample", "amx_segaug_sample_bytes"
+    DEFAULTS = {"affine": np.eye(3, dtype=np.float32).reshape(9), "gamma": 1.0}
 
 
 def gaussian_taps(sigma):
@@ -181,13 +155,7 @@ def draw_params(rng, crop_size, volume_shapes, batch):
 # ---- the stages on a batch ------------------------------------------------------------------------------------------------
 
 def _minmax(x, scratch=None):
-    B, V = x.shape[0], x[0].numel()
-    lib = _lib.load()
-    mm = torch.empty((B, 2), dtype=torch.float32, device=x.device)
-    nb = lib.amx_segaug_scratch_bytes(B, V)
-    sc = _lib.scratch(nb, x.device) if scratch is None else scratch
-    _lib.check_envelope(lib.amx_segaug_minmax(_lib.ptr(x), B, V, _lib.ptr(mm), _lib.ptr(sc), nb, _lib.stream(x.device)))
-    return mm
+    return _stream.minmax(x, scratch)
 
 
 def _pointwise(x, out, mm, op, table):
@@ -461,7 +429,5 @@ def augment_batch(volumes, labels, params, noise=None):
         if on["sharpen"]:
             x = _gaussian(x, _GAUSS_SHARPEN, table)
         out, olab, sc, nb = _affine(x, lab, crop, table)
-        mm = torch.empty((B, 2), dtype=torch.float32, device=dev)
-        _lib.check_envelope(_lib.load().amx_segaug_minmax_finalize(_lib.ptr(sc), nb, B, out[0].numel(), _lib.ptr(mm), _lib.stream(dev)))
-        _pointwise(out, out, mm, _OP_SCALE, table)
+        _pointwise(out, out, _stream.minmax_finalize(sc, nb, B, out[0].numel(), dev), _OP_SCALE, table)
     return out, olab

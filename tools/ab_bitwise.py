@@ -1,5 +1,5 @@
-"""Bitwise A/B of two builds of libanatomix_amd.so over the entries of the streaming units (segmentation loss, augmentation,
-registration metrics, instance optimisation, MIND-SSC / correlation): the proof that a refactor of their shared helpers changed no
+"""Bitwise A/B of two builds of libanatomix_amd.so over the entries of the streaming units (segmentation loss, the three augmentation
+units, registration metrics, instance optimisation, MIND-SSC / correlation): the proof that a refactor of their shared helpers changed no
 summation order and no contraction.
 
     python tools/ab_bitwise.py --old PATH/libanatomix_amd.so [--new PATH/libanatomix_amd.so]
@@ -9,6 +9,7 @@ its own (``--child``), one after the other and each under its own time limit.  A
 prints one SHA-256 per output tensor; the two listings are compared here and THAT comparison sets the exit status: 0 identical,
 1 different, 2 a child failed (the second one is then not started)."""
 import argparse
+import ctypes
 import hashlib
 import os
 import subprocess
@@ -23,7 +24,9 @@ def child():
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
-    from anatomix_amd import _lib
+    from anatomix_amd import _lib, _stream
+    from anatomix_amd.datagen import views as SV
+    from anatomix_amd.pretraining import augment as P
     from anatomix_amd.registration import convex_adam_utils as CU, instance_optimization as IO, metrics as RM
     from anatomix_amd.segmentation import augment as G
 
@@ -43,8 +46,8 @@ def child():
         buf[offset:] = torch.randn(int(np.prod(shape)), generator=gen).to(dev)
         return buf[offset:].view(*shape)
 
-    def empty(*shape, offset=0):
-        return torch.empty(int(np.prod(shape)) + offset, dtype=torch.float32, device=dev)[offset:].view(*shape)
+    def empty(*shape, offset=0, dtype=torch.float32):
+        return torch.empty(int(np.prod(shape)) + offset, dtype=dtype, device=dev)[offset:].view(*shape)
 
     # ---- amx_seg_loss_forward / _backward / amx_seg_argmax, head mode and logits mode
     LABEL = (torch.float32, torch.int64, torch.uint8)
@@ -123,6 +126,84 @@ def child():
         _lib.check(lib.amx_segaug_minmax_finalize(_lib.ptr(sc), nb, B, out[0].numel(), _lib.ptr(mm2), _lib.stream(dev)))
         emit(f"segaug_minmax_finalize/{tag}/minmax", mm2)
         del vols, labs, img, lab, out, olab, pos
+
+    # ---- preaug: spatial (image and label), blur, intensity on 2 views; off = 1 puts every base one element past an allocation
+    st = _lib.stream(dev)
+    for tag, shape, off in (("12x10x8", (12, 10, 8), 0), ("12x10x8_off1", (12, 10, 8), 1), ("9x11x7", (9, 11, 7), 0), ("37x35x70", (37, 35, 70), 0)):
+        x, noise = rand(2, *shape, offset=off), rand(2, *shape, offset=off)
+        lab = empty(*shape, offset=off, dtype=torch.uint8)
+        lab.copy_(torch.randint(0, 7, shape, generator=gen).to(torch.uint8))
+        mm = P._minmax(x)
+        for which in ("both_on", "view1_copied"):
+            t = P._Table(2)
+            t.host["flags"] = P.SPATIAL | P.BLUR | P.NOISE | P.BIAS | P.GAMMA
+            if which == "view1_copied":
+                t.host["flags"][1] = P.NOISE | P.GAMMA
+            t.host["map"][0] = P.spatial_map(shape, (True, False, True), (1.2, 0.8, 1.1), (20.0, -35.0, 10.0)).reshape(12)
+            t.host["map"][1] = P.spatial_map(shape, (False, True, False), (0.7, 1.3, 0.9), (-40.0, 5.0, 25.0)).reshape(12)
+            P._set_taps(t, np.array([[2.0, 2.0, 2.0], [0.6, 1.3, 0.0]]))
+            t.host["noise_std"], t.host["gamma"] = (0.1, 0.2), (0.7, 1.4)
+            t.host["bias"] = np.linspace(-0.5, 0.5, 20)[None] * np.array([[1.0], [-0.6]])
+            t.device(dev)
+            with_lab = which == "both_on"
+            out, tmp = empty(2, *shape, offset=off), empty(2, *shape, offset=off)
+            olab = empty(*shape, offset=off, dtype=torch.uint8) if with_lab else None
+            _lib.check(lib.amx_preaug_spatial(_lib.ptr(x), _lib.ptr(lab if with_lab else None), 2, *shape, _lib.ptr(mm), _lib.ptr(out),
+                                              _lib.ptr(olab), *t.args, st))
+            emit(f"preaug_spatial/{tag}/{which}/img", out)
+            if with_lab:
+                emit(f"preaug_spatial/{tag}/{which}/lab", olab)
+            _lib.check(lib.amx_preaug_blur(_lib.ptr(x), _lib.ptr(out), _lib.ptr(tmp), 2, *shape, *t.args, st))
+            emit(f"preaug_blur/{tag}/{which}/out", out)
+            _lib.check(lib.amx_preaug_intensity(_lib.ptr(x), _lib.ptr(noise), _lib.ptr(tmp), 2, *shape, *t.args, st))
+            emit(f"preaug_intensity/{tag}/{which}/out", tmp)
+        del x, noise, lab, out, tmp, olab
+
+    # ---- synth: every entry on batch 2 (4 rows); noff = 1 puts the noise one float past an allocation.  k-space is a seeded tensor.
+    n = 4
+    for tag, shape, scales, noff in (("16x32x48", (16, 32, 48), (4, 8, 16), 0), ("16x32x48_noise_off1", (16, 32, 48), (4, 8, 16), 1),
+                                     ("9x15x21", (9, 15, 21), (1, 3), 0)):
+        V = int(np.prod(shape))
+        uniq = [np.arange(5), np.arange(6)]
+        params = dict(unique_labels=uniq, means=[np.linspace(25, 255, 2 * u.size).reshape(2, -1) for u in uniq],
+                      stds=[np.linspace(5, 20, 2 * u.size).reshape(2, -1) for u in uniq],
+                      zero_background=np.array([[False, False], [True, False]]), perl_mult_factor=0.02)
+        t = SV._appearance_table(params, 2)
+        t.host["flags"] |= np.array([SV.SPIKE, SV.SPIKE | SV.SPIKE_FIXED | SV.LOWRES, SV.LOWRES, SV.LOWRES])
+        t.host["spike_loc"] = (shape[0] // 2 + 1, shape[1] // 3, 1)
+        t.host["spike_loc"][1] = (0, shape[1] - 1, shape[2] // 2)
+        t.host["spike_slot"], t.host["spike_factor"], t.host["spike_intensity"] = (0, 1, 0, 0), 1.0, 3.0
+        t.host["lowres"] = [SV.low_resolution_shape(shape, z) for z in (1.0, 0.5, 0.8, 0.5)]
+        t.device(dev)
+        lab = torch.cat([torch.randint(0, u.size, (1, V), generator=gen) for u in uniq]).to(torch.uint8).to(dev)
+        noise = rand(n, V, offset=noff)
+        grids = [rand(n, *[a // s for a in shape]) * (1.0 + i) for i, s in enumerate(scales)]
+        sc, nb = SV._scratch(n, V, dev)
+        _lib.check(lib.amx_synth_gmm_minmax(_lib.ptr(lab), _lib.ptr(noise), 2, V, *t.args, _lib.ptr(sc), nb, st))
+        mm = _stream.minmax_finalize(sc, nb, n, V, dev)
+        emit(f"synth_gmm_minmax/{tag}/minmax", mm)
+        x = empty(n, V)
+        gp = (ctypes.c_void_p * len(scales))(*[g.data_ptr() for g in grids])
+        _lib.check(lib.amx_synth_appearance(_lib.ptr(lab), _lib.ptr(noise), gp, (ctypes.c_int * len(scales))(*scales), len(scales),
+                                            _lib.ptr(mm), _lib.ptr(x), 2, *shape, *t.args, _lib.ptr(sc), nb, st))
+        emit(f"synth_appearance/{tag}/out", x)
+        emit(f"synth_appearance/{tag}/minmax", _stream.minmax_finalize(sc, nb, n, V, dev))
+        k, mean = rand(2, V, 2), empty(2)
+        _lib.check(lib.amx_synth_logk_mean(_lib.ptr(k), 2, V, _lib.ptr(mean), _lib.ptr(sc), nb, st))
+        emit(f"synth_logk_mean/{tag}/mean", mean)
+        _lib.check(lib.amx_synth_spike(_lib.ptr(x), _lib.ptr(k), 2, _lib.ptr(mean), n, *shape, *t.args, st))
+        emit(f"synth_spike/{tag}/out", x)
+        low = empty(n, V)
+        _lib.check(lib.amx_synth_lowres(_lib.ptr(x), _lib.ptr(low), n, *shape, *t.args, st))
+        emit(f"synth_lowres/{tag}/out", low)
+        _lib.check(lib.amx_synth_clip_minmax(_lib.ptr(low), n, V, _lib.ptr(sc), nb, st))
+        mm = _stream.minmax_finalize(sc, nb, n, V, dev)
+        emit(f"synth_clip_minmax/{tag}/minmax", mm)
+        for u8 in (0, 1):
+            fin = empty(n, V, dtype=torch.uint8 if u8 else torch.float32)
+            _lib.check(lib.amx_synth_finish(_lib.ptr(low), _lib.ptr(fin), n, V, _lib.ptr(mm), u8, st))
+            emit(f"synth_finish/{tag}/{'uint8' if u8 else 'float32'}", fin)
+        del lab, noise, grids, x, low, k
 
     # ---- registration metrics
     for shape in ((7, 9, 11), (32, 32, 32)):

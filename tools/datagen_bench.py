@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from _timing import TIMED, WARMUP, stats, timed            # noqa: E402
 import _datagen_ref as DR                                   # noqa: E402
 import _segaug_ref as AR                                    # noqa: E402
 from anatomix_amd.datagen import views as V                 # noqa: E402
@@ -32,29 +33,10 @@ from anatomix_amd.segmentation import augment as SA         # noqa: E402
 B, N, SCALES = 8, 128, (4, 8, 16, 32)
 SHAPE = (N, N, N)
 R = 2 * B
-WARMUP, TIMED = 3, 10
 # bytes per view voxel that each kernel stage has to move at least once (fp32 views, uint8 labels shared by the two views of a sample;
 # the coarse grids are 1/64 of a volume and less and are left out)
 STAGE_BYTES = {"gmm_minmax": 4 + 0.5, "appearance": 4 + 0.5 + 4, "rescale": 8, "bias": 4 + 1 + 4 + 1, "spike_logk": 8, "spike_wave": 8,
                "contrast": 4 + 8, "smooth": 3 * 8, "sharpen": 5 * 8 + 12, "lowres": 8, "tail_u8": 4 + 4 + 1}
-
-
-def timed(routes):
-    out = {k: [] for k in routes}
-    for it in range(WARMUP + TIMED):
-        for k, fn in routes.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if it >= WARMUP:
-                out[k].append(a.elapsed_time(b))
-    return out
-
-
-def stats(ms):
-    return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms)), "n": len(ms)}
 
 
 class TorchRoute:

@@ -23,11 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from _timing import TIMED, WARMUP, stats, timed            # noqa: E402
 import _preaug_ref as PR                                    # noqa: E402
 from anatomix_amd.pretraining import augment as G           # noqa: E402
 
 VOL, CROP = (160, 192, 160), 128
-WARMUP, TIMED = 3, 10
 # bytes per voxel and view that each kernel stage has to move at least once (fp32 image; the label adds 2 bytes to one view)
 STAGE_BYTES = {"spatial": 4 + 4 + 1, "blur": 2 * (4 + 4), "intensity": 4 + 4 + 4}
 
@@ -132,25 +132,6 @@ class HipStages:
 
     def motion(self, x):
         return torch.stack([G._motion_one(x[v], r["motion_degrees"], r["motion_translation"], r["motion_times"]) for v, r in enumerate(self.p["views"])])
-
-
-def timed(routes):
-    """routes: {name: callable}.  Alternates them, WARMUP + TIMED times each -> {name: [ms] * TIMED}."""
-    out = {k: [] for k in routes}
-    for it in range(WARMUP + TIMED):
-        for k, fn in routes.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if it >= WARMUP:
-                out[k].append(a.elapsed_time(b))
-    return out
-
-
-def stats(ms):
-    return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms)), "n": len(ms)}
 
 
 def main():

@@ -27,11 +27,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from _timing import TIMED, WARMUP, stats, timed            # noqa: E402
 import _segaug_ref as AR                                    # noqa: E402
 from anatomix_amd.segmentation import augment as G          # noqa: E402
 
 B, CROP, VOL = 4, 128, (160, 192, 160)
-WARMUP, TIMED = 3, 10
 # bytes per output voxel that each stage has to move at least once (fp32 image, uint8 label)
 STAGE_BYTES = {"crop_noise_bias": 4 + 1 + 4 + 4 + 1, "contrast": 4 + 4 + 4, "smooth": 3 * 8, "sharpen": 5 * 8 + 12, "affine": 5 + 5, "rescale": 8}
 
@@ -133,29 +133,7 @@ class HipStages:
 
     def rescale(self, x):
         _, _, sc, nb = self.aff
-        mm = torch.empty((B, 2), dtype=torch.float32, device=self.dev)
-        G._lib.check_envelope(G._lib.load().amx_segaug_minmax_finalize(G._lib.ptr(sc), nb, B, x[0].numel(), G._lib.ptr(mm),
-                              G._lib.stream(self.dev)))
-        return G._pointwise(x, torch.empty_like(x), mm, G._OP_SCALE, self.t)
-
-
-def timed(routes):
-    """routes: {name: callable}.  Alternates them, WARMUP + TIMED times each -> {name: [ms] * TIMED}."""
-    out = {k: [] for k in routes}
-    for it in range(WARMUP + TIMED):
-        for k, fn in routes.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if it >= WARMUP:
-                out[k].append(a.elapsed_time(b))
-    return out
-
-
-def stats(ms):
-    return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms)), "n": len(ms)}
+        return G._pointwise(x, torch.empty_like(x), G._stream.minmax_finalize(sc, nb, B, x[0].numel(), self.dev), G._OP_SCALE, self.t)
 
 
 def main():
