@@ -89,7 +89,6 @@ static int conv3d_single(const void* d_x0, int c0, const void* d_x1, int c1, con
   if (is_mx(precision) && weight_mode != 0) return fail(AMX_ERR_INVALID, "f16x2mx packs forward weights only");
   // strict precision: x0 / x1 / out16 voxels hold [hi(C) | lo(C)]; f16x2mx: [hi(C) | lo(C) | e4m3 copies (2C bytes)] -- the INPUT
   // voxels must carry valid copies (tests/_util.py to_ndhwc_mx), the output's copy section is left untouched
-  const long long eb = elem_bytes(precision);
   const int q = amx::conv_pick_q(cout, w, precision);
   if (d_out32 && (q > 2 || w < 32)) return fail(AMX_ERR_INVALID, "fp32 planar output needs cout <= 32 and w >= 32");
   if (cin_real < 1 || cin_real > c0 + c1 || cout_real < 1 || cout_real > cout || (weight_mode != 0 && weight_mode != 1))
@@ -104,30 +103,23 @@ static int conv3d_single(const void* d_x0, int c0, const void* d_x1, int c1, con
     AMX_HIP(amx::launch_pack_weights(d_weight, d_scale, d_wpk, cin_real, c0 + c1, cout, q, precision, st, weight_mode, cout_real));
   }
   p.N = n; p.D = d; p.H = hh; p.W = w; p.Cout = cout;
-  p.src0 = (const char*)d_x0; p.C0 = c0;
-  p.s0x = (long long)c0 * eb; p.s0y = p.s0x * w; p.s0z = p.s0y * hh; p.s0n = p.s0z * d;
+  amx::set_src0(p, d_x0, c0, d, hh, w, precision);
   if (c1) {
-    p.src1 = (const char*)d_x1; p.C1 = c1; p.up_shift = 1;
-    p.s1x = (long long)c1 * eb; p.s1y = p.s1x * (w / 2); p.s1z = p.s1y * (hh / 2); p.s1n = p.s1z * (d / 2);
-  }
-  if (is_mx(precision)) {      // row-planar tensors (amx_common.h FMT 2)
-    p.s0x = 32; p.cs0 = w * 32;
-    p.s1x = 32; p.cs1 = (w / 2) * 32;
+    amx::set_src1(p, d_x1, c1, d / 2, hh / 2, w / 2, precision);
+    p.up_shift = 1;
   }
   p.wpk = (const char*)d_wpk;
   p.bias = d_shift;
   p.act = act; p.slope = slope;
   if (d_out16) {
-    p.out = (char*)d_out16;
-    p.ox = (long long)cout * eb; p.oy = p.ox * w; p.oz = p.oy * hh; p.on = p.oz * d;
-    if (is_mx(precision)) { p.ox = 32; p.ocs = w * 32; }
+    amx::set_out(p, d_out16, cout, d, hh, w, precision);
   } else {
     p.out32 = d_out32;
     p.py = w; p.pz = (long long)hh * w; p.pc = p.pz * d; p.pn = p.pc * cout;
   }
-  if (prepacked && !is_split(precision) && weight_mode == 0 && cin_real == 48 && c0 == 16 && c1 == 32 && cout == 16 && amx::conv_upcat16_eligible(p))
-    return fail(AMX_ERR_INVALID, "prepacked weights: the 16 + up32 -> 16 merged-tap layer packs its own format (call without the flag)");
   if (!is_split(precision) && weight_mode == 0 && cin_real == 48 && c0 == 16 && c1 == 32 && cout == 16 && amx::conv_upcat16_eligible(p)) {
+    if (prepacked)
+      return fail(AMX_ERR_INVALID, "prepacked weights: the 16 + up32 -> 16 merged-tap layer packs its own format (call without the flag)");
     char* up = (char*)d_wpk + ((size_t)cout * (c0 + c1) * 28 * 2 + 255) / 256 * 256;
     AMX_HIP(amx::launch_pack_upcat16(d_weight, d_scale, up, precision, st));
     p.wpk = up;
@@ -253,7 +245,6 @@ int amx_conv3d_upcat_merged(const void* d_x0, int c0, const void* d_x1, int c1, 
   if (!d_x0 || !d_x1 || !d_weight || !d_wpk || !d_partial || !d_out16) return fail(AMX_ERR_INVALID, "null argument");
   if (precision < AMX_PREC_F16 || precision > AMX_PREC_BF16X2) return fail(AMX_ERR_INVALID, "unsupported precision %d", precision);
   const bool split = is_split(precision);
-  const long long eb = split ? 4 : 2;
   if (c0 != cout || !amx::conv_upmerge_eligible(c0, c1, cout, d, hh, w, 1, split))
     return fail(AMX_ERR_INVALID, "merged concat conv needs c0 == cout >= 32 (16 in the strict precisions), c1 %% 32 == 0, w >= 16, even dims "
                 "(c0=%d c1=%d cout=%d dims %d,%d,%d)", c0, c1, cout, d, hh, w);
@@ -265,16 +256,13 @@ int amx_conv3d_upcat_merged(const void* d_x0, int c0, const void* d_x1, int c1, 
   amx::ConvParams p;
   memset(&p, 0, sizeof p);
   p.N = n; p.D = d; p.H = hh; p.W = w; p.Cout = cout;
-  p.src0 = (const char*)d_x0; p.C0 = c0;
-  p.s0x = (long long)c0 * eb; p.s0y = p.s0x * w; p.s0z = p.s0y * hh; p.s0n = p.s0z * d;
+  amx::set_src0(p, d_x0, c0, d, hh, w, precision);
   p.wpk = (const char*)d_wpk; p.act = AMX_ACT_NONE;
-  p.out = (char*)d_partial;
-  p.ox = (long long)cout * eb; p.oy = p.ox * w; p.oz = p.oy * hh; p.on = p.oz * d;
+  amx::set_out(p, d_partial, cout, d, hh, w, precision);
   AMX_HIP(amx::launch_conv(p, precision, q, st));
   amx::UpmergeParams u;
   memset(&u, 0, sizeof u);
-  u.src = (const char*)d_x1; u.C1 = c1;
-  u.sx = (long long)c1 * eb; u.sy = u.sx * (w / 2); u.sz = u.sy * (hh / 2); u.sn = u.sz * (d / 2);
+  amx::set_src(u, d_x1, c1, d / 2, hh / 2, w / 2, precision);
   u.N = n; u.LD = d / 2; u.LH = hh / 2; u.LW = w / 2; u.Cout = cout;
   u.wpk = wmerge; u.part = (const char*)d_partial; u.out = (char*)d_out16;
   u.bias = d_shift; u.act = act; u.slope = slope;
@@ -379,11 +367,10 @@ int amx_conv3d_wgrad(const void* d_dy, long long dy_sn, long long dy_sz, long lo
   amx::WgradParams p;
   memset(&p, 0, sizeof p);
   p.dy = (const char*)d_dy; p.yn = dy_sn; p.yz = dy_sz; p.yy = dy_sy; p.yx = dy_sx;
-  p.src0 = (const char*)d_x0; p.C0 = c0;
-  p.s0x = (long long)c0 * 2; p.s0y = p.s0x * w; p.s0z = p.s0y * hh; p.s0n = p.s0z * d;
+  amx::set_src0(p, d_x0, c0, d, hh, w, AMX_PREC_F16);          // 16-bit channels-last in either precision this kernel takes
   if (c1) {
-    p.src1 = (const char*)d_x1; p.C1 = c1; p.up_shift = 1;
-    p.s1x = (long long)c1 * 2; p.s1y = p.s1x * (w / 2); p.s1z = p.s1y * (hh / 2); p.s1n = p.s1z * (d / 2);
+    amx::set_src1(p, d_x1, c1, d / 2, hh / 2, w / 2, AMX_PREC_F16);
+    p.up_shift = 1;
   }
   p.N = n; p.D = d; p.H = hh; p.W = w; p.Cout = cout;
   AMX_HIP(amx::launch_wgrad(p, cin_real, d_dw, accumulate, d_scratch, precision, (hipStream_t)stream));

@@ -15,7 +15,6 @@
 //   B operand  = activations: lane (i = lane&15, g = lane>>4) reads ONE 16-byte LDS slot = 8
 //                channels of voxel i at the tap selected by g (see amx_common.h step table).
 //   MFMA       = v_mfma_f32_16x16x32_{f16,bf16}: K = 32 = 2 taps x 16 input channels.
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "amx_device.h"
@@ -263,9 +262,6 @@ __global__ void pool2_kernel(const char* __restrict__ in, char* __restrict__ out
 // -------------------------------------------------------------------------------------------
 // host-side launchers
 // -------------------------------------------------------------------------------------------
-static thread_local char g_kernel_name[64] = "";
-const char* last_conv_kernel_name() { return g_kernel_name; }
-
 // Tile-shape heuristic.  Returns the Q (16-channel MFMA tiles per workgroup) a layer will be
 // launched with; the packed-weight layout depends on it.
 int conv_pick_q(int Cout, int W, int precision) {
@@ -283,30 +279,32 @@ int conv_pick_q(int Cout, int W, int precision) {
   return q;
 }
 
-// true when launch_conv runs the generic kernel for this layer -- the one whose epilogue can write InstanceNorm partial sums
-bool conv_fuses_stats(const ConvParams& p, int precision, int Q) {
-  if (p.src0_f32c1 || p.out32) return false;
-  return !((((precision < 2 && conv_zmarch_eligible(p)) || ((precision == 2 || precision == 3) && conv_zmarch_eligible_split(p))) && Q == p.Cout / 16));
+// The kernel launch_conv runs for a layer: the z-marching ring kernel for the narrow full / half-resolution layers, the register-stationary
+// split-K kernel for the deep levels, else the generic persistent kernel.  None: the fp32 stem (amx_conv3d_stem.hip) and frame-reading
+// sources (z-march only).  Asked with p.stats and p.part as the launch will carry them: conv_ks_eligible refuses the one, plans by the other.
+enum class ConvRoute { ZMarch, Ks, V2, None };
+static ConvRoute conv_route(const ConvParams& p, int precision, int Q) {
+  const bool zmarch = precision < 2 ? conv_zmarch_eligible(p) : (precision == 2 || precision == 3) && conv_zmarch_eligible_split(p);
+  if (zmarch && Q == p.Cout / 16) return ConvRoute::ZMarch;
+  if (p.src0_f32c1 || p.raw_halo) return ConvRoute::None;
+  return conv_ks_eligible(p, precision, Q) ? ConvRoute::Ks : ConvRoute::V2;
 }
-int last_conv_stats_slots() { return last_conv_v2_stats_slots(); }
 
-hipError_t launch_conv(const ConvParams& p, int precision, int Q, hipStream_t st) {
-  if (((precision < 2 && conv_zmarch_eligible(p)) || ((precision == 2 || precision == 3) && conv_zmarch_eligible_split(p))) && Q == p.Cout / 16) {
-    // narrow full/half-resolution layers: z-marching ring kernel
-    hipError_t e = launch_conv_zmarch(p, precision, st);
-    snprintf(g_kernel_name, sizeof g_kernel_name, "%s", last_conv_zm_kernel_name());
-    return e;
+// true when launch_conv runs the generic kernel for this layer once p.stats is set -- the one whose epilogue can write InstanceNorm
+// partial sums.  Asked BEFORE p.stats / p.part are set, hence "not the z-march route, not the stem, not planar": a layer that fuses
+// its statistics runs on the generic kernel even where the split-K kernel would otherwise take it.
+bool conv_fuses_stats(const ConvParams& p, int precision, int Q) {
+  return !p.src0_f32c1 && !p.out32 && conv_route(p, precision, Q) != ConvRoute::ZMarch;
+}
+
+hipError_t launch_conv(const ConvParams& p, int precision, int Q, hipStream_t st, ConvLaunchInfo* info) {
+  switch (conv_route(p, precision, Q)) {
+    case ConvRoute::ZMarch: return launch_conv_zmarch(p, precision, st, info);
+    case ConvRoute::Ks: return launch_conv_ks(p, precision, Q, st, info);
+    case ConvRoute::V2: return launch_conv_v2(p, precision, Q, st, info);
+    case ConvRoute::None: break;
   }
-  if (p.src0_f32c1) return hipErrorInvalidValue;   // the fp32 stem has its own kernel (amx_conv3d_stem.hip)
-  if (p.raw_halo) return hipErrorInvalidValue;     // frame-reading sources: the z-march kernels only
-  if (conv_ks_eligible(p, precision, Q)) {           // deep levels: register-stationary weights, K split over the waves
-    hipError_t e = launch_conv_ks(p, precision, Q, st);
-    snprintf(g_kernel_name, sizeof g_kernel_name, "%s", last_conv_ks_kernel_name());
-    return e;
-  }
-  hipError_t e = launch_conv_v2(p, precision, Q, st);   // generic path: persistent double-buffered DMA kernel
-  snprintf(g_kernel_name, sizeof g_kernel_name, "%s", last_conv_v2_kernel_name());
-  return e;
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_pack_weights(const float* w, const float* scale, void* wpk, int CinReal, int CinPad,

@@ -30,7 +30,6 @@
 // B = activations from a plane-major halo image, 14 paired-tap steps per 16 channels; reflect padding resolved in the gather.
 // Replaces nn.Conv3d(k=3, padding_mode='reflect') + folded eval BatchNorm3d + ReLU of /root/reference/anatomix/model/network.py:334-445
 // at the levels below 64^3.
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -448,14 +447,11 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ part, int S, cons
 // -------------------------------------------------------------------------------------------
 // launcher
 // -------------------------------------------------------------------------------------------
-static thread_local char g_kernel_name_ks[64] = "";
-const char* last_conv_ks_kernel_name() { return g_kernel_name_ks; }
-static int g_ks_cus = 0;
-
 template <typename T, typename C, bool PART>
-static hipError_t launch_ks_cfg(ConvParams p, hipStream_t st) {
-  snprintf(g_kernel_name_ks, sizeof g_kernel_name_ks, "conv3d_k3_ks<%s,%dx%dx%d,q%d,k%dx%d,c%d,t%d,h%d,b%d%s>", __is_same(T, f16) ? "f16" : "bf16",
-           C::TZ, C::TY, C::TX, C::Q, C::KW, C::CPW, C::CW, C::TEAMS, C::NH, C::NBUF, PART ? ",part" : "");
+static hipError_t launch_ks_cfg(ConvParams p, hipStream_t st, ConvLaunchInfo* info) {
+  if (info)                                                   // (0 slots: ks_plan refuses a launch with p.stats)
+    info->report(0, "conv3d_k3_ks<%s,%dx%dx%d,q%d,k%dx%d,c%d,t%d,h%d,b%d%s>", __is_same(T, f16) ? "f16" : "bf16", C::TZ, C::TY, C::TX, C::Q,
+                 C::KW, C::CPW, C::CW, C::TEAMS, C::NH, C::NBUF, PART ? ",part" : "");
   auto kern = conv3d_k3_ks_kernel<T, C, PART>;
   static amx::DeviceOnce attr_once;
   if (!attr_once.done()) {
@@ -463,24 +459,15 @@ static hipError_t launch_ks_cfg(ConvParams p, hipStream_t st) {
     if (e != hipSuccess) return e;
     attr_once.set();
   }
-  static int ks_cus_dev = -1;                                 // (the CU count of the device it was read on)
-  {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorUnknown;
-    if (g_ks_cus == 0 || dev != ks_cus_dev) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-      g_ks_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-      ks_cus_dev = dev;
-    }
-  }
+  const int cus = device_cus(attr_once.dev);
+  if (cus == 0) return hipErrorUnknown;
   p.nbz = (p.D + C::TZ - 1) / C::TZ;
   p.nby = (p.H + C::TY - 1) / C::TY;
   p.nbx = (p.W + C::TX - 1) / C::TX;
   const int nbricks = p.nbz * p.nby * p.nbx * p.N;
   const int S = p.kslices > 0 ? p.kslices : 1;
   const int combos = p.Cout / (16 * C::Q * C::CW) * S;
-  int wpc = g_ks_cus * C::WGS_PER_CU / combos;              // workgroups per (cout group, slice): WGS_PER_CU workgroups per CU in total
+  int wpc = cus * C::WGS_PER_CU / combos;              // workgroups per (cout group, slice): WGS_PER_CU workgroups per CU in total
   if (wpc < 1) wpc = 1;
   const int runs = (nbricks + C::TEAMS - 1) / C::TEAMS;      // a workgroup needs at least one brick per team to be useful
   if (wpc > runs) wpc = runs;
@@ -544,7 +531,7 @@ size_t conv_ks_part_bytes(int C0, int Cout, int N, int D, int H, int W, int prec
 }
 
 template <typename T>
-static hipError_t launch_ks_t(ConvParams p, const KsPlan& pl, int Q, hipStream_t st) {
+static hipError_t launch_ks_t(ConvParams p, const KsPlan& pl, int Q, hipStream_t st, ConvLaunchInfo* info) {
   const bool wide = p.W >= 16;
   p.kslices = pl.slices;
   const bool part = pl.slices > 1;
@@ -552,7 +539,7 @@ static hipError_t launch_ks_t(ConvParams p, const KsPlan& pl, int Q, hipStream_t
 #define AMX_KS(TZ, TY, TX, QW, QP, CPW, KW, CW, TEAMS, NH, ...)                              \
   do {                                                                                       \
     typedef KsCfg<TZ, TY, TX, QW, QP, CPW, KW, CW, TEAMS, NH, ##__VA_ARGS__> CC;             \
-    e = part ? launch_ks_cfg<T, CC, true>(p, st) : launch_ks_cfg<T, CC, false>(p, st);       \
+    e = part ? launch_ks_cfg<T, CC, true>(p, st, info) : launch_ks_cfg<T, CC, false>(p, st, info);      \
   } while (0)
   //                                                 brick     Q/wave packed CPW KW CW teams groups
   // Measured and NOT kept (profiles/r05_ks_shapes.txt, r05_ks_flags_trace.txt): NBUF = 1 -- two un-prefetched 4-wave workgroups per CU
@@ -581,10 +568,10 @@ static hipError_t launch_ks_t(ConvParams p, const KsPlan& pl, int Q, hipStream_t
   return hipGetLastError();
 }
 
-hipError_t launch_conv_ks(const ConvParams& p, int precision, int Q, hipStream_t st) {
+hipError_t launch_conv_ks(const ConvParams& p, int precision, int Q, hipStream_t st, ConvLaunchInfo* info) {
   const KsPlan pl = ks_plan(p, precision, Q, p.part != nullptr);
   if (!pl.ok) return hipErrorInvalidValue;
-  return precision == 0 ? launch_ks_t<f16>(p, pl, Q, st) : launch_ks_t<bf16>(p, pl, Q, st);
+  return precision == 0 ? launch_ks_t<f16>(p, pl, Q, st, info) : launch_ks_t<bf16>(p, pl, Q, st, info);
 }
 
 }  // namespace amx

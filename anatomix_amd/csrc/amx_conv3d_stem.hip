@@ -11,7 +11,6 @@
 // reference numerics emulation applies to the network input) and feeds them as the B fragment.
 // The input may be a strided window of a larger volume (sliding-window caller): nothing is
 // gathered or converted in HBM.
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "amx_device.h"
@@ -547,9 +546,6 @@ __global__ void pack_stem_kernel(const float* __restrict__ w, const float* __res
   wpk[idx] = part ? (T)(v - (float)(T)v) : (T)v;
 }
 
-static thread_local char g_kernel_name4[64] = "";
-const char* last_conv_stem_kernel_name() { return g_kernel_name4; }
-
 // z segments per (n, y, x) tile -- tiny LDS footprint: several workgroups per CU
 static void stem_segments(const ConvParams& p, int TY, int TX, int TZ, int* zseg_out, int* nseg_out) {
   const int tiles = ((p.H + TY - 1) / TY) * ((p.W + TX - 1) / TX) * p.N;
@@ -576,12 +572,9 @@ int conv_stem_stats_slots(const ConvParams& p, int precision) {
 }
 
 template <typename T, int Q, bool SPLIT>
-static hipError_t launch_stem_t(ConvParams p, hipStream_t st) {
+static hipError_t launch_stem_t(ConvParams p, hipStream_t st, ConvLaunchInfo* info) {
   constexpr int TY = 8, TX = 32, TZ = 2, NC = 8, R = 10;
   typedef StemCfg<TY, TX, TZ, NC, R> C;
-  snprintf(g_kernel_name4, sizeof g_kernel_name4, "conv3d_stem<%s,q%d,%dx%dx%d,c%d+l1,r%d>",
-           __is_same(T, f16) ? (SPLIT ? "f16x2" : "f16") : (SPLIT ? "bf16x2" : "bf16"), Q,
-           TZ, TY, TX, NC, R);
   p.nby = (p.H + TY - 1) / TY;
   p.nbx = (p.W + TX - 1) / TX;
   const int tiles = p.nby * p.nbx * p.N;
@@ -593,26 +586,28 @@ static hipError_t launch_stem_t(ConvParams p, hipStream_t st) {
   if constexpr (!SPLIT) {
     if (!p.stats) {
       typedef Stem2Cfg<TY, TX, TZ, NC, R, SPLIT> C2;
-      snprintf(g_kernel_name4, sizeof g_kernel_name4, "conv3d_stem<%s,q%d,%dx%dx%d,c%d+cv1,r%d,rows>",
-               __is_same(T, f16) ? "f16" : "bf16", Q, TZ, TY, TX, NC, R);
+      if (info) info->report(0, "conv3d_stem<%s,q%d,%dx%dx%d,c%d+cv1,r%d,rows>", __is_same(T, f16) ? "f16" : "bf16", Q, TZ, TY, TX, NC, R);
       hipLaunchKernelGGL((conv3d_stem2_kernel<T, Q, TY, TX, TZ, NC, R, SPLIT>), dim3((unsigned)(tiles * nseg)), dim3((NC + 1) * 64),
                          C2::LDS_BYTES, st, p, zseg, nseg);
       return hipGetLastError();
     }
   }
+  if (info)                                                  // slots: one per (tile, z segment, wave), as conv_stem_stats_slots
+    info->report(p.stats ? p.nby * p.nbx * nseg * NC : 0, "conv3d_stem<%s,q%d,%dx%dx%d,c%d+l1,r%d>",
+                 __is_same(T, f16) ? (SPLIT ? "f16x2" : "f16") : (SPLIT ? "bf16x2" : "bf16"), Q, TZ, TY, TX, NC, R);
   hipLaunchKernelGGL((conv3d_stem_kernel<T, Q, TY, TX, TZ, NC, R, SPLIT>), dim3((unsigned)(tiles * nseg)), dim3((NC + 1) * 64),
                      C::LDS_BYTES, st, p, zseg, nseg);
   return hipGetLastError();
 }
 
-hipError_t launch_conv_stem(const ConvParams& p, int precision, hipStream_t st) {
+hipError_t launch_conv_stem(const ConvParams& p, int precision, hipStream_t st, ConvLaunchInfo* info) {
   const int Q = p.Cout / 16;
   if (Q != 1 && Q != 2) return hipErrorInvalidValue;
   switch (precision) {
-    case 0: return Q == 1 ? launch_stem_t<f16, 1, false>(p, st) : launch_stem_t<f16, 2, false>(p, st);
-    case 1: return Q == 1 ? launch_stem_t<bf16, 1, false>(p, st) : launch_stem_t<bf16, 2, false>(p, st);
-    case 2: return Q == 1 ? launch_stem_t<f16, 1, true>(p, st) : launch_stem_t<f16, 2, true>(p, st);
-    case 3: return Q == 1 ? launch_stem_t<bf16, 1, true>(p, st) : launch_stem_t<bf16, 2, true>(p, st);
+    case 0: return Q == 1 ? launch_stem_t<f16, 1, false>(p, st, info) : launch_stem_t<f16, 2, false>(p, st, info);
+    case 1: return Q == 1 ? launch_stem_t<bf16, 1, false>(p, st, info) : launch_stem_t<bf16, 2, false>(p, st, info);
+    case 2: return Q == 1 ? launch_stem_t<f16, 1, true>(p, st, info) : launch_stem_t<f16, 2, true>(p, st, info);
+    case 3: return Q == 1 ? launch_stem_t<bf16, 1, true>(p, st, info) : launch_stem_t<bf16, 2, true>(p, st, info);
   }
   return hipErrorInvalidValue;
 }

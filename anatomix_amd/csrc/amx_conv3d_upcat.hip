@@ -23,7 +23,6 @@
 // parity-split along x in LDS (even voxels, then odd voxels of a row) so that a tile's 16 voxels
 // are 16 consecutive 16-byte slots for every tap (conflict-free ds_read_b128).  Three loader waves
 // stream the skip planes (one per 8-channel plane) and the low-res planes by LDS-DMA.
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "amx_device.h"
@@ -366,9 +365,6 @@ __global__ void pack_upcat16_kernel(const float* __restrict__ w, const float* __
   wpk[idx] = (T)v;
 }
 
-static thread_local char g_kernel_name5[64] = "";
-const char* last_conv_upcat_kernel_name() { return g_kernel_name5; }
-
 size_t conv_upcat16_packed_bytes() { return (size_t)(kSteps + 64) * 1024; }
 
 bool conv_upcat16_eligible(const ConvParams& p) {
@@ -377,10 +373,9 @@ bool conv_upcat16_eligible(const ConvParams& p) {
 }
 
 template <typename T, int OUTMODE>
-static hipError_t launch_upcat_t(ConvParams p, hipStream_t st) {
+static hipError_t launch_upcat_t(ConvParams p, hipStream_t st, ConvLaunchInfo* info) {
   typedef UpcatCfg C;
-  snprintf(g_kernel_name5, sizeof g_kernel_name5, "conv3d_upcat16<%s,2x8x32,c8+l3,r%d/%d,o%d>", __is_same(T, f16) ? "f16" : "bf16",
-           C::R, C::RL, OUTMODE);
+  if (info) info->report(0, "conv3d_upcat16<%s,2x8x32,c8+l3,r%d/%d,o%d>", __is_same(T, f16) ? "f16" : "bf16", C::R, C::RL, OUTMODE);
   auto kern = conv3d_upcat16_kernel<T, OUTMODE>;
   static amx::DeviceOnce attr_once;
   if (!attr_once.done()) {
@@ -398,10 +393,10 @@ static hipError_t launch_upcat_t(ConvParams p, hipStream_t st) {
 }
 
 // p.wpk must point at the upcat16 packing (pack_upcat16_kernel).
-hipError_t launch_conv_upcat16(const ConvParams& p, int precision, hipStream_t st) {
+hipError_t launch_conv_upcat16(const ConvParams& p, int precision, hipStream_t st, ConvLaunchInfo* info) {
   const bool planar = p.out32 != nullptr;
-  if (precision == 0) return planar ? launch_upcat_t<f16, 1>(p, st) : launch_upcat_t<f16, 0>(p, st);
-  return planar ? launch_upcat_t<bf16, 1>(p, st) : launch_upcat_t<bf16, 0>(p, st);
+  if (precision == 0) return planar ? launch_upcat_t<f16, 1>(p, st, info) : launch_upcat_t<f16, 0>(p, st, info);
+  return planar ? launch_upcat_t<bf16, 1>(p, st, info) : launch_upcat_t<bf16, 0>(p, st, info);
 }
 
 hipError_t launch_pack_upcat16(const float* w, const float* scale, void* wpk, int precision, hipStream_t st) {

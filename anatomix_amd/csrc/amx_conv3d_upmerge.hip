@@ -24,7 +24,6 @@
 // voxels x 32 channels, replicate-clamped = reflect padding of the upsampled tensor) sits in LDS, plane-major like every other
 // kernel here, fetched by LDS-DMA two stages ahead into a ring of buffers.  Reflect padding at high resolution is
 // replicate padding at low resolution (-1 -> 1 -> low 0; N -> N-2 -> low N/2-1).
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "amx_device.h"
@@ -372,9 +371,6 @@ __global__ void pack_upmerge_kernel(const float* __restrict__ w, const float* __
   }
 }
 
-static thread_local char g_kernel_name6[64] = "";
-const char* last_conv_upmerge_kernel_name() { return g_kernel_name6; }
-
 size_t conv_upmerge_packed_bytes(int C1, int Cout, int split) { return (size_t)Cout * C1 * 64 * 2 * (split ? 2 : 1); }   // 8 classes x 8 taps per (cout, cin)
 size_t conv_upmerge_partial_bytes(int N, int D, int H, int W, int Cout) { return (size_t)N * D * H * W * Cout * 2; }
 int conv_upmerge_q(int Cout, int split) { return (!split && Cout % 32 == 0) ? 2 : 1; }
@@ -386,13 +382,12 @@ bool conv_upmerge_eligible(int C0, int C1, int Cout, int D, int H, int W, int up
          !(W & 1) && D >= 4 && H >= 4;
 }
 
-static int g_num_cus6 = 0;
-
 template <typename T, int Q, int TZ, int TY, int NBUF, int KS, bool SPLIT = false, int LXT = 16>
-static hipError_t launch_upm(UpmergeParams p, hipStream_t st) {
+static hipError_t launch_upm(UpmergeParams p, hipStream_t st, ConvLaunchInfo* info) {
   typedef UpmCfg<Q, TZ, TY, NBUF, KS, SPLIT, LXT> C;
-  snprintf(g_kernel_name6, sizeof g_kernel_name6, "conv3d_upmerge<%s,q%d,%dx%dx%d,b%d,k%d>", __is_same(T, f16) ? (SPLIT ? "f16x2" : "f16") : (SPLIT ? "bf16x2" : "bf16"), Q,
-           TZ, C::BY, LXT, NBUF, 32 * KS);
+  if (info)
+    info->report(0, "conv3d_upmerge<%s,q%d,%dx%dx%d,b%d,k%d>", __is_same(T, f16) ? (SPLIT ? "f16x2" : "f16") : (SPLIT ? "bf16x2" : "bf16"), Q,
+                 TZ, C::BY, LXT, NBUF, 32 * KS);
   auto kern = conv3d_upmerge_kernel<T, Q, TZ, TY, NBUF, KS, SPLIT, LXT>;
   static amx::DeviceOnce attr_once;
   if (!attr_once.done()) {
@@ -400,35 +395,31 @@ static hipError_t launch_upm(UpmergeParams p, hipStream_t st) {
     if (e != hipSuccess) return e;
     attr_once.set();
   }
-  if (g_num_cus6 == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-    g_num_cus6 = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
+  const int cus = device_cus(attr_once.dev);
+  if (cus == 0) return hipErrorUnknown;
   p.nbz = (p.LD + TZ - 1) / TZ;
   p.nby = (p.LH + C::BY - 1) / C::BY;
   p.nbx = (p.LW + LXT - 1) / LXT;
   const long long items = (long long)p.nbz * p.nby * p.nbx * p.N * (p.Cout / (16 * Q));
-  const long long grid = items < g_num_cus6 ? items : g_num_cus6;
+  const long long grid = items < cus ? items : cus;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), C::LDS_BYTES, st, p);
   return hipGetLastError();
 }
 
 template <typename T>
-static hipError_t launch_upm_split(const UpmergeParams& p, hipStream_t st) {
-  if (p.LW < 16) return launch_upm<T, 1, 2, 2, 3, 1, true, 8>(p, st);        // rows shorter than a 16-cell tile: 8 cells x 2 rows
+static hipError_t launch_upm_split(const UpmergeParams& p, hipStream_t st, ConvLaunchInfo* info) {
+  if (p.LW < 16) return launch_upm<T, 1, 2, 2, 3, 1, true, 8>(p, st, info);        // rows shorter than a 16-cell tile: 8 cells x 2 rows
   const long long cells = (long long)p.N * p.LD * p.LH * ((p.LW + 15) / 16);
-  if (cells / 8 * (p.Cout / 16) >= 256) return launch_upm<T, 1, 2, 4, 2, 1, true>(p, st);   // two buffers: hi + lo planes are 55 KB
-  return launch_upm<T, 1, 2, 2, 3, 1, true>(p, st);
+  if (cells / 8 * (p.Cout / 16) >= 256) return launch_upm<T, 1, 2, 4, 2, 1, true>(p, st, info);   // two buffers: hi + lo planes are 55 KB
+  return launch_upm<T, 1, 2, 2, 3, 1, true>(p, st, info);
 }
 
 template <typename T>
-static hipError_t launch_upm_t(const UpmergeParams& p, hipStream_t st) {
+static hipError_t launch_upm_t(const UpmergeParams& p, hipStream_t st, ConvLaunchInfo* info) {
   const int Q = conv_upmerge_q(p.Cout, 0);
   if (p.LW < 16) {                                                             // rows shorter than a 16-cell tile: 8 cells x 2 rows
-    if (Q == 2) return p.C1 % 64 == 0 ? launch_upm<T, 2, 2, 2, 2, 2, false, 8>(p, st) : launch_upm<T, 2, 2, 2, 3, 1, false, 8>(p, st);
-    return launch_upm<T, 1, 2, 2, 3, 1, false, 8>(p, st);
+    if (Q == 2) return p.C1 % 64 == 0 ? launch_upm<T, 2, 2, 2, 2, 2, false, 8>(p, st, info) : launch_upm<T, 2, 2, 2, 3, 1, false, 8>(p, st, info);
+    return launch_upm<T, 1, 2, 2, 3, 1, false, 8>(p, st, info);
   }
   const long long cells = (long long)p.N * p.LD * p.LH * ((p.LW + 15) / 16);       // tiles of 16 cells
   const long long groups = p.Cout / (16 * Q);
@@ -437,18 +428,18 @@ static hipError_t launch_upm_t(const UpmergeParams& p, hipStream_t st) {
   // half the barriers per item.
   const bool k64 = p.C1 % 64 == 0;
   if (Q == 2) {
-    if (cells / 8 * groups >= 256) return launch_upm<T, 2, 2, 4, 3, 1>(p, st);   // (64-channel stages spill 8 registers here)
-    return k64 ? launch_upm<T, 2, 2, 2, 2, 2>(p, st) : launch_upm<T, 2, 2, 2, 3, 1>(p, st);
+    if (cells / 8 * groups >= 256) return launch_upm<T, 2, 2, 4, 3, 1>(p, st, info);   // (64-channel stages spill 8 registers here)
+    return k64 ? launch_upm<T, 2, 2, 2, 2, 2>(p, st, info) : launch_upm<T, 2, 2, 2, 3, 1>(p, st, info);
   }
-  if (cells / 16 * groups >= 256) return launch_upm<T, 1, 2, 8, 3, 1>(p, st);
-  return k64 ? launch_upm<T, 1, 2, 4, 2, 2>(p, st) : launch_upm<T, 1, 2, 4, 3, 1>(p, st);
+  if (cells / 16 * groups >= 256) return launch_upm<T, 1, 2, 8, 3, 1>(p, st, info);
+  return k64 ? launch_upm<T, 1, 2, 4, 2, 2>(p, st, info) : launch_upm<T, 1, 2, 4, 3, 1>(p, st, info);
 }
 
-hipError_t launch_conv_upmerge(const UpmergeParams& p, int precision, hipStream_t st) {
-  if (precision == 0) return launch_upm_t<f16>(p, st);
-  if (precision == 1) return launch_upm_t<bf16>(p, st);
-  if (precision == 2) return launch_upm_split<f16>(p, st);
-  if (precision == 3) return launch_upm_split<bf16>(p, st);
+hipError_t launch_conv_upmerge(const UpmergeParams& p, int precision, hipStream_t st, ConvLaunchInfo* info) {
+  if (precision == 0) return launch_upm_t<f16>(p, st, info);
+  if (precision == 1) return launch_upm_t<bf16>(p, st, info);
+  if (precision == 2) return launch_upm_split<f16>(p, st, info);
+  if (precision == 3) return launch_upm_split<bf16>(p, st, info);
   return hipErrorInvalidValue;
 }
 

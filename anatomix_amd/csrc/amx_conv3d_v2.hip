@@ -19,7 +19,6 @@
 //     instead of in front of the next barrier;
 //   * item coordinates advance by increment-and-carry on the scalar unit (no integer divisions
 //     in the loop); accumulators start from the bias, so the epilogue is activation + pack.
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "amx_device.h"
@@ -697,25 +696,27 @@ __global__ __launch_bounds__((NWZ * NWY + NLW) * 64) void conv3d_k3_v2_kernel(co
 // -------------------------------------------------------------------------------------------
 // launcher
 // -------------------------------------------------------------------------------------------
-static thread_local char g_kernel_name2[64] = "";
-const char* last_conv_v2_kernel_name() { return g_kernel_name2; }
-static thread_local int g_stats_slots = 0;
-int last_conv_v2_stats_slots() { return g_stats_slots; }       // partial-statistics slots per sample written by the last launch
-
-static int g_num_cus = 0;
-
+// `query`: fill info->stats_slots with the slots per sample that a launch of this shape writes when it is given ConvParams::stats
+// (bricks x MFMA waves) and return before anything touches the device -- conv_v2_stats_slots, which sizes the scratch.
 template <typename T, int SPLITM, int WZ, int WY, int WX, int NWZ, int NWY, int Q, int NCH, int OUTMODE, int NLW = 0, int NBUF = 2>
-static hipError_t launch_cfg2(ConvParams p, hipStream_t st) {
+static hipError_t launch_cfg2(ConvParams p, hipStream_t st, ConvLaunchInfo* info, bool query) {
   constexpr bool SPLIT = SPLITM >= 1, MX = SPLITM == 2;          // SPLITM: 0 single value, 1 hi / lo split, 2 split + fp8 correction stages
   typedef Conv2Cfg<T, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE, NLW, NBUF> C;
+  p.nbz = (p.D + C::TZ - 1) / C::TZ;
+  p.nby = (p.H + C::TY - 1) / C::TY;
+  p.nbx = (p.W + C::TX - 1) / C::TX;
+  const int stats_slots = p.nbz * p.nby * p.nbx * C::NW;
+  if (query) {
+    info->stats_slots = stats_slots;
+    return hipSuccess;
+  }
   if (MX && !p.mxs) return hipErrorInvalidValue;
   const char* tn = __is_same(T, f16) ? (MX ? "f16x2mx" : (SPLIT ? "f16x2" : "f16")) : (SPLIT ? "bf16x2" : "bf16");
-  if (NLW)
-    snprintf(g_kernel_name2, sizeof g_kernel_name2, "conv3d_k3_v2<%s,%dx%dx%d,w%d+l%d,b%d,q%d,nch%d,o%d>",
-             tn, C::TZ, C::TY, C::TX, C::NW, NLW, NBUF, Q, NCH, OUTMODE);
-  else
-    snprintf(g_kernel_name2, sizeof g_kernel_name2, "conv3d_k3_v2<%s,%dx%dx%d,w%d,q%d,nch%d,o%d>",
-             tn, C::TZ, C::TY, C::TX, C::NW, Q, NCH, OUTMODE);
+  if (info && NLW)
+    info->report(p.stats ? stats_slots : 0, "conv3d_k3_v2<%s,%dx%dx%d,w%d+l%d,b%d,q%d,nch%d,o%d>", tn, C::TZ, C::TY, C::TX, C::NW, NLW, NBUF,
+                 Q, NCH, OUTMODE);
+  else if (info)
+    info->report(p.stats ? stats_slots : 0, "conv3d_k3_v2<%s,%dx%dx%d,w%d,q%d,nch%d,o%d>", tn, C::TZ, C::TY, C::TX, C::NW, Q, NCH, OUTMODE);
   auto kern = conv3d_k3_v2_kernel<T, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE, NLW, NBUF, SPLIT, MX>;
   static amx::DeviceOnce attr_once;
   if (!attr_once.done()) {
@@ -723,21 +724,11 @@ static hipError_t launch_cfg2(ConvParams p, hipStream_t st) {
     if (e != hipSuccess) return e;
     attr_once.set();
   }
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-    g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  p.nbz = (p.D + C::TZ - 1) / C::TZ;
-  p.nby = (p.H + C::TY - 1) / C::TY;
-  p.nbx = (p.W + C::TX - 1) / C::TX;
-  g_stats_slots = p.nbz * p.nby * p.nbx * C::NW;
-  // the forward sizes its statistics scratch with conv_v2_stats_slots(): the two must agree, or the epilogue would write past it
-  if (p.stats && g_stats_slots != conv_v2_stats_slots(p.D, p.H, p.W, Q)) return hipErrorInvalidConfiguration;
+  const int cus = device_cus(attr_once.dev);
+  if (cus == 0) return hipErrorUnknown;
   const long long items = (long long)p.nbz * p.nby * p.nbx * p.N * (p.Cout / (16 * Q));
   const int per_cu = C::LDS_BYTES <= 80 * 1024 ? 2 : 1;
-  long long grid = items < (long long)g_num_cus * per_cu ? items : (long long)g_num_cus * per_cu;
+  long long grid = items < (long long)cus * per_cu ? items : (long long)cus * per_cu;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((C::NW + NLW) * 64), C::LDS_BYTES, st, p);
   return hipGetLastError();
 }
@@ -746,75 +737,66 @@ static hipError_t launch_cfg2(ConvParams p, hipStream_t st) {
 // whose stages are short: 128 -> 128 @16^3 32 -> 27 us, 384 -> 128 @16^3 66 -> 52 us, 256 -> 256 @8^3 36 -> 30 us at batch 4.
 // With only two buffers the loaders cannot run ahead and the classic barrier pipeline is faster (96 -> 32 @64^3: 202 vs 223 us).
 template <typename T, int SPLIT, int WZ, int WY, int WX, int NWZ, int NWY, int Q, int NCH, int OUTMODE>
-static hipError_t launch_pick(const ConvParams& p, hipStream_t st) {
+static hipError_t launch_pick(const ConvParams& p, hipStream_t st, ConvLaunchInfo* info, bool query) {
   typedef Conv2Cfg<T, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE> C0;
   constexpr bool can = 3 * C0::BUF + 64 <= 160 * 1024 && NWZ * NWY <= 8;
   if constexpr (can)
-    return launch_cfg2<T, SPLIT, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE, 4, 3>(p, st);
+    return launch_cfg2<T, SPLIT, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE, 4, 3>(p, st, info, query);
   else
-    return launch_cfg2<T, SPLIT, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE>(p, st);
+    return launch_cfg2<T, SPLIT, WZ, WY, WX, NWZ, NWY, Q, NCH, OUTMODE>(p, st, info, query);
 }
 
 template <typename T, int OUTMODE, int SPLIT>
-static hipError_t launch_conv2_t(const ConvParams& p, int Q, hipStream_t st) {
+static hipError_t launch_conv2_t(const ConvParams& p, int Q, hipStream_t st, ConvLaunchInfo* info, bool query = false) {
   const int nch = (p.C0 + p.C1) / 16;
   if (p.W >= 32) {
-    if (Q == 1) return launch_pick<T, SPLIT, 1, 4, 32, 4, 2, 1, 1, OUTMODE>(p, st);       // brick 4x8x32, 8 waves
+    if (Q == 1) return launch_pick<T, SPLIT, 1, 4, 32, 4, 2, 1, 1, OUTMODE>(p, st, info, query);       // brick 4x8x32, 8 waves
     if (Q == 2) {
       // (brick 4x4x16 instead -- three stage buffers fit the LDS, so the loader-wave pipeline applies -- measured on 96 -> 32 @64^3,
       //  batch 4: 206 -> 197 us (+5 %); not kept: the same instantiation also serves the 16^3 layers, and one kernel name per layer
       //  class keeps the per-kernel tables of bench.py and rocprofv3 comparable)
       // (brick 4x8x16 instead -- 12 % less halo, 84 % instead of 53 % of the DMA lanes used -- measured on f16x2mx, batch 4: 64 -> 64 @64^3
       //  506 -> 508 us, 192 -> 64 @64^3 1337 -> 1377, 96 -> 32 @128^3 2815 -> 2854: these layers are not fill-bound)
-      return launch_pick<T, SPLIT, 1, 2, 32, 4, 2, 2, 1, OUTMODE>(p, st);       // brick 4x4x32, 8 waves
+      return launch_pick<T, SPLIT, 1, 2, 32, 4, 2, 2, 1, OUTMODE>(p, st, info, query);       // brick 4x4x32, 8 waves
     }
-    if (OUTMODE == 0 && Q == 4) return launch_pick<T, SPLIT, 1, 2, 16, 4, 2, 4, 1, 0>(p, st);  // brick 4x4x16, 8 waves
+    if (OUTMODE == 0 && Q == 4) return launch_pick<T, SPLIT, 1, 2, 16, 4, 2, 4, 1, 0>(p, st, info, query);  // brick 4x4x16, 8 waves
     return hipErrorInvalidValue;
   }
   if (OUTMODE == 1) return hipErrorInvalidValue;
   if (p.W >= 16) {
-    if (Q == 1) return launch_pick<T, SPLIT, 1, 2, 16, 4, 1, 1, 1, 0>(p, st);
-    if (Q == 2) return launch_pick<T, SPLIT, 1, 2, 16, 4, 2, 2, 1, 0>(p, st);       // brick 4x4x16, 8 waves
-    if (Q == 4) return launch_pick<T, SPLIT, 1, 2, 16, 4, 2, 4, 1, 0>(p, st);
+    if (Q == 1) return launch_pick<T, SPLIT, 1, 2, 16, 4, 1, 1, 1, 0>(p, st, info, query);
+    if (Q == 2) return launch_pick<T, SPLIT, 1, 2, 16, 4, 2, 2, 1, 0>(p, st, info, query);       // brick 4x4x16, 8 waves
+    if (Q == 4) return launch_pick<T, SPLIT, 1, 2, 16, 4, 2, 4, 1, 0>(p, st, info, query);
   }
   if (Q == 1) {
-    if (nch % 2 == 0) return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 1, 2, 0>(p, st);
-    return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 1, 1, 0>(p, st);
+    if (nch % 2 == 0) return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 1, 2, 0>(p, st, info, query);
+    return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 1, 1, 0>(p, st, info, query);
   }
   // 4-wide levels: half bricks (4x2x8, 4 waves) -- twice the workgroups (1024 -> 1024 @4^3, batch 4: 128 -> 256 on 256 CUs) and half as
   // many waves streaming the same weight fragments from L2
-  if (Q == 2 && p.W <= 4) return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 2, 1, 0>(p, st);
-  if (Q == 2) return launch_pick<T, SPLIT, 1, 2, 8, 4, 2, 2, 1, 0>(p, st);           // brick 4x4x8, 8 waves
-  if (Q == 4) return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 4, 1, 0>(p, st);
+  if (Q == 2 && p.W <= 4) return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 2, 1, 0>(p, st, info, query);
+  if (Q == 2) return launch_pick<T, SPLIT, 1, 2, 8, 4, 2, 2, 1, 0>(p, st, info, query);           // brick 4x4x8, 8 waves
+  if (Q == 4) return launch_pick<T, SPLIT, 1, 2, 8, 4, 1, 4, 1, 0>(p, st, info, query);
   return hipErrorInvalidValue;
 }
 
-// Partial-statistics slots per sample a launch of this layer writes (ConvParams::stats): bricks x MFMA waves of the brick shape
-// launch_conv2_t picks for (W, Q) -- keep in step with the dispatch above.
+// Partial-statistics slots per sample a launch of this layer writes (ConvParams::stats), asked of the dispatch above: the brick
+// shape depends on (W, Q) only, so the f16, 16-bit-output instantiation answers for every precision.  0: no kernel for (W, Q).
 int conv_v2_stats_slots(int D, int H, int W, int Q) {
-  int tz = 4, ty, tx, nw;
-  if (W >= 32) {
-    if (Q == 1) { ty = 8; tx = 32; nw = 8; }
-    else if (Q == 2) { ty = 4; tx = 32; nw = 8; }
-    else { ty = 4; tx = 16; nw = 8; }
-  } else if (W >= 16) {
-    if (Q == 1) { ty = 2; tx = 16; nw = 4; }
-    else { ty = 4; tx = 16; nw = 8; }
-  } else {
-    if (Q == 2 && W > 4) { ty = 4; tx = 8; nw = 8; }
-    else { ty = 2; tx = 8; nw = 4; }
-  }
-  return ((D + tz - 1) / tz) * ((H + ty - 1) / ty) * ((W + tx - 1) / tx) * nw;
+  ConvParams p{};
+  p.D = D; p.H = H; p.W = W; p.C0 = 16;
+  ConvLaunchInfo info{};
+  return launch_conv2_t<f16, 0, false>(p, Q, nullptr, &info, true) == hipSuccess ? info.stats_slots : 0;
 }
 
-hipError_t launch_conv_v2(const ConvParams& p, int precision, int Q, hipStream_t st) {
+hipError_t launch_conv_v2(const ConvParams& p, int precision, int Q, hipStream_t st, ConvLaunchInfo* info) {
   const bool planar = p.out32 != nullptr;
   switch (precision) {
-    case 0: return planar ? launch_conv2_t<f16, 1, false>(p, Q, st) : launch_conv2_t<f16, 0, false>(p, Q, st);
-    case 1: return planar ? launch_conv2_t<bf16, 1, false>(p, Q, st) : launch_conv2_t<bf16, 0, false>(p, Q, st);
-    case 2: return planar ? launch_conv2_t<f16, 1, true>(p, Q, st) : launch_conv2_t<f16, 0, true>(p, Q, st);
-    case 3: return planar ? launch_conv2_t<bf16, 1, true>(p, Q, st) : launch_conv2_t<bf16, 0, true>(p, Q, st);
-    case 4: return planar ? launch_conv2_t<f16, 1, 2>(p, Q, st) : launch_conv2_t<f16, 0, 2>(p, Q, st);
+    case 0: return planar ? launch_conv2_t<f16, 1, false>(p, Q, st, info) : launch_conv2_t<f16, 0, false>(p, Q, st, info);
+    case 1: return planar ? launch_conv2_t<bf16, 1, false>(p, Q, st, info) : launch_conv2_t<bf16, 0, false>(p, Q, st, info);
+    case 2: return planar ? launch_conv2_t<f16, 1, true>(p, Q, st, info) : launch_conv2_t<f16, 0, true>(p, Q, st, info);
+    case 3: return planar ? launch_conv2_t<bf16, 1, true>(p, Q, st, info) : launch_conv2_t<bf16, 0, true>(p, Q, st, info);
+    case 4: return planar ? launch_conv2_t<f16, 1, 2>(p, Q, st, info) : launch_conv2_t<f16, 0, 2>(p, Q, st, info);
   }
   return hipErrorInvalidValue;
 }

@@ -24,7 +24,6 @@
 //     counters in LDS (amx_device.h), so a wave stalled on VMEM issue only delays the waves that
 //     depend on it and the store bursts of different waves de-synchronise.
 // Arithmetic is identical to the generic kernel (same packed-weight layout, same 14 paired-tap steps).
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -883,23 +882,19 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
   if (OUTMODE == 0 && RangeCheck<T>::on) raise_flag(p.oflow, bad);
 }
 
-static thread_local char g_kernel_name3[64] = "";
-const char* last_conv_zm_kernel_name() { return g_kernel_name3; }
-
 template <typename T, int NCK, int QT, int TY, int R, int OUTMODE, int NS, bool POOL = false, bool SPLIT = false, int TX = 32, bool STEM = false>
-static hipError_t launch_zm_ns(ConvParams p, hipStream_t st, const StemIn& si = StemIn{}) {
+static hipError_t launch_zm_ns(ConvParams p, hipStream_t st, ConvLaunchInfo* info, const StemIn& si = StemIn{}) {
   if constexpr (OUTMODE == 0 && NS == 0 && !POOL && !STEM)
-    if (p.out2) return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, NS, true, SPLIT, TX, STEM>(p, st, si);
+    if (p.out2) return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, NS, true, SPLIT, TX, STEM>(p, st, info, si);
   constexpr int TZ = 2;
   typedef ZmCfg<SPLIT ? 2 : NCK, QT, TY, TX, R> C;
   constexpr int LDS = STEM ? C::FLAGOFF + 128 + ZmStemCfg<TY, TX>::BYTES : NS ? C::FLAGOFF + 128 + ZmStage<QT, TY, TX, OUTMODE>::TOTAL : C::LDS_BYTES;
-  if (STEM)
-    snprintf(g_kernel_name3, sizeof g_kernel_name3, "conv3d_k3_zmarch<%s,stem1->16->16,%dx%dx%d,c8+st%d+ld1,r%d/%d%s>",
-             __is_same(T, f16) ? "f16" : "bf16", TZ, TY, TX, ZmStemCfg<TY, TX>::NSW, R, ZmStemCfg<TY, TX>::RC, p.out2 ? ",pool" : "");
-  else
-  snprintf(g_kernel_name3, sizeof g_kernel_name3, "conv3d_k3_zmarch<%s%s,%d->%d,%dx%dx%d,c8+l%d+s%d,r%d,o%d%s>",
-           __is_same(T, f16) ? "f16" : "bf16", SPLIT ? "x2" : "", 16 * NCK, 16 * QT, TZ, TY, TX, C::NL, NS, R, OUTMODE,
-           p.out2 ? ",pool" : "");
+  if (info && STEM)                                          // (0 slots: no statistics epilogue in this kernel)
+    info->report(0, "conv3d_k3_zmarch<%s,stem1->16->16,%dx%dx%d,c8+st%d+ld1,r%d/%d%s>", __is_same(T, f16) ? "f16" : "bf16", TZ, TY, TX,
+                 ZmStemCfg<TY, TX>::NSW, R, ZmStemCfg<TY, TX>::RC, p.out2 ? ",pool" : "");
+  else if (info)
+    info->report(0, "conv3d_k3_zmarch<%s%s,%d->%d,%dx%dx%d,c8+l%d+s%d,r%d,o%d%s>", __is_same(T, f16) ? "f16" : "bf16", SPLIT ? "x2" : "",
+                 16 * NCK, 16 * QT, TZ, TY, TX, C::NL, NS, R, OUTMODE, p.out2 ? ",pool" : "");
   auto kern = conv3d_k3_zmarch_kernel<T, NCK, QT, TY, TX, R, OUTMODE, NS, POOL, SPLIT, STEM>;
   static amx::DeviceOnce attr_once;
   if (!attr_once.done()) {
@@ -928,14 +923,14 @@ static bool zm_can_stage(const ConvParams& p) {
 }
 
 template <typename T, int NCK, int QT, int TY, int R, int OUTMODE>
-static hipError_t launch_zm(const ConvParams& p, hipStream_t st) {
+static hipError_t launch_zm(const ConvParams& p, hipStream_t st, ConvLaunchInfo* info) {
   // 12 waves = 3 per SIMD keep the 170-VGPR budget of the MFMA waves; the 32 -> 32 kernel already has 4 loaders
   // Measured (batch 4, 128^3, 16 -> 16): fp32 planar output 253 -> 177 us with storers (whole 128-byte lines, eight
   // rows per store instruction, instead of 64-byte pieces from the MFMA lanes); 16-bit NDHWC output 130 -> 155 us
   // (its direct stores are already 512-byte runs; the staging round trip only adds LDS traffic) -- so planar only.
   if constexpr (NCK == 1 && OUTMODE == 1)
-    if (zm_can_stage<TY>(p)) return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, 2>(p, st);
-  return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, 0>(p, st);
+    if (zm_can_stage<TY>(p)) return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, 2>(p, st, info);
+  return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, 0>(p, st, info);
 }
 
 // Eligibility: one full-resolution input segment of 16 or 32 channels, 16 or 32 output channels
@@ -967,7 +962,8 @@ bool conv_zmarch_stem_eligible(const ConvParams& p, int precision) {
 // x_offs (host array of p.N element offsets, or null; at most 16 samples then): sample i reads its volume at x + x_offs[i]
 // (sliding-window batches: every window is reflect-padded as its own input).
 hipError_t launch_conv_zmarch_stem(const ConvParams& p, const float* x, long long xs_n, long long xs_z, long long xs_y, const long long* x_offs,
-                                   const void* stem_wpk, const float* stem_bias, int stem_act, float stem_slope, int precision, hipStream_t st) {
+                                   const void* stem_wpk, const float* stem_bias, int stem_act, float stem_slope, int precision, hipStream_t st,
+                                   ConvLaunchInfo* info) {
   if (stem_act != ACT_NONE && stem_act != ACT_RELU) return hipErrorInvalidValue;   // the stem waves clip with one v_med3
   if ((precision != 0 && precision != 1) || (x_offs && p.N > 16)) return hipErrorInvalidValue;
   StemIn si;
@@ -978,26 +974,26 @@ hipError_t launch_conv_zmarch_stem(const ConvParams& p, const float* x, long lon
     for (int i = 0; i < p.N; ++i) si.offs[i] = x_offs[i] * 4;
   }
   si.wpk = (const char*)stem_wpk; si.bias = stem_bias; si.act = stem_act; si.slope = stem_slope;
-  if (precision == 0) return launch_zm_ns<f16, 1, 1, 8, 10, 0, 0, false, false, 32, true>(p, st, si);
-  return launch_zm_ns<bf16, 1, 1, 8, 10, 0, 0, false, false, 32, true>(p, st, si);
+  if (precision == 0) return launch_zm_ns<f16, 1, 1, 8, 10, 0, 0, false, false, 32, true>(p, st, info, si);
+  return launch_zm_ns<bf16, 1, 1, 8, 10, 0, 0, false, false, 32, true>(p, st, info, si);
 }
 
-hipError_t launch_conv_zmarch(const ConvParams& p, int precision, hipStream_t st) {
+hipError_t launch_conv_zmarch(const ConvParams& p, int precision, hipStream_t st, ConvLaunchInfo* info) {
   const bool planar = p.out32 != nullptr;
   if (precision >= 2) {   // strict: 16 -> 16 only; ring of 7 planes x 4 channel planes, stores from the accumulators
     if (p.C0 != 16 || p.Cout != 16) return hipErrorInvalidValue;
-    if (precision == 2) return planar ? launch_zm_ns<f16, 1, 1, 8, 7, 1, 0, false, true>(p, st) : launch_zm_ns<f16, 1, 1, 8, 7, 0, 0, false, true>(p, st);
-    return planar ? launch_zm_ns<bf16, 1, 1, 8, 7, 1, 0, false, true>(p, st) : launch_zm_ns<bf16, 1, 1, 8, 7, 0, 0, false, true>(p, st);
+    if (precision == 2) return planar ? launch_zm_ns<f16, 1, 1, 8, 7, 1, 0, false, true>(p, st, info) : launch_zm_ns<f16, 1, 1, 8, 7, 0, 0, false, true>(p, st, info);
+    return planar ? launch_zm_ns<bf16, 1, 1, 8, 7, 1, 0, false, true>(p, st, info) : launch_zm_ns<bf16, 1, 1, 8, 7, 0, 0, false, true>(p, st, info);
   }
   if (p.Cout == 16) {
-    if (precision == 0) return planar ? launch_zm<f16, 1, 1, 8, 10, 1>(p, st) : launch_zm<f16, 1, 1, 8, 10, 0>(p, st);
-    return planar ? launch_zm<bf16, 1, 1, 8, 10, 1>(p, st) : launch_zm<bf16, 1, 1, 8, 10, 0>(p, st);
+    if (precision == 0) return planar ? launch_zm<f16, 1, 1, 8, 10, 1>(p, st, info) : launch_zm<f16, 1, 1, 8, 10, 0>(p, st, info);
+    return planar ? launch_zm<bf16, 1, 1, 8, 10, 1>(p, st, info) : launch_zm<bf16, 1, 1, 8, 10, 0>(p, st, info);
   }
   // (8 x 16 instead of 4 x 32 (y, x) tiles for the 32-cout layers -- halo 1.41 instead of 1.59 loaded voxels per output, the re-tiling
   //  that gave the normalise-on-load kernel 15 % -- runs (launch_zm_ns<..., TX = 16>) and was measured at batch 4: 32 -> 32 @64^3
   //  722 -> 730 TF, 16 -> 32 unchanged: these layers do not pay for their halo)
-  if (p.C0 == 16) return precision == 0 ? launch_zm<f16, 1, 2, 4, 10, 0>(p, st) : launch_zm<bf16, 1, 2, 4, 10, 0>(p, st);
-  return precision == 0 ? launch_zm<f16, 2, 2, 4, 10, 0>(p, st) : launch_zm<bf16, 2, 2, 4, 10, 0>(p, st);
+  if (p.C0 == 16) return precision == 0 ? launch_zm<f16, 1, 2, 4, 10, 0>(p, st, info) : launch_zm<bf16, 1, 2, 4, 10, 0>(p, st, info);
+  return precision == 0 ? launch_zm<f16, 2, 2, 4, 10, 0>(p, st, info) : launch_zm<bf16, 2, 2, 4, 10, 0>(p, st, info);
 }
 
 }  // namespace amx

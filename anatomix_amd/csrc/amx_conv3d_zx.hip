@@ -17,7 +17,6 @@
 //     fixed-order fold later: deterministic, no atomics) and stores the raw f16 pair, row-planar like every f16x2mx tensor.
 // Tile: 2 output planes x 2 rows x 32 x per step (one 2 x 2 x 16 block per consumer wave), marched along z through a ring of
 // R input planes; 12 waves per workgroup, one workgroup per CU.
-#include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -522,13 +521,9 @@ bool conv_zx_eligible(const ConvParams& p) {
 }
 int conv_zx_stats_slots(int H, int W) { return H * W / 32; }       // one per (tile, half tile), whichever tile shape runs
 
-static thread_local char g_kernel_name_zx[64] = "";
-const char* last_conv_zx_kernel_name() { return g_kernel_name_zx; }
-
 template <typename C>
-static hipError_t launch_conv_zx_t(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st) {
-  snprintf(g_kernel_name_zx, sizeof g_kernel_name_zx, "conv3d_k3_zx<f16x2mx,32->32,%dx%dx%d,m4+x4+cv4,r%d%s%s>", C::TZ, C::TY, C::TX, C::R,
-           in_ab ? ",norm-in" : "", p.out32 ? ",o1" : "");
+static hipError_t launch_conv_zx_t(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st,
+                                   ConvLaunchInfo* info) {
   static amx::DeviceOnce attr_once;
   auto kern = conv3d_k3_zx_kernel<C>;
   if (!attr_once.done()) {
@@ -538,19 +533,22 @@ static hipError_t launch_conv_zx_t(ConvParams p, const float* in_ab, int in_act,
   }
   p.nby = p.H / C::TY;
   p.nbx = p.W / C::TX;
+  if (info)                                                  // slots: one per (tile, x half), as conv_zx_stats_slots
+    info->report(p.stats ? p.nby * p.nbx * 2 : 0, "conv3d_k3_zx<f16x2mx,32->32,%dx%dx%d,m4+x4+cv4,r%d%s%s>", C::TZ, C::TY, C::TX, C::R,
+                 in_ab ? ",norm-in" : "", p.out32 ? ",o1" : "");
   ZxExtra e;
   e.in_ab = in_ab; e.in_act = in_act; e.in_slope = in_slope; e.wx = (const char*)wx;
   hipLaunchKernelGGL(kern, dim3((unsigned)(p.nby * p.nbx * p.N)), dim3((C::NC + C::NCV) * 64), C::LDS_BYTES, st, p, e);
   return hipGetLastError();
 }
 
-hipError_t launch_conv_zx(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st) {
+hipError_t launch_conv_zx(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st, ConvLaunchInfo* info) {
   // 4x16 tiles wherever they fit, 2x32 otherwise (conv_zx_eligible admits nothing else)
   const bool tall_ok = p.W % 16 == 0 && p.H % 4 == 0;
   // (a ring of 8 planes instead of 6 for the 4x16 tiles: 1016 / 1067 -> 1015 / 1037 us, inside the noise -- not instantiated)
   // (two mailbox sets -- NBOX = 2, an mx wave one step ahead of its main waves: 1030 / 1014 -> 1036 / 1015 us, nothing -- not instantiated)
-  if (tall_ok) return launch_conv_zx_t<ZxCfgT<4, 16>>(p, in_ab, in_act, in_slope, wx, st);
-  return launch_conv_zx_t<ZxCfgT<2, 32>>(p, in_ab, in_act, in_slope, wx, st);
+  if (tall_ok) return launch_conv_zx_t<ZxCfgT<4, 16>>(p, in_ab, in_act, in_slope, wx, st, info);
+  return launch_conv_zx_t<ZxCfgT<2, 32>>(p, in_ab, in_act, in_slope, wx, st, info);
 }
 
 }  // namespace amx

@@ -1,14 +1,33 @@
 // anatomix_amd -- host-side declarations shared between translation units: every amx:: function that one .hip file defines and
-// another calls, with its default arguments (stated here and nowhere else), plus the error helper of the C ABI entries.
+// another calls, with its default arguments (stated here and nowhere else), plus the error helper of the C ABI entries, the cached CU
+// count of a device and the one statement of the stored tensor layouts (the stride setters at the end).  The conv launchers keep no
+// state between calls: what a launch ran, and how many statistics slots it wrote, comes back through the caller's ConvLaunchInfo.
 // Not part of the public C ABI (that is include/anatomix_amd.h).  The ViT engine's launchers and parameter structs are in amx_gemm.h.
 #pragma once
+#include <stdarg.h>
+#include <stdio.h>
+
 #include "../../include/anatomix_amd.h"
 #include "amx_common.h"
 
 namespace amx {
 
+// What a conv launcher ran, for the callers that ask (null: nothing is formatted).  name: as in amx_launch_record::kernel; stats_slots:
+// partial-statistics slots per sample that the launch writes into ConvParams::stats, 0 when that is null.  A launcher reports both at once.
+struct ConvLaunchInfo {
+  char name[64];
+  int stats_slots;
+  __attribute__((format(printf, 3, 4))) void report(int slots, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name, sizeof name, fmt, ap);
+    va_end(ap);
+    stats_slots = slots;
+  }
+};
+
 // amx_conv3d.hip
-hipError_t launch_conv(const ConvParams& p, int precision, int Q, hipStream_t st);
+hipError_t launch_conv(const ConvParams& p, int precision, int Q, hipStream_t st, ConvLaunchInfo* info = nullptr);
 hipError_t launch_pack_weights(const float* w, const float* scale, void* wpk, int CinReal, int CinPad,
                                int Cout, int Q, int precision, hipStream_t st, int mode = 0, int CoutReal = 0, int CinStride = 0,
                                int C0Real = 0, int C0Phys = 0);
@@ -23,60 +42,51 @@ hipError_t launch_pool2(const void* in, void* out, int N, int Do, int Ho, int Wo
                         int precision, hipStream_t st, int skip_lo = 0);
 int conv_pick_q(int Cout, int W, int precision);
 bool conv_fuses_stats(const ConvParams& p, int precision, int Q);
-int last_conv_stats_slots();
-const char* last_conv_kernel_name();
 
 // amx_conv3d_v2.hip
 int conv_v2_stats_slots(int D, int H, int W, int Q);
-hipError_t launch_conv_v2(const ConvParams& p, int precision, int Q, hipStream_t st);
-const char* last_conv_v2_kernel_name();
-int last_conv_v2_stats_slots();
+hipError_t launch_conv_v2(const ConvParams& p, int precision, int Q, hipStream_t st, ConvLaunchInfo* info = nullptr);
 
 // amx_conv3d_ks.hip
 size_t conv_ks_part_bytes(int C0, int Cout, int N, int D, int H, int W, int precision, int Q);
 bool conv_ks_eligible(const ConvParams& p, int precision, int Q);
-hipError_t launch_conv_ks(const ConvParams& p, int precision, int Q, hipStream_t st);
-const char* last_conv_ks_kernel_name();
+hipError_t launch_conv_ks(const ConvParams& p, int precision, int Q, hipStream_t st, ConvLaunchInfo* info = nullptr);
 
 // amx_conv3d_zmarch.hip
 bool conv_zmarch_can_pool(const ConvParams& p);
 bool conv_zmarch_can_pool_split(const ConvParams& p);
 bool conv_zmarch_eligible(const ConvParams& p);
 bool conv_zmarch_stem_eligible(const ConvParams& p, int precision);
-const char* last_conv_zm_kernel_name();
 hipError_t launch_conv_zmarch_stem(const ConvParams& p, const float* x, long long xs_n, long long xs_z, long long xs_y, const long long* x_offs,
-                                   const void* stem_wpk, const float* stem_bias, int stem_act, float stem_slope, int precision, hipStream_t st);
+                                   const void* stem_wpk, const float* stem_bias, int stem_act, float stem_slope, int precision, hipStream_t st,
+                                   ConvLaunchInfo* info = nullptr);
 bool conv_zmarch_eligible_split(const ConvParams& p);
-hipError_t launch_conv_zmarch(const ConvParams& p, int precision, hipStream_t st);
+hipError_t launch_conv_zmarch(const ConvParams& p, int precision, hipStream_t st, ConvLaunchInfo* info = nullptr);
 
 // amx_conv3d_zx.hip
 bool conv_zx_eligible(const ConvParams& p);
 int conv_zx_stats_slots(int H, int W);
 size_t conv_zx_packed_bytes();
 hipError_t launch_pack_weights_zx(const float* w, const float* scale, void* wx, const int* mxs, int CoutReal, hipStream_t st);
-hipError_t launch_conv_zx(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st);
-const char* last_conv_zx_kernel_name();
+hipError_t launch_conv_zx(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st, ConvLaunchInfo* info = nullptr);
 
 // amx_conv3d_stem.hip
-hipError_t launch_conv_stem(const ConvParams& p, int precision, hipStream_t st);
+hipError_t launch_conv_stem(const ConvParams& p, int precision, hipStream_t st, ConvLaunchInfo* info = nullptr);
 hipError_t launch_pack_stem(const float* w, const float* scale, void* wpk, int Cout, int precision, hipStream_t st, int CoutReal = 0);
-const char* last_conv_stem_kernel_name();
 int conv_stem_stats_slots(const ConvParams& p, int precision);
 
 // amx_conv3d_upcat.hip
 size_t conv_upcat16_packed_bytes();
 bool conv_upcat16_eligible(const ConvParams& p);
-hipError_t launch_conv_upcat16(const ConvParams& p, int precision, hipStream_t st);
+hipError_t launch_conv_upcat16(const ConvParams& p, int precision, hipStream_t st, ConvLaunchInfo* info = nullptr);
 hipError_t launch_pack_upcat16(const float* w, const float* scale, void* wpk, int precision, hipStream_t st);
-const char* last_conv_upcat_kernel_name();
 
 // amx_conv3d_upmerge.hip
 size_t conv_upmerge_packed_bytes(int C1, int Cout, int split);
 bool conv_upmerge_eligible(int C0, int C1, int Cout, int D, int H, int W, int up_shift, int split);
-hipError_t launch_conv_upmerge(const UpmergeParams& p, int precision, hipStream_t st);
+hipError_t launch_conv_upmerge(const UpmergeParams& p, int precision, hipStream_t st, ConvLaunchInfo* info = nullptr);
 hipError_t launch_pack_upmerge(const float* w, const float* scale, void* wpk, int c_off, int CinTotal, int C1, int Cout, int precision,
                                hipStream_t st);
-const char* last_conv_upmerge_kernel_name();
 
 // amx_norm.hip
 size_t instnorm_scratch_bytes(int N, int C, long long max_slots_x_C);
@@ -266,6 +276,54 @@ inline bool is_mx(int precision) { return precision == AMX_PREC_F16X2_MX; }
 inline long long elem_bytes(int precision) { return fmt_elem_bytes(fmt_of_precision(precision)); }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// compute units of device `dev` -- the current one, as the launcher's DeviceOnce has just read it -- asked once per device ordinal
+// (0: the runtime could not say); sizes the persistent grids
+inline int device_cus(int dev) {
+  static int cus[64] = {};
+  hipDeviceProp_t prop;
+  if (dev >= 0 && dev < 64 && cus[dev]) return cus[dev];
+  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+  const int n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  if (dev >= 0 && dev < 64) cus[dev] = n;
+  return n;
+}
+
+// ---- the stored tensor layouts (amx_common.h, FMT 0 / 1 / 2), stated once: the byte strides of a dense [N][D][H][W][C] tensor; returns
+// the bytes between a voxel's 16-channel chunks.  A row is C * elem_bytes * W bytes in every layout.  Channels-last voxels (all but
+// f16x2mx): x = one voxel, chunks 32 bytes apart.  Row-planar (f16x2mx): 32 bytes per voxel inside a row plane, chunks W * 32 apart.
+inline int dense_strides(int C, int D, int H, int W, int precision, long long& n, long long& z, long long& y, long long& x) {
+  const long long voxel = (long long)C * elem_bytes(precision);
+  x = is_mx(precision) ? 32 : voxel; y = voxel * W; z = y * H; n = z * D;
+  return is_mx(precision) ? W * 32 : 32;
+}
+// the input segments of a conv or weight-gradient launch, each at its OWN extents (a half-resolution src1: D / 2, H / 2, W / 2)
+template <typename P>
+inline void set_src0(P& p, const void* ptr, int C, int D, int H, int W, int precision) {
+  p.src0 = (const char*)ptr; p.C0 = C;
+  const int cs = dense_strides(C, D, H, W, precision, p.s0n, p.s0z, p.s0y, p.s0x);
+  if constexpr (__is_same(P, ConvParams)) p.cs0 = cs;        // (WgradParams: channels-last only)
+}
+template <typename P>
+inline void set_src1(P& p, const void* ptr, int C, int D, int H, int W, int precision) {
+  p.src1 = (const char*)ptr; p.C1 = C;
+  const int cs = dense_strides(C, D, H, W, precision, p.s1n, p.s1z, p.s1y, p.s1x);
+  if constexpr (__is_same(P, ConvParams)) p.cs1 = cs;
+}
+// the 16-bit output of a conv launch; the max-pooled second output of the z-march kernels at ITS extents (channels-last: those kernels
+// have no row-planar form); the low-resolution source of a merged-tap launch
+inline void set_out(ConvParams& p, void* ptr, int C, int D, int H, int W, int precision) {
+  p.out = (char*)ptr;
+  p.ocs = dense_strides(C, D, H, W, precision, p.on, p.oz, p.oy, p.ox);
+}
+inline void set_out2(ConvParams& p, void* ptr, int C, int D, int H, int W, int precision) {
+  p.out2 = (char*)ptr;
+  dense_strides(C, D, H, W, precision, p.qn, p.qz, p.qy, p.qx);
+}
+inline void set_src(UpmergeParams& u, const void* ptr, int C, int D, int H, int W, int precision) {
+  u.src = (const char*)ptr; u.C1 = C;
+  u.cs = dense_strides(C, D, H, W, precision, u.sn, u.sz, u.sy, u.sx);
+}
 
 }  // namespace amx
 

@@ -445,7 +445,7 @@ struct Forward : ForwardArgs {
     p.N = n; p.D = dd; p.H = dh; p.W = dw; p.Cout = Nx.cout_p; p.C0 = 16; p.C1 = 0;
     p.wpk = (const char*)Nx.wpk; p.bias = Nx.shift; p.oflow = h->d_flag;
     p.act = Nx.has_act ? c.activation : AMX_ACT_NONE; p.slope = c.act_slope;
-    p.ox = 16 * eb; p.oy = p.ox * dw; p.oz = p.oy * dh; p.on = p.oz * dd;
+    amx::set_out(p, nullptr, Nx.cout_p, dd, dh, dw, c.precision);          // (the slot is taken once the pair is known to run)
     if (!(ok && amx::conv_zmarch_stem_eligible(p, c.precision))) return AMX_OK;
     Tensor out;
     out.level = 0; out.C = Nx.cout_p; out.Cr = Nx.cout;
@@ -455,9 +455,10 @@ struct Forward : ForwardArgs {
     if (int e = record(L.module_idx, L.cin, Nx.cout, dd, dh, dw, 2.0 * 27.0 * (L.cin * L.cout + Nx.cin * Nx.cout) * vox,
                        4.0 * vox + 2.0 * Nx.cout * vox + 2.0 * 27.0 * (L.cin * L.cout + Nx.cin * Nx.cout)))   // fp32 input once, 16-bit output once
       return e;
+    amx::ConvLaunchInfo info;
     AMX_HIP(amx::launch_conv_zmarch_stem(p, x, xs_n, xs_z, xs_y, x_offs, L.wpk, L.shift, L.has_act ? c.activation : AMX_ACT_NONE,
-                                         c.act_slope, c.precision, st));
-    if (prof) name_last("%s", amx::last_conv_zm_kernel_name());
+                                         c.act_slope, c.precision, st, prof ? &info : nullptr));
+    if (prof) name_last("%s", info.name);
     ++conv_i;
     cur = out;
     i = g1 - 1;
@@ -477,24 +478,17 @@ struct Forward : ForwardArgs {
       const Tensor& lo = cur;
       // nearest: `lo` is the half-resolution tensor, read through >> 1; trilinear: already materialised at this level
       const int lw = cur_is_full_up ? dw : dw / 2, lh = cur_is_full_up ? dh : dh / 2, ld = cur_is_full_up ? dd : dd / 2;
-      // row-planar layout of f16x2mx (amx_common.h FMT 2): a voxel's 32-byte pieces are 32 bytes apart along x and one row
-      // plane (W * 32 bytes) apart per 16-channel chunk; rows, planes and samples keep their channels-last sizes
-      const long long lx = (long long)lo.C * eb, ly = lx * lw, lz = ly * lh;
       p.up_shift = cur_is_full_up ? 0 : 1;
       if (have_skip) {
-        const long long sx = (long long)pend_skip.C * eb, sy = sx * dw, sz = sy * dh;
-        p.src0 = mem(pend_skip);
-        p.s0n = sz * dd; p.s0z = sz; p.s0y = sy; p.s0x = mx ? 32 : sx; p.C0 = pend_skip.C; p.cs0 = mx ? dw * 32 : 32;
+        amx::set_src0(p, mem(pend_skip), pend_skip.C, dd, dh, dw, c.precision);
       } else {  // no skip connection: the whole input is the upsampled tensor
         p.src0 = mem(lo);  // unused segment of zero channels
         p.C0 = 0;
       }
-      p.src1 = mem(lo);
-      p.s1n = lz * ld; p.s1z = lz; p.s1y = ly; p.s1x = mx ? 32 : lx; p.C1 = lo.C; p.cs1 = mx ? lw * 32 : 32;
+      amx::set_src1(p, mem(lo), lo.C, ld, lh, lw, c.precision);
     } else {
-      const long long sx = (long long)cur.C * eb, sy = sx * dw, sz = sy * dh;
-      p.src0 = mem(cur);
-      p.s0n = sz * dd; p.s0z = sz; p.s0y = sy; p.s0x = mx ? 32 : sx; p.C0 = cur.C; p.C1 = 0; p.cs0 = mx ? dw * 32 : 32;
+      amx::set_src0(p, mem(cur), cur.C, dd, dh, dw, c.precision);
+      p.C1 = 0;
     }
     if (p.C0 + p.C1 != L.cin_pad)
       return fail(AMX_ERR_INVALID, "internal: conv model.%d expects %d channels, schedule has %d",
@@ -554,9 +548,7 @@ struct Forward : ForwardArgs {
       p.wmap = wmap;
     } else {
       if (int e = slot(lv, &out.slot)) return e;
-      p.out = mem(out);
-      p.ox = (long long)L.cout_p * eb; p.oy = p.ox * dw; p.oz = p.oy * dh; p.on = p.oz * dd;
-      if (mx) { p.ox = 32; p.ocs = dw * 32; }
+      amx::set_out(p, mem(out), L.cout_p, dd, dh, dw, c.precision);
     }
     const double vox = (double)n * dd * dh * dw;
     // ALGORITHMIC bytes: 16-bit activations read once and written once + the weights, the upsampled
@@ -574,8 +566,7 @@ struct Forward : ForwardArgs {
     if (fuse_max_pool) {
       fused_pool.level = lv + 1; fused_pool.C = L.cout_p; fused_pool.Cr = L.cout;
       if (int e = slot(lv + 1, &fused_pool.slot)) return e;
-      p.out2 = mem(fused_pool);
-      p.qx = (long long)L.cout_p * eb; p.qy = p.qx * (dw / 2); p.qz = p.qy * (dh / 2); p.qn = p.qz * (dd / 2);
+      amx::set_out2(p, mem(fused_pool), L.cout_p, dd / 2, dh / 2, dw / 2, c.precision);
       have_fused_pool = true;
     }
     if (p.src0_f32c1 && (L.is_final || L.cout_p > 32))
@@ -591,13 +582,13 @@ struct Forward : ForwardArgs {
     memset(&u, 0, sizeof u);
     if (use_merge) {
       if (int e = slot(lv, &p_slot)) return e;
-      u.src = p.src1; u.sn = p.s1n; u.sz = p.s1z; u.sy = p.s1y; u.sx = p.s1x; u.C1 = p.C1;
+      amx::set_src(u, p.src1, p.C1, dd / 2, dh / 2, dw / 2, c.precision);
       u.N = n; u.LD = dd / 2; u.LH = dh / 2; u.LW = dw / 2; u.Cout = L.cout;
       u.wpk = (const char*)L.wpk_merge;
       u.part = slots[lv][p_slot]; u.out = p.out;
       u.bias = p.bias; u.act = p.act; u.slope = p.slope;
       u.oflow = h->d_flag;
-      u.cs = p.cs1; u.ocs = p.ocs;                 // the low-resolution source / the partial sums and the output (same layout)
+      u.ocs = p.ocs;                               // the partial sums and the output (same layout)
       p.out = slots[lv][p_slot];                   // same strides as the layer's output
       p.bias = nullptr; p.act = AMX_ACT_NONE;
       p.src1 = nullptr; p.C1 = 0; p.up_shift = 0;
@@ -618,11 +609,14 @@ struct Forward : ForwardArgs {
     // tensor whose norm was left pending (instance_norm_after), and takes already-normalised inputs too.
     const bool use_zx = zx_shape;
     if (cur.ab && !use_zx) return fail(AMX_ERR_INVALID, "internal: model.%d got an input whose norm is pending but cannot run the fused kernel", L.module_idx);
+    // what the launch ran and the statistics slots it wrote, for the record and for the norm behind it (window loops: the last window's)
+    amx::ConvLaunchInfo info{}, merge_info;
+    amx::ConvLaunchInfo* const want = (prof || fuse_stats) ? &info : nullptr;
     auto launch_one = [&](const amx::ConvParams& q) -> hipError_t {
-      if (q.src0_f32c1) return amx::launch_conv_stem(q, stem_precision(c.precision), st);
-      if (use_upcat) return amx::launch_conv_upcat16(q, c.precision, st);
-      if (use_zx) return amx::launch_conv_zx(q, cur.ab, cur.ab_act, c.act_slope, L.wx, st);
-      return amx::launch_conv(q, c.precision, L.q, st);
+      if (q.src0_f32c1) return amx::launch_conv_stem(q, stem_precision(c.precision), st, want);
+      if (use_upcat) return amx::launch_conv_upcat16(q, c.precision, st, want);
+      if (use_zx) return amx::launch_conv_zx(q, cur.ab, cur.ab_act, c.act_slope, L.wx, st, want);
+      return amx::launch_conv(q, c.precision, L.q, st, want);
     };
     // pipelined windows (two batches in flight on two streams): the accumulating launches of this batch wait for the other
     // slot's accumulations, so that overlapping windows still add up in window order
@@ -647,13 +641,11 @@ struct Forward : ForwardArgs {
     }
     if (x_offs && L.is_final && acc_done) AMX_HIP(hipEventRecord(acc_done, st));
     if (use_merge) {
-      AMX_HIP(amx::launch_conv_upmerge(u, c.precision, st));
+      AMX_HIP(amx::launch_conv_upmerge(u, c.precision, st, prof ? &merge_info : nullptr));
       used[lv][p_slot] = false;                    // the partial sums are dead once their consumer is enqueued (stream order)
-      if (prof) name_last("%.34s + %.26s", amx::last_conv_kernel_name(), amx::last_conv_upmerge_kernel_name() + 7);
+      if (prof) name_last("%.34s + %.26s", info.name, merge_info.name + 7);      // (+ 7: without its "conv3d_")
     } else if (prof) {
-      name_last("%s", p.src0_f32c1 ? amx::last_conv_stem_kernel_name()
-                                   : use_upcat ? amx::last_conv_upcat_kernel_name()
-                                               : (use_zx ? amx::last_conv_zx_kernel_name() : amx::last_conv_kernel_name()));
+      name_last("%s", info.name);
     }
     if (raw_bn) {
       AMX_HIP(export_slot(out, tap_conv));
@@ -663,7 +655,7 @@ struct Forward : ForwardArgs {
       AMX_HIP(export_slot(out, tap_conv));     // the stored raw convolution output, before the instance norm below
     }
     if (inorm) {
-      if (int e = instance_norm_after(L, p, out, nxt, act_on, fuse_stats, use_zx, stem_slots)) return e;
+      if (int e = instance_norm_after(L, p, out, nxt, act_on, fuse_stats ? info.stats_slots : 0)) return e;
     }
     if (final_via_export)
       AMX_HIP(amx::launch_export_ncdhw(mem(out), L.cout, nullptr, 0, 0, n, dd, dh, dw, y, c.precision, st, L.cout_p, 0));
@@ -690,10 +682,9 @@ struct Forward : ForwardArgs {
 
   // InstanceNorm behind a conv that stored its RAW output in `out`: statistics, then the apply pass here, in the consumer, or
   // together with the pool
-  // nxt: module index of the next group; act_on: the group's activation runs (encode_only may end before it); fuse_stats: the conv's
-  // epilogue wrote the partial sums of the statistics (use_zx / stem_slots: which kernel did, and into how many slots)
-  int instance_norm_after(const ConvLayer& L, const amx::ConvParams& p, Tensor& out, size_t nxt, bool act_on, bool fuse_stats, bool use_zx,
-                          int stem_slots) {
+  // nxt: module index of the next group; act_on: the group's activation runs (encode_only may end before it); slots_written: the
+  // partial-statistics slots per sample that the conv's epilogue wrote (0: it wrote none, the statistics pass runs)
+  int instance_norm_after(const ConvLayer& L, const amx::ConvParams& p, Tensor& out, size_t nxt, bool act_on, int slots_written) {
     const int lv = L.level, dd = p.D, dh = p.H, dw = p.W;
     if (L.is_final) return fail(AMX_ERR_INVALID, "internal: instance norm after the output conv");
     if (int e = record(L.norm_idx, L.cout, L.cout, dd, dh, dw, 0.0, (double)eb * L.cout * (double)n * dd * dh * dw * 3.0)) return e;
@@ -718,11 +709,10 @@ struct Forward : ForwardArgs {
     const bool defer_up = !defer && !apply_pool && !taps && !x_offs && act_on == L.has_act && nxt < h->kinds.size() &&
                           h->kinds[nxt] == K_UP && c.interp == AMX_INTERP_TRILINEAR;
     if (defer_up) defer = true;
-    const int slots_written = !fuse_stats ? 0 : p.src0_f32c1 ? stem_slots : use_zx ? amx::conv_zx_stats_slots(dh, dw) : amx::last_conv_stats_slots();
     float* abo = (defer || apply_pool) ? ab_buf[ab_next] : nullptr;
     AMX_HIP(amx::launch_instnorm(mem(out), L.in_gamma, L.in_beta, c.norm_eps, n, (long long)dd * dh * dw,
                                  L.cout_p, act_on ? c.activation : AMX_ACT_NONE, c.act_slope, in_scratch, c.precision, st, h->d_flag,
-                                 slots_written, fuse_stats ? L.shift : nullptr, dw, conv_only(nxt), (defer || apply_pool) ? 0 : 1, abo));
+                                 slots_written, slots_written ? L.shift : nullptr, dw, conv_only(nxt), (defer || apply_pool) ? 0 : 1, abo));
     if (apply_pool) {
       fused_pool.level = lv + 1; fused_pool.C = L.cout_p; fused_pool.Cr = L.cout;
       if (int e = slot(lv + 1, &fused_pool.slot)) return e;

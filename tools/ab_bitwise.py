@@ -1,14 +1,17 @@
-"""Bitwise A/B of two builds of libanatomix_amd.so over the entries of the streaming units (segmentation loss, the three augmentation
-units, registration metrics, instance optimisation, MIND-SSC / correlation): the proof that a refactor of their shared helpers changed no
-summation order and no contraction.
+"""Bitwise A/B of two builds of libanatomix_amd.so.  Section ``streams``: the entries of the streaming units (segmentation loss, the
+three augmentation units, registration metrics, instance optimisation, MIND-SSC / correlation) -- the proof that a refactor of their
+shared helpers changed no summation order and no contraction.  Section ``unet``: the UNet forward (output, feature taps, sliding
+window, the kernel names of a profiled forward) and the single-layer conv entries, one shape per route of the conv dispatch -- the
+proof that a refactor of the launch path moved no layer to another kernel and changed no launch.
 
-    python tools/ab_bitwise.py --old PATH/libanatomix_amd.so [--new PATH/libanatomix_amd.so]
+    python tools/ab_bitwise.py --old PATH/libanatomix_amd.so [--new PATH/libanatomix_amd.so] [--section streams|unet|all]
 
 One process uses one library (anatomix_amd/_lib.py reads AMX_LIB_PATH at import), so each side runs in a fresh child process of
 its own (``--child``), one after the other and each under its own time limit.  A child runs every entry on seeded inputs and
 prints one SHA-256 per output tensor; the two listings are compared here and THAT comparison sets the exit status: 0 identical,
 1 different, 2 a child failed (the second one is then not started)."""
 import argparse
+import contextlib
 import ctypes
 import hashlib
 import os
@@ -20,7 +23,68 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # ---- child: one listing --------------------------------------------------------------------------------------------------
 
-def child():
+def unet_section(dev, emit):
+    """The 6 M variant and anatomix-dev in every precision they support, and the single-layer entries on one shape per route."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import torch
+    import _util as U              # run_conv / run_conv_merged: the tensor layouts of the single-layer entries
+    import anatomix_amd
+    from anatomix_amd.registration.sliding_window import sliding_window_inference
+    from oracle import unet_ref as R
+
+    def emit_names(name, names):
+        """Kernel names: one compared line each, and the whole list hashed like a tensor."""
+        for i, k in enumerate(names):
+            print(f"{name}[{i}] (text) {k}", flush=True)
+        emit(name, torch.frombuffer(bytearray("\n".join(names).encode()), dtype=torch.uint8))
+
+    # (variant, precisions, (forward shape, sliding-window volume) pairs, roi).  anatomix-dev at 64^3 runs its five levels at
+    # W = 64, 32, 16, 8, 4: every row of the generic kernel's brick table.  Modules 2 / 5: inside / right behind the stem pair.
+    nets = (("anatomix", ("f16", "bf16", "f16x2", "strict"), (((32, 32, 32), (32, 32, 48)), ((48, 64, 96), (48, 64, 96))), 32),
+            ("anatomix-dev", ("f16", "bf16", "f16x2", "strict", "f16x2mx"), (((64, 64, 64), (64, 64, 96)),), 64))
+    for variant, precisions, shapes, roi in nets:
+        kw = R.VARIANTS[variant]
+        with contextlib.redirect_stdout(sys.stderr):       # (the constructor prints its skip ids, as the reference does)
+            m = anatomix_amd.Unet(**kw)
+        m.load_state_dict(R.synthetic_state_dict(kw, 0), strict=True)
+        m = m.to(dev).eval()
+        for precision in precisions:
+            m.precision = precision
+            for shape, volume in shapes:
+                tag = f"unet/{variant}/{precision}/{'x'.join(map(str, shape))}"
+                x = R.synthetic_input(100, 1, shape).to(dev)
+                with torch.no_grad():
+                    emit(f"{tag}/forward", m(x))
+                    for module in (2, 5):
+                        y, feats = m.forward_hip_taps(x, [module])
+                        emit(f"{tag}/taps{module}/out", y)
+                        emit(f"{tag}/taps{module}/feat", feats[0])
+                    xv = R.synthetic_input(101, 1, volume).to(dev)
+                    emit(f"{tag}/sliding_window_{'x'.join(map(str, volume))}",
+                         sliding_window_inference(xv, roi, 4, m, overlap=0.25, mode="gaussian"))
+                    y, recs = m.profile_forward(x)
+                emit(f"{tag}/profile_forward/out", y)
+                emit_names(f"{tag}/profile_forward/names", [r["kernel"] for r in recs])
+
+    # ---- amx_conv3d_k3_reflect_ws / amx_conv3d_upcat_merged: (route, c0, c1, cout, size, precision, planar output)
+    g = torch.Generator().manual_seed(20250301)
+    layers = (("zmarch", 16, 0, 16, 32, "f16", False), ("zmarch_out32", 16, 0, 16, 32, "f16", True), ("ks", 64, 0, 64, 16, "f16", False),
+              ("ks_split", 128, 0, 256, 8, "f16", False), ("v2_upseg", 32, 64, 32, 32, "f16", False), ("upcat16", 16, 32, 16, 32, "f16", False),
+              ("upmerge", 32, 64, 32, 32, "f16", False), ("ks_shape_mx", 64, 0, 64, 16, "f16x2mx", False),
+              ("v2_upseg_mx", 32, 64, 32, 32, "f16x2mx", False))
+    for route, c0, c1, cout, s, precision, planar in layers:
+        x0 = torch.randn(1, c0, s, s, s, generator=g)
+        x1 = torch.randn(1, c1, s // 2, s // 2, s // 2, generator=g) if c1 else None
+        w = torch.randn(cout, c0 + c1, 3, 3, 3, generator=g) / (27 * (c0 + c1)) ** 0.5
+        scale, shift = 0.5 + torch.rand(cout, generator=g), torch.randn(cout, generator=g) * 0.1
+        if route == "upmerge":
+            out = U.run_conv_merged(dev, x0, x1, w, scale, shift, 1, precision)
+        else:
+            out = U.run_conv(dev, x0, x1, w, scale, shift, 1, precision, planar=planar)      # (offers the split-K scratch)
+        emit(f"conv_layer/{route}/{c0}+up{c1}->{cout}@{s}/{precision}/out", out)
+
+
+def child(section):
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -48,6 +112,15 @@ def child():
 
     def empty(*shape, offset=0, dtype=torch.float32):
         return torch.empty(int(np.prod(shape)) + offset, dtype=dtype, device=dev)[offset:].view(*shape)
+
+    def done():
+        torch.cuda.synchronize()
+        print(f"# {count[0]} tensors from {_lib.LIB_PATH}", flush=True)
+
+    if section in ("unet", "all"):
+        unet_section(dev, emit)
+    if section == "unet":
+        return done()
 
     # ---- amx_seg_loss_forward / _backward / amx_seg_argmax, head mode and logits mode
     LABEL = (torch.float32, torch.int64, torch.uint8)
@@ -231,16 +304,15 @@ def child():
     ssd, amin = CU.correlate(rand(1, 7, 6, 9, 11), rand(1, 7, 6, 9, 11), 1, 1, (6, 9, 11), 7)
     emit("correlate_ssd/6x9x11/hw1/ssd", ssd)
     emit("correlate_ssd/6x9x11/hw1/argmin", amin)
-    torch.cuda.synchronize()
-    print(f"# {count[0]} tensors from {_lib.LIB_PATH}", flush=True)
+    done()
 
 
 # ---- parent: two children, one comparison -----------------------------------------------------------------------------------
 
-def run_side(name, lib_path, timeout):
+def run_side(name, lib_path, timeout, section):
     env = dict(os.environ, AMX_LIB_PATH=os.path.abspath(lib_path))
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--section", section], env=env, cwd=ROOT, stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True, timeout=timeout)
     except subprocess.TimeoutExpired:
         print(f"{name}: no listing within {timeout} s")
@@ -256,11 +328,12 @@ def main():
     ap.add_argument("--child", action="store_true", help="print this process's listing (AMX_LIB_PATH selects the library)")
     ap.add_argument("--old", help="the library to compare against (e.g. the parent commit's build)")
     ap.add_argument("--new", default=os.path.join(ROOT, "anatomix_amd", "csrc", "libanatomix_amd.so"))
+    ap.add_argument("--section", choices=("streams", "unet", "all"), default="all")
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds per child")
     ap.add_argument("--print-listings", action="store_true")
     a = ap.parse_args()
     if a.child:
-        return child()
+        return child(a.section)
     if not a.old:
         ap.error("--old is required")
     listings = {}
@@ -268,7 +341,7 @@ def main():
         if not os.path.exists(path):
             print(f"{name}: {path} does not exist")
             return 2
-        listings[name] = run_side(name, path, a.timeout)
+        listings[name] = run_side(name, path, a.timeout, a.section)
         if listings[name] is None:
             return 2
     old, new = listings["old"], listings["new"]
