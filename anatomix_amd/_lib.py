@@ -195,6 +195,14 @@ SYMBOLS = {
     "amx_synth_lowres": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "amx_synth_clip_minmax": (_I, [_P, _I, C.c_longlong, _P, C.c_size_t, _P]),
     "amx_synth_finish": (_I, [_P, _P, _I, C.c_longlong, _P, _I, _P]),
+    "amx_labels_template_bytes": (C.c_size_t, []),
+    "amx_labels_ensemble_bytes": (C.c_size_t, []),
+    "amx_labels_scratch_bytes": (C.c_size_t, [_I, C.c_longlong]),
+    "amx_labels_compose": (_I, [_P, C.c_size_t, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "amx_labels_median3": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "amx_labels_sphere_mask": (_I, [C.POINTER(_P), _P, _I, _I, _P, _P, _P]),
+    "amx_labels_apply_mask": (_I, [_P, _P, _P, _I, C.c_longlong, _P, _P, _P, C.c_size_t, _P]),
+    "amx_labels_envelope": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "amx_label_overlap": (_I, [_P, _I, _P, _I, C.c_longlong, _I, _P, _P, _P]),
     "amx_jacobian_det_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "amx_jacobian_det": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),

@@ -1,4 +1,4 @@
-// anatomix_amd -- what the streaming units (amx_segloss.hip, amx_segaug.hip, amx_preaug.hip, amx_synth.hip, amx_regmetrics.hip,
+// anatomix_amd -- what the streaming units (amx_segloss.hip, amx_segaug.hip, amx_preaug.hip, amx_synth.hip, amx_labels.hip, amx_regmetrics.hip,
 // amx_reginstopt.hip) share: the four-voxel tile access, the ascending xor butterfly over a wave and the LDS tree sum over a
 // workgroup, and for the three augmentation units the volume dims, the workgroup min / max with its partial slab, the
 // degree-3 polynomial sum and the centred taps.  Each reduction here has ONE order; a reduction in another order
@@ -42,6 +42,23 @@ struct StreamTile {
       for (int j = 0; j < VPT; ++j) {
         const long long o = voxel<false>(t, j);
         v[j] = o < V ? row[o] : 0.f;
+      }
+    }
+  }
+
+  // uint8 voxels (labels) as ints; VEC: one 4-byte load (a 4-byte aligned base)
+  template <bool VEC>
+  static __device__ __forceinline__ void load4(const unsigned char* __restrict__ row, int t, long long V, int (&l)[VPT]) {
+    if (VEC) {
+      const long long o = voxel<true>(t, 0);
+      uchar4 q = make_uchar4(0, 0, 0, 0);
+      if (o < V) q = *(const uchar4*)(row + o);
+      l[0] = q.x, l[1] = q.y, l[2] = q.z, l[3] = q.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < VPT; ++j) {
+        const long long o = voxel<false>(t, j);
+        l[j] = o < V ? row[o] : 0;
       }
     }
   }
@@ -146,6 +163,16 @@ __device__ __forceinline__ void block_minmax(float lo, float hi, float* __restri
 }
 // the slab pair of this workgroup of a (chunks, rows) grid: pair [row][chunk], what the finalize kernel of amx_segaug.hip reads
 __device__ __forceinline__ float* minmax_slab(float* __restrict__ part) { return part + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2; }
+
+// ---- trilinear upsample ------------------------------------------------------------------------------------------------------
+// torch's source index of the trilinear upsample (align_corners=False) of output voxel o of an axis with cn coarse points and
+// rs = 1 / scale: neighbours i0, i1 (the upper one clamped) and the weight of i1
+__device__ __forceinline__ void trilinear_src(int o, float rs, int cn, int& i0, int& i1, float& l1) {
+  const float src = fmaxf(rs * ((float)o + 0.5f) - 0.5f, 0.f);
+  i0 = min((int)src, cn - 1);
+  i1 = min(i0 + 1, cn - 1);
+  l1 = src - (float)i0;
+}
 
 // ---- bias field and taps ----------------------------------------------------------------------------------------------------
 // coordinate i of linspace(-1, 1, n)

@@ -23,23 +23,6 @@ using Syn = StreamTile<>;
 using SynView = amx_synth_view;
 constexpr int kSynMaxLdsFloats = 12288;      // 48 KiB of collapsed coarse rows per workgroup, the two label tables besides
 
-// labels of this thread's four voxels; voxels past V read as 0
-template <bool VEC>
-__device__ __forceinline__ void syn_load_labels(const unsigned char* __restrict__ row, int t, long long V, int (&l)[Syn::kVpt]) {
-  if (VEC) {
-    const long long o = Syn::voxel<true>(t, 0);
-    uchar4 q = make_uchar4(0, 0, 0, 0);
-    if (o < V) q = *(const uchar4*)(row + o);
-    l[0] = q.x, l[1] = q.y, l[2] = q.z, l[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < Syn::kVpt; ++j) {
-      const long long o = Syn::voxel<false>(t, j);
-      l[j] = o < V ? row[o] : 0;
-    }
-  }
-}
-
 // mean and std by LABEL (through the rank table) into LDS; rank 0 of a view with a zero background gets (0, 0), so that g is exactly 0
 __device__ __forceinline__ void syn_label_tables(const SynView& s, float* __restrict__ lmean, float* __restrict__ lstd) {
   const bool zero_bg = s.flags & AMX_SYNTH_ZERO_BACKGROUND;
@@ -71,7 +54,7 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_gmm_minmax_kernel(const uns
     float v[Syn::kVpt];
     int l[Syn::kVpt];
     Syn::load4<VEC>(z, t, V, v);
-    syn_load_labels<VEC>(lab, t, V, l);
+    Syn::load4<VEC>(lab, t, V, l);
 #pragma unroll
     for (int j = 0; j < Syn::kVpt; ++j)
       if (Syn::voxel<VEC>(t, j) < V) {
@@ -90,14 +73,6 @@ struct SynApp : StreamDims {
   int cd[AMX_SYNTH_MAX_SCALES], ch[AMX_SYNTH_MAX_SCALES], cw[AMX_SYNTH_MAX_SCALES], off[AMX_SYNTH_MAX_SCALES + 1];
   const float* grid[AMX_SYNTH_MAX_SCALES];       // [n][cd][ch][cw], already multiplied by its std
 };
-
-// torch's source index of the trilinear upsample (align_corners=False) of output voxel o: neighbours i0, i1 and the weight of i1
-__device__ __forceinline__ void syn_src(int o, float rs, int cn, int& i0, int& i1, float& l1) {
-  const float src = fmaxf(rs * ((float)o + 0.5f) - 0.5f, 0.f);
-  i0 = min((int)src, cn - 1);
-  i1 = min(i0 + 1, cn - 1);
-  l1 = src - (float)i0;
-}
 
 // A tile of 1024 consecutive voxels lies in at most `maxrows` rows (z, y) of the volume.  For those rows the coarse grids are
 // interpolated along z and y first, which leaves one coarse row of cw values per scale and volume row in LDS; a voxel then blends
@@ -128,8 +103,8 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_appearance_kernel(SynApp a,
       const int cx = q - a.off[sc], vz = (row0 + r) / a.h, vy = (row0 + r) - vz * a.h;
       int z0, z1, y0, y1;
       float lz, ly;
-      syn_src(vz, a.rs[sc], a.cd[sc], z0, z1, lz);
-      syn_src(vy, a.rs[sc], a.ch[sc], y0, y1, ly);
+      trilinear_src(vz, a.rs[sc], a.cd[sc], z0, z1, lz);
+      trilinear_src(vy, a.rs[sc], a.ch[sc], y0, y1, ly);
       const float* g = a.grid[sc] + (long long)row * a.cd[sc] * a.ch[sc] * a.cw[sc] + cx;
       const int sy = a.cw[sc], sz = a.ch[sc] * a.cw[sc];
       const float p0 = (1.f - ly) * g[z0 * sz + y0 * sy] + ly * g[z0 * sz + y1 * sy];
@@ -140,7 +115,7 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_appearance_kernel(SynApp a,
     float v[Syn::kVpt];
     int l[Syn::kVpt];
     Syn::load4<VEC>(z, t, a.V, v);
-    syn_load_labels<VEC>(lab, t, a.V, l);
+    Syn::load4<VEC>(lab, t, a.V, l);
 #pragma unroll
     for (int j = 0; j < Syn::kVpt; ++j) {
       const long long o = Syn::voxel<VEC>(t, j);
@@ -154,7 +129,7 @@ __global__ __launch_bounds__(Syn::kThreads) void syn_appearance_kernel(SynApp a,
       for (int sc = 0; sc < a.nscales; ++sc) {
         int x0, x1;
         float lx;
-        syn_src(x, a.rs[sc], a.cw[sc], x0, x1, lx);
+        trilinear_src(x, a.rs[sc], a.cw[sc], x0, x1, lx);
         P += (1.f - lx) * cr[a.off[sc] + x0] + lx * cr[a.off[sc] + x1];
       }
       const float g = syn_gmm(v[j], l[j], lmean, lstd);

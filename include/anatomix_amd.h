@@ -964,6 +964,83 @@ int amx_synth_lowres(const float* d_in, float* d_out, int n, int d, int h, int w
 int amx_synth_clip_minmax(const float* d_x, int n, long long voxels, void* d_scratch, size_t scratch_bytes, void* stream);
 int amx_synth_finish(const float* d_in, void* d_out, int n, long long voxels, const float* d_minmax, int out_u8, void* stream);
 
+/* ---- synthetic data generation, step 1: label ensembles (synthetic-data-generation/step1_generate_labels.py with
+ * datagen_utils.py:26-447) on a batch (csrc/amx_labels.hip).  All volumes are uint8 [batch][d][h][w], on
+ * `stream` without host synchronisation, read-back or allocation, one launch per stage with the ensemble on a grid axis.  What
+ * differs per ensemble sits in a table of `batch` amx_labels_ensemble records, and what differs per template in a table of
+ * amx_labels_template records; both are filled on the host and copied to the device once per batch, and every entry takes the
+ * host copy (read for validation only) and the device copy (read by the kernels).  An ensemble whose switch for a stage is off
+ * passes that launch bit for bit.  Integer arithmetic and fixed-order float arithmetic only: two runs agree bit for bit.  Every
+ * entry validates its arguments and returns an error without launching anything. ---- */
+enum {
+  AMX_LABELS_MASK = 1,     /* the deformed-sphere foreground mask (step1_generate_labels.py:101-116) */
+  AMX_LABELS_ENVELOPE = 2  /* the envelope around it (step1_generate_labels.py:119-138); needs AMX_LABELS_MASK */
+};
+enum { AMX_LABELS_MAX_TEMPLATES = 64 };
+
+typedef struct amx_labels_template {
+  int64_t offset;   /* of the cropped template [c0][c1][c2] in the byte buffer */
+  int32_t crop[3];  /* c: shape of the non-zero bounding box */
+  int32_t before[3];/* p: zero voxels in front of it, pad / 2 + (pad & 1) with pad = padded - crop */
+  int32_t padded[3];/* P = max(size, c): the wrap period */
+  int32_t reserved;
+  double affine[12];/* rows (M_a0, M_a1, M_a2, t_a) of the output -> source map */
+} amx_labels_template;
+
+typedef struct amx_labels_ensemble {
+  int32_t flags;       /* AMX_LABELS_* switches */
+  int32_t first, count;/* its templates: records first .. first + count - 1, 1 <= count <= AMX_LABELS_MAX_TEMPLATES */
+  int32_t radius;      /* of the sphere, >= 0 */
+  int32_t shift[3];    /* of its centre from size / 2, per axis (d, h, w) */
+  int32_t ball;        /* radius of the envelope's ball: 2, 3 or 4 */
+} amx_labels_ensemble;
+
+/* sizeof the two records, for a caller that lays the tables out without this header */
+size_t amx_labels_template_bytes(void);
+size_t amx_labels_ensemble_bytes(void);
+/* bytes of d_scratch of amx_labels_apply_mask (0 for arguments outside the envelope) */
+size_t amx_labels_scratch_bytes(int batch, long long voxels);
+
+/* Compose (step1_generate_labels.py:69-95, datagen_utils.py:71-194): d_out [batch][d][h][w] is, per voxel o, the largest k whose
+ * template has a non-zero sample there, else 0 -- the reference's in-order `label_ensemble[roi > 0] = k`.  Template k's sample is
+ * scipy's affine_transform(order=0, mode='grid-wrap') of the cropped and padded template without materialising it:
+ * x_a = t_a + o_0 M_a0 + o_1 M_a1 + o_2 M_a2 in float64 in that order without contraction, i_a = floor(x_a + 0.5) mod P_a, and the
+ * value is the cropped template at i - p, 0 outside it.  d_templates: template_bytes bytes, any alignment.  One launch. */
+int amx_labels_compose(const unsigned char* d_templates, size_t template_bytes, const amx_labels_template* h_templates,
+                       const amx_labels_template* d_templates_table, int ntemplates, const amx_labels_ensemble* h_table,
+                       const amx_labels_ensemble* d_table, unsigned char* d_out, int batch, int d, int h, int w, void* stream);
+
+/* The exact 3 x 3 x 3 median of uint8 with border replication (step1_generate_labels.py:98, 111: skimage.filters.median's default
+ * footprint and mode='nearest'): element 13 of the 27 sorted neighbours, for a 0 / 1 mask "at least 14 of 27".  Ensembles whose
+ * flags lack one of the bits of `require` are copied.  d_in and d_out must not overlap.  One launch. */
+int amx_labels_median3(const unsigned char* d_in, unsigned char* d_out, int batch, int d, int h, int w, int require,
+                       const amx_labels_ensemble* h_table, const amx_labels_ensemble* d_table, void* stream);
+
+/* The deformed-sphere foreground mask (datagen_utils.py:371-447, negated as at step1_generate_labels.py:107-110) of the ensembles
+ * with AMX_LABELS_MASK as one fused kernel; the others' volumes are not touched.  d_grids: HOST array of 3 device pointers, the
+ * coarse Gaussian grids [batch][3][size / s]^3 float32 of the scales s = size / 16, size / 8, size / 4, already multiplied by
+ * their std.  Per voxel and component c (0 indexes w, 1 h, 2 d), float32 in torch's order of operations (products and sums of the
+ * blends rounded one by one; the blend weight may differ from torch's in the last bit): the displacement is the sum over the scales of
+ * the trilinear upsample (align_corners=False), g = base(o) + 2 disp / (size - 1), x = ((g + 1) size - 1) / 2, reflected about
+ * [-0.5, size - 0.5], clipped to [0, size - 1] and rounded half to even to q; the mask is 1 where
+ * |q - (size / 2 + shift)|^2 <= radius^2 in integers.  Cubes with size % 16 == 0, 16 <= size <= 256.  One launch. */
+int amx_labels_sphere_mask(const float* const* d_grids, unsigned char* d_mask, int batch, int size, const amx_labels_ensemble* h_table,
+                           const amx_labels_ensemble* d_table, void* stream);
+
+/* step1_generate_labels.py:115-116 in place: label = mask ? label + 1 : 0 for the ensembles with AMX_LABELS_MASK, and
+ * d_max [batch] int32 = the maximum label of every ensemble afterwards (per-workgroup partials in d_scratch, then a finalize
+ * launch).  Two launches. */
+int amx_labels_apply_mask(unsigned char* d_labels, const unsigned char* d_mask, int* d_max, int batch, long long voxels,
+                          const amx_labels_ensemble* h_table, const amx_labels_ensemble* d_table, void* d_scratch, size_t scratch_bytes,
+                          void* stream);
+
+/* step1_generate_labels.py:123-138 in place for the ensembles with AMX_LABELS_ENVELOPE: label = 1 + d_max[ensemble] where
+ * dilate(mask, ball) & ~erode(mask, ball), ball = {x^2 + y^2 + z^2 <= ball^2}, the border scipy's `reflect` (the edge voxel
+ * repeated; skimage's default for both operators), erosion evaluated as ~dilate(~mask).  Rows packed as bits in LDS; the ball is
+ * a union of x-runs.  Every axis must be at least 9.  One launch. */
+int amx_labels_envelope(unsigned char* d_labels, const unsigned char* d_mask, const int* d_max, int batch, int d, int h, int w,
+                        const amx_labels_ensemble* h_table, const amx_labels_ensemble* d_table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
