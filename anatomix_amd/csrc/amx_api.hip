@@ -343,6 +343,37 @@ int amx_adamw_step_dev(const amx_adamw_tensor* tensors, int count, const double*
   return AMX_OK;
 }
 
+int amx_adamw_step_clip_dev(const amx_adamw_tensor* tensors, int count, const double* d_hyper, int maximize, const float* d_total_norm,
+                            double max_norm, void* stream) {
+  if (count < 0 || (count && !tensors) || !d_hyper || !d_total_norm || !(max_norm >= 0.0))
+    return fail(AMX_ERR_INVALID, "adamw: bad argument (max_norm %g)", max_norm);
+  for (int t = 0; t < count; ++t) {
+    const amx_adamw_tensor& r = tensors[t];
+    if (!r.param || !r.grad || !r.exp_avg || !r.exp_avg_sq || !r.step || r.numel < 0)
+      return fail(AMX_ERR_INVALID, "adamw: tensor %d has a null pointer or a negative size", t);
+  }
+  AMX_HIP(amx::launch_adamw((const long long*)tensors, count, 0.0, 0.0, 0.0, 0.0, 0.0, maximize, (hipStream_t)stream, d_hyper, d_total_norm,
+                            max_norm));
+  return AMX_OK;
+}
+
+size_t amx_grad_norms_scratch_bytes(const amx_grad_tensor* tensors, int count, int groups) {
+  static_assert(sizeof(amx_grad_tensor) == 24, "three 64-bit fields");
+  if (count < 0 || groups < 0 || (count && !tensors)) return 0;
+  return amx::grad_norms_scratch_bytes((const long long*)tensors, count, groups);
+}
+
+int amx_grad_norms(const amx_grad_tensor* tensors, int count, int groups, float* d_out, void* d_scratch, size_t scratch_bytes,
+                   void* stream) {
+  if (count < 0 || groups < 0 || (count && !tensors) || (groups && !d_out) || !d_scratch) return fail(AMX_ERR_INVALID, "bad argument");
+  for (int t = 0; t < count; ++t)
+    if (!tensors[t].grad && tensors[t].numel) return fail(AMX_ERR_INVALID, "grad_norms: tensor %d has a null pointer", t);
+  if (amx_grad_norms_scratch_bytes(tensors, count, groups) == 0 || scratch_bytes < amx_grad_norms_scratch_bytes(tensors, count, groups))
+    return fail(AMX_ERR_INVALID, "grad_norms: a negative size, a group outside [0, %d), too many blocks, or too little scratch", groups);
+  AMX_HIP(amx::launch_grad_norms((const long long*)tensors, count, groups, d_out, d_scratch, scratch_bytes, (hipStream_t)stream));
+  return AMX_OK;
+}
+
 int amx_pool2_max_backward(const void* d_dp, const void* d_in, void* d_din, int n, int dout, int hout, int wout, int c,
                            int accumulate, int precision, void* stream) {
   if (!d_dp || !d_in || !d_din || c % 8) return fail(AMX_ERR_INVALID, "bad argument");

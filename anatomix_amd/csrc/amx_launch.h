@@ -140,7 +140,10 @@ hipError_t launch_wgrad(WgradParams p, int CinReal, float* dw, int accumulate, v
 
 // amx_optim.hip
 hipError_t launch_adamw(const long long* table, int count, double lr, double b1, double b2, double eps, double wd, int maximize,
-                        hipStream_t st, const double* d_hyper = nullptr);
+                        hipStream_t st, const double* d_hyper = nullptr, const float* d_norm = nullptr, double max_norm = 0.0);
+size_t grad_norms_scratch_bytes(const long long* table, int count, int groups);
+hipError_t launch_grad_norms(const long long* table, int count, int groups, float* out, void* scratch, size_t scratch_bytes,
+                             hipStream_t st);
 
 // amx_supcon.hip
 size_t supcon_scratch_bytes(int N, int C);

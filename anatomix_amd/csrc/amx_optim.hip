@@ -5,32 +5,20 @@
 //     p *= 1 - lr wd;  m += (g - m)(1 - b1);  v = v b2 + (1 - b2) g g;
 //     p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // with the step count t read from the device (one fp32 scalar per tensor, as torch's capturable state keeps it).
+//
+// Gradient clipping (supcl_model.py:631-655: clip_grad_norm_(max_norm_G / max_norm_F) between unscale_ and the step) lives here
+// too.  launch_grad_norms gives the L2 norm of each of `groups` lists of gradients: per-block partial sums of squares into a
+// caller's scratch, then a SECOND TINY LAUNCH that adds the partials of each group in a fixed order -- not a last-block pass: a
+// kernel boundary (~2 us) orders the partials without any fence, counter or spin, and the result has the same bits on every
+// run and replay (no floating-point atomics anywhere).  The clipping itself costs no pass: adamw_clip_kernel reads the norm from
+// the device and scales each gradient as it loads it.
 #include <hip/hip_runtime.h>
 
 #include "amx_launch.h"
+#include "amx_optim_args.h"
+#include "amx_stream.h"
 
 namespace amx {
-
-constexpr int kAdamTensors = 48;             // descriptors per launch: 48 x 48 B + the prefix table < the 4 KiB of kernel arguments
-constexpr int kAdamChunk = 4096;             // elements per block: 256 threads x 4 x float4
-
-struct AdamArgs {
-  float* p[kAdamTensors];
-  const float* g[kAdamTensors];
-  float* m[kAdamTensors];
-  float* v[kAdamTensors];
-  const float* step[kAdamTensors];
-  long long n[kAdamTensors];
-  int blk0[kAdamTensors + 1];
-  int count;
-  int maximize;
-  double lr, b1, b2;                         // for the bias corrections (torch forms them in double on the host)
-  float decay, w1, b2f, w2, eps;             // 1 - lr wd, 1 - b1, b2, 1 - b2: formed in double, then rounded once, as torch's scalars are
-  // non-null: {lr, beta1, beta2, eps, weight_decay} are READ FROM THE DEVICE at launch time instead of the values above -- a step
-  // captured in a HIP graph then follows an lr schedule (the reference changes lr every epoch: base_model.py update_learning_rate)
-  // through a captured host-to-device copy of five doubles, instead of replaying the lr that was current at capture
-  const double* hyper;
-};
 
 struct AdamCoef {
   float decay, w1, b1, b2, w2, inv_bc2s, eps, step_size, gsign;
@@ -45,7 +33,12 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   p = p - c.step_size * (m / denom);
 }
 
-__global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
+// The body of both kernels.  CLIP: every gradient is first multiplied by coef = min(max_norm / (norm + 1e-6), 1), the factor of
+// torch.nn.utils.clip_grad_norm_ formed as torch forms it on the device -- fp32, `max_norm / t` being t.reciprocal() * max_norm
+// there, a NaN coefficient kept as torch.clamp keeps it -- with the product rounded to fp32 on its own (__fmul_rn: never
+// contracted into the multiply-adds of adam_one, it is torch's separate _foreach_mul_ pass over the gradients).
+template <bool CLIP>
+__device__ __forceinline__ void adamw_body(const AdamArgs& a, const float* __restrict__ d_norm, float max_norm) {
   int t = 0;
   while (t + 1 < a.count && (int)blockIdx.x >= a.blk0[t + 1]) ++t;           // uniform: scalar loads from the argument segment
   const long long n = a.n[t], base = (long long)((int)blockIdx.x - a.blk0[t]) * kAdamChunk;
@@ -74,6 +67,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
   c.inv_bc2s = (float)(1.0 / sqrt(bc2));
   c.step_size = (float)(lr / bc1);
   c.gsign = a.maximize ? -1.f : 1.f;
+  float coef = 1.f;
+  if (CLIP) {
+    const float q = __fmul_rn(1.0f / (*d_norm + 1e-6f), max_norm);
+    coef = q > 1.f ? 1.f : q;                  // (a NaN stays a NaN)
+  }
   const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
   if (vec && base + kAdamChunk <= n) {
     float4 P[4], G[4], M[4], V[4];
@@ -84,6 +82,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
+      if (CLIP) {
+        G[k].x = __fmul_rn(G[k].x, coef); G[k].y = __fmul_rn(G[k].y, coef); G[k].z = __fmul_rn(G[k].z, coef); G[k].w = __fmul_rn(G[k].w, coef);
+      }
       adam_one(P[k].x, G[k].x, M[k].x, V[k].x, c);
       adam_one(P[k].y, G[k].y, M[k].y, V[k].y, c);
       adam_one(P[k].z, G[k].z, M[k].z, V[k].z, c);
@@ -96,38 +97,104 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
   const long long end = base + kAdamChunk < n ? base + kAdamChunk : n;
   for (long long i = base + threadIdx.x; i < end; i += 256) {
     float P = p[i], M = m[i], V = v[i];
-    adam_one(P, g[i], M, V, c);
+    adam_one(P, CLIP ? __fmul_rn(g[i], coef) : g[i], M, V, c);
     p[i] = P; m[i] = M; v[i] = V;
   }
 }
 
-// table: count rows of 6 x 64-bit {p, g, m, v, step, numel} on the HOST
+__global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) { adamw_body<false>(a, nullptr, 0.f); }
+
+__global__ __launch_bounds__(256) void adamw_clip_kernel(AdamArgs a, const float* __restrict__ d_norm, float max_norm) {
+  adamw_body<true>(a, d_norm, max_norm);
+}
+
+// table: count rows of 6 x 64-bit {p, g, m, v, step, numel} on the HOST.  d_norm non-null: the clipping step
 hipError_t launch_adamw(const long long* table, int count, double lr, double b1, double b2, double eps, double wd, int maximize,
-                        hipStream_t st, const double* d_hyper) {
+                        hipStream_t st, const double* d_hyper, const float* d_norm, double max_norm) {
   for (int t0 = 0; t0 < count; t0 += kAdamTensors) {
     AdamArgs a;
-    const int c = count - t0 < kAdamTensors ? count - t0 : kAdamTensors;
-    long long blocks = 0;
-    for (int t = 0; t < c; ++t) {
-      const long long* r = table + (size_t)(t0 + t) * 6;
-      a.p[t] = (float*)r[0]; a.g[t] = (const float*)r[1]; a.m[t] = (float*)r[2]; a.v[t] = (float*)r[3];
-      a.step[t] = (const float*)r[4]; a.n[t] = r[5];
-      a.blk0[t] = (int)blocks;
-      blocks += (r[5] + kAdamChunk - 1) / kAdamChunk;
-      if (blocks > 0x3fffffff) return hipErrorInvalidValue;
-    }
-    for (int t = c; t < kAdamTensors; ++t) {
-      a.p[t] = nullptr; a.g[t] = nullptr; a.m[t] = nullptr; a.v[t] = nullptr; a.step[t] = nullptr; a.n[t] = 0;
-    }
-    for (int t = c; t <= kAdamTensors; ++t) a.blk0[t] = (int)blocks;
-    a.count = c; a.maximize = maximize; a.lr = lr; a.b1 = b1; a.b2 = b2; a.hyper = d_hyper;
+    const long long blocks = fill_adam_args(a, table, t0, count - t0 < kAdamTensors ? count - t0 : kAdamTensors);
+    if (blocks < 0) return hipErrorInvalidValue;
+    a.maximize = maximize; a.lr = lr; a.b1 = b1; a.b2 = b2; a.hyper = d_hyper;
     a.decay = (float)(1.0 - lr * wd); a.w1 = (float)(1.0 - b1); a.b2f = (float)b2; a.w2 = (float)(1.0 - b2); a.eps = (float)eps;
     if (blocks == 0) continue;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    if (d_norm)
+      hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, d_norm, (float)max_norm);
+    else
+      hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// ---- gradient norms ----------------------------------------------------------------------------------------------------------
+// One block per 4096-element chunk of a tensor, found from the prefix table as above.  A thread sums the squares of its 16
+// values in fp32 (15 additions), the wave adds its 64 lanes with the xor butterfly (6 more: 21 sequential fp32 additions on the
+// longest path), and from there on everything is double: the four waves of the block, then the blocks of a group.
+__global__ __launch_bounds__(256) void grad_sq_kernel(NormArgs a) {
+  int t = 0;
+  while (t + 1 < a.count && (int)blockIdx.x >= a.blk0[t + 1]) ++t;
+  const long long n = a.n[t], base = (long long)((int)blockIdx.x - a.blk0[t]) * kAdamChunk;
+  const float* __restrict__ g = a.g[t];
+  float s = 0.f;
+  if ((((uintptr_t)g) & 15) == 0 && base + kAdamChunk <= n) {
+    float4 G[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) G[k] = *(const float4*)(g + base + (k * 256 + threadIdx.x) * 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      s += G[k].x * G[k].x; s += G[k].y * G[k].y; s += G[k].z * G[k].z; s += G[k].w * G[k].w;
+    }
+  } else {
+    const long long end = base + kAdamChunk < n ? base + kAdamChunk : n;
+    for (long long i = base + threadIdx.x; i < end; i += 256) s += g[i] * g[i];       // <= 16 values per thread
+  }
+  s = wave_reduce_xor<SumOp>(s);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = (double)s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a.part[a.part0 + (int)blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    a.pgrp[a.part0 + (int)blockIdx.x] = a.grp[t];
+  }
+}
+
+// block = group: its partials in a fixed order (thread i takes partials i, i + 256, ..., then the halving tree), in double
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ part, const int* __restrict__ pgrp, int nblocks,
+                                                               float* __restrict__ out) {
+  __shared__ double red[256];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nblocks; i += 256)
+    if (pgrp[i] == (int)blockIdx.x) acc += part[i];
+  acc = block_tree_sum<double, 256>(acc, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = (float)sqrt(acc);
+}
+
+size_t grad_norms_scratch_bytes(const long long* table, int count, int groups) {
+  const long long blocks = norm_total_blocks(table, count, groups);
+  return blocks < 0 ? 0 : norm_scratch_bytes(blocks);
+}
+
+// table: count rows of 3 x 64-bit {grad, numel, group} on the HOST
+hipError_t launch_grad_norms(const long long* table, int count, int groups, float* out, void* scratch, size_t scratch_bytes,
+                             hipStream_t st) {
+  const long long total = norm_total_blocks(table, count, groups);
+  if (total < 0 || scratch_bytes < norm_scratch_bytes(total)) return hipErrorInvalidValue;
+  if (groups == 0) return hipSuccess;
+  long long part0 = 0;
+  NormArgs a;
+  for (int t0 = 0; t0 < count; t0 += kAdamTensors) {
+    const long long blocks = fill_norm_args(a, table, t0, count - t0 < kAdamTensors ? count - t0 : kAdamTensors, part0, total, scratch);
+    if (blocks == 0) continue;
+    hipLaunchKernelGGL(grad_sq_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    part0 += blocks;
+  }
+  fill_norm_args(a, table, 0, 0, 0, total, scratch);           // (for the two array bases)
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3((unsigned)groups), dim3(256), 0, st, a.part, a.pgrp, (int)total, out);
+  return hipGetLastError();
 }
 
 }  // namespace amx

@@ -201,6 +201,24 @@ def _grad_norms(netG, netF):
     return total(netG), total(netF)
 
 
+def _clips(optimizers):
+    """True when the step clips: some optimizer carries a ``max_norm`` (``FusedAdamW(max_norm=...)``, the reference's --clip_grad)."""
+    return optimizers is not None and any(getattr(o, "max_norm", None) is not None for o in optimizers)
+
+
+def _step_norms(netG, netF, optimizers):
+    """The two recorded norms.  A clipping step takes them from ``grad_norms`` -- one call that also hands every optimizer the norm
+    its step kernel clips by (the norm BEFORE clipping, as clip_grad_norm_ returns it, supcl_model.py:635-655); every other step
+    keeps ``_grad_norms``."""
+    if not _clips(optimizers):
+        return _grad_norms(netG, netF)
+    if len(optimizers) != 2:
+        raise ValueError("a clipping step takes optimizers=(opt_G, opt_F): the recorded norms are those of their gradients")
+    from .optim import grad_norms
+    norms = grad_norms(list(optimizers))
+    return norms[0], norms[1]
+
+
 def contrastive_step(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, nce_weights=None, num_patches=512,
                      lambda_nce=1.0, optimizers=None, sample_ids=None, grad_accum_iters=1, grad_sync=None, do_step=None,
                      iters=None, grad_buckets=None, scaler=None):
@@ -209,7 +227,9 @@ def contrastive_step(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, 
 
     netG: Unet (train mode: BatchNorm batch statistics over the two views, supcl_model.py:735-742);
     netF: PatchSampleF; criterions: one SupPatchNCELoss per nce layer; nce_weights default 1/len (supcl_model.py:388-393);
-    optimizers: (opt_G, opt_F) or None (gradients only); sample_ids: captured coordinates per layer or None (randperm);
+    optimizers: (opt_G, opt_F) or None (gradients only) -- ``FusedAdamW(max_norm=...)`` ones make it a clipping step: the norms then come
+    from ``grad_norms`` (one launch pair for both networks) and each optimizer clips by its own as it steps, after ``unscale_``
+    when a scaler is given (supcl_model.py:631-655); the recorded norms are those before clipping; sample_ids: captured coordinates per layer or None (randperm);
     grad_sync: callable run between backward and the optimizer steps (data parallel: the gradient all-reduce);
     grad_buckets: a ``data_parallel.GradientBuckets`` over (netG, netF) -- its ``sync()`` gathers the gradients into flat
     buckets and all-reduces them, its ``release()`` replaces ``optimizer.zero_grad()``.
@@ -249,7 +269,7 @@ def contrastive_step(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, 
     # the reference records the norms on stepping iterations only (supcl_model.py:631-655, after unscale_): on a non-stepping call the
     # gradients are partial sums still multiplied by the loss scale -- reported as NaN rather than as a number that means something else
     if do_step:
-        gG, gF = _grad_norms(netG, netF)
+        gG, gF = _step_norms(netG, netF, optimizers)
     else:
         gG = gF = torch.full((), float("nan"), device=total.device)
     if optimizers is not None and do_step:
@@ -276,6 +296,42 @@ def contrastive_step(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, 
     # those nodes on the stream of THIS call, outside the capture
     return OrderedDict(loss=scalars[0], per_layer=per_layer, grad_norm_G=scalars[1], grad_norm_F=scalars[2], sample_ids=ids,
                        out=out.detach() if torch.is_tensor(out) else out)
+
+
+def validation_loss(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, nce_weights=None, num_patches=512, lambda_nce=1.0,
+                    sample_ids=None):
+    """The validation loss of one pair as the reference's training loop evaluates it (train.py:325-347 driving supcl_model.py:723-757,
+    777-843): both networks in ``eval()`` -- netG's HIP inference forward with feature taps on its BatchNorm RUNNING statistics, the
+    heads' BatchNorm1d on theirs -- sampling, heads and the per-layer losses under ``no_grad``, no backward.  The layer losses are
+    weighted as in ``contrastive_step``.  ONE host read for all scalars.  The networks get their previous training mode back.
+    Volumes whose sides are not multiples of ``2 ** num_downs`` are outside the forward's envelope and raise before any launch.
+    Returns an OrderedDict(loss, per_layer, sample_ids)."""
+    if nce_weights is None:
+        nce_weights = [1.0 / len(nce_layers)] * len(nce_layers)
+    cfg = getattr(netG, "_cfg", None)
+    for t in (real_A, real_B):
+        if t is not None and cfg is not None and any(int(v) % (1 << cfg["num_downs"]) for v in t.shape[2:]):
+            raise ValueError(f"validation_loss: volume {tuple(t.shape[2:])} has a side that is no multiple of 2 ** num_downs = "
+                             f"{1 << cfg['num_downs']}: outside the forward's envelope (crop or pad the validation volumes)")
+    modes = (netG.training, netF.training)
+    netG.eval()
+    netF.eval()
+    try:
+        with torch.no_grad():
+            reals = torch.cat((real_A, real_B), dim=0) if real_B is not None else real_A
+            _, feats = netG(reals, list(nce_layers), False)
+            pooled, ids = netF(feats, num_patches, sample_ids, None, False)
+            means = []
+            for f_kq, sid, crit, feat in zip(pooled, ids, criterions, feats):
+                m = crit(f_kq, seg_A, sid, feat.size()[2:])
+                means.append(m if m.dim() == 0 else m.mean())
+            wv = torch.tensor([w * lambda_nce for w in nce_weights][: len(means)], dtype=torch.float32, device=reals.device)
+            stacked = torch.stack(means).float()
+            scalars = torch.cat(((stacked * wv).sum().view(1), stacked)).tolist()
+    finally:
+        netG.train(modes[0])
+        netF.train(modes[1])
+    return OrderedDict(loss=scalars[0], per_layer=OrderedDict((str(l), v) for l, v in zip(nce_layers, scalars[1:])), sample_ids=ids)
 
 
 class StepRecord(Mapping):
@@ -332,8 +388,9 @@ class GraphedContrastiveStep:
     AccumulateGrad nodes would run there, outside the capture.  ``contrastive_step`` returns detached records for that reason."""
 
     def __init__(self, netG, netF, criterions, nce_layers, optimizers, nce_weights=None, num_patches=512, lambda_nce=1.0,
-                 grad_sync=None, warmup=3, grad_buckets=None, tail_graph=True, lazy_scalars=False):
+                 grad_sync=None, warmup=3, grad_buckets=None, tail_graph=True, lazy_scalars=False, sample_ids=None):
         self.netG, self.netF, self.criterions, self.nce_layers = netG, netF, criterions, list(nce_layers)
+        self.sample_ids = sample_ids              # fixed coordinates per layer for every replay (tests, A/B runs); None: drawn anew
         self.lazy_scalars, self._slots, self._slot_owner, self._slot_next = bool(lazy_scalars), None, None, 0
         self.optimizers, self.nce_weights, self.num_patches, self.lambda_nce = optimizers, nce_weights, num_patches, lambda_nce
         self.grad_buckets = grad_buckets
@@ -353,11 +410,11 @@ class GraphedContrastiveStep:
 
     def _eager(self):
         return _forward_backward(self.netG, self.netF, self.criterions, self.A, self.B, self.seg, self.nce_layers,
-                                 self.nce_weights, self.num_patches, self.lambda_nce, None, 1)
+                                 self.nce_weights, self.num_patches, self.lambda_nce, self.sample_ids, 1)
 
     def _tail(self, total, layer_losses):
         """gradient norms (+ optimizers): inside the graph when possible, else eagerly after the replay."""
-        gG, gF = _grad_norms(self.netG, self.netF)
+        gG, gF = _step_norms(self.netG, self.netF, self.optimizers)
         if self.optimizers is not None:
             for opt in self.optimizers:
                 opt.step()

@@ -554,6 +554,26 @@ int amx_adamw_step(const amx_adamw_tensor* tensors, int count, double lr, double
  * schedulers (pretraining/models/base_model.py: update_learning_rate / get_scheduler), so a graph-replayed step takes them from a
  * buffer that a captured host-to-device copy refreshes (anatomix_amd/pretraining/optim.py).  Values are not range-checked here. */
 int amx_adamw_step_dev(const amx_adamw_tensor* tensors, int count, const double* d_hyper, int maximize, void* stream);
+/* amx_adamw_step_dev with gradient clipping folded into the read of the gradients (supcl_model.py:631-655: clip_grad_norm_ between
+ * unscale_ and the step): the kernel reads the group's total norm from d_total_norm (one fp32 on the device, e.g. written by
+ * amx_grad_norms), forms coef = min(max_norm / (norm + 1e-6), 1) in fp32 as torch.nn.utils.clip_grad_norm_ does, and uses
+ * g * coef -- rounded to fp32 on its own, like torch's separate multiply -- in place of g.  The gradients themselves are NOT
+ * modified.  max_norm = inf reproduces amx_adamw_step_dev bit for bit. */
+int amx_adamw_step_clip_dev(const amx_adamw_tensor* tensors, int count, const double* d_hyper, int maximize, const float* d_total_norm,
+                            double max_norm, void* stream);
+/* L2 norms of `groups` lists of contiguous fp32 device tensors (netG's gradients, netF's gradients) in one call: `tensors` is
+ * a HOST array, `group` in [0, groups) says which list a tensor belongs to; d_out = float[groups] on the device (0 for a group
+ * without tensors; an inf / NaN reaches the norm of its own group only).  Deterministic: per-block partial sums of squares in
+ * d_scratch (amx_grad_norms_scratch_bytes of the same table; never 0, 0 = invalid table) and a fixed-order reduction in a second
+ * small launch, no atomics; at most 21 sequential fp32 additions, double from there on.  Does not synchronise; capturable. */
+typedef struct {
+  const void* grad;
+  long long numel;
+  long long group;
+} amx_grad_tensor;
+size_t amx_grad_norms_scratch_bytes(const amx_grad_tensor* tensors, int count, int groups);
+int amx_grad_norms(const amx_grad_tensor* tensors, int count, int groups, float* d_out, void* d_scratch, size_t scratch_bytes,
+                   void* stream);
 
 /* ---- registration feature post-processing (what the reference does to the extracted features before the convex
  * optimisation; all fp32, planar [C][H][W][D] device tensors, batch 1 as everywhere in that pipeline) ---- */
