@@ -37,103 +37,129 @@ def _layer_streams(device, n):
 
 
 
+def _taps(netG, netF, reals, nce_layers, num_patches, sample_ids, capturing):
+    """The network forward with its feature taps: ``(out, rows, coords, sizes)`` on the sampled route -- per tap the fp32 rows
+    [views, P, C] at the drawn coordinates -- or ``(out, dense features, None, sizes)``."""
+    sampled = _sampled_route(netG, netF, reals, nce_layers, num_patches)
+    if sampled is None:
+        out, feats = netG(reals, list(nce_layers), False)
+        return out, feats, None, [tuple(f.size()[2:]) for f in feats]
+    # netF only ever reads num_patches voxels of each tapped feature map (pretraining_networks.py:472-480): the network hands
+    # back those rows -- drawn with netF's own sampler when the forward reaches each tap, i.e. in netF's order, so the generator
+    # is consumed exactly as by netG(...) followed by netF(...) -- instead of dense fp32 copies of six tensors
+    from ..model import train as _train
+    # The coordinates do not depend on the features: once the tap shapes of this (network, input shape) are known from an earlier
+    # step they are all drawn up front, in netF's layer order (the generator is consumed exactly as before), on a side stream the
+    # forward joins at its first tap -- six draw + filter launches leave the main stream's critical path.
+    # (the cache lives ON the module -- a dict keyed by id(netG) would hand a recycled id the plan of a dead network)
+    skey = (tuple(reals.shape), tuple(int(l) for l in nce_layers), int(num_patches))
+    tap_shapes = netG.__dict__.setdefault("_amx_tap_shapes", {})
+    shapes = tap_shapes.get(skey)
+    pre, seen, joined = {}, {}, []
+    draw_all = None
+    if shapes is not None and sample_ids is None and capturing:   # (eagerly the stream switches cost more than they return)
+        side = _draw_stream(reals.device)
+
+        # a replayed graph hands its nodes to the device in capture order: six draw + filter launches in front of the forward
+        # kept the first convolution waiting for ~170 us of launch latency; behind the first block they cost nothing -- so this is the
+        # forward's on_start hook.  (Measured and
+        # dropped: the head + loss chains started at their taps, beside the rest of the forward, on detached leaves of the rows with a
+        # second backward call for the network -- 7.04 against 6.86 ms per step whether forked tap by tap or once in front of the
+        # 128^3 level: the forward's own chain changes hardware queue at every fork of the replayed graph and its short deep-level
+        # kernels queue behind the heads'.)
+        def draw_all():
+            main = torch.cuda.current_stream(reals.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                for l in sorted(sampled):
+                    pre[l] = netF.draw_coords(sampled[l], shapes[l], num_patches, None, reals.device)
+                    pre[l].record_stream(main)
+
+        def sampler(i, shape):
+            if not joined:
+                torch.cuda.current_stream(reals.device).wait_stream(side)
+                joined.append(1)
+            if tuple(shape) != tuple(shapes[i]):
+                raise RuntimeError("contrastive step: the tap shapes changed under a cached sampling plan")
+            return pre[i]
+    else:
+        def sampler(i, shape):
+            seen[i] = tuple(shape)
+            return netF.draw_coords(sampled[i], shape, num_patches, sample_ids, reals.device)
+    out, rows, coords, dims = _train.forward_train_sampled(netG, reals, list(nce_layers), sampler, draw_all)
+    if shapes is None and sample_ids is None:
+        tap_shapes[skey] = dict(seen)
+    return out, rows, coords, dims
+
+
+def _head_route(netF, criterions, seg_A, rows, coords, sizes, capturing):
+    """How the per-layer chains (head -> loss) run, decided before any head does: 'batched' / 'streams' / 'serial'.
+    The chains are independent of each other and made of small kernels that each occupy a fraction of the GPU.
+    'streams': one side stream per layer so they overlap -- autograd runs a node's backward on the stream of its forward, so the adjoint
+    chains overlap too -- and join before the sum.  Only while a HIP graph is being captured: launched eagerly ('serial'), the extra
+    stream switches cost the host more than the overlap returns -- 16.9 vs 15.8 ms -- while a replayed graph gets the parallel branches
+    for free: 12.6 -> 11.8 ms.
+    'batched': inside a HIP graph the six chains run as ONE chain of batched launches (amx_mlp_heads_*, amx_supcon_loss_batch: every
+    launch serves all layers): a replayed graph pays ~8 us per dependent node whatever its size, and six chains of ~30 small nodes on
+    three streams were 1.5 ms of a 7 ms step.  Taken where both the heads and the losses can be batched on sampled rows."""
+    if not capturing:
+        return "serial"
+    if coords is None or seg_A.device != rows[0].device:
+        return "streams"
+    from . import mlp_head, supcon
+    shapes = [tuple(r.shape) for r in rows]
+    if netF.use_mlp:
+        if not netF.mlp_init:                                     # (heads that do not exist yet: created layer by layer)
+            return "streams"
+        mlps = [getattr(netF, "mlp_%d" % k) for k in range(len(rows))]
+        if mlp_head.batchable(mlps, [r.flatten(0, 1) for r in rows]) is not None:
+            return "streams"
+        shapes = [s[:2] + (mlp_head.cached_spec(m)[0][-1][0].out_features,) for s, m in zip(shapes, mlps)]
+    return "batched" if supcon.batchable(criterions, seg_A, coords, sizes, shapes) is None else "streams"
+
+
+def _heads_and_losses(route, netF, criterions, seg_A, feats, coords, sizes, nce_layers, num_patches, sample_ids):
+    """``(means, ids)``: the per-layer loss means -- one tensor [layers] on the batched route, else a list of scalars -- and the
+    sampled coordinates.  The heads run exactly once on every route."""
+    if route == "batched":
+        from . import supcon
+        pooled, ids = netF.forward_rows(feats, coords, None, batched=True)
+        stacked = supcon.batched_losses(criterions, pooled, seg_A, ids, sizes)
+        if stacked is None:
+            raise RuntimeError("contrastive step: the batched loss refused what supcon.batchable accepted")
+        return stacked, ids
+    dev = feats[0].device
+    streams = _layer_streams(dev, len(sizes)) if route == "streams" else None
+    ambient = torch.cuda.current_stream(dev) if streams is not None else None
+    if coords is not None:
+        pooled, ids = netF.forward_rows(feats, coords, streams)
+    else:
+        pooled, ids = netF(feats, num_patches, sample_ids, None, False, **({"streams": streams} if streams is not None else {}))
+    means = []
+    for k, (f_kq, sid, crit, layer, fsize) in enumerate(zip(pooled, ids, criterions, nce_layers, sizes)):
+        with (torch.cuda.stream(streams[k]) if streams is not None else contextlib.nullcontext()):
+            m = crit(f_kq, seg_A, sid, torch.Size(fsize))
+            if m.dim() != 0:                                  # (the HIP criterion returns the scalar: a mean of it would be three more launches)
+                m = m.mean()
+        means.append(m)                                       # (the caller keeps them alive until after the backward: no cross-stream reuse)
+    if streams is not None:
+        for s in dict.fromkeys(streams):                      # (each distinct stream once: layers share streams)
+            ambient.wait_stream(s)
+    return means, ids
+
+
 def _forward_backward(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, nce_weights, num_patches, lambda_nce,
                       sample_ids, grad_accum_iters, scaler=None):
     """forward with taps -> sampler + heads -> per-layer losses -> backward.  Nothing here synchronises with the host."""
     if nce_weights is None:
         nce_weights = [1.0 / len(nce_layers)] * len(nce_layers)
     reals = torch.cat((real_A, real_B), dim=0) if real_B is not None else real_A
-    sampled = _sampled_route(netG, netF, reals, nce_layers, num_patches)
-    if sampled is not None:
-        # netF only ever reads num_patches voxels of each tapped feature map (pretraining_networks.py:472-480): the network hands
-        # back those rows -- drawn with netF's own sampler when the forward reaches each tap, i.e. in netF's order, so the generator
-        # is consumed exactly as by netG(...) followed by netF(...) -- instead of dense fp32 copies of six tensors
-        from ..model import train as _train
-        # The coordinates do not depend on the features: once the tap shapes of this (network, input shape) are known from an earlier
-        # step they are all drawn up front, in netF's layer order (the generator is consumed exactly as before), on a side stream the
-        # forward joins at its first tap -- six draw + filter launches leave the main stream's critical path.
-        # (the cache lives ON the module -- a dict keyed by id(netG) would hand a recycled id the plan of a dead network)
-        skey = (tuple(reals.shape), tuple(int(l) for l in nce_layers), int(num_patches))
-        tap_shapes = netG.__dict__.setdefault("_amx_tap_shapes", {})
-        shapes = tap_shapes.get(skey)
-        pre = {}
-        capturing = reals.is_cuda and torch.cuda.is_current_stream_capturing()
-        if shapes is not None and sample_ids is None and capturing:   # (eagerly the stream switches cost more than they return)
-            side = _draw_stream(reals.device)
-
-            def draw_all():
-                main = torch.cuda.current_stream(reals.device)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    for l in sorted(sampled):
-                        pre[l] = netF.draw_coords(sampled[l], shapes[l], num_patches, None, reals.device)
-                        pre[l].record_stream(main)
-            joined = []
-
-            def sampler(i, shape):
-                if not joined:
-                    torch.cuda.current_stream(reals.device).wait_stream(side)
-                    joined.append(1)
-                if tuple(shape) != tuple(shapes[i]):
-                    raise RuntimeError("contrastive step: the tap shapes changed under a cached sampling plan")
-                return pre[i]
-            # a replayed graph hands its nodes to the device in capture order: six draw + filter launches in front of the forward
-            # kept the first convolution waiting for ~170 us of launch latency; behind the first block they cost nothing.  (Measured and
-            # dropped: the head + loss chains started at their taps, beside the rest of the forward, on detached leaves of the rows with a
-            # second backward call for the network -- 7.04 against 6.86 ms per step whether forked tap by tap or once in front of the
-            # 128^3 level: the forward's own chain changes hardware queue at every fork of the replayed graph and its short deep-level
-            # kernels queue behind the heads'.)
-            sampler.on_start = draw_all
-        else:
-            seen = {}
-
-            def sampler(i, shape):
-                seen[i] = tuple(shape)
-                return netF.draw_coords(sampled[i], shape, num_patches, sample_ids, reals.device)
-        out, rows, coords, dims = _train.forward_train_sampled(netG, reals, list(nce_layers), sampler)
-        if shapes is None and sample_ids is None:
-            tap_shapes[skey] = dict(seen)
-        feat_sizes = dims
-        feat_kq = None
-    else:
-        out, feat_kq = netG(reals, list(nce_layers), False)
-        feat_sizes = [tuple(f.size()[2:]) for f in feat_kq]
-    # The per-layer chains (sampling -> head -> loss, and their adjoints) are independent of each other and made of small
-    # kernels that each occupy a fraction of the GPU: on CUDA they run on one stream per layer so they overlap -- autograd runs
-    # a node's backward on the stream of its forward, so the adjoint chains overlap too -- and join before the sum.
-    # (only while a HIP graph is being captured: launched eagerly, the extra stream switches cost the host more than the overlap
-    # returns -- 16.9 vs 15.8 ms -- while a replayed graph gets the parallel branches for free: 12.6 -> 11.8 ms)
-    # Inside a HIP graph the six chains run as ONE chain of batched launches (amx_mlp_heads_*, amx_supcon_loss_batch: every launch
-    # serves all layers): a replayed graph pays ~8 us per dependent node whatever its size, and six chains of ~30 small nodes on
-    # three streams were 1.5 ms of a 7 ms step.
-    stacked = None
-    capturing_now = reals.is_cuda and torch.cuda.is_current_stream_capturing()
-    if sampled is not None and capturing_now:
-        from . import supcon as _supcon
-        pooled, ids = netF.forward_rows(rows, coords, None, batched=True)
-        stacked = _supcon.batched_losses(criterions, pooled, seg_A, ids, feat_sizes)
-    if stacked is not None:
-        means = None
-        layer_losses = list(stacked.detach().unbind(0))
-        streams = None
-    else:
-        streams = _layer_streams(reals.device, len(feat_sizes)) if (reals.is_cuda and capturing_now) else None
-        ambient = torch.cuda.current_stream(reals.device) if streams is not None else None
-        if sampled is not None:
-            pooled, ids = netF.forward_rows(rows, coords, streams)
-        else:
-            pooled, ids = netF(feat_kq, num_patches, sample_ids, None, False, **({"streams": streams} if streams is not None else {}))
-        means, layer_losses = [], []
-        for k, (f_kq, sid, crit, layer, fsize) in enumerate(zip(pooled, ids, criterions, nce_layers, feat_sizes)):
-            with (torch.cuda.stream(streams[k]) if streams is not None else contextlib.nullcontext()):
-                m = crit(f_kq, seg_A, sid, torch.Size(fsize))
-                if m.dim() != 0:                                  # (the HIP criterion returns the scalar: a mean of it would be three more launches)
-                    m = m.mean()
-            means.append(m)                                       # (kept alive until after the backward: no cross-stream reuse)
-            layer_losses.append(m.detach())                       # the recorded per-layer loss IS this mean (it was reduced a second time)
-        if streams is not None:
-            for s in dict.fromkeys(streams):                      # (each distinct stream once: layers share streams)
-                ambient.wait_stream(s)
+    capturing = reals.is_cuda and torch.cuda.is_current_stream_capturing()
+    out, feats, coords, sizes = _taps(netG, netF, reals, nce_layers, num_patches, sample_ids, capturing)
+    route = _head_route(netF, criterions, seg_A, feats, coords, sizes, capturing)
+    means, ids = _heads_and_losses(route, netF, criterions, seg_A, feats, coords, sizes, nce_layers, num_patches, sample_ids)
+    # the recorded per-layer loss IS this mean (it was reduced a second time)
+    layer_losses = list(means.detach().unbind(0)) if torch.is_tensor(means) else [m.detach() for m in means]
     # total = sum_k mean_k * w_k * lambda_nce (supcl_model.py:815-843) as ONE weighted sum of the stacked means: the chain of scalar
     # multiplies and adds was a dozen 2-us launches on the main stream, forward and backward
     wkey = (str(reals.device), tuple(float(w) for w in nce_weights), float(lambda_nce), float(grad_accum_iters))
@@ -141,7 +167,7 @@ def _forward_backward(netG, netF, criterions, real_A, real_B, seg_A, nce_layers,
     if wv is None:                                            # (first built in an eager warm-up step: a host copy cannot be captured)
         wv = _WEIGHTS[wkey] = torch.tensor([w * lambda_nce / grad_accum_iters for w in nce_weights][: len(layer_losses)], dtype=torch.float32,
                                            device=reals.device)
-    loss = ((stacked if stacked is not None else torch.stack(means)) * wv).sum()
+    loss = ((means if torch.is_tensor(means) else torch.stack(means)) * wv).sum()
     total = loss * grad_accum_iters if grad_accum_iters != 1 else loss
     (scaler.scale(loss) if scaler is not None else loss).backward()      # supcl_model.py:624-626
     return total, layer_losses, ids, out

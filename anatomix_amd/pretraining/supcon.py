@@ -69,29 +69,35 @@ class _SupConBatchHip(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(g[b].to(dt) for b, dt in enumerate(ctx.in_dtypes))
 
 
+def batchable(criterions, labels_seg, coords, ranges, row_shapes):
+    """None when ``batched_losses`` covers these criteria on features of ``row_shapes`` (fp32, on the segmentation's device), else the
+    reason.  Reads settings and shapes only: criteria of equal settings, features of one shape [views, P, C], one fp32 [1, 1, D, H, W]
+    device segmentation, 3-D coordinate ranges, int64 [P, 3] coordinates on that device."""
+    if not (1 <= len(criterions) <= 8 and all(type(c) is SupPatchNCELoss for c in criterions)):
+        return "1 to 8 SupPatchNCELoss criteria per batch"
+    key = lambda c: (c.temperature, bool(c.weigh_rarity), bool(c.balance_denominator), c.weighting_mode)
+    if any(key(c) != key(criterions[0]) for c in criterions):
+        return "criteria of different settings"
+    s0 = tuple(row_shapes[0])
+    if len(s0) != 3 or any(tuple(s) != s0 for s in row_shapes):
+        return "features of different shapes"
+    if not (labels_seg.is_cuda and labels_seg.dtype == torch.float32 and labels_seg.dim() == 5 and labels_seg.shape[:2] == (1, 1)):
+        return "expects one fp32 [1, 1, D, H, W] device segmentation"
+    for c, r in zip(coords, ranges):
+        if not (len(r) == 3 and torch.is_tensor(c) and c.dtype == torch.int64 and c.is_cuda and c.device == labels_seg.device and
+                tuple(c.shape) == (s0[1], 3)):
+            return "expects 3-D coordinate ranges and int64 [P, 3] device coordinates"
+    return None
+
+
 def batched_losses(criterions, features, labels_seg, coords, ranges):
     """[crit(f, labels_seg, c, r) for ...] as ONE tensor [len(criterions)] from one chain of launches, or None when the criteria or
-    their inputs are not of one kind (the caller then evaluates them one by one): CUDA fp32 features of one shape, 3-D coordinate
-    ranges, int64 [P, 3] device coordinates, one fp32 [1, 1, D, H, W] device segmentation, criteria of equal settings."""
-    nb = len(criterions)
-    if not (1 <= nb <= 8 and all(type(c) is SupPatchNCELoss for c in criterions)):
+    their inputs are not of one kind (the caller then evaluates them one by one): ``batchable``, on CUDA fp32 features."""
+    if batchable(criterions, labels_seg, coords, ranges, [f.shape for f in features]) is not None or not all(
+            f.is_cuda and f.device == labels_seg.device and f.dtype == torch.float32 for f in features):
         return None
-    c0 = criterions[0]
-    key = lambda c: (c.temperature, bool(c.weigh_rarity), bool(c.balance_denominator), c.weighting_mode)
-    if any(key(c) != key(c0) for c in criterions):
-        return None
-    f0 = features[0]
-    if not (f0.is_cuda and f0.dim() == 3 and all(f.is_cuda and f.device == f0.device and f.shape == f0.shape and f.dtype == torch.float32
-                                                   for f in features)):
-        return None
+    nb, c0, f0 = len(criterions), criterions[0], features[0]
     ntps, num_patches, nc = f0.shape
-    if not (labels_seg.is_cuda and labels_seg.dtype == torch.float32 and labels_seg.dim() == 5 and labels_seg.shape[:2] == (1, 1) and
-            labels_seg.device == f0.device):
-        return None
-    for c, r in zip(coords, ranges):
-        if not (len(r) == 3 and torch.is_tensor(c) and c.dtype == torch.int64 and c.is_cuda and c.device == f0.device and
-                tuple(c.shape) == (num_patches, 3)):
-            return None
     lib = _lib.load()
     seg = labels_seg.contiguous()
     cs = [c.contiguous() for c in coords]
