@@ -4,7 +4,8 @@ operands, the same MFMA sequence and the same rounding, so the two routes must a
 (reflected stem OUTPUT in the ring halo), for tiles in every position, batches, both 16-bit storage types, feature taps behind the
 pair, and sliding-window batches (each window is reflect-padded on its own).  A feature tap inside the pair (module 2) is what
 selects the two-launch route in the product library; the whole-forward parity against the CPU oracle is tests/test_unet_gpu.py,
-which runs the fused launch."""
+which runs the fused launch, and tests/test_forward_layers_gpu.py, which checks the pair's output and every layer behind it
+against float64 references at ragged volume sizes."""
 import pytest
 import torch
 
