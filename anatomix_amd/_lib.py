@@ -17,6 +17,8 @@ POOL = {"Max": 0, "Avg": 1}
 INTERP = {"nearest": 0, "trilinear": 1}
 WARP = {"bilinear": 0, "nearest": 1}
 SEG_LABEL = {"float32": 0, "int64": 1, "uint8": 2}
+SW_MAP = {"constant": 0, "gaussian": 1}
+SW_OUT = {"features": 0, "logits": 1, "labels": 2}
 # "strict" = bf16x2: split hi + lo operands, fp32-grade results with fp32's exponent range (include/anatomix_amd.h)
 # "f16x2mx" (alias "strict_mx") = f16 hi + lo pairs whose correction products run on the block-scaled fp8 MFMA (2 instead of 3 MFMA-
 # equivalents per product); implemented for the InstanceNorm configurations, where it is the default (Unet.precision)
@@ -83,6 +85,13 @@ SYMBOLS = {
     "amx_unet_forward_windows_pipelined": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_int), _I, _I, _I, _P, _P, _P, C.c_size_t, _I, _P]),
     "amx_sw_normalize": (_I, [_P, _P, _I, C.c_longlong, _P]),
     "amx_sw_count": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "amx_sw_plan": (_I, [_I, _I, _I, _I, _I, _I, C.c_double, C.POINTER(C.c_int), _I]),
+    "amx_sw_importance_map": (_I, [_P, _I, _I, _I, _I, C.c_double, _P]),
+    "amx_sw_count_all": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_double, _P, _P]),
+    "amx_sw_finish": (_I, [_I, _P, _P, _I, C.c_longlong, _P, _P, _I, _P, _P]),
+    "amx_sliding_window_workspace_bytes": (C.c_size_t, [_P, _I, _I, _I, _I]),
+    "amx_sliding_window": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_double, _I, C.c_double, _I, _I, _P, _P, _I, _P, _P, _P, _P,
+                                C.c_size_t, _P]),
     "amx_conv3d_packed_bytes": (C.c_size_t, [_I, _I]),
     "amx_conv3d_k3_reflect": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, _I, _P, _P, _P, _P]),
     "amx_conv3d_dgrad_interior_supported": (_I, [_I, _I, _I, _I, _I, _I]),

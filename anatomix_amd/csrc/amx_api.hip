@@ -64,6 +64,40 @@ int amx_sw_count(float* d_cnt, int vd, int vh, int vw, int oz, int oy, int ox, i
   return AMX_OK;
 }
 
+int amx_sw_plan(int vd, int vh, int vw, int rd, int rh, int rw, double overlap, int* offsets_zyx, int capacity) {
+  if (capacity < 0 || (capacity > 0 && !offsets_zyx)) return fail(AMX_ERR_INVALID, "bad offsets buffer");
+  amx::SwPlan plan;
+  if (int rc = amx::sw_make_plan(vd, vh, vw, rd, rh, rw, overlap, &plan)) return rc;
+  const int n = plan.windows();
+  for (int i = 0; i < n && i < capacity; ++i) plan.corner(i, offsets_zyx + 3 * i);
+  return n;
+}
+
+int amx_sw_importance_map(float* d_wmap, int rd, int rh, int rw, int mode, double sigma_scale, void* stream) {
+  if (!d_wmap) return fail(AMX_ERR_INVALID, "null argument");
+  if (rd < 1 || rh < 1 || rw < 1) return fail(AMX_ERR_SHAPE, "non-positive roi");
+  if (mode != AMX_SW_MAP_CONSTANT && mode != AMX_SW_MAP_GAUSSIAN) return fail(AMX_ERR_INVALID, "mode: constant (0) or gaussian (1) (got %d)", mode);
+  if (mode == AMX_SW_MAP_GAUSSIAN && !(sigma_scale > 0.0)) return fail(AMX_ERR_INVALID, "sigma_scale must be positive (got %g)", sigma_scale);
+  AMX_HIP(amx::launch_sw_importance_map(d_wmap, rd, rh, rw, mode, sigma_scale, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_sw_count_all(float* d_cnt, int vd, int vh, int vw, int rd, int rh, int rw, double overlap, const float* d_wmap,
+                     void* stream) {
+  if (!d_cnt || !d_wmap) return fail(AMX_ERR_INVALID, "null argument");
+  amx::SwPlan plan;
+  if (int rc = amx::sw_make_plan(vd, vh, vw, rd, rh, rw, overlap, &plan)) return rc;
+  AMX_HIP(amx::launch_sw_count_all(d_cnt, plan, d_wmap, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_sw_finish(int kind, float* d_acc, const float* d_cnt, int feat, long long voxels, const float* d_w, const float* d_b,
+                  int classes, void* d_out, void* stream) {
+  if (int rc = amx::sw_finish_check(kind, d_acc, d_cnt, feat, voxels, d_w, classes, d_out)) return rc;
+  AMX_HIP(amx::launch_sw_finish(kind, d_acc, d_cnt, feat, voxels, d_w, d_b, classes, d_out, (hipStream_t)stream));
+  return AMX_OK;
+}
+
 size_t amx_conv3d_packed_bytes(int cin, int cout) {
   const int cin_pad = (cin + 15) / 16 * 16;
   size_t bytes = (size_t)cout * cin_pad * 28 * 2;

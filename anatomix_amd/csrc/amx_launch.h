@@ -114,6 +114,30 @@ hipError_t launch_upsample2_trilinear_backward(const void* gout, void* gin, int 
 hipError_t launch_sw_normalize(float* acc, const float* cnt, int channels, long long voxels, hipStream_t st);
 hipError_t launch_sw_count(float* cnt, int vd, int vh, int vw, int oz, int oy, int ox, int rd, int rh,
                            int rw, const float* wmap, hipStream_t st);
+// The window schedule of one axis (registration/sliding_window.py window_starts): start i = min(i * interval, size - roi) for
+// i in [0, count).  The one statement of that arithmetic: amx_sw_plan lists the corners from it, the count-map kernel walks it.
+struct SwAxis {
+  int size, roi, interval, count;
+  __host__ __device__ int start(int i) const { return i * interval < size - roi ? i * interval : size - roi; }
+};
+struct SwPlan {
+  SwAxis ax[3];      // z, y, x
+  int windows() const { return ax[0].count * ax[1].count * ax[2].count; }
+  void corner(int i, int* zyx) const {      // window i in MONAI's order: first axis outermost
+    zyx[2] = ax[2].start(i % ax[2].count);
+    zyx[1] = ax[1].start(i / ax[2].count % ax[1].count);
+    zyx[0] = ax[0].start(i / (ax[2].count * ax[1].count));
+  }
+};
+constexpr int kSwMaxWindows = 1 << 20;
+// AMX_OK and the plan, or AMX_ERR_SHAPE (a volume smaller than the roi, a non-positive size, more than kSwMaxWindows windows)
+int sw_make_plan(int vd, int vh, int vw, int rd, int rh, int rw, double overlap, SwPlan* plan);
+constexpr int kSwMaxF = 64, kSwMaxC = 32;      // the head envelope of sw_finish: amx_seg_argmax's (amx_segloss.hip)
+hipError_t launch_sw_count_all(float* cnt, const SwPlan& plan, const float* wmap, hipStream_t st);
+hipError_t launch_sw_importance_map(float* wmap, int rd, int rh, int rw, int mode, double sigma_scale, hipStream_t st);
+// kind: AMX_SW_FEATURES (acc /= cnt in place, launch_sw_normalize's arithmetic), AMX_SW_LOGITS, AMX_SW_LABELS
+hipError_t launch_sw_finish(int kind, float* acc, const float* cnt, int feat, long long voxels, const float* w, const float* b, int classes,
+                            void* out, hipStream_t st);
 
 // amx_train.hip
 size_t train_scratch_bytes(int C);
@@ -244,6 +268,19 @@ int fail(int code, const char* fmt, ...);
 // the scratch check of the C ABI entries: AMX_OK, or AMX_ERR_WORKSPACE when the caller's `got` bytes are fewer than `need`
 inline int need_scratch(size_t need, size_t got) {
   return got < need ? fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, got) : AMX_OK;
+}
+
+// the argument check of amx_sw_finish, shared with amx_sliding_window (amx_unet.hip), which makes it before its first launch
+inline int sw_finish_check(int kind, const float* acc, const float* cnt, int feat, long long voxels, const float* w, int classes,
+                           const void* out) {
+  if (kind != AMX_SW_FEATURES && kind != AMX_SW_LOGITS && kind != AMX_SW_LABELS)
+    return fail(AMX_ERR_INVALID, "output kind: features (0), logits (1) or labels (2) (got %d)", kind);
+  if (!acc || !cnt || feat < 1 || voxels < 1 || voxels >= (1LL << 40)) return fail(AMX_ERR_INVALID, "bad argument");
+  if (kind == AMX_SW_FEATURES) return AMX_OK;
+  if (classes < 2 || classes > kSwMaxC) return fail(AMX_ERR_INVALID, "2 <= classes <= %d (got %d)", kSwMaxC, classes);
+  if (feat > kSwMaxF) return fail(AMX_ERR_INVALID, "1 <= feat <= %d head input channels (got %d)", kSwMaxF, feat);
+  if (!w || !out) return fail(AMX_ERR_INVALID, "logits and labels need the head's weight and an output buffer");
+  return AMX_OK;
 }
 
 // the checks of the row-streaming C ABI units (amx_segaug.hip, amx_preaug.hip, amx_synth.hip).  A unit names its rows: `count` is

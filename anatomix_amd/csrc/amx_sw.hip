@@ -1,7 +1,10 @@
 // anatomix_amd -- bandwidth kernels around the sliding-window caller
 // (monai.inferers.sliding_window_inference as used by
 //  /root/reference/anatomix/registration/convex_adam_utils.py:202-219).
+#include <math.h>
+
 #include "amx_launch.h"
+#include "amx_stream.h"
 
 namespace amx {
 
@@ -54,6 +57,206 @@ hipError_t launch_sw_count(float* cnt, int vd, int vh, int vw, int oz, int oy, i
   const long long total = (long long)rd * rh * rw;
   const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
   hipLaunchKernelGGL(sw_count_kernel, dim3(blocks), dim3(256), 0, st, cnt, vh, vw, oz, oy, ox, rd, rh, rw, wmap);
+  return hipGetLastError();
+}
+
+// ---- the window schedule ------------------------------------------------------------------------------------------------------
+// registration/sliding_window.py window_starts, axis by axis: scan interval int(roi * (1 - overlap)) floored at 1 (roi itself when
+// the axis equals the roi), count = 1 + the first d with d * interval + roi >= size
+int sw_make_plan(int vd, int vh, int vw, int rd, int rh, int rw, double overlap, SwPlan* plan) {
+  const int size[3] = {vd, vh, vw}, roi[3] = {rd, rh, rw};
+  long long windows = 1;
+  if (!(overlap >= 0.0 && overlap < 1.0)) return fail(AMX_ERR_INVALID, "0 <= overlap < 1 (got %g)", overlap);
+  for (int k = 0; k < 3; ++k) {
+    if (roi[k] < 1 || size[k] < 1) return fail(AMX_ERR_SHAPE, "non-positive size (volume %d x %d x %d, roi %d x %d x %d)", vd, vh, vw, rd, rh, rw);
+    if (size[k] < roi[k])
+      return fail(AMX_ERR_SHAPE, "volume %d x %d x %d is smaller than the roi %d x %d x %d: pad it first", vd, vh, vw, rd, rh, rw);
+    SwAxis& a = plan->ax[k];
+    a.size = size[k], a.roi = roi[k];
+    a.interval = size[k] == roi[k] ? roi[k] : (int)(roi[k] * (1.0 - overlap));
+    if (a.interval < 1) a.interval = 1;
+    a.count = (size[k] - roi[k] + a.interval - 1) / a.interval + 1;
+    windows *= a.count;
+    if (windows > kSwMaxWindows) return fail(AMX_ERR_SHAPE, "more than %d windows", kSwMaxWindows);
+  }
+  return AMX_OK;
+}
+
+// ---- count map of every window --------------------------------------------------------------------------------------------------
+// windows of axis `a` that cover coordinate c: indices [lo, hi)
+__device__ __forceinline__ void sw_covering(const SwAxis& a, int c, int& lo, int& hi) {
+  lo = c >= a.roi ? (c - a.roi + a.interval) / a.interval : 0;       // the first i with i * interval + roi > c
+  if (lo > a.count - 1) lo = a.count - 1;                            // (the last window covers the end of the axis)
+  hi = lo;
+  while (hi < a.count && a.start(hi) <= c) ++hi;
+}
+
+// cnt[z][y][x] = sum of wmap[z - oz][y - oy][x - ox] over the windows that cover the voxel, in window order (z outermost), plain fp32
+// additions from zero: what the sequence of sw_count_kernel launches leaves on a zeroed map, bit for bit.  Writes every voxel.
+__global__ __launch_bounds__(256) void sw_count_all_kernel(float* __restrict__ cnt, SwPlan p, const float* __restrict__ wmap) {
+  const int vh = p.ax[1].size, vw = p.ax[2].size, rh = p.ax[1].roi, rw = p.ax[2].roi;
+  const long long total = (long long)p.ax[0].size * vh * vw;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int x = i % vw;
+    const long long r = i / vw;
+    const int y = r % vh;
+    const int z = r / vh;
+    int z0, z1, y0, y1, x0, x1;
+    sw_covering(p.ax[0], z, z0, z1);
+    sw_covering(p.ax[1], y, y0, y1);
+    sw_covering(p.ax[2], x, x0, x1);
+    float s = 0.f;
+    for (int iz = z0; iz < z1; ++iz) {
+      const int wz = z - p.ax[0].start(iz);
+      if (wz >= p.ax[0].roi) continue;
+      for (int iy = y0; iy < y1; ++iy) {
+        const int wy = y - p.ax[1].start(iy);
+        if (wy >= rh) continue;
+        const float* row = wmap + ((long long)wz * rh + wy) * rw;
+        // eight windows of the row at a time: their loads are issued together, the additions stay in window order (a window that
+        // does not cover the voxel contributes +0, which leaves the sum as it is)
+        for (int ix = x0; ix < x1; ix += 8) {
+          float v[8];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const int wx = ix + k < x1 ? x - p.ax[2].start(ix + k) : rw;
+            v[k] = wx < rw ? row[wx] : 0.f;
+          }
+#pragma unroll
+          for (int k = 0; k < 8; ++k) s += v[k];
+        }
+      }
+    }
+    cnt[i] = s;
+  }
+}
+
+// ---- importance map -------------------------------------------------------------------------------------------------------------
+// registration/sliding_window.py importance_map: ones, or the separable Gaussian exp(-x^2 / (2 sigma^2)), x = i - (r - 1) / 2, the
+// three lines multiplied first axis first, clamped below at max(min(map), 1e-3).  The minimum is the corner voxel.
+__device__ __forceinline__ float sw_gauss(int i, int r, float den) {
+  const float x = (float)i - (float)(r - 1) * 0.5f;
+  return expf(x * x / den);
+}
+__global__ __launch_bounds__(256) void sw_importance_map_kernel(float* __restrict__ wmap, int rd, int rh, int rw, int gaussian, float den_z,
+                                                                float den_y, float den_x) {
+  const long long total = (long long)rd * rh * rw;
+  const float floor_ = gaussian ? fmaxf((sw_gauss(0, rd, den_z) * sw_gauss(0, rh, den_y)) * sw_gauss(0, rw, den_x), 1e-3f) : 1.f;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int x = i % rw;
+    const long long r = i / rw;
+    const int y = r % rh;
+    const int z = r / rh;
+    wmap[i] = gaussian ? fmaxf((sw_gauss(z, rd, den_z) * sw_gauss(y, rh, den_y)) * sw_gauss(x, rw, den_x), floor_) : 1.f;
+  }
+}
+
+// ---- finish: accumulators -> logits or labels ------------------------------------------------------------------------------------
+// out = b + W (acc / cnt) per voxel, the head [C][F] transposed and padded to CP classes in LDS; a thread owns four voxels, reads
+// their F accumulator values once and keeps the CP logits in registers.  LABELS: arg-max, the first maximum winning (amx_seg_argmax's
+// rule), uint8; the logits are never written.  acc and cnt are only read.
+using SwTile = StreamTile<>;
+struct SwFinishArgs {
+  const float* acc;     // [F][V]
+  const float* cnt;     // [V]
+  const float* w;       // [C][F]
+  const float* b;       // [C] or null
+  int F, C;
+  long long V;
+  int ntiles;
+};
+
+template <int CP, bool LABELS, bool VEC>
+__global__ __launch_bounds__(SwTile::kThreads) void sw_finish_head_kernel(SwFinishArgs a, void* __restrict__ out) {
+  __shared__ float wT[kSwMaxF * CP], bias[CP];
+  for (int i = threadIdx.x; i < a.F * CP; i += SwTile::kThreads) {
+    const int f = i / CP, c = i % CP;
+    wT[i] = c < a.C ? a.w[c * a.F + f] : 0.f;
+  }
+  for (int c = threadIdx.x; c < CP; c += SwTile::kThreads) bias[c] = (c < a.C && a.b) ? a.b[c] : 0.f;
+  __syncthreads();
+  for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+    float r[SwTile::kVpt], z[CP][SwTile::kVpt];
+    SwTile::load4<VEC>(a.cnt, t, a.V, r);
+#pragma unroll
+    for (int j = 0; j < SwTile::kVpt; ++j) r[j] = 1.f / r[j];         // (voxels past V: never stored)
+#pragma unroll
+    for (int c = 0; c < CP; ++c)
+#pragma unroll
+      for (int j = 0; j < SwTile::kVpt; ++j) z[c][j] = bias[c];
+    const float* row = a.acc;
+    for (int f = 0; f < a.F; ++f, row += a.V) {
+      float x[SwTile::kVpt];
+      SwTile::load4<VEC>(row, t, a.V, x);
+#pragma unroll
+      for (int j = 0; j < SwTile::kVpt; ++j) x[j] *= r[j];
+#pragma unroll
+      for (int c = 0; c < CP; ++c) {
+        const float wc = wT[f * CP + c];
+#pragma unroll
+        for (int j = 0; j < SwTile::kVpt; ++j) z[c][j] += wc * x[j];
+      }
+    }
+    if (LABELS) {
+      unsigned char best[SwTile::kVpt];
+#pragma unroll
+      for (int j = 0; j < SwTile::kVpt; ++j) {
+        float m = z[0][j];
+        int bi = 0;
+#pragma unroll
+        for (int c = 1; c < CP; ++c)
+          if (c < a.C && z[c][j] > m) m = z[c][j], bi = c;
+        best[j] = (unsigned char)bi;
+      }
+      SwTile::store4<VEC>((unsigned char*)out, t, a.V, best);
+    } else {
+#pragma unroll
+      for (int c = 0; c < CP; ++c)
+        if (c < a.C) SwTile::store4<VEC>((float*)out + (long long)c * a.V, t, a.V, z[c]);
+    }
+  }
+}
+
+hipError_t launch_sw_count_all(float* cnt, const SwPlan& plan, const float* wmap, hipStream_t st) {
+  const long long total = (long long)plan.ax[0].size * plan.ax[1].size * plan.ax[2].size;
+  const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+  hipLaunchKernelGGL(sw_count_all_kernel, dim3(blocks), dim3(256), 0, st, cnt, plan, wmap);
+  return hipGetLastError();
+}
+
+hipError_t launch_sw_importance_map(float* wmap, int rd, int rh, int rw, int mode, double sigma_scale, hipStream_t st) {
+  const long long total = (long long)rd * rh * rw;
+  const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+  const double sz = rd * sigma_scale, sy = rh * sigma_scale, sx = rw * sigma_scale;
+  hipLaunchKernelGGL(sw_importance_map_kernel, dim3(blocks), dim3(256), 0, st, wmap, rd, rh, rw, mode == AMX_SW_MAP_GAUSSIAN ? 1 : 0,
+                     (float)(-2.0 * sz * sz), (float)(-2.0 * sy * sy), (float)(-2.0 * sx * sx));
+  return hipGetLastError();
+}
+
+template <int CP>
+static void sw_finish_dispatch(bool labels, bool vec, int grid, hipStream_t st, const SwFinishArgs& a, void* out) {
+  if (labels) {
+    if (vec) sw_finish_head_kernel<CP, true, true><<<grid, SwTile::kThreads, 0, st>>>(a, out);
+    else sw_finish_head_kernel<CP, true, false><<<grid, SwTile::kThreads, 0, st>>>(a, out);
+  } else {
+    if (vec) sw_finish_head_kernel<CP, false, true><<<grid, SwTile::kThreads, 0, st>>>(a, out);
+    else sw_finish_head_kernel<CP, false, false><<<grid, SwTile::kThreads, 0, st>>>(a, out);
+  }
+}
+
+hipError_t launch_sw_finish(int kind, float* acc, const float* cnt, int feat, long long voxels, const float* w, const float* b, int classes,
+                            void* out, hipStream_t st) {
+  if (kind == AMX_SW_FEATURES) return launch_sw_normalize(acc, cnt, feat, voxels, st);
+  const bool labels = kind == AMX_SW_LABELS;
+  SwFinishArgs a;
+  a.acc = acc, a.cnt = cnt, a.w = w, a.b = b, a.F = feat, a.C = classes, a.V = voxels, a.ntiles = (int)SwTile::tiles(voxels);
+  // the 16-byte path: every plane of acc (and of the logits) starts on a 16-byte boundary and holds whole quads
+  const bool vec = voxels % 4 == 0 && aligned16(acc) && aligned16(cnt) && (labels ? aligned4(out) : aligned16(out));
+  const int grid = a.ntiles < kStreamMaxBlocks ? a.ntiles : kStreamMaxBlocks;
+  if (classes <= 4) sw_finish_dispatch<4>(labels, vec, grid, st, a, out);
+  else if (classes <= 8) sw_finish_dispatch<8>(labels, vec, grid, st, a, out);
+  else if (classes <= 16) sw_finish_dispatch<16>(labels, vec, grid, st, a, out);
+  else sw_finish_dispatch<32>(labels, vec, grid, st, a, out);
   return hipGetLastError();
 }
 

@@ -418,3 +418,107 @@ def _run_fused(inputs, roi, starts, wmap, model, cnt):
             # the accumulation volume leaves the library here: one synchronising range check per volume (f16 storage only)
             model.check_numerics(synchronize=True)
     return acc
+
+
+def _volume_unsupported_reason(model, inputs, roi, head, out):
+    """Why ``sliding_window_volume`` cannot take this call (None: it can).  The envelope is amx_sliding_window's: the fused window
+    step's (``_fused_ok``), and for logits / labels a head made of one 1x1x1 convolution within amx_sw_finish's sizes."""
+    from ..model.network import Unet
+    if not isinstance(model, Unet):
+        return f"model must be a bare anatomix_amd.Unet (got {type(model).__name__}); pass the head of a Sequential as head="
+    if not inputs.is_cuda:
+        return f"there is no host path (got a {inputs.device} tensor)"
+    if inputs.dim() != 5 or inputs.shape[1] != 1 or model._cfg["input_nc"] != 1:
+        return f"inputs [B, 1, D, H, W] and input_nc == 1 (got {tuple(inputs.shape)}, input_nc {model._cfg['input_nc']})"
+    cout = model._cfg["output_nc"]
+    if cout % 16 or cout > 32:
+        return f"output_nc must be 16 or 32 for the in-place accumulation (got output_nc={cout})"
+    if roi[2] < 32:
+        return f"roi width >= 32 (got {roi[2]})"
+    reason = model.hip_unsupported_reason(inputs[:, :, :1, :1, :1].expand(-1, -1, 2, 2, 2))
+    if reason is not None:
+        return reason
+    if out != "features":
+        from ..segmentation.losses import MAX_CLASSES, MAX_HEAD_CHANNELS, _single_conv_head
+        conv = _single_conv_head(head) if head is not None else None
+        if conv is None:
+            return f"out={out!r} needs head= made of exactly one 1x1x1 convolution"
+        if conv.in_channels != cout or not 2 <= conv.out_channels <= MAX_CLASSES or cout > MAX_HEAD_CHANNELS:
+            return (f"head of {conv.in_channels} -> {conv.out_channels} channels on {cout} features: 2 <= classes <= {MAX_CLASSES}, "
+                    f"input channels == output_nc <= {MAX_HEAD_CHANNELS}")
+        if conv.weight.device != inputs.device:
+            return "the head and the inputs must be on one device"
+    return None
+
+
+def sliding_window_volume(inputs: torch.Tensor, roi_size, model, overlap: float = 0.25, mode: str = "constant",
+                          sigma_scale: float = 0.125, head=None, out: str = "features"):
+    """``sliding_window_inference(inputs, roi_size, FUSED_WINDOW_BATCH, model, overlap, mode, sigma_scale)`` as ONE C call per batch
+    element (``amx_sliding_window``: schedule, window weights, count map, pipelined window batches and the finishing pass all behind
+    the C ABI).  ``model`` is a bare ``anatomix_amd.Unet``; ``out``:
+      * ``"features"`` -> fp32 [B, output_nc, D, H, W], the window average of the Unet's output;
+      * ``"logits"``   -> fp32 [B, classes, D, H, W], ``head`` (one 1x1x1 convolution) applied to that average;
+      * ``"labels"``   -> uint8 [B, 1, D, H, W], the arg-max of those logits (lowest index on ties), which are never written.
+    Volumes smaller than the ROI are zero padded and cropped back like ``sliding_window_inference``.  Configurations outside the
+    call's envelope raise ``_lib.AmxEnvelopeError`` with the reason -- there is no fallback here; ``sliding_window_inference`` takes
+    any predictor.  The call cannot be captured into a graph yet (the C entry refuses while the stream is capturing)."""
+    if out not in _lib.SW_OUT:
+        raise ValueError(f"out must be one of {sorted(_lib.SW_OUT)} (got {out!r})")
+    if mode not in _lib.SW_MAP:
+        raise ValueError(f"unsupported mode {mode!r}")
+    if isinstance(roi_size, int):
+        roi_size = (roi_size,) * 3
+    roi = tuple(int(r) for r in roi_size)
+    reason = _volume_unsupported_reason(model, inputs, roi, head, out)
+    if reason is not None:
+        raise _lib.AmxEnvelopeError(_lib.AMX_ERR_SHAPE, "sliding_window_volume: " + reason + ".  sliding_window_inference takes any predictor.")
+    B = inputs.shape[0]
+    orig = tuple(inputs.shape[2:])
+    pads, need_pad = [], False
+    for k in range(2, -1, -1):
+        diff = max(roi[k] - orig[k], 0)
+        half = diff // 2
+        pads += [half, diff - half]
+        need_pad |= diff > 0
+    if need_pad:
+        inputs = F.pad(inputs, pads, mode="constant", value=0.0)
+    size = tuple(inputs.shape[2:])
+    dev = inputs.device
+    x = _lib.f32c(inputs.detach())
+    cout = model._cfg["output_nc"]
+    w = b = res = None
+    classes = 0
+    if out != "features":
+        from ..segmentation.losses import _single_conv_head
+        conv = _single_conv_head(head)
+        classes = conv.out_channels
+        w = _lib.f32c(conv.weight.detach()).reshape(classes, cout)
+        b = _lib.f32c(conv.bias.detach()) if conv.bias is not None else None
+        res = torch.empty((B, classes) + size, dtype=torch.float32, device=dev) if out == "logits" else \
+            torch.empty((B, 1) + size, dtype=torch.uint8, device=dev)
+    # features: every batch element keeps its accumulator (it is the result); logits / labels: one accumulator is reused
+    acc = torch.empty((B if out == "features" else 1, cout) + size, dtype=torch.float32, device=dev)
+    cnt = torch.empty(size, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        model._ensure_handle(dev)
+        if model._weights_stale():
+            model._upload_weights(lib, dev)
+        need = lib.amx_sliding_window_workspace_bytes(model._handle, FUSED_WINDOW_BATCH, *roi)
+        if getattr(model, "_swv_ws", None) is None or model._swv_ws.numel() < need or model._swv_ws.device != dev:
+            model._swv_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        st = _lib.stream(dev)
+        for i in range(B):
+            _lib.check_envelope(lib.amx_sliding_window(
+                model._handle, _lib.ptr(x[i]), *size, *roi, float(overlap), _lib.SW_MAP[mode], float(sigma_scale), FUSED_WINDOW_BATCH,
+                _lib.SW_OUT[out], _lib.ptr(w), _lib.ptr(b), classes, _lib.ptr(acc[i if out == "features" else 0]), _lib.ptr(cnt),
+                _lib.ptr(res[i]) if res is not None else None, _lib.ptr(model._swv_ws), need, st))
+        if model.precision in ("f16", "fp16", "float16", "f16x2", "f16x2mx", "strict_mx") and not torch.cuda.is_current_stream_capturing():
+            # the accumulation volume leaves the library here: one synchronising range check per call (f16 storage only)
+            model.check_numerics(synchronize=True)
+    if out == "features":
+        res = acc
+    if need_pad:
+        zs, ys, xs = pads[4], pads[2], pads[0]
+        res = res[:, :, zs:zs + orig[0], ys:ys + orig[1], xs:xs + orig[2]]
+    return res

@@ -201,6 +201,74 @@ int amx_sw_normalize(float* d_acc, const float* d_cnt, int channels, long long v
 int amx_sw_count(float* d_cnt, int vd, int vh, int vw, int oz, int oy, int ox, int rd, int rh, int rw,
                  const float* d_wmap, void* stream);
 
+/* ---- whole-volume sliding-window inference behind one call ------------------------------------------------------------
+ * monai.inferers.sliding_window_inference as the reference calls it: for features at
+ * anatomix/registration/convex_adam_utils.py:202-219, for the logits of a finetuned head at
+ * anatomix/segmentation/train_segmentation.py:194-199.  MONAI's schedule is restated in SURVEY.md Appendix D. */
+typedef enum amx_sw_map { AMX_SW_MAP_CONSTANT = 0, AMX_SW_MAP_GAUSSIAN = 1 } amx_sw_map;
+typedef enum amx_sw_out {
+  AMX_SW_FEATURES = 0, /* d_acc /= d_cnt in place (amx_sw_normalize's arithmetic, bit for bit); d_out is not used */
+  AMX_SW_LOGITS = 1,   /* d_out fp32 [classes][V] = b + W (d_acc / d_cnt); d_acc is left as it is */
+  AMX_SW_LABELS = 2    /* d_out uint8 [V] = arg-max of those logits, the lowest index on ties; they are never written */
+} amx_sw_out;
+
+/* The window corners of sliding_window_inference(..., roi_size, overlap) (convex_adam_utils.py:202-219) in MONAI's order,
+ * first axis outermost.  Host only.  Per axis: scan interval int(roi * (1 - overlap)), floored at 1, roi itself when the
+ * axis equals the roi; windows 0 .. d with d the first one that reaches the end, the last start being size - roi.
+ * Returns the number of windows (>= 1) and writes the first min(count, capacity) corners to offsets_zyx [capacity][3]
+ * (may be NULL with capacity 0).  A volume smaller than the roi on any axis is AMX_ERR_SHAPE: padding is the caller's.
+ * overlap outside [0, 1) is AMX_ERR_INVALID. */
+int amx_sw_plan(int vd, int vh, int vw, int rd, int rh, int rw, double overlap, int* offsets_zyx, int capacity);
+
+/* The window weights of sliding_window_inference(mode=..., sigma_scale=...) (convex_adam_utils.py:202-219): d_wmap fp32
+ * [rd][rh][rw] = 1 (AMX_SW_MAP_CONSTANT) or the separable Gaussian exp(-x^2 / (2 sigma^2)), sigma = roi * sigma_scale per
+ * axis, clamped below at max(min(map), 1e-3).  May differ from a torch-built map in the last bits of expf: measured at 32^3 / 0.125
+ * and 64^3 / 0.25, identical to the map torch builds on the device and within 4.3e-7 relative of the one it builds on the host. */
+int amx_sw_importance_map(float* d_wmap, int rd, int rh, int rw, int mode, double sigma_scale, void* stream);
+
+/* The count map of ALL windows of amx_sw_plan(vd, .., overlap) in one launch (the `count_map` of sliding_window_inference,
+ * convex_adam_utils.py:202-219): d_cnt[v] = sum of d_wmap over the windows that cover v, added in window order from zero.
+ * Every voxel of d_cnt is written; the result is bit-identical to amx_sw_count per window on a zeroed map. */
+int amx_sw_count_all(float* d_cnt, int vd, int vh, int vw, int rd, int rh, int rw, double overlap, const float* d_wmap,
+                     void* stream);
+
+/* The last pass of sliding_window_inference over (d_acc fp32 [feat][voxels], d_cnt fp32 [voxels]), kind an amx_sw_out:
+ * the `output_image / count_map` of convex_adam_utils.py:202-219, followed for LOGITS / LABELS by the 1x1x1 head and the
+ * arg-max of train_segmentation.py:194-199 / :84-86 (a per-voxel affine head commutes with the window average).
+ * d_w fp32 [classes][feat], d_b fp32 [classes] or NULL; both unused for FEATURES.  Envelope (amx_seg_argmax's):
+ * 2 <= classes <= 32, 1 <= feat <= 64, AMX_ERR_INVALID outside it before anything is launched.  Any voxels count and
+ * alignment. */
+int amx_sw_finish(int kind, float* d_acc, const float* d_cnt, int feat, long long voxels, const float* d_w, const float* d_b,
+                  int classes, void* d_out, void* stream);
+
+/* Bytes of workspace amx_sliding_window needs: two window batches of n_batch roi-sized windows in flight (the sw_batch_size
+ * windows MONAI hands to the predictor at a time, convex_adam_utils.py:202-219, twice). */
+size_t amx_sliding_window_workspace_bytes(const amx_unet_t* h, int n_batch, int rd, int rh, int rw);
+
+/* sliding_window_inference(volume, roi, n_batch, model, overlap, mode, sigma_scale) in one call
+ * (convex_adam_utils.py:202-219; with a head, the validation inference of train_segmentation.py:194-199).
+ * d_vol fp32 [vd][vh][vw] single channel, at least the roi on every axis (padding is the caller's).  The call zeroes
+ * d_acc fp32 [output_nc][vd*vh*vw], builds the window weights (cached on the handle per roi, mode and sigma_scale; the
+ * first call with a new key allocates them), writes d_cnt fp32
+ * [vd*vh*vw] with amx_sw_count_all, runs the windows of amx_sw_plan in batches of n_batch (1 .. 64) through
+ * amx_unet_forward_windows and ends with amx_sw_finish(out_kind, ...): features in d_acc, or logits / labels in d_out
+ * (d_w, d_b, classes: the head, NULL / 0 for features).
+ * With 4 or more batches two of them are kept in flight: the even ones on `stream`,
+ * the odd ones on a non-blocking stream of the handle, created at the first such call, which forks from and joins
+ * `stream` (amx_unet_forward_windows_pipelined's ordering: only the accumulating launches of consecutive batches are
+ * ordered, the sums are those of the single-stream sequence bit for bit).  For the caller the whole call is ordered on
+ * `stream`.  No host synchronisation.  While `stream` is capturing the call is refused (AMX_ERR_INVALID): its pieces
+ * (amx_sw_count_all, amx_unet_forward_windows, amx_sw_finish) replay correctly from a graph, the whole call did not yet.
+ * Envelope: input_nc == 1, output_nc a multiple of 16 and <= 32, rw >= 32, the roi a shape the forward takes:
+ * AMX_ERR_SHAPE otherwise; too small a workspace is AMX_ERR_WORKSPACE; the head as for amx_sw_finish.  Every check
+ * comes before the first launch: a refused call leaves all buffers untouched.
+ * f16 / f16x2 storage: the range check stays amx_unet_numerics_status's -- call it with synchronize != 0 after this call
+ * before trusting d_acc / d_out. */
+int amx_sliding_window(amx_unet_t* h, const float* d_vol, int vd, int vh, int vw, int rd, int rh, int rw, double overlap,
+                       int mode, double sigma_scale, int n_batch, int out_kind, const float* d_w, const float* d_b,
+                       int classes, float* d_acc, float* d_cnt, void* d_out, void* d_workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* Single-layer entry (per-kernel parity / roofline tests): y = act(conv3x3x3_reflect(cat(x0,
  * up2_nearest(x1))) * scale + shift).  x0: 16-bit NDHWC [n][d][h][w][c0]; x1: 16-bit NDHWC
  * [n][d/2][h/2][w/2][c1] or NULL (c1 = 0); d_weight fp32 [cout][c0+c1][27]; d_scale/d_shift fp32
