@@ -215,6 +215,7 @@ SYMBOLS = {
     "amx_labels_sphere_mask": (_I, [C.POINTER(_P), _P, _I, _I, _P, _P, _P]),
     "amx_labels_apply_mask": (_I, [_P, _P, _P, _I, C.c_longlong, _P, _P, _P, C.c_size_t, _P]),
     "amx_labels_envelope": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "amx_labels_merge_masks": (_I, [_P, _I, C.c_longlong, C.c_longlong, C.POINTER(_I), _P, _P, _P, _I, _P]),
     "amx_label_overlap": (_I, [_P, _I, _P, _I, C.c_longlong, _I, _P, _P, _P]),
     "amx_jacobian_det_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "amx_jacobian_det": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),

@@ -337,6 +337,120 @@ __global__ __launch_bounds__(256) void lab_envelope_kernel(int d, int h, int w, 
   }
 }
 
+// ---- step 0: merge of a segmentation folder ----------------------------------------------------------------------------------
+// One pass over a batch of n mask rows: the sum of every row (its emptiness test) and the two merged rows (ribs, vertebrae).  A
+// lane owns 16 consecutive voxels of every row per step; the merged voxels sit in registers as 16-bit halves (even bytes in one
+// word, odd bytes in the other), which hold 256 rows of 255 plus an accumulated 255 without a carry.
+struct LabMerge {
+  unsigned char group[AMX_LABELS_MAX_MERGE];      // kernel argument: read through scalar loads
+};
+typedef __attribute__((ext_vector_type(4))) unsigned lab_u32x4;
+constexpr int kMergeInFlight = 4;
+
+__device__ __forceinline__ unsigned lab_byte_sum(unsigned w) { return __builtin_amdgcn_sad_u8(w, 0u, 0u); }
+
+// adds v, which only the lanes of a wave's file share hold, into the block's slot: the wave's sum by lane 0
+__device__ __forceinline__ void lab_wave_add(unsigned long long* slot, unsigned v) {
+  v = wave_reduce_xor<SumOp>(v);
+  if ((threadIdx.x & 63) == 0) atomicAdd(slot, (unsigned long long)v);
+}
+
+// 16-bit halves of a merged quad -> bytes clamped to 255; `over` is set when a half passed 255
+__device__ __forceinline__ unsigned lab_pack_clamped(unsigned even, unsigned odd, bool& over) {
+  over |= ((even | odd) & 0xff00ff00u) != 0;
+  const unsigned e0 = min(even & 0xffffu, 255u), e1 = min(even >> 16, 255u), o0 = min(odd & 0xffffu, 255u), o1 = min(odd >> 16, 255u);
+  return e0 | (o0 << 8) | (e1 << 16) | (o1 << 24);
+}
+
+__global__ __launch_bounds__(256) void lab_merge_kernel(LabMerge a, const unsigned char* __restrict__ masks, int n, long long voxels,
+                                                        long long stride, unsigned char* __restrict__ merged,
+                                                        unsigned long long* __restrict__ sums, int* __restrict__ overflow, int accumulate) {
+  __shared__ unsigned long long part[AMX_LABELS_MAX_MERGE + 2];
+  for (int i = threadIdx.x; i < n + 2; i += 256) part[i] = 0;
+  __syncthreads();
+  const long long nvec = voxels >> 4;
+  unsigned long long msum[2] = {0, 0};
+  bool over[2] = {false, false};
+  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v - threadIdx.x < nvec; v += (long long)gridDim.x * 256) {
+    // (the loop bound is uniform over the workgroup, so that every wave takes part in the shuffles below; lanes past nvec hold zeros)
+    const bool live = v < nvec;
+    unsigned even[2][4], odd[2][4];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      lab_u32x4 q = {0u, 0u, 0u, 0u};
+      if (accumulate && live) q = *(const lab_u32x4*)(merged + g * stride + v * 16);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) even[g][j] = q[j] & 0x00ff00ffu, odd[g][j] = (q[j] >> 8) & 0x00ff00ffu;
+    }
+    for (int f0 = 0; f0 < n; f0 += kMergeInFlight) {
+      lab_u32x4 qs[kMergeInFlight];      // the loads of kMergeInFlight files are issued before the first is used
+#pragma unroll
+      for (int k = 0; k < kMergeInFlight; ++k) {
+        qs[k] = lab_u32x4{0u, 0u, 0u, 0u};
+        if (live && f0 + k < n) qs[k] = *(const lab_u32x4*)(masks + (f0 + k) * stride + v * 16);
+      }
+#pragma unroll
+      for (int k = 0; k < kMergeInFlight; ++k) {
+        const lab_u32x4 q = qs[k];
+        const int f = f0 + k;
+        const unsigned s = lab_byte_sum(q[0]) + lab_byte_sum(q[1]) + lab_byte_sum(q[2]) + lab_byte_sum(q[3]);
+        if (__ballot(s != 0) == 0) continue;      // wave-uniform: most of a mask is background (and files past n read as zeros)
+        lab_wave_add(part + f, s);
+        const int grp = a.group[f];
+        if (grp == 0) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const unsigned e = q[j] & 0x00ff00ffu, o = (q[j] >> 8) & 0x00ff00ffu;
+          if (grp == 1) even[0][j] += e, odd[0][j] += o;
+          else even[1][j] += e, odd[1][j] += o;
+        }
+      }
+    }
+    if (live) {
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        lab_u32x4 q;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q[j] = lab_pack_clamped(even[g][j], odd[g][j], over[g]), msum[g] += lab_byte_sum(q[j]);
+        *(lab_u32x4*)(merged + g * stride + v * 16) = q;
+      }
+    }
+  }
+  // the voxels % 16 tail: one voxel per lane of the first wave of workgroup 0
+  const int tail = (int)(voxels & 15);
+  if (blockIdx.x == 0 && threadIdx.x < 64 && tail) {
+    const bool live = (int)threadIdx.x < tail;
+    const long long o = (nvec << 4) + threadIdx.x;
+    unsigned acc[2] = {0, 0};
+    if (accumulate && live) acc[0] = merged[o], acc[1] = merged[stride + o];
+    for (int f = 0; f < n; ++f) {
+      const unsigned s = live ? masks[f * stride + o] : 0u;
+      if (__ballot(s != 0) == 0) continue;
+      lab_wave_add(part + f, s);
+      const int grp = a.group[f];
+      if (grp) acc[grp - 1] += s;
+    }
+    if (live) {
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        over[g] |= acc[g] > 255u;
+        acc[g] = min(acc[g], 255u);
+        msum[g] += acc[g];
+        merged[g * stride + o] = (unsigned char)acc[g];
+      }
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const unsigned long long m = wave_reduce_xor<SumOp>(msum[g]);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(part + n + g, m);
+    if (over[g]) overflow[g] = 1;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n + 2; i += 256)
+    if (part[i]) atomicAdd(sums + i, part[i]);
+}
+
 }  // namespace amx
 
 namespace {
@@ -507,6 +621,34 @@ int amx_labels_envelope(unsigned char* d_labels, const unsigned char* d_mask, co
   int tiles_y;
   if (int rc = lab_stencil_grid(batch, d, h, w, amx::kEnvX, amx::kEnvY, amx::kEnvZ, grid, tiles_y)) return rc;
   amx::lab_envelope_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(d, h, w, tiles_y, d_labels, d_mask, d_max, d_table);
+  AMX_HIP(hipGetLastError());
+  return AMX_OK;
+}
+
+int amx_labels_merge_masks(const unsigned char* d_masks, int n, long long voxels, long long stride, const int* h_group,
+                           unsigned char* d_merged, unsigned long long* d_sums, int* d_overflow, int accumulate, void* stream) {
+  if (n < 1 || n > AMX_LABELS_MAX_MERGE) return fail(AMX_ERR_SHAPE, "1 <= n <= %d mask files per call (got %d)", AMX_LABELS_MAX_MERGE, n);
+  if (!amx::row_voxels_ok(voxels)) return fail(AMX_ERR_SHAPE, "1 <= voxels < 2^31 per mask (got %lld)", voxels);
+  if (stride < voxels || stride % 16) return fail(AMX_ERR_SHAPE, "stride must be a multiple of 16 and at least voxels (got %lld for %lld)", stride, voxels);
+  if (!d_masks || !h_group || !d_merged || !d_sums || !d_overflow) return fail(AMX_ERR_INVALID, "null masks, groups, merged rows, sums or overflow flags");
+  if (!amx::aligned16(d_masks) || !amx::aligned16(d_merged)) return fail(AMX_ERR_INVALID, "d_masks and d_merged must be 16-byte aligned");
+  if (((uintptr_t)d_sums & 7) || !amx::aligned4(d_overflow)) return fail(AMX_ERR_INVALID, "d_sums must be 8-byte and d_overflow 4-byte aligned");
+  if (amx::overlap(d_masks, (size_t)n * stride, d_merged, (size_t)2 * stride)) return fail(AMX_ERR_INVALID, "d_masks and d_merged must not overlap");
+  amx::LabMerge a;
+  for (int i = 0; i < n; ++i) {
+    if (h_group[i] < 0 || h_group[i] > 2) return fail(AMX_ERR_INVALID, "mask %d: group 0 (neither), 1 (rib) or 2 (vertebra) (got %d)", i, h_group[i]);
+    a.group[i] = (unsigned char)h_group[i];
+  }
+  for (int i = n; i < AMX_LABELS_MAX_MERGE; ++i) a.group[i] = 0;
+  const hipStream_t st = (hipStream_t)stream;
+  int dev = 0;
+  AMX_HIP(hipGetDevice(&dev));
+  const int cus = amx::device_cus(dev);
+  const long long want = ((voxels >> 4) + 255) / 256, cap = (long long)(cus > 0 ? cus : 256) * 8;
+  const int blocks = (int)(want < 1 ? 1 : (want < cap ? want : cap));
+  AMX_HIP(hipMemsetAsync(d_sums, 0, (size_t)(n + 2) * sizeof(unsigned long long), st));
+  if (!accumulate) AMX_HIP(hipMemsetAsync(d_overflow, 0, 2 * sizeof(int), st));
+  amx::lab_merge_kernel<<<blocks, 256, 0, st>>>(a, d_masks, n, voxels, stride, d_merged, d_sums, d_overflow, accumulate);
   AMX_HIP(hipGetLastError());
   return AMX_OK;
 }

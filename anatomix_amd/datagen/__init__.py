@@ -1,7 +1,9 @@
-"""Synthetic data generation, steps 1 and 2 of the reference's ``synthetic-data-generation/`` on the device: label ensembles
+"""Synthetic data generation, the four steps of the reference's ``synthetic-data-generation/``: label ensembles
 (``labels``, csrc/amx_labels.hip; ``python -m anatomix_amd.datagen.step1_generate_labels``) and two paired views per label map
-(``views``, csrc/amx_synth.hip and csrc/amx_segaug.hip; ``python -m anatomix_amd.datagen.step2_generate_views``).  Step 3 (the HDF5
-writer) is not here.  MONAI and skimage are not dependencies; their documented algorithms are restated (DESIGN.md sections 4.17 and
+(``views``, csrc/amx_synth.hip and csrc/amx_segaug.hip; ``python -m anatomix_amd.datagen.step2_generate_views``) on the device, before
+them the preprocessing of the TotalSegmentator tree with its merge on the device (``premerge``;
+``python -m anatomix_amd.datagen.step0_preprocess_totalsegmentator``) and after them the HDF5 containers the pretraining reads
+(``python -m anatomix_amd.datagen.step3_generate_h5_w_segs``, host only).  MONAI and skimage are not dependencies; their documented algorithms are restated (DESIGN.md sections 4.17 and
 4.18) and parity with an installed MONAI or skimage is not pinned.
 
 Both steps have a ``draw_params`` and a ``concat_params``; the names exported here are step 2's, as before.  Step 1's are

@@ -1129,6 +1129,21 @@ int amx_labels_apply_mask(unsigned char* d_labels, const unsigned char* d_mask, 
 int amx_labels_envelope(unsigned char* d_labels, const unsigned char* d_mask, const int* d_max, int batch, int d, int h, int w,
                         const amx_labels_ensemble* h_table, const amx_labels_ensemble* d_table, void* stream);
 
+/* ---- synthetic data generation, step 0: the merge of a TotalSegmentator segmentation folder
+ * (synthetic-data-generation/step0_preprocess_totalsegmentator.py:57-76: `segdata.sum() == 0`, `rib_labels += segdata`,
+ * `vert_labels += segdata`) for a batch of its mask files in one pass and one launch (csrc/amx_labels.hip).
+ * d_masks: n rows of uint8, `stride` bytes apart (stride % 16 == 0, stride >= voxels, 16-byte aligned base), the first `voxels`
+ * bytes of a row being the file.  h_group: HOST array of n entries, 0 = neither, 1 = rib, 2 = vertebra.  d_merged: [2][stride]
+ * uint8, row 0 the ribs, row 1 the vertebrae; with accumulate == 0 it is written (all zero for a group without files), otherwise
+ * the batch is added to what it holds.  d_sums: n + 2 uint64, written: [i] the sum of the voxels of file i (0 = the file is blank),
+ * [n] and [n + 1] the sums of the two merged rows as they stand after the call.  d_overflow: 2 int32, zeroed when accumulate == 0,
+ * then set to 1 for a group one of whose merged voxels passed 255 (the stored voxel is 255 then); with accumulate != 0 a flag stays
+ * set.  Integer arithmetic only: the result does not depend on the order of anything.  1 <= n <= AMX_LABELS_MAX_MERGE,
+ * 1 <= voxels < 2^31. */
+enum { AMX_LABELS_MAX_MERGE = 256 };
+int amx_labels_merge_masks(const unsigned char* d_masks, int n, long long voxels, long long stride, const int* h_group,
+                           unsigned char* d_merged, unsigned long long* d_sums, int* d_overflow, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
