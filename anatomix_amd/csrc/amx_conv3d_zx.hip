@@ -514,11 +514,13 @@ hipError_t launch_pack_weights_zx(const float* w, const float* scale, void* wx, 
 
 // One full-resolution row-planar f16x2mx segment of 32 channels -> 32 channels, whole tiles; 16-bit row-planar output, or the network's
 // fp32 planar output (no importance map, no activation of its own)
-bool conv_zx_eligible(const ConvParams& p) {
-  const bool out_ok = p.out32 ? (!p.wmap && p.act == ACT_NONE && !p.stats) : (p.out && p.ox == 32);
+// shape-only form, for a caller that plans a layer before its 16-bit output has memory: p.out is not asked, its strides are
+bool conv_zx_shape_eligible(const ConvParams& p) {
+  const bool out_ok = p.out32 ? (!p.wmap && p.act == ACT_NONE && !p.stats) : p.ox == 32;
   return !p.src0_f32c1 && p.C0 == 32 && p.C1 == 0 && p.Cout == 32 && out_ok && p.mxs &&
          ((p.W % 32 == 0 && p.H % 2 == 0) || (p.W % 16 == 0 && p.H % 4 == 0)) && p.D % 2 == 0 && p.D >= 4 && p.s0x == 32;
 }
+bool conv_zx_eligible(const ConvParams& p) { return (p.out32 || p.out) && conv_zx_shape_eligible(p); }
 int conv_zx_stats_slots(int H, int W) { return H * W / 32; }       // one per (tile, half tile), whichever tile shape runs
 
 template <typename C>

@@ -65,6 +65,7 @@ hipError_t launch_conv_zmarch(const ConvParams& p, int precision, hipStream_t st
 
 // amx_conv3d_zx.hip
 bool conv_zx_eligible(const ConvParams& p);
+bool conv_zx_shape_eligible(const ConvParams& p);     // the same, less "the 16-bit output has memory"
 int conv_zx_stats_slots(int H, int W);
 size_t conv_zx_packed_bytes();
 hipError_t launch_pack_weights_zx(const float* w, const float* scale, void* wx, const int* mxs, int CoutReal, hipStream_t st);

@@ -293,6 +293,50 @@ struct Tensor {                                   // C: stored channels per voxe
   int ab_act = AMX_ACT_NONE;                      //   ... with this activation
 };
 
+// What a conv reads: the fp32 network input (in->slot < 0), cat(skip, upsample(in)), upsample(in) alone, or in
+struct Sources {
+  const Tensor* in;
+  bool up, full_up;                               // read through a x2 upsample; ... which is materialised (trilinear) at the conv's resolution
+  const Tensor* skip;                             // the skip connection in front of the upsampled channels (null: none)
+};
+
+// What one conv -> norm -> act group runs.  Forward::plan_conv decides all of it before the group takes a slot, marks a profiler event
+// or launches; the driver (Forward::conv_group) and the parameter builders only read it.
+enum class ConvKernel {
+  Dispatch,      // amx::launch_conv, which picks z-march / split-K / generic by its own conv_route
+  StemPair,      // the stem and the 16 -> 16 layer behind it as one launch (amx_conv3d_zmarch.hip, STEM)
+  Stem,          // the fp32 single-channel input (amx_conv3d_stem.hip)
+  Upcat16,       // 16 + up(32) -> 16 in one merged-tap launch (amx_conv3d_upcat.hip)
+  Zx             // f16x2mx 32 -> 32, normalise-on-load z-march (amx_conv3d_zx.hip)
+};
+enum class ConvOut { Slot, Planar, SlotThenExport };   // a 16-bit slot; fp32 planar into y; a slot, then the export pass into y
+enum class NormApply { Here, NextConv, Upsample, WithPool };   // who runs the apply pass of an instance norm (Forward::plan_norm)
+struct ConvTerms {                                // what one launch reads and what its epilogue applies
+  const void* wpk;
+  const float* bias;
+  int act;
+};
+struct ConvPlan {
+  const ConvLayer* L;            // the group's conv
+  const ConvLayer* Nx;           // StemPair: the 16 -> 16 layer, whose group this launch covers too (else null)
+  Sources src;
+  int lv, dd, dh, dw;            // level and extents the conv runs at
+  size_t nxt;                    // module index of the next group
+  ConvKernel kernel;
+  bool merge;                    // merged taps: `first` covers the skip channels into a partial slot, amx::launch_conv_upmerge follows with `second`
+  ConvTerms first, second;       // StemPair: the stem's and Nx's, applied by the one launch
+  ConvOut out;
+  bool inorm, act_on;            // an instance norm follows the conv; the group's activation runs (encode_only may end before it)
+  bool raw_bn;                   // unfolded weights, pre-norm tap, then the folded BatchNorm as a pass of its own
+  bool pool;                     // the epilogue also writes the max-pooled tensor
+  bool stats;                    // the epilogue writes the InstanceNorm partial sums into the statistics scratch
+  bool ks;                       // the split-K scratch is offered
+  bool per_window;               // sliding windows: one launch per window, each at its own place in the volume
+  float* tap_pre;                // exported from the stored RAW conv output, before the norm
+  float* tap_post[3];            // exported from the finished tensor: the conv (no norm), norm and activation ids (in-place modules alias)
+  float* tap_y;                  // the output conv: copied from y
+};
+
 // The launch schedule of one forward: the state that the modules hand to each other, and one method per step.
 struct Forward : ForwardArgs {
   amx_unet* const h;
@@ -335,7 +379,7 @@ struct Forward : ForwardArgs {
       }
     return fail(AMX_ERR_INVALID, "internal: arena exhausted at level %d", level);
   }
-  char* mem(const Tensor& t) const { return slots[t.level][t.slot]; }
+  char* mem(const Tensor& t) const { return t.slot < 0 ? nullptr : slots[t.level][t.slot]; }   // (no slot: the planar output conv's `out`)
   void release(const Tensor& t) { used[t.level][t.slot] = false; }
   // a tensor that was pushed as a skip connection stays alive until its decoder block has read it
   void release_unless_skip(const Tensor& t) {
@@ -426,75 +470,154 @@ struct Forward : ForwardArgs {
     return AMX_OK;
   }
 
+  Sources sources() const { return Sources{&cur, have_cur_up, cur_is_full_up, have_skip ? &pend_skip : nullptr}; }
+
+  // ---- the plan of a group: what does not depend on the kernel.  Norm, activation and tap terms, the weights they call for, where the
+  // output goes, and the refusals that follow from those
+  int plan_terms(ConvPlan& pl) const {
+    const ConvLayer& L = *pl.L;
+    pl.inorm = L.norm_idx >= 0 && (c.norm == AMX_NORM_INSTANCE || c.norm == AMX_NORM_INSTANCE_AFFINE);
+    if (pl.inorm && L.is_final) return fail(AMX_ERR_INVALID, "internal: instance norm after the output conv");
+    // encode_only whose last layer is this group's conv / norm id: the modules after it never run in the reference,
+    // so the (in-place) activation must not touch the tapped tensor
+    const int idx_act = L.has_act ? L.module_idx + 1 + (L.norm_idx >= 0 ? 1 : 0) : -1;
+    pl.act_on = L.has_act && !(stop >= L.module_idx && stop < idx_act);
+    // ---- feature taps inside this conv -> norm -> act group.  The reference's activations are in-place modules
+    // (network.py:188-196), so what the caller holds for a tap at the NORM id (or at the conv id when there is no
+    // norm) is the activated tensor; only a conv followed by a norm yields a distinct, pre-norm tensor.
+    float* const tap_conv = tap_of(L.module_idx);
+    if (L.is_final) {
+      pl.tap_y = tap_conv;   // contiguous [n][Cout][d][h][w] output (taps are only offered by the plain forward)
+    } else {
+      pl.tap_pre = L.norm_idx >= 0 ? tap_conv : nullptr;
+      pl.tap_post[0] = L.norm_idx < 0 ? tap_conv : nullptr;
+      pl.tap_post[1] = L.norm_idx >= 0 ? tap_of(L.norm_idx) : nullptr;
+      pl.tap_post[2] = idx_act >= 0 ? tap_of(idx_act) : nullptr;
+    }
+    // pre-norm tap of a FOLDED eval-BatchNorm layer: run the conv with the unfolded weights, export, apply the norm
+    pl.raw_bn = pl.tap_pre && !pl.inorm;
+    if (pl.raw_bn && !L.wpk_raw) return fail(AMX_ERR_INVALID, "internal: model.%d has no unfolded packing", L.module_idx);
+    if (pl.raw_bn && L.raw_has_bias)
+      return fail(AMX_ERR_INVALID, "pre-norm tap of model.%d: conv bias under BatchNorm is not supported", L.module_idx);
+    // InstanceNorm needs the whole (n, c) plane of RAW conv outputs first: the conv stores un-activated values and
+    // amx::launch_instnorm normalises + activates them in place afterwards.  raw_bn: s * conv + L.shift is the whole folded norm
+    // (amx::launch_affine_act)
+    pl.first = pl.raw_bn ? ConvTerms{L.wpk_raw, nullptr, AMX_ACT_NONE}
+                         : ConvTerms{L.wpk, L.shift, (pl.act_on && !pl.inorm) ? c.activation : AMX_ACT_NONE};
+    if (L.is_final && c.final_act != AMX_ACT_NONE && stop != L.module_idx) pl.first.act = c.final_act;
+    // the fp32 planar epilogues need W >= 32 and <= 32 output channels; outside that the output conv stores 16-bit
+    // channels-last like any other layer and one export pass produces the fp32 NCDHW tensor
+    const bool planar_ok = pl.dw >= 32 && L.cout_p <= 32 && L.cout_p == L.cout;
+    pl.out = !L.is_final ? ConvOut::Slot : planar_ok ? ConvOut::Planar : ConvOut::SlotThenExport;
+    if (pl.out == ConvOut::SlotThenExport && (wmap || x_offs))
+      return fail(AMX_ERR_SHAPE, "sliding-window accumulation needs roi width >= 32 and output_nc <= 32");
+    if (pl.src.in->slot < 0 && (L.is_final || L.cout_p > 32))
+      return fail(AMX_ERR_INVALID, "stem kernel supports ngf in {16, 32} and a following layer (ngf=%d)", L.cout);
+    return AMX_OK;
+  }
+
   // ---- stem + the 16 -> 16 layer behind it as ONE launch (amx_conv3d_zmarch.hip, STEM): the stem's output never reaches HBM.
   // Plain forward only: no taps, folded (or no) norm on both layers, nothing else reads the stem's tensor.
-  // L: the stem, conv_i: the layer behind it.  Returns 1 when the pair was launched (the module index then stands at its last
-  // module), AMX_OK when the two layers run on their own, or an error.
-  int try_stem_pair(const ConvLayer& L, int dd, int dh, int dw) {
-    const bool candidate = cur.slot < 0 && !split && (!x_offs || n <= 16) && L.cout_p == 16 && L.cout == 16 && !L.is_final && conv_i < h->convs.size() &&
-                           (!L.has_act || c.activation == AMX_ACT_RELU || c.activation == AMX_ACT_NONE) &&
-                           !(L.norm_idx >= 0 && (c.norm == AMX_NORM_INSTANCE || c.norm == AMX_NORM_INSTANCE_AFFINE));
-    if (!candidate) return AMX_OK;
-    const ConvLayer& Nx = h->convs[conv_i];
-    const size_t g0 = next_group(i, L);       // module index of the next group
+  // pl: the stem's plan so far (conv `ci` at module `at`).  True: pl is now the pair's, and covers the group of conv ci + 1 too.
+  bool plan_stem_pair(size_t ci, size_t at, ConvPlan& pl) const {
+    const ConvLayer& L = *pl.L;
+    const bool candidate = pl.src.in->slot < 0 && !split && (!x_offs || n <= 16) && L.cout_p == 16 && L.cout == 16 && !L.is_final && ci + 1 < h->convs.size() &&
+                           (!L.has_act || c.activation == AMX_ACT_RELU || c.activation == AMX_ACT_NONE) && !pl.inorm;
+    if (!candidate) return false;
+    const ConvLayer& Nx = h->convs[ci + 1];
+    const size_t g0 = pl.nxt;                 // module index of the next group
     const size_t g1 = next_group(g0, Nx);     // ... and of the one after it
     bool ok = g0 < h->kinds.size() && h->kinds[g0] == K_CONV && Nx.level == 0 && !Nx.is_final && !Nx.after_up && Nx.cin_pad == 16 &&
               Nx.cout_p == 16 && Nx.cout == 16 && Nx.q == 1 && Nx.loaded;
     for (int e : h->encoder_idx)
-      if (e >= (int)i && e < (int)g0) ok = false;                                     // the stem's tensor would be a skip connection
+      if (e >= (int)at && e < (int)g0) ok = false;                                    // the stem's tensor would be a skip connection
     if (taps) {   // feature taps: only behind the pair (its activated output is module g1 - 1); the stem's tensor is never stored
       for (int t = 0; t < taps->n; ++t)
         if (taps->modules[t] + 1 < (int)g1) ok = false;
       if (taps->stop >= 0 && taps->stop + 1 < (int)g1) ok = false;
     }
-    amx::ConvParams p;
-    memset(&p, 0, sizeof p);
-    p.N = n; p.D = dd; p.H = dh; p.W = dw; p.Cout = Nx.cout_p; p.C0 = 16; p.C1 = 0;
-    p.wpk = (const char*)Nx.wpk; p.bias = Nx.shift; p.oflow = h->d_flag;
-    p.act = Nx.has_act ? c.activation : AMX_ACT_NONE; p.slope = c.act_slope;
-    amx::set_out(p, nullptr, Nx.cout_p, dd, dh, dw, c.precision);          // (the slot is taken once the pair is known to run)
-    if (!(ok && amx::conv_zmarch_stem_eligible(p, c.precision))) return AMX_OK;
-    Tensor out;
-    out.level = 0; out.C = Nx.cout_p; out.Cr = Nx.cout;
-    if (int e = slot(0, &out.slot)) return e;
-    p.out = mem(out);
-    const double vox = (double)n * dd * dh * dw;
-    if (int e = record(L.module_idx, L.cin, Nx.cout, dd, dh, dw, 2.0 * 27.0 * (L.cin * L.cout + Nx.cin * Nx.cout) * vox,
-                       4.0 * vox + 2.0 * Nx.cout * vox + 2.0 * 27.0 * (L.cin * L.cout + Nx.cin * Nx.cout)))   // fp32 input once, 16-bit output once
-      return e;
-    amx::ConvLaunchInfo info;
-    AMX_HIP(amx::launch_conv_zmarch_stem(p, x, xs_n, xs_z, xs_y, x_offs, L.wpk, L.shift, L.has_act ? c.activation : AMX_ACT_NONE,
-                                         c.act_slope, c.precision, st, prof ? &info : nullptr));
-    if (prof) name_last("%s", info.name);
-    ++conv_i;
-    cur = out;
-    i = g1 - 1;
-    if (float* t = tap_of((int)i)) AMX_HIP(export_slot(out, t));
-    push_skip_after(i);
-    if (stop == (int)i) done = true;
-    return 1;
+    if (!ok) return false;      // (from here on no tap and no stop lies inside the stem's group: its terms are the plain ones)
+    ConvPlan pair = pl;
+    pair.kernel = ConvKernel::StemPair;
+    pair.Nx = &Nx;
+    pair.nxt = g1;
+    pair.second = ConvTerms{Nx.wpk, Nx.shift, Nx.has_act ? c.activation : AMX_ACT_NONE};
+    pair.tap_post[0] = tap_of((int)g1 - 1);
+    if (!amx::conv_zmarch_stem_eligible(pair_params(pair, nullptr), c.precision)) return false;
+    pl = pair;
+    return true;
   }
 
-  // the input segments of a conv at dd x dh x dw: the fp32 network input, cat(skip, upsample(cur)), or cur
-  int bind_sources(amx::ConvParams& p, const ConvLayer& L, int dd, int dh, int dw) {
-    if (cur.slot < 0) {  // stem: fp32 single-channel input
+  // ---- the plan of the group of conv `ci`, whose conv is module `at` and reads `src`.  Takes no slot, marks no event, launches
+  // nothing; every refusal of a group is made here.  Each eligibility question is asked of ONE probe: the layer's launch parameters
+  // as its builder binds them, with the memory that is not taken yet left null and nothing fused.
+  int plan_conv(size_t ci, size_t at, const Sources& src, ConvPlan& pl) const {
+    const ConvLayer& L = h->convs[ci];
+    pl = ConvPlan{};
+    pl.L = &L; pl.src = src; pl.lv = L.level; pl.dd = d >> L.level; pl.dh = hh >> L.level; pl.dw = w >> L.level;
+    pl.nxt = next_group(at, L);
+    if (int e = plan_terms(pl)) return e;
+    if (plan_stem_pair(ci, at, pl)) return AMX_OK;
+    amx::ConvParams p;
+    if (int e = layer_params(pl, nullptr, nullptr, p)) return e;
+    const bool stem = src.in->slot < 0, concat = src.up && src.skip, direct = !stem && !src.up;
+    if (stem)
+      pl.kernel = ConvKernel::Stem;
+    else if (!split && !pl.raw_bn && L.wpk_up && concat && amx::conv_upcat16_eligible(p))
+      pl.kernel = ConvKernel::Upcat16;
+    // f16x2mx 32 -> 32 at whole tiles: the normalise-on-load z-march kernel.  It is the ONLY consumer of a tensor whose norm was
+    // left pending (plan_norm), and takes already-normalised inputs too.
+    else if (mx && L.wx && direct && !x_offs && (pl.inorm || pl.out == ConvOut::Planar) && amx::conv_zx_shape_eligible(p))
+      pl.kernel = ConvKernel::Zx;
+    else
+      pl.kernel = ConvKernel::Dispatch;
+    if (src.in->ab && pl.kernel != ConvKernel::Zx)
+      return fail(AMX_ERR_INVALID, "internal: model.%d got an input whose norm is pending but cannot run the fused kernel", L.module_idx);
+    if (pl.kernel == ConvKernel::Upcat16) pl.first.wpk = L.wpk_up;
+    // wider concat layers: the ordinary convolution over the skip channels first (raw partial sums into a free slot of this
+    // level), then the merged-tap convolution over the upsampled channels, which adds them, the bias and the activation
+    pl.merge = pl.kernel == ConvKernel::Dispatch && !pl.raw_bn && L.wpk_merge && concat && !src.full_up && !L.is_final && L.cout_p == L.cout &&
+               p.C0 == L.cout && amx::conv_upmerge_eligible(p.C0, p.C1, L.cout, pl.dd, pl.dh, pl.dw, p.up_shift, split);
+    if (pl.merge) {
+      pl.second = ConvTerms{L.wpk_merge, pl.first.bias, pl.first.act};
+      pl.first = ConvTerms{L.wpk_skip, nullptr, AMX_ACT_NONE};
+    }
+    // nn.MaxPool3d(2) right after this block (network.py:368): fuse it into the z-marching epilogue
+    pl.pool = !L.is_final && !pl.inorm && !pl.raw_bn && pl.nxt < h->kinds.size() && h->kinds[pl.nxt] == K_POOL && c.pooling == AMX_POOL_MAX && direct &&
+              (split ? amx::conv_zmarch_can_pool_split(p) : amx::conv_zmarch_can_pool(p)) && L.q == L.cout_p / 16;
+    // InstanceNorm layers on the generic kernel (and on Zx): the conv epilogue writes the partial sums of the statistics pass itself
+    // (the stem of the split precisions likewise: amx_conv3d_stem.hip)
+    const int stem_slots = (stem && pl.inorm && !x_offs) ? amx::conv_stem_stats_slots(p, stem_precision(c.precision)) : 0;
+    pl.stats = pl.inorm && !pl.merge && pl.kernel != ConvKernel::Upcat16 && !x_offs &&
+               (stem ? stem_slots > 0 : (pl.kernel == ConvKernel::Zx || amx::conv_fuses_stats(p, c.precision, L.q)));
+    pl.ks = ks_scratch && direct && !L.is_final && !pl.raw_bn && !pl.merge &&
+            amx::conv_ks_part_bytes(p.C0, p.Cout, n, pl.dd, pl.dh, pl.dw, c.precision, L.q) <= ks_bytes;
+    // only the stem and the output conv see the volume: those two run once per window
+    pl.per_window = x_offs && (stem || L.is_final);
+    return AMX_OK;
+  }
+
+  // ---- launch parameters, one builder per launch kind; what a builder returns is launched as it stands
+  // the input segments of a conv at dd x dh x dw
+  int bind_sources(amx::ConvParams& p, const ConvLayer& L, const Sources& s, int dd, int dh, int dw) const {
+    if (s.in->slot < 0) {  // stem: fp32 single-channel input
       p.src0 = (const char*)x;
       p.s0n = xs_n; p.s0z = xs_z; p.s0y = xs_y; p.s0x = 4;
       p.C0 = 16; p.C1 = 0; p.src0_f32c1 = 1;
-    } else if (have_cur_up) {
-      const Tensor& lo = cur;
+    } else if (s.up) {
+      const Tensor& lo = *s.in;
       // nearest: `lo` is the half-resolution tensor, read through >> 1; trilinear: already materialised at this level
-      const int lw = cur_is_full_up ? dw : dw / 2, lh = cur_is_full_up ? dh : dh / 2, ld = cur_is_full_up ? dd : dd / 2;
-      p.up_shift = cur_is_full_up ? 0 : 1;
-      if (have_skip) {
-        amx::set_src0(p, mem(pend_skip), pend_skip.C, dd, dh, dw, c.precision);
+      const int lw = s.full_up ? dw : dw / 2, lh = s.full_up ? dh : dh / 2, ld = s.full_up ? dd : dd / 2;
+      p.up_shift = s.full_up ? 0 : 1;
+      if (s.skip) {
+        amx::set_src0(p, mem(*s.skip), s.skip->C, dd, dh, dw, c.precision);
       } else {  // no skip connection: the whole input is the upsampled tensor
         p.src0 = mem(lo);  // unused segment of zero channels
         p.C0 = 0;
       }
       amx::set_src1(p, mem(lo), lo.C, ld, lh, lw, c.precision);
     } else {
-      amx::set_src0(p, mem(cur), cur.C, dd, dh, dw, c.precision);
+      amx::set_src0(p, mem(*s.in), s.in->C, dd, dh, dw, c.precision);
       p.C1 = 0;
     }
     if (p.C0 + p.C1 != L.cin_pad)
@@ -503,177 +626,149 @@ struct Forward : ForwardArgs {
     return AMX_OK;
   }
 
-  int conv_group() {
-    const ConvLayer& L = h->convs[conv_i++];
-    const int lv = L.level;
-    const int dd = d >> lv, dh = hh >> lv, dw = w >> lv;
-    if (const int r = try_stem_pair(L, dd, dh, dw)) return r < 0 ? r : AMX_OK;
-    amx::ConvParams p;
+  // the layer's own launch (merged taps: its skip-channel half, `out` then being the partial slot).  out / pooled: the memory of the
+  // 16-bit output and of the fused pool's, null where the plan has none -- and in plan_conv's probe
+  int layer_params(const ConvPlan& pl, char* out, char* pooled, amx::ConvParams& p) const {
+    const ConvLayer& L = *pl.L;
     memset(&p, 0, sizeof p);
-    p.N = n; p.D = dd; p.H = dh; p.W = dw; p.Cout = L.cout_p;
-    if (int e = bind_sources(p, L, dd, dh, dw)) return e;
-    p.wpk = (const char*)L.wpk;
+    p.N = n; p.D = pl.dd; p.H = pl.dh; p.W = pl.dw; p.Cout = L.cout_p;
+    if (int e = bind_sources(p, L, pl.src, pl.dd, pl.dh, pl.dw)) return e;
+    p.wpk = (const char*)pl.first.wpk; p.bias = pl.first.bias; p.act = pl.first.act; p.slope = c.act_slope;
     p.mxs = L.mxs;
-    p.bias = L.shift;
     p.oflow = h->d_flag;
-    const bool inorm = L.norm_idx >= 0 && (c.norm == AMX_NORM_INSTANCE || c.norm == AMX_NORM_INSTANCE_AFFINE);
-    // InstanceNorm needs the whole (n, c) plane of RAW conv outputs first: the conv stores un-activated values
-    // and amx::launch_instnorm normalises + activates them in place afterwards
-    // encode_only whose last layer is this group's conv / norm id: the modules after it never run in the reference,
-    // so the (in-place) activation must not touch the tapped tensor
-    const int idx_act = L.has_act ? L.module_idx + 1 + (L.norm_idx >= 0 ? 1 : 0) : -1;
-    const bool act_on = L.has_act && !(stop >= L.module_idx && stop < idx_act);
-    p.act = (act_on && !inorm) ? c.activation : AMX_ACT_NONE;
-    p.slope = c.act_slope;
-    // ---- feature taps inside this conv -> norm -> act group.  The reference's activations are in-place modules
-    // (network.py:188-196), so what the caller holds for a tap at the NORM id (or at the conv id when there is no
-    // norm) is the activated tensor; only a conv followed by a norm yields a distinct, pre-norm tensor.
-    float* tap_conv = tap_of(L.module_idx);
-    float* tap_norm = L.norm_idx >= 0 ? tap_of(L.norm_idx) : nullptr;
-    float* tap_act = idx_act >= 0 ? tap_of(idx_act) : nullptr;
-    // pre-norm tap of a FOLDED eval-BatchNorm layer: run the conv with the unfolded weights, export, apply the norm
-    const bool raw_bn = tap_conv && L.norm_idx >= 0 && !inorm && !L.is_final;
-    if (raw_bn) {
-      if (!L.wpk_raw) return fail(AMX_ERR_INVALID, "internal: model.%d has no unfolded packing", L.module_idx);
-      p.wpk = (const char*)L.wpk_raw;
-      if (L.raw_has_bias)
-        return fail(AMX_ERR_INVALID, "pre-norm tap of model.%d: conv bias under BatchNorm is not supported", L.module_idx);
-      p.bias = nullptr;   // s * conv + L.shift is the whole folded norm (applied by launch_affine_act below)
-      p.act = AMX_ACT_NONE;
-    }
-    Tensor out;
-    out.level = lv; out.C = L.cout_p; out.Cr = L.cout;
-    // the fp32 planar epilogues need W >= 32 and <= 32 output channels; outside that the output conv stores 16-bit
-    // channels-last like any other layer and one export pass produces the fp32 NCDHW tensor
-    const bool final_via_export = L.is_final && (dw < 32 || L.cout_p > 32 || L.cout_p != L.cout);
-    if (final_via_export && (wmap || x_offs))
-      return fail(AMX_ERR_SHAPE, "sliding-window accumulation needs roi width >= 32 and output_nc <= 32");
-    if (L.is_final && c.final_act != AMX_ACT_NONE && stop != L.module_idx) p.act = c.final_act;
-    if (L.is_final && !final_via_export) {
+    if (pl.out == ConvOut::Planar) {
       p.out32 = y;
       p.pn = ys_n; p.pc = ys_c; p.pz = ys_z; p.py = ys_y;
       p.wmap = wmap;
     } else {
-      if (int e = slot(lv, &out.slot)) return e;
-      amx::set_out(p, mem(out), L.cout_p, dd, dh, dw, c.precision);
+      amx::set_out(p, out, L.cout_p, pl.dd, pl.dh, pl.dw, c.precision);
     }
-    const double vox = (double)n * dd * dh * dw;
-    // ALGORITHMIC bytes (SURVEY.md section 8d): 16-bit activations read once and written once + the weights, the upsampled
-    // segment counted at its LOW resolution for either interpolation (a materialised trilinear tensor and the hi / lo / e4m3
-    // planes of the split precisions are this build's storage choices, not the layer's traffic requirement)
-    const double in_b = cur.slot < 0 ? 4.0 * vox : (p.C0 * vox + p.C1 * vox / 8.0) * 2.0;
-    const double out_b = L.is_final ? 4.0 * L.cout * vox : 2.0 * L.cout * vox;
-    if (int e = record(L.module_idx, L.cin, L.cout, dd, dh, dw, 2.0 * 27.0 * L.cin * L.cout * vox, in_b + out_b + 2.0 * 27.0 * L.cin * L.cout))
-      return e;
-    const size_t nxt = next_group(i, L);
-    // nn.MaxPool3d(2) right after this block (network.py:368): fuse it into the z-marching epilogue
-    const bool fuse_max_pool = !L.is_final && !inorm && !raw_bn && nxt < h->kinds.size() && h->kinds[nxt] == K_POOL && c.pooling == AMX_POOL_MAX &&
-                               cur.slot >= 0 && !have_cur_up && (split ? amx::conv_zmarch_can_pool_split(p) : amx::conv_zmarch_can_pool(p)) &&
-                               L.q == L.cout_p / 16;
-    if (fuse_max_pool) {
-      fused_pool.level = lv + 1; fused_pool.C = L.cout_p; fused_pool.Cr = L.cout;
-      if (int e = slot(lv + 1, &fused_pool.slot)) return e;
-      amx::set_out2(p, mem(fused_pool), L.cout_p, dd / 2, dh / 2, dw / 2, c.precision);
-      have_fused_pool = true;
-    }
-    if (p.src0_f32c1 && (L.is_final || L.cout_p > 32))
-      return fail(AMX_ERR_INVALID, "stem kernel supports ngf in {16, 32} and a following layer (ngf=%d)", L.cout);
-    const bool use_upcat = !split && !p.src0_f32c1 && !raw_bn && L.wpk_up && have_cur_up && have_skip && amx::conv_upcat16_eligible(p);
-    if (use_upcat) p.wpk = (const char*)L.wpk_up;
-    // wider concat layers: the ordinary convolution over the skip channels first (raw partial sums into a free slot of this
-    // level), then the merged-tap convolution over the upsampled channels, which adds them, the bias and the activation
-    const bool use_merge = !use_upcat && !raw_bn && L.wpk_merge && have_cur_up && have_skip && !cur_is_full_up && !L.is_final &&
-                           L.cout_p == L.cout && p.C0 == L.cout && amx::conv_upmerge_eligible(p.C0, p.C1, L.cout, dd, dh, dw, p.up_shift, split);
-    int p_slot = -1;
+    if (pl.pool) amx::set_out2(p, pooled, L.cout_p, pl.dd / 2, pl.dh / 2, pl.dw / 2, c.precision);
+    if (pl.stats) p.stats = (float*)in_scratch;
+    if (pl.ks) p.part = ks_scratch;
+    if (pl.merge) { p.src1 = nullptr; p.C1 = 0; p.up_shift = 0; }      // the skip channels only
+    return AMX_OK;
+  }
+  // the merged-tap launch behind `skip` (layer_params of the same plan): reads the partial sums that one wrote, same layout as `out`
+  amx::UpmergeParams merge_params(const ConvPlan& pl, const amx::ConvParams& skip, char* out) const {
     amx::UpmergeParams u;
     memset(&u, 0, sizeof u);
-    if (use_merge) {
-      if (int e = slot(lv, &p_slot)) return e;
-      amx::set_src(u, p.src1, p.C1, dd / 2, dh / 2, dw / 2, c.precision);
-      u.N = n; u.LD = dd / 2; u.LH = dh / 2; u.LW = dw / 2; u.Cout = L.cout;
-      u.wpk = (const char*)L.wpk_merge;
-      u.part = slots[lv][p_slot]; u.out = p.out;
-      u.bias = p.bias; u.act = p.act; u.slope = p.slope;
-      u.oflow = h->d_flag;
-      u.ocs = p.ocs;                               // the partial sums and the output (same layout)
-      p.out = slots[lv][p_slot];                   // same strides as the layer's output
-      p.bias = nullptr; p.act = AMX_ACT_NONE;
-      p.src1 = nullptr; p.C1 = 0; p.up_shift = 0;
-      p.wpk = (const char*)L.wpk_skip;
+    amx::set_src(u, mem(*pl.src.in), pl.src.in->C, pl.dd / 2, pl.dh / 2, pl.dw / 2, c.precision);
+    u.N = n; u.LD = pl.dd / 2; u.LH = pl.dh / 2; u.LW = pl.dw / 2; u.Cout = pl.L->cout;
+    u.wpk = (const char*)pl.second.wpk; u.bias = pl.second.bias; u.act = pl.second.act; u.slope = c.act_slope;
+    u.part = skip.out; u.out = out; u.ocs = skip.ocs;
+    u.oflow = h->d_flag;
+    return u;
+  }
+  // the stem pair: the 16 -> 16 layer's parameters (the stem's terms go to the launcher beside them); out null: plan_stem_pair's probe
+  amx::ConvParams pair_params(const ConvPlan& pl, char* out) const {
+    const ConvLayer& Nx = *pl.Nx;
+    amx::ConvParams p;
+    memset(&p, 0, sizeof p);
+    p.N = n; p.D = pl.dd; p.H = pl.dh; p.W = pl.dw; p.Cout = Nx.cout_p; p.C0 = 16; p.C1 = 0;
+    p.wpk = (const char*)pl.second.wpk; p.bias = pl.second.bias; p.act = pl.second.act; p.slope = c.act_slope;
+    p.oflow = h->d_flag;
+    amx::set_out(p, out, Nx.cout_p, pl.dd, pl.dh, pl.dw, c.precision);
+    return p;
+  }
+  // window wi of a per-window launch: the stem reads its window of the volume, the output conv accumulates into its window of y
+  amx::ConvParams window_params(const amx::ConvParams& p, int wi) const {
+    amx::ConvParams q = p;
+    q.N = 1;
+    if (p.src0_f32c1) {
+      q.src0 = (const char*)(x + x_offs[wi]);
+      q.out = p.out + (long long)wi * p.on;
+      if (p.out2) q.out2 = p.out2 + (long long)wi * p.qn;
+    } else {
+      q.src0 = p.src0 + (long long)wi * p.s0n;
+      if (p.src1) q.src1 = p.src1 + (long long)wi * p.s1n;
+      q.out32 = y + y_offs[wi];
     }
-    // InstanceNorm layers on the generic kernel: the conv epilogue writes the partial sums of the statistics pass itself
-    const bool zx_shape = mx && L.wx && !have_cur_up && !x_offs && cur.slot >= 0 && (inorm || (L.is_final && !final_via_export)) &&
-                          amx::conv_zx_eligible(p);
-    // (the stem of the split precisions likewise: amx_conv3d_stem.hip)
-    const int stem_slots = (p.src0_f32c1 && inorm && !x_offs) ? amx::conv_stem_stats_slots(p, stem_precision(c.precision)) : 0;
-    const bool fuse_stats = inorm && !use_merge && !use_upcat && !L.is_final && !x_offs &&
-                            (p.src0_f32c1 ? stem_slots > 0 : (zx_shape || amx::conv_fuses_stats(p, c.precision, L.q)));
-    if (fuse_stats) p.stats = (float*)in_scratch;
-    if (ks_scratch && !have_cur_up && !L.is_final && cur.slot >= 0 && !raw_bn && !use_merge &&
-        amx::conv_ks_part_bytes(p.C0, p.Cout, n, dd, dh, dw, c.precision, L.q) <= ks_bytes)
-      p.part = ks_scratch;
-    // f16x2mx 32 -> 32 at whole tiles: the normalise-on-load z-march kernel (amx_conv3d_zx.hip).  It is the ONLY consumer of a
-    // tensor whose norm was left pending (instance_norm_after), and takes already-normalised inputs too.
-    const bool use_zx = zx_shape;
-    if (cur.ab && !use_zx) return fail(AMX_ERR_INVALID, "internal: model.%d got an input whose norm is pending but cannot run the fused kernel", L.module_idx);
-    // what the launch ran and the statistics slots it wrote, for the record and for the norm behind it (window loops: the last window's)
-    amx::ConvLaunchInfo info{}, merge_info;
-    amx::ConvLaunchInfo* const want = (prof || fuse_stats) ? &info : nullptr;
-    auto launch_one = [&](const amx::ConvParams& q) -> hipError_t {
-      if (q.src0_f32c1) return amx::launch_conv_stem(q, stem_precision(c.precision), st, want);
-      if (use_upcat) return amx::launch_conv_upcat16(q, c.precision, st, want);
-      if (use_zx) return amx::launch_conv_zx(q, cur.ab, cur.ab_act, c.act_slope, L.wx, st, want);
-      return amx::launch_conv(q, c.precision, L.q, st, want);
-    };
+    return q;
+  }
+
+  // ---- the launches of a group
+  hipError_t launch_one(const ConvPlan& pl, const amx::ConvParams& q, amx::ConvLaunchInfo* want) {
+    switch (pl.kernel) {
+      case ConvKernel::StemPair:
+        return amx::launch_conv_zmarch_stem(q, x, xs_n, xs_z, xs_y, x_offs, pl.first.wpk, pl.first.bias, pl.first.act, c.act_slope, c.precision, st, want);
+      case ConvKernel::Stem: return amx::launch_conv_stem(q, stem_precision(c.precision), st, want);
+      case ConvKernel::Upcat16: return amx::launch_conv_upcat16(q, c.precision, st, want);
+      case ConvKernel::Zx: return amx::launch_conv_zx(q, pl.src.in->ab, pl.src.in->ab_act, c.act_slope, pl.L->wx, st, want);
+      case ConvKernel::Dispatch: break;
+    }
+    return amx::launch_conv(q, c.precision, pl.L->q, st, want);
+  }
+  // one launch, or one per window between the two event gates; then the merged-tap launch.  info: what the (last) launch ran and the
+  // statistics slots it wrote, for the record and for the norm behind it
+  int launch_group(const ConvPlan& pl, const Tensor& out, const Tensor& part, amx::ConvLaunchInfo& info) {
+    amx::ConvParams p;
+    if (pl.kernel == ConvKernel::StemPair)
+      p = pair_params(pl, mem(out));
+    else if (int e = layer_params(pl, mem(pl.merge ? part : out), pl.pool ? mem(fused_pool) : nullptr, p))
+      return e;
+    amx::ConvLaunchInfo* const want = (prof || pl.stats) ? &info : nullptr;
     // pipelined windows (two batches in flight on two streams): the accumulating launches of this batch wait for the other
     // slot's accumulations, so that overlapping windows still add up in window order
-    if (x_offs && L.is_final && acc_gate) AMX_HIP(hipStreamWaitEvent(st, acc_gate, 0));
-    if (x_offs && (p.src0_f32c1 || L.is_final)) {
-      for (int wi = 0; wi < n; ++wi) {
-        amx::ConvParams q = p;
-        q.N = 1;
-        if (p.src0_f32c1) {
-          q.src0 = (const char*)(x + x_offs[wi]);
-          q.out = p.out + (long long)wi * p.on;
-          if (p.out2) q.out2 = p.out2 + (long long)wi * p.qn;
-        } else {
-          q.src0 = p.src0 + (long long)wi * p.s0n;
-          if (p.src1) q.src1 = p.src1 + (long long)wi * p.s1n;
-          q.out32 = y + y_offs[wi];
-        }
-        AMX_HIP(launch_one(q));
-      }
+    const bool accumulates = x_offs && pl.L->is_final;
+    if (accumulates && acc_gate) AMX_HIP(hipStreamWaitEvent(st, acc_gate, 0));
+    if (pl.per_window) {
+      for (int wi = 0; wi < n; ++wi) AMX_HIP(launch_one(pl, window_params(p, wi), want));
     } else {
-      AMX_HIP(launch_one(p));
+      AMX_HIP(launch_one(pl, p, want));
     }
-    if (x_offs && L.is_final && acc_done) AMX_HIP(hipEventRecord(acc_done, st));
-    if (use_merge) {
-      AMX_HIP(amx::launch_conv_upmerge(u, c.precision, st, prof ? &merge_info : nullptr));
-      used[lv][p_slot] = false;                    // the partial sums are dead once their consumer is enqueued (stream order)
+    if (accumulates && acc_done) AMX_HIP(hipEventRecord(acc_done, st));
+    if (pl.merge) {
+      amx::ConvLaunchInfo merge_info;
+      AMX_HIP(amx::launch_conv_upmerge(merge_params(pl, p, mem(out)), c.precision, st, prof ? &merge_info : nullptr));
       if (prof) name_last("%.34s + %.26s", info.name, merge_info.name + 7);      // (+ 7: without its "conv3d_")
     } else if (prof) {
       name_last("%s", info.name);
     }
-    if (raw_bn) {
-      AMX_HIP(export_slot(out, tap_conv));
-      AMX_HIP(amx::launch_affine_act(mem(out), L.scale, L.shift, n, (long long)dd * dh * dw, L.cout_p,
-                                     act_on ? c.activation : AMX_ACT_NONE, c.act_slope, c.precision, st, h->d_flag));
-    } else if (tap_conv && !L.is_final && inorm) {
-      AMX_HIP(export_slot(out, tap_conv));     // the stored raw convolution output, before the instance norm below
+    return AMX_OK;
+  }
+
+  // the profiler record of the group's conv (call BEFORE its launch)
+  int record_group(const ConvPlan& pl) {
+    const ConvLayer& L = *pl.L;
+    const double vox = (double)n * pl.dd * pl.dh * pl.dw;
+    if (pl.Nx) {
+      const double macs = L.cin * L.cout + pl.Nx->cin * pl.Nx->cout;
+      return record(L.module_idx, L.cin, pl.Nx->cout, pl.dd, pl.dh, pl.dw, 2.0 * 27.0 * macs * vox,
+                    4.0 * vox + 2.0 * pl.Nx->cout * vox + 2.0 * 27.0 * macs);   // fp32 input once, 16-bit output once
     }
-    if (inorm) {
-      if (int e = instance_norm_after(L, p, out, nxt, act_on, fuse_stats ? info.stats_slots : 0)) return e;
+    // ALGORITHMIC bytes (SURVEY.md section 8d): 16-bit activations read once and written once + the weights, the upsampled
+    // segment counted at its LOW resolution for either interpolation (a materialised trilinear tensor and the hi / lo / e4m3
+    // planes of the split precisions are this build's storage choices, not the layer's traffic requirement)
+    const Sources& s = pl.src;
+    const int C0 = s.up ? (s.skip ? s.skip->C : 0) : s.in->C, C1 = s.up ? s.in->C : 0;
+    const double in_b = s.in->slot < 0 ? 4.0 * vox : (C0 * vox + C1 * vox / 8.0) * 2.0;
+    const double out_b = L.is_final ? 4.0 * L.cout * vox : 2.0 * L.cout * vox;
+    return record(L.module_idx, L.cin, L.cout, pl.dd, pl.dh, pl.dw, 2.0 * 27.0 * L.cin * L.cout * vox, in_b + out_b + 2.0 * 27.0 * L.cin * L.cout);
+  }
+
+  // ---- one conv -> norm -> act group (the stem pair: two): plan; take slots; launch; then norm, taps, releases and bookkeeping
+  int conv_group() {
+    ConvPlan pl;
+    if (int e = plan_conv(conv_i, i, sources(), pl)) return e;
+    conv_i += pl.Nx ? 2 : 1;
+    const ConvLayer& O = pl.Nx ? *pl.Nx : *pl.L;      // the layer whose output the group stores
+    Tensor out, part;
+    out.level = part.level = pl.lv; out.C = O.cout_p; out.Cr = O.cout;
+    if (pl.out != ConvOut::Planar)
+      if (int e = slot(pl.lv, &out.slot)) return e;
+    if (pl.pool) {
+      fused_pool.level = pl.lv + 1; fused_pool.C = O.cout_p; fused_pool.Cr = O.cout;
+      if (int e = slot(pl.lv + 1, &fused_pool.slot)) return e;
+      have_fused_pool = true;
     }
-    if (final_via_export)
-      AMX_HIP(amx::launch_export_ncdhw(mem(out), L.cout, nullptr, 0, 0, n, dd, dh, dw, y, c.precision, st, L.cout_p, 0));
-    if (L.is_final) {
-      if (tap_conv)   // contiguous [n][Cout][d][h][w] output (taps are only offered by the plain forward)
-        AMX_HIP(hipMemcpyAsync(tap_conv, y, (size_t)n * L.cout * dd * dh * dw * sizeof(float), hipMemcpyDeviceToDevice, st));
-    } else {
-      if (tap_conv && L.norm_idx < 0) AMX_HIP(export_slot(out, tap_conv));   // aliased by the in-place activation
-      if (tap_norm) AMX_HIP(export_slot(out, tap_norm));
-      if (tap_act) AMX_HIP(export_slot(out, tap_act));
-    }
+    if (pl.merge)
+      if (int e = slot(pl.lv, &part.slot)) return e;
+    if (int e = record_group(pl)) return e;
+    amx::ConvLaunchInfo info{};
+    if (int e = launch_group(pl, out, part, info)) return e;
+    if (pl.merge) release(part);                      // the partial sums are dead once their consumer is enqueued (stream order)
+    if (int e = finish_group(pl, out, pl.stats ? info.stats_slots : 0)) return e;
     // inputs are dead once their consumer is enqueued (stream order)
     if (cur.slot >= 0) release(cur);
     if (have_skip) release(pend_skip);
@@ -681,59 +776,82 @@ struct Forward : ForwardArgs {
     have_cur_up = false;
     cur_is_full_up = false;
     cur = out;
-    i = nxt - 1;                 // step over the fused norm / activation modules
+    i = pl.nxt - 1;              // step over the fused norm / activation modules (the stem pair: over the second group too)
     push_skip_after(i);
-    if (stop >= L.module_idx && stop <= (int)i) done = true;   // encode_only: layers[-1] lies in this group
+    if (stop >= pl.L->module_idx && stop <= (int)i) done = true;   // encode_only: layers[-1] lies in this group
     return AMX_OK;
   }
 
-  // InstanceNorm behind a conv that stored its RAW output in `out`: statistics, then the apply pass here, in the consumer, or
-  // together with the pool
-  // nxt: module index of the next group; act_on: the group's activation runs (encode_only may end before it); slots_written: the
-  // partial-statistics slots per sample that the conv's epilogue wrote (0: it wrote none, the statistics pass runs)
-  int instance_norm_after(const ConvLayer& L, const amx::ConvParams& p, Tensor& out, size_t nxt, bool act_on, int slots_written) {
-    const int lv = L.level, dd = p.D, dh = p.H, dw = p.W;
-    if (L.is_final) return fail(AMX_ERR_INVALID, "internal: instance norm after the output conv");
+  // what follows the conv's launch: the pre-norm tap, the norm, the export pass, the taps of the finished tensor
+  int finish_group(const ConvPlan& pl, Tensor& out, int slots_written) {
+    const ConvLayer& L = *pl.L;
+    if (pl.tap_pre) AMX_HIP(export_slot(out, pl.tap_pre));     // the stored raw convolution output, before the norm below
+    if (pl.raw_bn)
+      AMX_HIP(amx::launch_affine_act(mem(out), L.scale, L.shift, n, (long long)pl.dd * pl.dh * pl.dw, L.cout_p,
+                                     pl.act_on ? c.activation : AMX_ACT_NONE, c.act_slope, c.precision, st, h->d_flag));
+    if (pl.inorm)
+      if (int e = instance_norm_after(pl, out, slots_written)) return e;
+    if (pl.out == ConvOut::SlotThenExport)
+      AMX_HIP(amx::launch_export_ncdhw(mem(out), L.cout, nullptr, 0, 0, n, pl.dd, pl.dh, pl.dw, y, c.precision, st, L.cout_p, 0));
+    if (pl.tap_y)
+      AMX_HIP(hipMemcpyAsync(pl.tap_y, y, (size_t)n * L.cout * pl.dd * pl.dh * pl.dw * sizeof(float), hipMemcpyDeviceToDevice, st));
+    for (float* t : pl.tap_post)
+      if (t) AMX_HIP(export_slot(out, t));
+    return AMX_OK;
+  }
+
+  // Who runs the apply pass of the instance norm behind the group's conv, whose raw output is `out`.  Anyone but this group only in a
+  // plain forward whose activation runs: a tap or a window batch reads the finished tensor.
+  NormApply plan_norm(const ConvPlan& pl, const Tensor& out) const {
+    if (taps || x_offs || pl.act_on != pl.L->has_act || pl.nxt >= h->kinds.size()) return NormApply::Here;
+    switch (h->kinds[pl.nxt]) {
+      case K_CONV: {
+        // the module after this group is a conv that runs the normalise-on-load kernel on this tensor (so the tensor is no skip
+        // connection, no pool / upsample input): asked of that layer's own plan, reading `out` as it will.  (The output conv takes a
+        // pending norm too: fp32 planar epilogue, no importance map, no activation of its own.)
+        ConvPlan nx;
+        if (!mx || conv_i >= h->convs.size() || plan_conv(conv_i, pl.nxt, Sources{&out, false, false, nullptr}, nx) != AMX_OK) return NormApply::Here;
+        return nx.kernel == ConvKernel::Zx ? NormApply::NextConv : NormApply::Here;
+      }
+      case K_POOL:
+        // f16x2mx, pool right after this group: the apply pass also writes the pooled tensor (amx_norm.hip in_apply_pool_kernel); the
+        // in-place tensor then has no reader left but the decoder's convolution, which takes hi and the copies
+        return mx && !have_fused_pool && amx::in_apply_pool_eligible(c.precision, pl.dd, pl.dh, pl.dw, pl.L->cout_p) ? NormApply::WithPool : NormApply::Here;
+      case K_UP:   // trilinear upsample right after this group (decoder): the upsample pass normalises its eight inputs on the way in
+        return c.interp == AMX_INTERP_TRILINEAR ? NormApply::Upsample : NormApply::Here;
+      default: return NormApply::Here;
+    }
+  }
+
+  // InstanceNorm behind a conv that stored its RAW output in `out`: statistics, then the apply pass where plan_norm puts it.
+  // slots_written: the partial-statistics slots per sample that the conv's epilogue wrote (0: it wrote none, the statistics pass runs)
+  int instance_norm_after(const ConvPlan& pl, Tensor& out, int slots_written) {
+    const ConvLayer& L = *pl.L;
+    const int dd = pl.dd, dh = pl.dh, dw = pl.dw, act = pl.act_on ? c.activation : AMX_ACT_NONE;
     if (int e = record(L.norm_idx, L.cout, L.cout, dd, dh, dw, 0.0, (double)eb * L.cout * (double)n * dd * dh * dw * 3.0)) return e;
     name_last("instnorm+act");
-    // Leave the apply pass to the consumer when that is the fused 32 -> 32 kernel: the module after this conv -> norm -> act group is
-    // a conv of that shape at this resolution (so this tensor is no skip connection, no pool / upsample input, no tap)
-    bool defer = false;
-    if (mx && !taps && !x_offs && act_on == L.has_act && nxt < h->kinds.size() && h->kinds[nxt] == K_CONV && conv_i < h->convs.size()) {
-      const ConvLayer& Nx = h->convs[conv_i];
-      amx::ConvParams t;
-      memset(&t, 0, sizeof t);
-      t.N = n; t.D = dd; t.H = dh; t.W = dw; t.C0 = L.cout_p; t.C1 = 0; t.Cout = Nx.cout_p; t.out = (char*)1; t.mxs = Nx.mxs; t.s0x = 32; t.ox = 32;
-      // (the output conv takes a pending norm too: fp32 planar epilogue, no importance map, no activation of its own)
-      const bool nx_kind = Nx.is_final ? (!wmap && c.final_act == AMX_ACT_NONE && dw >= 32 && Nx.cout_p == Nx.cout) : Nx.norm_idx >= 0;
-      defer = Nx.wx && Nx.level == lv && nx_kind && Nx.cin_pad == L.cout_p && amx::conv_zx_eligible(t);
-    }
-    // f16x2mx, pool right after this group: the apply pass also writes the pooled tensor (amx_norm.hip in_apply_pool_kernel); the
-    // in-place tensor then has no reader left but the decoder's convolution, which takes hi and the copies
-    const bool apply_pool = !defer && mx && !taps && !x_offs && act_on == L.has_act && nxt < h->kinds.size() && h->kinds[nxt] == K_POOL &&
-                            !have_fused_pool && amx::in_apply_pool_eligible(c.precision, dd, dh, dw, L.cout_p);
-    // trilinear upsample right after this group (decoder): the upsample pass normalises its eight inputs on the way in
-    const bool defer_up = !defer && !apply_pool && !taps && !x_offs && act_on == L.has_act && nxt < h->kinds.size() &&
-                          h->kinds[nxt] == K_UP && c.interp == AMX_INTERP_TRILINEAR;
-    if (defer_up) defer = true;
-    float* abo = (defer || apply_pool) ? ab_buf[ab_next] : nullptr;
-    AMX_HIP(amx::launch_instnorm(mem(out), L.in_gamma, L.in_beta, c.norm_eps, n, (long long)dd * dh * dw,
-                                 L.cout_p, act_on ? c.activation : AMX_ACT_NONE, c.act_slope, in_scratch, c.precision, st, h->d_flag,
-                                 slots_written, slots_written ? L.shift : nullptr, dw, conv_only(nxt), (defer || apply_pool) ? 0 : 1, abo));
-    if (apply_pool) {
-      fused_pool.level = lv + 1; fused_pool.C = L.cout_p; fused_pool.Cr = L.cout;
-      if (int e = slot(lv + 1, &fused_pool.slot)) return e;
-      AMX_HIP(amx::launch_in_apply_pool(mem(out), abo, mem(fused_pool), n, dd, dh, dw, L.cout_p,
-                                        act_on ? c.activation : AMX_ACT_NONE, c.act_slope, c.pooling == AMX_POOL_AVG, 1,
-                                        conv_only(nxt + 1), h->d_flag, st));
-      have_fused_pool = true;
-      name_last("instnorm+act+pool2<%s>", c.pooling == AMX_POOL_AVG ? "avg" : "max");
-    }
-    if (defer) {
-      out.ab = abo;
-      out.ab_act = act_on ? c.activation : AMX_ACT_NONE;
-      ab_next ^= 1;
-      name_last("instnorm statistics only (apply fused into the next %s)", defer_up ? "upsample" : "conv");
+    const NormApply where = plan_norm(pl, out);
+    float* const abo = where == NormApply::Here ? nullptr : ab_buf[ab_next];      // the (a, b) pairs, for whoever applies them
+    AMX_HIP(amx::launch_instnorm(mem(out), L.in_gamma, L.in_beta, c.norm_eps, n, (long long)dd * dh * dw, L.cout_p, act, c.act_slope,
+                                 in_scratch, c.precision, st, h->d_flag, slots_written, slots_written ? L.shift : nullptr, dw,
+                                 conv_only(pl.nxt), where == NormApply::Here ? 1 : 0, abo));
+    switch (where) {
+      case NormApply::Here: break;
+      case NormApply::WithPool:
+        fused_pool.level = pl.lv + 1; fused_pool.C = L.cout_p; fused_pool.Cr = L.cout;
+        if (int e = slot(pl.lv + 1, &fused_pool.slot)) return e;
+        AMX_HIP(amx::launch_in_apply_pool(mem(out), abo, mem(fused_pool), n, dd, dh, dw, L.cout_p, act, c.act_slope,
+                                          c.pooling == AMX_POOL_AVG, 1, conv_only(pl.nxt + 1), h->d_flag, st));
+        have_fused_pool = true;
+        name_last("instnorm+act+pool2<%s>", c.pooling == AMX_POOL_AVG ? "avg" : "max");
+        break;
+      case NormApply::NextConv:
+      case NormApply::Upsample:      // the tensor stays RAW: its reader applies y = act(a x + b)
+        out.ab = abo;
+        out.ab_act = act;
+        ab_next ^= 1;
+        name_last("instnorm statistics only (apply fused into the next %s)", where == NormApply::Upsample ? "upsample" : "conv");
+        break;
     }
     return AMX_OK;
   }

@@ -6,13 +6,14 @@ float64 convolution of those values with the weights folded as the pack step fol
 bound is what ONE rounding of the result can cost.  A wrong row of a ragged tile at a deep level is then a failure of that layer at that voxel, not 1e-4 of an
 end-of-network rel-L2.
 
-Which taps keep the production schedule (amx_unet.hip, ``Forward::conv_group`` / ``try_stem_pair`` / ``pool``).  On a batch-norm /
+Which taps keep the production schedule (amx_unet.hip, ``Forward::plan_conv`` and what it calls, ``plan_norm``, ``pool``).  On a batch-norm /
 nearest / max-pool network a feature tap at an ACTIVATION id or at a POOL id is a plain export of the tensor the production kernel
 stored: it changes no launch.  Exactly three things reroute a forward:
 
-  1. a tap at a conv id that a BatchNorm follows (``raw_bn``: the conv runs on its unfolded weights, the norm in a pass of its own);
-  2. a tap before module ``g1 - 1`` in ``try_stem_pair`` (the stem's tensor has to reach memory: two launches instead of the pair);
-  3. on the ``f16x2mx`` networks, any tap at all (``!taps`` in ``instance_norm_after`` and ``conv_only``).
+  1. a tap at a conv id that a BatchNorm follows (``ConvPlan::raw_bn``, set in ``plan_terms``: the conv runs on its unfolded weights,
+     the norm in a pass of its own);
+  2. a tap before module ``g1 - 1`` in ``plan_stem_pair`` (the stem's tensor has to reach memory: two launches instead of the pair);
+  3. on the ``f16x2mx`` networks, any tap at all (``taps`` in the first line of ``plan_norm``, and ``conv_only``).
 
 So the walk of the plain forward taps the activation ids from the one behind the stem pair on, the pool ids and the output conv;
 a second run adds the stem's activation id and must agree with the first bit for bit behind the pair.  Because of 3. the

@@ -1,7 +1,8 @@
 """Bitwise A/B of two builds of libanatomix_amd.so.  Section ``streams``: the entries of the streaming units (segmentation loss, the
 three augmentation units, registration metrics, instance optimisation, MIND-SSC / correlation) -- the proof that a refactor of their
-shared helpers changed no summation order and no contraction.  Section ``unet``: the UNet forward (output, feature taps, sliding
-window, the kernel names of a profiled forward) and the single-layer conv entries, one shape per route of the conv dispatch -- the
+shared helpers changed no summation order and no contraction.  Section ``unet``: the UNet forward (output, feature taps, encode_only,
+sliding window by window batches and as one call, the kernel names of a profiled forward) on the shipped variants and on every
+configuration tests/test_unet_gpu.py parametrises, and the single-layer conv entries, one shape per route of the conv dispatch -- the
 proof that a refactor of the launch path moved no layer to another kernel and changed no launch.  Section ``train``: the training
 function (model/train.py) over every configuration tests/test_train_step_gpu.py parametrises, the 6 M variant on both tap routes, and
 eager / graphed contrastive steps with FusedAdamW -- the proof that a refactor of the Python side of the training path changed no
@@ -37,12 +38,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ---- child: one listing --------------------------------------------------------------------------------------------------
 
 def unet_section(dev, emit, tree):
-    """The 6 M variant and anatomix-dev in every precision they support, and the single-layer entries on one shape per route."""
+    """The 6 M variant and anatomix-dev in every precision they support (forward, taps, encode_only, both sliding-window routes), the
+    other configurations of tests/test_unet_gpu.py -- between them every branch of the forward's conv plan -- and the single-layer
+    entries on one shape per route."""
     sys.path.insert(0, os.path.join(tree, "tests"))
     import torch
     import _util as U              # run_conv / run_conv_merged: the tensor layouts of the single-layer entries
     import anatomix_amd
-    from anatomix_amd.registration.sliding_window import sliding_window_inference
+    from anatomix_amd.registration.sliding_window import sliding_window_inference, sliding_window_volume
     from oracle import unet_ref as R
 
     def emit_names(name, names):
@@ -75,9 +78,40 @@ def unet_section(dev, emit, tree):
                     xv = R.synthetic_input(101, 1, volume).to(dev)
                     emit(f"{tag}/sliding_window_{'x'.join(map(str, volume))}",
                          sliding_window_inference(xv, roi, 4, m, overlap=0.25, mode="gaussian"))
+                    if shape == shapes[0][0]:
+                        # encode_only ending at the conv, norm and activation id of one group (the one behind the stem: no pair then),
+                        # and the whole-volume call: the window route with its event gates
+                        for module in (3, 4, 5):
+                            emit(f"{tag}/encode_only{module}/feat", m.forward_hip_taps(x, [module], encode_only=True)[0])
+                        emit(f"{tag}/sliding_window_volume_{'x'.join(map(str, volume))}",
+                             sliding_window_volume(xv, roi, m, overlap=0.25, mode="gaussian"))
                     y, recs = m.profile_forward(x)
                 emit(f"{tag}/profile_forward/out", y)
                 emit_names(f"{tag}/profile_forward/names", [r["kernel"] for r in recs])
+
+    # ---- every configuration tests/test_unet_gpu.py parametrises beside the shipped ones, at its shapes, seeds and tap lists: the
+    # export-pass outputs, doubleconv=False, padded widths, ngf = 8, instance norm + Avg + trilinear, no skips, input_nc > 1
+    import test_unet_gpu as T
+    cases = lambda test: test.pytestmark[0].args[1]
+    configs = ([(kw, size, [], 4) for kw, size in cases(T.test_small_volumes_and_wide_outputs)]
+               + [(kw, size, layers, 6) for kw, size, layers in cases(T.test_widths_that_are_not_multiples_of_16)]
+               + [(kw, size, layers, 8) for kw, size, layers in cases(T.test_input_and_output_channel_counts_of_the_constructor_envelope)])
+    for k, (kw, size, layers, seed) in enumerate(configs):
+        full = {**dict(ngf=24), **kw}
+        with contextlib.redirect_stdout(sys.stderr):
+            m = anatomix_amd.Unet(**kw)
+        m.load_state_dict(R.synthetic_state_dict(full, seed), strict=True)
+        m = m.to(dev).eval()
+        tag = "unet/config%d/%s/%s" % (k, ",".join(f"{a}={full[a]}" for a in sorted(full) if a != "dimension"), "x".join(map(str, size)))
+        x = torch.cat([R.synthetic_input(50 + ch, 2, size) for ch in range(kw["input_nc"])], dim=1).to(dev)
+        with torch.no_grad():
+            y, feats = m(x, layers) if layers else (m(x), [])
+            emit(f"{tag}/forward", y)
+            for layer, f in zip(sorted(layers), feats):
+                emit(f"{tag}/tap{layer}", f)
+            y, recs = m.profile_forward(x)
+        emit(f"{tag}/profile_forward/out", y)
+        emit_names(f"{tag}/profile_forward/names", [r["kernel"] for r in recs])
 
     # ---- amx_conv3d_k3_reflect_ws / amx_conv3d_upcat_merged: (route, c0, c1, cout, size, precision, planar output)
     g = torch.Generator().manual_seed(20250301)
