@@ -105,10 +105,19 @@ size_t amx_conv3d_packed_bytes(int cin, int cout) {
   return 2 * bytes + 256;     // room for the [Wh | Wl] packing of the strict precisions (+ the block-scale words of f16x2mx)
 }
 
+// what amx_conv3d_k3_reflect_probe adds to a single-layer call: the fused max-pool output, the importance map of the fp32 planar
+// epilogue, the range flag, and where the launch's name goes
+struct ConvProbe {
+  void* pool16;
+  const float* wmap;
+  int* oflow;
+  char* kernel;      // 64 bytes
+};
+
 static int conv3d_single(const void* d_x0, int c0, const void* d_x1, int c1, const float* d_weight, int weight_mode,
                          int cin_real, int cout_real, const float* d_scale, const float* d_shift, int cout, int n, int d,
                          int hh, int w, int act, float slope, int precision, void* d_wpk, void* d_out16, float* d_out32,
-                         void* stream, void* d_scratch = nullptr, size_t scratch_bytes = 0) {
+                         void* stream, void* d_scratch = nullptr, size_t scratch_bytes = 0, const ConvProbe* probe = nullptr) {
   if (!d_x0 || (!d_weight && !(weight_mode & AMX_WEIGHTS_PREPACKED)) || !d_wpk || (!d_out16 == !d_out32)) return fail(AMX_ERR_INVALID, "bad pointer arguments");
   if (c0 % 16 || c1 % 16 || c0 + c1 < 16 || cout % 16 || cout < 16)
     return fail(AMX_ERR_INVALID, "channel counts must be multiples of 16 (c0=%d c1=%d cout=%d)", c0, c1, cout);
@@ -151,13 +160,25 @@ static int conv3d_single(const void* d_x0, int c0, const void* d_x1, int c1, con
     p.out32 = d_out32;
     p.py = w; p.pz = (long long)hh * w; p.pc = p.pz * d; p.pn = p.pc * cout;
   }
+  amx::ConvLaunchInfo info{};
+  amx::ConvLaunchInfo* const want = probe ? &info : nullptr;
+  if (probe) {
+    p.wmap = probe->wmap;
+    p.oflow = probe->oflow;
+    if (probe->wmap && !d_out32) return fail(AMX_ERR_INVALID, "the importance map belongs to the fp32 planar output");
+    if (probe->pool16) {
+      if (!d_out16 || !amx::conv_zmarch_can_pool(p)) return fail(AMX_ERR_SHAPE, "the fused max-pool needs a z-march layer with even extents");
+      amx::set_out2(p, probe->pool16, cout, d / 2, hh / 2, w / 2, precision);
+    }
+  }
   if (!is_split(precision) && weight_mode == 0 && cin_real == 48 && c0 == 16 && c1 == 32 && cout == 16 && amx::conv_upcat16_eligible(p)) {
     if (prepacked)
       return fail(AMX_ERR_INVALID, "prepacked weights: the 16 + up32 -> 16 merged-tap layer packs its own format (call without the flag)");
     char* up = (char*)d_wpk + ((size_t)cout * (c0 + c1) * 28 * 2 + 255) / 256 * 256;
     AMX_HIP(amx::launch_pack_upcat16(d_weight, d_scale, up, precision, st));
     p.wpk = up;
-    AMX_HIP(amx::launch_conv_upcat16(p, precision, st));
+    AMX_HIP(amx::launch_conv_upcat16(p, precision, st, want));
+    if (probe && probe->kernel) memcpy(probe->kernel, info.name, sizeof info.name);
     return AMX_OK;
   }
   // split-K scratch offered by the caller (amx_conv3d_k3_reflect_ws): deep layers with few voxels split K across workgroups
@@ -167,7 +188,8 @@ static int conv3d_single(const void* d_x0, int c0, const void* d_x1, int c1, con
       return fail(AMX_ERR_WORKSPACE, "split-K scratch needs %zu bytes, 16-byte aligned (got %zu)", need, scratch_bytes);
     if (need) p.part = (float*)d_scratch;
   }
-  AMX_HIP(amx::launch_conv(p, precision, q, st));
+  AMX_HIP(amx::launch_conv(p, precision, q, st, want));
+  if (probe && probe->kernel) memcpy(probe->kernel, info.name, sizeof info.name);
   return AMX_OK;
 }
 
@@ -251,6 +273,15 @@ int amx_conv3d_k3_reflect_ws(const void* d_x0, int c0, const void* d_x1, int c1,
                              void* d_scratch, size_t scratch_bytes, void* stream) {
   return conv3d_single(d_x0, c0, d_x1, c1, d_weight, 0, c0 + c1, cout, d_scale, d_shift, cout, n, d, hh, w, act, slope,
                        precision, d_wpk, d_out16, d_out32, stream, d_scratch, scratch_bytes);
+}
+
+int amx_conv3d_k3_reflect_probe(const void* d_x0, int c0, const void* d_x1, int c1, const float* d_weight, const float* d_scale,
+                                const float* d_shift, int cout, int n, int d, int hh, int w, int act, float slope, int precision,
+                                void* d_wpk, void* d_out16, float* d_out32, void* d_pool16, const float* d_wmap, int* d_oflow,
+                                char* kernel_name, void* stream) {
+  const ConvProbe probe{d_pool16, d_wmap, d_oflow, kernel_name};
+  return conv3d_single(d_x0, c0, d_x1, c1, d_weight, 0, c0 + c1, cout, d_scale, d_shift, cout, n, d, hh, w, act, slope,
+                       precision, d_wpk, d_out16, d_out32, stream, nullptr, 0, &probe);
 }
 
 int amx_conv3d_k3_reflect(const void* d_x0, int c0, const void* d_x1, int c1, const float* d_weight,

@@ -55,7 +55,9 @@ struct UpcatCfg {
   static_assert(R * NDMA <= 60 && RL * NDMAL <= 60, "vmcnt range");
 };
 
-template <typename T, int OUTMODE>
+// ACT: the activation is a compile-time variant (its own kernel symbol, picked by launch_upcat_t from ConvParams::act), so the epilogue
+// holds no activation test -- amx_conv3d_zmarch.hip has the reasons.
+template <typename T, int OUTMODE, int ACT>
 __global__ __launch_bounds__((UpcatCfg::NC + UpcatCfg::NL) * 64) void conv3d_upcat16_kernel(const ConvParams p, int zseg,
                                                                                            int nseg) {
   typedef UpcatCfg C;
@@ -201,12 +203,62 @@ __global__ __launch_bounds__((UpcatCfg::NC + UpcatCfg::NL) * 64) void conv3d_upc
 
   const bool full_xy = (y0 + TY <= p.H) & (x0 + TX <= p.W);
   const int yl = y0 + py, xl = x0 + 2 * li + px;
-  char* out_l = OUTMODE == 0 ? p.out + (long long)n * p.on + (long long)yl * p.oy + (long long)xl * p.ox + g * 8 : nullptr;
-  char* out_w = OUTMODE == 0 ? p.out + (long long)n * p.on + (long long)yl * p.oy + (long long)xl * p.ox + (g >> 1) * 16 : nullptr;
+  // 16-bit output: a wave-uniform plane pointer that advances by two planes per step in scalar registers + a 32-bit lane offset that
+  // never changes (amx_conv3d_zmarch.hip states the rule).  Lane (g, li) stores channels 8 (g >> 1) .. + 7 of voxel (row yl + 2 (g & 1)
+  // + 4 cp, xl) for the row pairs cp = 0, 1; ok_w: the lane predicates of a partial tile, fixed for the march.
+  const unsigned lo_w = OUTMODE == 0 ? (unsigned)((yl + 2 * (g & 1)) * (int)p.oy + xl * (int)p.ox + (g >> 1) * 16) : 0u;
+  char* zb = OUTMODE == 0 ? p.out + (long long)n * p.on + (long long)(zs + pz) * p.oz : nullptr;
+  const bool ok_w0 = full_xy || ((yl + 2 * (g & 1) < p.H) & (xl < p.W)), ok_w1 = full_xy || ((yl + 2 * (2 + (g & 1)) < p.H) & (xl < p.W));
   float* out32_l = OUTMODE == 1 ? p.out32 + (long long)n * p.pn + (long long)(g * 4) * p.pc + (long long)yl * p.py + xl
                                 : nullptr;
+  const bool fast = OUTMODE == 0 && full_xy;                 // whole tile: no store of the march needs a predicate (ze - zs is even)
+  unsigned amax = 0;                                         // running range check (RangeCheck<T>::track), reduced once after the march
 
-  bool bad = false;
+  // One step's epilogue, compiled per path (FAST: no per-store predicate).
+  auto epilogue = [&](auto fast_c, const int s, f32x4 (&acc)[4]) {
+    constexpr bool FAST = decltype(fast_c)::value != 0;
+    const int zo = zs + 2 * s + pz;
+    act_values<ACT, 4>(&acc[0], p.slope);
+    if constexpr (OUTMODE == 0) {
+      // 16-bit channels-last output: the lane groups g and g ^ 1 exchange one row each (v_permlane16_swap), so that a lane
+      // stores 8 consecutive channels of ONE voxel -- one 16-byte store per lane and row pair instead of two 8-byte ones.
+      unsigned ow = lo_w;
+      asm volatile("" : "+v"(ow));                           // (opaque: "scalar base + lane offset" stores, see amx_conv3d_zmarch.hip)
+#pragma unroll
+      for (int cp = 0; cp < 2; ++cp) {
+        unsigned pk[2][2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const f32x4 v = acc[2 * cp + h];
+          if (RangeCheck<T>::on) {                           // the values about to be stored
+            amax = RangeCheck<T>::template track<ACT == ACT_RELU>(amax, v[0], v[1]);
+            amax = RangeCheck<T>::template track<ACT == ACT_RELU>(amax, v[2], v[3]);
+          }
+          pk[h][0] = Ops<T>::pack2(v[0], v[1]);
+          pk[h][1] = Ops<T>::pack2(v[2], v[3]);
+        }
+        const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
+        const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
+        // even g: row of c = 2 cp, odd g: row of c = 2 cp + 1, i.e. row 2 (2 cp + (g & 1)) of the lane's column
+        if (FAST || (zo < ze && (cp ? ok_w1 : ok_w0))) *(uint4*)(zb + (cp ? 4 * p.oy : 0) + ow) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+      }
+    } else if (zo < ze) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (!full_xy && !((yl + 2 * c < p.H) & (xl < p.W))) continue;
+        float* dst = out32_l + (long long)zo * p.pz + (2 * c) * p.py;
+        if (p.wmap) {
+          const float wgt = p.wmap[((long long)zo * p.H + yl + 2 * c) * p.W + xl];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) dst[(long long)j * p.pc] += wgt * acc[c][j];
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) dst[(long long)j * p.pc] = acc[c][j];
+        }
+      }
+    }
+  };
+
   for (int s = 0; s < nsteps; ++s) {
     {
       int need = 2 * s + 4, needl = s + 3;                   // skip planes q <= 2s+3 and low planes ql <= s+2
@@ -220,7 +272,6 @@ __global__ __launch_bounds__((UpcatCfg::NC + UpcatCfg::NL) * 64) void conv3d_upc
       }
       asm volatile("" ::: "memory");
     }
-    const int zo = zs + 2 * s + pz;
     // ring offsets of the three input planes and the two low-resolution planes: wave-uniform, kept in scalar registers
     int slo[3], llo[2];
 #pragma unroll
@@ -233,7 +284,7 @@ __global__ __launch_bounds__((UpcatCfg::NC + UpcatCfg::NL) * 64) void conv3d_upc
 #pragma unroll
     for (int c = 0; c < 4; ++c) acc[c] = bias;
 
-    if (!(p.dbg & 2)) {
+    {
       // The step's 88 fragment uses -- 14 paired-tap steps of the skip part (tile c = low row ly = c <-> output row y0 + 2c + py), then
       // the 8 merged taps e = (ez, ey, ex) of the upsampled part on the low-resolution ring, 4 row tiles each, ONE MFMA per fragment --
       // as one static sequence with rolling reads: use i sits in slot i mod NSLOT, the read for use i + NSLOT is issued right after the
@@ -270,61 +321,11 @@ __global__ __launch_bounds__((UpcatCfg::NC + UpcatCfg::NL) * 64) void conv3d_upc
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // every ring read of this step has returned
     flag_store(done + wave, s + 1);
 
-    act_inplace<4>(&acc[0], p.act, p.slope);
-    if (OUTMODE == 0 && zo < ze && !(p.dbg & 4) && !(p.dbg & 32)) {
-      // 16-bit channels-last output: the lane groups g and g ^ 1 exchange one row each (v_permlane16_swap), so that a lane
-      // stores 8 consecutive channels of ONE voxel -- one 16-byte store per lane and row pair instead of two 8-byte ones.
-#pragma unroll
-      for (int cp = 0; cp < 2; ++cp) {
-        unsigned pk[2][2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          float v[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float f = acc[2 * cp + h][j];
-              if (RangeCheck<T>::on) bad |= RangeCheck<T>::bad(f);
-            v[j] = f;
-          }
-          pk[h][0] = (unsigned)to_bits<T>(v[0]) | ((unsigned)to_bits<T>(v[1]) << 16);
-          pk[h][1] = (unsigned)to_bits<T>(v[2]) | ((unsigned)to_bits<T>(v[3]) << 16);
-        }
-        const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
-        const int row = 2 * (2 * cp + (g & 1));            // even g: row of c = 2 cp, odd g: row of c = 2 cp + 1
-        if (!full_xy && !((yl + row < p.H) & (xl < p.W))) continue;
-        *(uint4*)(out_w + (long long)zo * p.oz + row * p.oy) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
-      }
-    } else if (zo < ze && !(p.dbg & 4)) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        if (!full_xy && !((yl + 2 * c < p.H) & (xl < p.W))) continue;
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float f = acc[c][j];
-          if (OUTMODE == 0 && RangeCheck<T>::on) bad |= RangeCheck<T>::bad(f);   // the value about to be stored
-          v[j] = f;
-        }
-        if (OUTMODE == 0) {
-          char* dst = out_l + (long long)zo * p.oz + (2 * c) * p.oy;
-          *(uint2*)dst = make_uint2((unsigned)to_bits<T>(v[0]) | ((unsigned)to_bits<T>(v[1]) << 16),
-                                    (unsigned)to_bits<T>(v[2]) | ((unsigned)to_bits<T>(v[3]) << 16));
-        } else {
-          float* dst = out32_l + (long long)zo * p.pz + (2 * c) * p.py;
-          if (p.wmap) {
-            const float wgt = p.wmap[((long long)zo * p.H + yl + 2 * c) * p.W + xl];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dst[(long long)j * p.pc] += wgt * v[j];
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dst[(long long)j * p.pc] = v[j];
-          }
-        }
-      }
-    }
+    if (OUTMODE == 0 && fast) epilogue(Const<1>{}, s, acc);
+    else epilogue(Const<0>{}, s, acc);
+    if constexpr (OUTMODE == 0) zb += 2 * p.oz;
   }
-  if (OUTMODE == 0 && RangeCheck<T>::on) raise_flag(p.oflow, bad);
+  if (OUTMODE == 0 && RangeCheck<T>::on) raise_flag(p.oflow, RangeCheck<T>::bad_bits(amax));
 }
 
 // Weights for conv3d_upcat16: fp32 w[16][48][27] (* folded gain) ->
@@ -372,17 +373,26 @@ bool conv_upcat16_eligible(const ConvParams& p) {
          !(p.D & 1) && !(p.H & 1) && !(p.W & 1);
 }
 
-template <typename T, int OUTMODE>
+template <typename T, int OUTMODE, int ACT = -1>
 static hipError_t launch_upcat_t(ConvParams p, hipStream_t st, ConvLaunchInfo* info) {
   typedef UpcatCfg C;
+  if constexpr (ACT < 0) {   // the activation's kernel symbol (anything but relu / leaky relu is "none", as in act_inplace)
+    if (p.act == ACT_RELU) return launch_upcat_t<T, OUTMODE, ACT_RELU>(p, st, info);
+    if (p.act == ACT_LRELU) return launch_upcat_t<T, OUTMODE, ACT_LRELU>(p, st, info);
+    return launch_upcat_t<T, OUTMODE, ACT_NONE>(p, st, info);
+  } else {
   if (info) info->report(0, "conv3d_upcat16<%s,2x8x32,c8+l3,r%d/%d,o%d>", __is_same(T, f16) ? "f16" : "bf16", C::R, C::RL, OUTMODE);
-  auto kern = conv3d_upcat16_kernel<T, OUTMODE>;
+  auto kern = conv3d_upcat16_kernel<T, OUTMODE, ACT>;
   static amx::DeviceOnce attr_once;
   if (!attr_once.done()) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
     if (e != hipSuccess) return e;
     attr_once.set();
   }
+  // the stores address a plane as "pointer + 32-bit lane offset": a 16-bit output plane (and a tile beyond it, for the masked lanes of a
+  // partial tile) must stay below 2 GiB -- refused here rather than wrapped in the kernel (H * W beyond 6e7 voxels at 16 channels; this
+  // kernel has no second output)
+  if (p.out && (p.H + C::TY) * p.oy + (p.W + C::TX) * p.ox >= (1LL << 31)) return hipErrorInvalidValue;
   p.nby = (p.H + C::TY - 1) / C::TY;
   p.nbx = (p.W + C::TX - 1) / C::TX;
   const int tiles = p.nby * p.nbx * p.N;
@@ -390,6 +400,7 @@ static hipError_t launch_upcat_t(ConvParams p, hipStream_t st, ConvLaunchInfo* i
   pick_z_segments(tiles, p.D, 2, 256 * (C::LDS_BYTES <= 80 * 1024 ? 2 : 1), &zseg, &nseg);
   hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * nseg)), dim3((C::NC + C::NL) * 64), C::LDS_BYTES, st, p, zseg, nseg);
   return hipGetLastError();
+  }
 }
 
 // p.wpk must point at the upcat16 packing (pack_upcat16_kernel).

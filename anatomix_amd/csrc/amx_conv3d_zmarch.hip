@@ -122,7 +122,10 @@ struct ZmStemCfg {
 // 32-channel input -- and the step is swept twice: the hi planes against Wh and Wl (two MFMAs per fragment read), the lo planes
 // against Wh (Wh / Wl are the two packed "chunks" and stay in registers like the two chunks of the 32-channel kernel); the
 // epilogue splits the fp32 result again.
-template <typename T, int NCK, int QT, int TY, int TX, int R, int OUTMODE, int NS, bool POOL, bool SPLIT = false, bool STEM = false>
+// ACT: the layer's activation is a compile-time variant too (launch_zm_ns picks the symbol from ConvParams::act): the epilogue holds no
+// activation test and no merge of differently activated accumulators (as a run-time branch around the values it cost a copy of all
+// 16 accumulators per step).
+template <typename T, int NCK, int QT, int TY, int TX, int R, int OUTMODE, int NS, bool POOL, bool SPLIT = false, bool STEM = false, int ACT = ACT_NONE>
 __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT ? 2 : NCK)) + NS) * 64) void conv3d_k3_zmarch_kernel(const ConvParams p, int zseg, int nseg, const StemIn si) {
   static_assert(!SPLIT || (NCK == 1 && QT == 1 && NS == 0), "strict z-march: 16 -> 16, direct stores");
   static_assert(!STEM || (NCK == 1 && !SPLIT && NS == 0 && OUTMODE == 0), "stem-fed z-march: 16 input channels, direct 16-bit stores");
@@ -189,7 +192,7 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         flag_store_asm(a_stored, s + 1);
         const int zo = zs + s * TZ + w;
-        if (zo >= ze || (p.dbg & 4)) continue;
+        if (zo >= ze) continue;
         char* dst = gbase + (long long)zo * p.oz;
 #pragma unroll
         for (int r = 0; r < NR; ++r) *(uint4*)(dst + (long long)(r / QT) * p.oy + (r % QT) * 1024) = v[r];
@@ -207,7 +210,7 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         flag_store_asm(a_stored, s + 1);
         const int zo = zs + s * TZ + w;
-        if (zo >= ze || (p.dbg & 4)) continue;
+        if (zo >= ze) continue;
         float* dst = gbase + (long long)zo * p.pz;
         if (p.wmap) {   // sliding-window accumulate: acc += wmap * feature
           const float4 wg = *(const float4*)(p.wmap + ((long long)zo * p.H + y0 + y) * p.W + x0 + xq * 4);
@@ -484,6 +487,7 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
     // =========================== loader wave: channel plane cp = wave - NC ===========================
     static_assert(STEM || C::VMCNT_OK, "loader wave must not exceed the 6-bit vmcnt range");
     const int cp = wave - NC;
+    const int lane = lane_id();        // (its own copy: the workgroup's lane-id register would stay alive across the consumers' march)
     int off[NDMA];                     // per-lane source offset of halo voxel hv = 64*j + lane (fixed for the march)
     bool valid[NDMA];
 #pragma unroll
@@ -533,8 +537,19 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
 #pragma unroll
     for (int s = 0; s < kSteps; ++s) wreg[k][s] = *(const vec8*)(p.wpk + ((k * kSteps + s) * QT + wq) * 1024 + lane * 16);
   const int cb = g * 4 * QT + wq * 4;                      // lane holds output channels cb .. cb+3
+  // TIGHT (two channel chunks: 28 resident weight fragments + the rolling slots fill the 168 registers of a 12-wave workgroup): what the
+  // sweep does not read stays out of the vector registers across it, or hipcc parks it in scratch memory and fetches it back every
+  // step through the vector-memory queue that the stores need.  The bias is ONE register (quad lane i holds channel cb + i) expanded
+  // by four DPP moves per step; the lane offsets of the stores are re-formed from the lane id per step; the range check is reduced
+  // per step into a scalar flag.
+  constexpr bool TIGHT = NCKP > 1 && !SPLIT;
   f32x4 bias = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (p.bias) bias = *(const f32x4*)(p.bias + cb);
+  float bias_q = 0.f;
+  if constexpr (TIGHT) {
+    if (p.bias) bias_q = p.bias[cb + (lane & 3)];
+  } else {
+    if (p.bias) bias = *(const f32x4*)(p.bias + cb);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
   const int lanebase = (g & 1) * PPL + ((wrow * HX) + wcx * 16 + li) * 16;
@@ -542,13 +557,21 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
   const int base_dx = lanebase + hi * 16 * HX;
   const bool full_xy = (y0 + TY <= p.H) & (x0 + TX <= p.W);
 
-  // per-lane output bases (plane z added per step)
+  // ---- output addresses: formed ONCE per march.  16-bit outputs (direct stores): a wave-uniform plane pointer that ADVANCES by the
+  // step's stride in scalar registers (the rule of the ring addresses) + a 32-bit lane offset inside the plane
+  // that never changes, so a store is "scalar base + lane offset" with no address arithmetic on the vector unit.
   const int yl = y0 + wrow, xl = x0 + wcx * 16 + li;
-  char* out_l = OUTMODE == 0 ? p.out + (long long)n * p.on + (long long)yl * p.oy + (long long)xl * p.ox + cb * 2 : nullptr;
-  float* out32_l = OUTMODE == 1 ? p.out32 + (long long)n * p.pn + (long long)cb * p.pc + (long long)yl * p.py + xl : nullptr;
   constexpr bool WIDE = OUTMODE == 0 && NS == 0 && QT == 1;
-  // WIDE: lane (g, li) stores channels 8 (g >> 1) .. + 7 of voxel (row yl + (g & 1), xl)
-  char* out_w = WIDE ? p.out + (long long)n * p.on + (long long)(yl + (g & 1)) * p.oy + (long long)xl * p.ox + (g >> 1) * 16 : nullptr;
+  constexpr bool DIRECT16 = OUTMODE == 0 && NS == 0;        // 16-bit stores from the accumulators: the fast / guarded split below
+  // WIDE: lane (g, li) stores channels 8 (g >> 1) .. + 7 of voxel (row yl + (g & 1), xl); else channels cb .. cb + 3 of (yl + cy, xl)
+  const unsigned lo_w = WIDE ? (unsigned)((yl + (g & 1)) * (int)p.oy + xl * (int)p.ox + (g >> 1) * 16) : 0u;
+  const unsigned lo_l = (DIRECT16 && !TIGHT) ? (unsigned)(yl * (int)p.oy + xl * (int)p.ox + cb * 2) : 0u;
+  char* zb = DIRECT16 ? p.out + (long long)n * p.on + (long long)zs * p.oz : nullptr;       // plane zs + 2 s of sample n (uniform)
+  if constexpr (TIGHT) zb += (long long)yl * p.oy + (long long)(x0 + wcx * 16) * p.ox + wq * 8;   // (the uniform part of the lane offset)
+  // lane predicates of the guarded path (partial tiles), fixed for the march
+  const bool ok_w = full_xy || ((yl + (g & 1) < p.H) & (xl < p.W));
+  const bool ok_l0 = full_xy || ((yl < p.H) & (xl < p.W)), ok_l1 = full_xy || ((yl + 1 < p.H) & (xl < p.W));
+  float* out32_l = OUTMODE == 1 ? p.out32 + (long long)n * p.pn + (long long)cb * p.pc + (long long)yl * p.py + xl : nullptr;
   // fp32 planar output with 16-byte stores needs x-quads that never straddle a row and aligned planes
   const bool vec_planar = OUTMODE == 1 && !(p.W & 3) && !(p.py & 3) && !(p.pz & 3) && !(p.pc & 3) && !(p.pn & 3) &&
                           !((size_t)p.out32 & 15) && !((size_t)p.wmap & 15);
@@ -556,21 +579,177 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
                                       x0 + wcx * 16 + (li & ~3)
                                 : nullptr;
   // fused 2x2x2 max-pool output (dense 16-bit NDHWC at half resolution); even lanes store
-  char* out2_l = (OUTMODE == 0 && POOL) ? p.out2 + (long long)n * p.qn + (long long)(yl >> 1) * p.qy +
-                                               (long long)(xl >> 1) * p.qx + cb * 2
-                                          : nullptr;
+  constexpr bool DOPOOL = OUTMODE == 0 && POOL;
+  const unsigned lo_p = (DOPOOL && !TIGHT) ? (unsigned)((yl >> 1) * (int)p.qy + (xl >> 1) * (int)p.qx + cb * 2) : 0u;
+  char* zb2 = DOPOOL ? p.out2 + (long long)n * p.qn + (long long)(zs >> 1) * p.qz : nullptr;   // pooled plane (zs >> 1) + s (uniform)
+  if constexpr (TIGHT && DOPOOL) zb2 += (long long)(yl >> 1) * p.qy + (long long)((x0 + wcx * 16) >> 1) * p.qx + wq * 8;   // (yl, x0 + 16 wcx: even)
+  const bool ok_p = !(li & 1) && (full_xy || ((yl + 1 < p.H) & (xl + 1 < p.W)));
 
-  bool bad = false;
-  // optional cycle trace (dbg bit 8, never set by the launcher): consumer waves 0 and 4 of a few workgroups stamp s_memtime per phase
-  unsigned long long* trace = (p.dbg & 8) && (wave == 0 || wave == 4) && lane == 0 && blockIdx.x < 500
-                                  ? (unsigned long long*)p.stats + ((long long)blockIdx.x * 2 + (wave >> 2)) * 128 : nullptr;
-  int tcount = 0;
-#define AMX_ZSTAMP()                                                             \
-  do {                                                                           \
-    if (trace && tcount < 128) trace[tcount] = __builtin_readcyclecounter();     \
-    ++tcount;                                                                    \
-  } while (0)
-  AMX_ZSTAMP();
+  // A step is FAST when nothing of it needs a predicate: the wave's tile is whole in y and x (picked once per march) and both output
+  // planes lie inside the segment (every step but an odd segment's last).  Its epilogue then has no per-store test at all; the
+  // guarded epilogue keeps the per-lane and per-plane predicates for the edge tiles and the tail step.
+  const int nfast = (DIRECT16 && full_xy) ? (ze - zs) / TZ : 0;
+  const unsigned a_done_w = lds_addr(done + wave);
+  unsigned amax_march = 0;                                  // running range check (RangeCheck<T>::track), reduced once after the march
+  unsigned long long bad = 0;                               // (TIGHT: reduced per step, as a lane mask in scalar registers)
+
+  // One step's epilogue, compiled per path (FAST) for the kernel's activation ACT: no activation test, no copy of the accumulators
+  // and no predicate inside the values.
+  auto epilogue = [&](auto fast_c, const int s, f32x4 (&acc)[2][2]) {
+    constexpr bool FAST = decltype(fast_c)::value != 0;
+    constexpr bool CHECK = OUTMODE == 0 && RangeCheck<T>::on;
+    // relu'd values are >= +0: their 16-bit patterns order like unsigned integers, so the pool runs on the PACKED pairs (rounding is
+    // monotonic: the maximum of the rounded values is the rounded maximum) -- one v_pk_max_u16 per two values, nothing live in fp32
+    constexpr bool PKPOOL = DOPOOL && ACT == ACT_RELU && !SPLIT;
+    act_values<ACT, 4>(&acc[0][0], p.slope);
+    // (opaque copies: the 32-bit lane offsets meet their scalar base inside this block, which is what selects the "scalar base + lane
+    //  offset" store form; hoisted out of the march as 64-bit values they cost an add on the vector unit per store)
+    unsigned ow = WIDE ? lo_w : lo_l, op = lo_p, amax = amax_march;
+    int li_e = li;
+    if constexpr (TIGHT) {
+      const int l = lane_id();
+      li_e = l & 15;
+      ow = (unsigned)(li_e * (int)p.ox + (l >> 4) * (8 * QT));
+      op = (unsigned)((li_e >> 1) * (int)p.qx + (l >> 4) * (8 * QT));
+      amax = 0;
+    } else {
+      if constexpr (DIRECT16) asm volatile("" : "+v"(ow));
+      if constexpr (DOPOOL) asm volatile("" : "+v"(op));
+    }
+    [[maybe_unused]] float pooled[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+    [[maybe_unused]] unsigned ppk[2] = {0u, 0u};
+#pragma unroll
+    for (int tz = 0; tz < 2; ++tz) {
+      const int zo = zs + s * TZ + tz;
+      const bool zok = FAST || zo < ze;                      // (uniform)
+      unsigned pk[2][2];
+      if constexpr (OUTMODE == 0) {
+#pragma unroll
+        for (int cy = 0; cy < 2; ++cy) {
+          const f32x4 v = acc[tz][cy];
+          if (CHECK && zok) {                                // the values about to be stored
+            amax = RangeCheck<T>::template track<ACT == ACT_RELU>(amax, v[0], v[1]);
+            amax = RangeCheck<T>::template track<ACT == ACT_RELU>(amax, v[2], v[3]);
+          }
+          pk[cy][0] = Ops<T>::pack2(v[0], v[1]);
+          pk[cy][1] = Ops<T>::pack2(v[2], v[3]);
+          if constexpr (PKPOOL) {
+            ppk[0] = pk_umax16(ppk[0], pk[cy][0]);
+            ppk[1] = pk_umax16(ppk[1], pk[cy][1]);
+          } else if constexpr (DOPOOL) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pooled[j] = v[j] > pooled[j] ? v[j] : pooled[j];
+          }
+        }
+      }
+      if constexpr (WIDE) {
+        // Cout = 16, 16-bit channels-last output: the rows cy = 0 / 1 of a lane quartet (g, g ^ 1) are exchanged with one
+        // v_permlane16_swap per dword so that every lane owns 8 consecutive channels of ONE voxel: one 16-byte store per lane
+        // (a wave instruction = two 512-byte rows) instead of two 8-byte ones.  SPLIT: the same for the lo halves, which sit
+        // Cout channels further on in the voxel.
+        // odd rows of pk[0] <-> even rows of pk[1]: even g keeps row cy = 0 (its own 4 channels + the 4 of g + 1), odd g row cy = 1
+        const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
+        const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
+        unsigned l0a = 0, l0b = 0, l1a = 0, l1b = 0;
+        if constexpr (SPLIT) {
+          unsigned pl[2][2];
+#pragma unroll
+          for (int cy = 0; cy < 2; ++cy) {
+            float r[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = acc[tz][cy][j] - (float)(T)acc[tz][cy][j];
+            pl[cy][0] = Ops<T>::pack2(r[0], r[1]);
+            pl[cy][1] = Ops<T>::pack2(r[2], r[3]);
+          }
+          const auto t0 = __builtin_amdgcn_permlane16_swap(pl[0][0], pl[1][0], false, false);
+          const auto t1 = __builtin_amdgcn_permlane16_swap(pl[0][1], pl[1][1], false, false);
+          l0a = t0[0]; l0b = t0[1]; l1a = t1[0]; l1b = t1[1];
+        }
+        if (FAST || (zok && ok_w)) {
+          char* dst = zb + (tz ? p.oz : 0) + ow;
+          *(uint4*)dst = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+          if constexpr (SPLIT) *(uint4*)(dst + p.Cout * 2) = make_uint4(l0a, l1a, l0b, l1b);
+        }
+      } else {
+#pragma unroll
+        for (int cy = 0; cy < 2; ++cy) {
+          if constexpr (NS > 0) {
+            if (OUTMODE == 0) {
+              char* dst = smem + STAGEOFF + (s % SG::NB) * SG::BYTES + (((tz * TY + wrow + cy) * TX) + wcx * 16 + li) * SG::CB + cb * 2;
+              *(uint2*)dst = make_uint2(pk[cy][0], pk[cy][1]);
+            } else {
+              float v[4] = {acc[tz][cy][0], acc[tz][cy][1], acc[tz][cy][2], acc[tz][cy][3]};
+              quad_transpose4(v, li);          // lane: channel cb + (li&3), x = (li&~3) .. +3
+              char* dst = smem + STAGEOFF + (cb + (li & 3)) * SG::CS + ((tz * TY + wrow + cy) * TX + wcx * 16 + (li & ~3)) * 4;
+              *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
+            }
+          } else if constexpr (OUTMODE == 0) {
+            if (FAST || (zok && (cy ? ok_l1 : ok_l0)))
+              *(uint2*)(zb + (tz ? p.oz : 0) + (cy ? p.oy : 0) + ow) = make_uint2(pk[cy][0], pk[cy][1]);
+          } else {
+            if (!zok || !(cy ? ok_l1 : ok_l0)) continue;
+            float v[4] = {acc[tz][cy][0], acc[tz][cy][1], acc[tz][cy][2], acc[tz][cy][3]};
+            if (vec_planar) {
+              // 4x4 transpose inside each lane quad (DPP, no LDS): lane (li, g) ends up with channel
+              // cb + (li&3) at x = (li&~3) .. +3, i.e. ONE 16-byte store per lane instead of four 4-byte ones.
+              quad_transpose4(v, li);
+              float* dst = out32_q + (long long)zo * p.pz + cy * p.py;
+              float4 o = make_float4(v[0], v[1], v[2], v[3]);
+              if (p.wmap) {
+                const float4 wg = *(const float4*)(p.wmap + ((long long)zo * p.H + yl + cy) * p.W + x0 + wcx * 16 + (li & ~3));
+                const float4 old = *(const float4*)dst;
+                o = make_float4(old.x + wg.x * o.x, old.y + wg.y * o.y, old.z + wg.z * o.z, old.w + wg.w * o.w);
+              }
+              *(float4*)dst = o;     // (a nontemporal store here measured 16 % slower: 282 vs 242 us at batch 4)
+            } else {
+              float* dst = out32_l + (long long)zo * p.pz + cy * p.py;
+              if (p.wmap) {
+                const float wgt = p.wmap[((long long)zo * p.H + yl + cy) * p.W + xl];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dst[(long long)j * p.pc] += wgt * v[j];
+              } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dst[(long long)j * p.pc] = v[j];
+              }
+            }
+          }
+        }
+      }
+    }
+    if constexpr (NS > 0) {
+      asm volatile("" ::: "memory");                        // LDS is in-order: the flag lands after the staged data
+      flag_store(staged + wave, s + 1);
+    }
+    if constexpr (DOPOOL) {
+      // the wave's 2 x 2 x 16 block is one max-pool window per x pair: exchange with lane ^ 1, even lanes store.
+      const bool pst = FAST || (zs + s * TZ + 1 < ze && ok_p);
+      if constexpr (PKPOOL) {
+        const unsigned m0 = pk_umax16(ppk[0], dpp_xor1(ppk[0])), m1 = pk_umax16(ppk[1], dpp_xor1(ppk[1]));
+        if (FAST ? !(li_e & 1) : pst) *(uint2*)(zb2 + op) = make_uint2(m0, m1);
+      } else {
+        // (rounding is monotonic, so pooling the fp32 values equals pooling the stored 16-bit values.)
+        float pm[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float o = dpp_quad<0xB1>(pooled[j]);
+          pm[j] = pooled[j] > o ? pooled[j] : o;
+        }
+        if (FAST ? !(li_e & 1) : pst) {
+          char* dst = zb2 + op;
+          *(uint2*)dst = make_uint2(Ops<T>::pack2(pm[0], pm[1]), Ops<T>::pack2(pm[2], pm[3]));
+          if constexpr (SPLIT) {    // hi + lo is monotonic in the fp32 value: the split of the maximum IS the stored maximum
+            float r[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = pm[j] - (float)(T)pm[j];
+            *(uint2*)(dst + p.Cout * 2) = make_uint2(Ops<T>::pack2(r[0], r[1]), Ops<T>::pack2(r[2], r[3]));
+          }
+        }
+      }
+    }
+    if constexpr (TIGHT) bad |= __builtin_amdgcn_ballot_w64(RangeCheck<T>::bad_bits(amax));
+    else amax_march = amax;
+  };
+
   for (int s = 0; s < nsteps; ++s) {
     {
       int need = TZ * s + TZ + 2;                          // planes q <= TZ*s + TZ + 1 must have landed
@@ -584,7 +763,6 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
       asm volatile("" ::: "memory");
     }
 
-    AMX_ZSTAMP();                                            // [planes landed]
     // ring slots of the four input planes zs+2s-1 .. zs+2s+2  (q = 2s + pl)
     int b1[4], bx3[4];
 #pragma unroll
@@ -598,12 +776,12 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
 #pragma unroll
     for (int tz = 0; tz < 2; ++tz)
 #pragma unroll
-      for (int cy = 0; cy < 2; ++cy) acc[tz][cy] = bias;
+      for (int cy = 0; cy < 2; ++cy) {
+        if constexpr (TIGHT) acc[tz][cy] = f32x4{dpp_quad<0x00>(bias_q), dpp_quad<0x55>(bias_q), dpp_quad<0xAA>(bias_q), dpp_quad<0xFF>(bias_q)};
+        else acc[tz][cy] = bias;
+      }
 
-    // TIMING-ONLY experiment (dbg bits 10..12 = extra sweeps per step; results are garbage): what a layer costs when its matrix
-    // work is doubled / tripled at unchanged traffic -- the lower bound of a conv -> conv chain through the ring
-    for (int rep = (p.dbg >> 10) & 7; rep >= 0; --rep)
-    if (!(p.dbg & 2)) {
+    {
       if constexpr ((NCKP > 1 && !SPLIT) || STEM) {   // (STEM: 16 waves per workgroup leave each 128 registers -- no room for the double-buffered plane sets below)
         // Two (or, SPLIT, two passes over) channel chunks: 28 resident weight fragments leave room for ONE set of six ring fragments, and
         // "read a plane's six, then its 16 MFMAs" (the first form) exposed the LDS round trip eight times per step -- a wave's sweep
@@ -738,154 +916,37 @@ __global__ __launch_bounds__((8 + (STEM ? ZmStemCfg<8, 32>::NSW + 1 : 2 * (SPLIT
       }
       }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // every ring read of this step has returned
-    flag_store(done + wave, s + 1);
-    AMX_ZSTAMP();                                            // [sweep done]
+    if constexpr (TIGHT) {   // (the flag's address re-formed from a scalar: no vector register holds it across the sweep)
+      unsigned da = a_done_w;
+      asm volatile("" : "+s"(da));
+      flag_store((int*)(__attribute__((address_space(3))) int*)(size_t)da, s + 1);
+    } else {
+      flag_store(done + wave, s + 1);
+    }
 
     // ---- epilogue: activation + store (never waited for)
-    if (p.dbg & 4) {
-      if (NS) flag_store(staged + wave, s + 1);
-      continue;
-    }
     if constexpr (NS > 0) {   // the staging tile still holds step s-1 until both storers have read it into registers
       if (s >= SG::NB)
         while (flag_min2(stored) < s + 1 - SG::NB) __builtin_amdgcn_s_sleep(1);
       asm volatile("" ::: "memory");
     }
-    act_inplace<4>(&acc[0][0], p.act, p.slope);
-    float pooled[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
-#pragma unroll
-    for (int tz = 0; tz < 2; ++tz) {
-      const int zo = zs + s * TZ + tz;
-      if (WIDE && (SPLIT || !(p.dbg & 32))) {
-        // Cout = 16, 16-bit channels-last output: the rows cy = 0 / 1 of a lane quartet (g, g ^ 1) are exchanged with one
-        // v_permlane16_swap per dword so that every lane owns 8 consecutive channels of ONE voxel: one 16-byte store per lane
-        // (a wave instruction = two 512-byte rows) instead of two 8-byte ones.  SPLIT: the same for the lo halves, which sit
-        // Cout channels further on in the voxel.
-        unsigned pk[2][2], pl[SPLIT ? 2 : 1][2];
-#pragma unroll
-        for (int cy = 0; cy < 2; ++cy) {
-          float v[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float f = acc[tz][cy][j];
-              if (RangeCheck<T>::on) bad |= RangeCheck<T>::bad(f);
-            v[j] = f;
-            pooled[j] = f > pooled[j] ? f : pooled[j];
-          }
-          pk[cy][0] = (unsigned)to_bits<T>(v[0]) | ((unsigned)to_bits<T>(v[1]) << 16);
-          pk[cy][1] = (unsigned)to_bits<T>(v[2]) | ((unsigned)to_bits<T>(v[3]) << 16);
-          if constexpr (SPLIT) {
-            float r[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) r[j] = v[j] - (float)(T)v[j];
-            pl[cy][0] = (unsigned)to_bits<T>(r[0]) | ((unsigned)to_bits<T>(r[1]) << 16);
-            pl[cy][1] = (unsigned)to_bits<T>(r[2]) | ((unsigned)to_bits<T>(r[3]) << 16);
-          }
-        }
-        // odd rows of pk[0] <-> even rows of pk[1]: even g keeps row cy = 0 (its own 4 channels + the 4 of g + 1), odd g row cy = 1
-        const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
-        unsigned l0a = 0, l0b = 0, l1a = 0, l1b = 0;
-        if constexpr (SPLIT) {
-          const auto t0 = __builtin_amdgcn_permlane16_swap(pl[0][0], pl[1][0], false, false);
-          const auto t1 = __builtin_amdgcn_permlane16_swap(pl[0][1], pl[1][1], false, false);
-          l0a = t0[0]; l0b = t0[1]; l1a = t1[0]; l1b = t1[1];
-        }
-        if (zo >= ze) continue;
-        if (!full_xy && !((yl + (g & 1) < p.H) & (xl < p.W))) continue;
-        *(uint4*)(out_w + (long long)zo * p.oz) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
-        if constexpr (SPLIT) *(uint4*)(out_w + (long long)zo * p.oz + p.Cout * 2) = make_uint4(l0a, l1a, l0b, l1b);
-        continue;
-      }
-#pragma unroll
-      for (int cy = 0; cy < 2; ++cy) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float f = acc[tz][cy][j];
-          if (OUTMODE == 0 && RangeCheck<T>::on) bad |= RangeCheck<T>::bad(f);   // the value about to be stored
-          v[j] = f;
-          pooled[j] = f > pooled[j] ? f : pooled[j];
-        }
-        if constexpr (NS > 0) {
-          if (OUTMODE == 0) {
-            char* dst = smem + STAGEOFF + (s % SG::NB) * SG::BYTES + (((tz * TY + wrow + cy) * TX) + wcx * 16 + li) * SG::CB + cb * 2;
-            *(uint2*)dst = make_uint2((unsigned)to_bits<T>(v[0]) | ((unsigned)to_bits<T>(v[1]) << 16),
-                                      (unsigned)to_bits<T>(v[2]) | ((unsigned)to_bits<T>(v[3]) << 16));
-          } else {
-            quad_transpose4(v, li);          // lane: channel cb + (li&3), x = (li&~3) .. +3
-            char* dst = smem + STAGEOFF + (cb + (li & 3)) * SG::CS + ((tz * TY + wrow + cy) * TX + wcx * 16 + (li & ~3)) * 4;
-            *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-          }
-          continue;
-        }
-        if (zo >= ze) continue;
-        if (!full_xy && !((yl + cy < p.H) & (xl < p.W))) continue;
-        if (OUTMODE == 0) {
-          char* dst = out_l + (long long)zo * p.oz + cy * p.oy;
-          *(uint2*)dst = make_uint2((unsigned)to_bits<T>(v[0]) | ((unsigned)to_bits<T>(v[1]) << 16),
-                                    (unsigned)to_bits<T>(v[2]) | ((unsigned)to_bits<T>(v[3]) << 16));
-        } else if (vec_planar) {
-          // 4x4 transpose inside each lane quad (DPP, no LDS): lane (li, g) ends up with channel
-          // cb + (li&3) at x = (li&~3) .. +3, i.e. ONE 16-byte store per lane instead of four 4-byte ones.
-          quad_transpose4(v, li);
-          float* dst = out32_q + (long long)zo * p.pz + cy * p.py;
-          float4 o = make_float4(v[0], v[1], v[2], v[3]);
-          if (p.wmap) {
-            const float4 wg = *(const float4*)(p.wmap + ((long long)zo * p.H + yl + cy) * p.W + x0 + wcx * 16 + (li & ~3));
-            const float4 old = *(const float4*)dst;
-            o = make_float4(old.x + wg.x * o.x, old.y + wg.y * o.y, old.z + wg.z * o.z, old.w + wg.w * o.w);
-          }
-          *(float4*)dst = o;     // (a nontemporal store here measured 16 % slower: 282 vs 242 us at batch 4)
-        } else {
-          float* dst = out32_l + (long long)zo * p.pz + cy * p.py;
-          if (p.wmap) {
-            const float wgt = p.wmap[((long long)zo * p.H + yl + cy) * p.W + xl];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dst[(long long)j * p.pc] += wgt * v[j];
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dst[(long long)j * p.pc] = v[j];
-          }
-        }
-      }
-    }
-    if constexpr (NS > 0) {
-      asm volatile("" ::: "memory");                        // LDS is in-order: the flag lands after the staged data
-      flag_store(staged + wave, s + 1);
-    }
-    if constexpr (OUTMODE == 0 && POOL) {
-      // the wave's 2 x 2 x 16 block is one max-pool window per x pair: exchange with lane ^ 1, even lanes store.
-      // (rounding is monotonic, so pooling the fp32 values equals pooling the stored 16-bit values.)
-      float pm[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float o = dpp_quad<0xB1>(pooled[j]);
-        pm[j] = pooled[j] > o ? pooled[j] : o;
-      }
-      const int zp = (zs + s * TZ) >> 1;
-      if (!(li & 1) && zs + s * TZ + 1 < ze && (full_xy || ((yl + 1 < p.H) & (xl + 1 < p.W)))) {
-        char* dst = out2_l + (long long)zp * p.qz;
-        *(uint2*)dst = make_uint2((unsigned)to_bits<T>(pm[0]) | ((unsigned)to_bits<T>(pm[1]) << 16),
-                                  (unsigned)to_bits<T>(pm[2]) | ((unsigned)to_bits<T>(pm[3]) << 16));
-        if constexpr (SPLIT) {    // hi + lo is monotonic in the fp32 value: the split of the maximum IS the stored maximum
-          float r[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) r[j] = pm[j] - (float)(T)pm[j];
-          *(uint2*)(dst + p.Cout * 2) = make_uint2((unsigned)to_bits<T>(r[0]) | ((unsigned)to_bits<T>(r[1]) << 16),
-                                                   (unsigned)to_bits<T>(r[2]) | ((unsigned)to_bits<T>(r[3]) << 16));
-        }
-      }
-    }
-    AMX_ZSTAMP();                                            // [epilogue issued]
+    if (DIRECT16 && s < nfast) epilogue(Const<1>{}, s, acc);
+    else epilogue(Const<0>{}, s, acc);
+    if constexpr (DIRECT16) zb += TZ * p.oz;
+    if constexpr (DOPOOL) zb2 += p.qz;
   }
-  if (OUTMODE == 0 && RangeCheck<T>::on) raise_flag(p.oflow, bad);
+  if (OUTMODE == 0 && RangeCheck<T>::on) raise_flag(p.oflow, (bad != 0) | RangeCheck<T>::bad_bits(amax_march));
 }
 
-template <typename T, int NCK, int QT, int TY, int R, int OUTMODE, int NS, bool POOL = false, bool SPLIT = false, int TX = 32, bool STEM = false>
+template <typename T, int NCK, int QT, int TY, int R, int OUTMODE, int NS, bool POOL = false, bool SPLIT = false, int TX = 32, bool STEM = false, int ACT = -1>
 static hipError_t launch_zm_ns(ConvParams p, hipStream_t st, ConvLaunchInfo* info, const StemIn& si = StemIn{}) {
   if constexpr (OUTMODE == 0 && NS == 0 && !POOL && !STEM)
     if (p.out2) return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, NS, true, SPLIT, TX, STEM>(p, st, info, si);
+  if constexpr (ACT < 0) {   // the activation's kernel symbol (anything but relu / leaky relu is "none", as in act_inplace)
+    if (p.act == ACT_RELU) return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, NS, POOL, SPLIT, TX, STEM, ACT_RELU>(p, st, info, si);
+    if (p.act == ACT_LRELU) return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, NS, POOL, SPLIT, TX, STEM, ACT_LRELU>(p, st, info, si);
+    return launch_zm_ns<T, NCK, QT, TY, R, OUTMODE, NS, POOL, SPLIT, TX, STEM, ACT_NONE>(p, st, info, si);
+  } else {
   constexpr int TZ = 2;
   typedef ZmCfg<SPLIT ? 2 : NCK, QT, TY, TX, R> C;
   constexpr int LDS = STEM ? C::FLAGOFF + 128 + ZmStemCfg<TY, TX>::BYTES : NS ? C::FLAGOFF + 128 + ZmStage<QT, TY, TX, OUTMODE>::TOTAL : C::LDS_BYTES;
@@ -895,13 +956,17 @@ static hipError_t launch_zm_ns(ConvParams p, hipStream_t st, ConvLaunchInfo* inf
   else if (info)
     info->report(0, "conv3d_k3_zmarch<%s%s,%d->%d,%dx%dx%d,c8+l%d+s%d,r%d,o%d%s>", __is_same(T, f16) ? "f16" : "bf16", SPLIT ? "x2" : "",
                  16 * NCK, 16 * QT, TZ, TY, TX, C::NL, NS, R, OUTMODE, p.out2 ? ",pool" : "");
-  auto kern = conv3d_k3_zmarch_kernel<T, NCK, QT, TY, TX, R, OUTMODE, NS, POOL, SPLIT, STEM>;
+  auto kern = conv3d_k3_zmarch_kernel<T, NCK, QT, TY, TX, R, OUTMODE, NS, POOL, SPLIT, STEM, ACT>;
   static amx::DeviceOnce attr_once;
   if (!attr_once.done()) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     if (e != hipSuccess) return e;
     attr_once.set();
   }
+  // the stores address a plane as "pointer + 32-bit lane offset": a 16-bit output plane (and a row beyond it, for the masked lanes of a
+  // partial tile) must stay below 2 GiB
+  if (p.out && (p.H + TY) * p.oy + (p.W + TX) * p.ox >= (1LL << 31)) return hipErrorInvalidValue;
+  if (p.out2 && (p.H / 2 + TY) * p.qy + (p.W / 2 + TX) * p.qx >= (1LL << 31)) return hipErrorInvalidValue;
   p.nby = (p.H + TY - 1) / TY;
   p.nbx = (p.W + TX - 1) / TX;
   // z segments: enough workgroups to fill 256 CUs, each segment a multiple of TZ planes, >= 8 planes
@@ -910,6 +975,7 @@ static hipError_t launch_zm_ns(ConvParams p, hipStream_t st, ConvLaunchInfo* inf
   pick_z_segments(tiles, p.D, TZ, 256 * (LDS <= 80 * 1024 ? 2 : 1), &zseg, &nseg);
   hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * nseg)), dim3((8 + (STEM ? ZmStemCfg<TY, TX>::NSW + 1 : C::NL) + NS) * 64), LDS, st, p, zseg, nseg, si);
   return hipGetLastError();
+  }
 }
 
 // Storer waves (fp32 planar output) need full tiles.  Planar rows move as float4 pieces; global dwordx4 accesses only need dword

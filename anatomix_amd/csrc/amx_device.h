@@ -41,13 +41,27 @@ template <> struct Ops<bf16> {
 // f16 storage overflows at 65504; bf16 shares fp32's exponent range.  Epilogues that store f16 (or f16x2) values test them
 // with RangeCheck<T>::bad and raise ConvParams::oflow -- an overflow must never turn into silent Inf (or, behind a ReLU or
 // max-pool, silently finite) features.
+// Epilogues that check many values per step (the z-march family) keep the test on the vector unit: `track` folds two values into a
+// running UNSIGNED maximum of the magnitudes' bit patterns -- non-negative floats order like their patterns, and every NaN pattern lies
+// above Inf's -- and `bad_bits` compares it once, after the march: bad_bits(track(.. track(0, a, b) ..)) is the OR of bad(v) over
+// every tracked value, NaN included.  (bad() per value compiled to a compare into a scalar register pair plus a dependent scalar OR
+// for each value.)  NONNEG: the caller knows the sign bits are clear (values behind a relu), which saves the two masks.
 template <typename T> struct RangeCheck {
   static constexpr bool on = false;
   static __device__ __forceinline__ bool bad(float) { return false; }
+  template <bool NONNEG> static __device__ __forceinline__ unsigned track(unsigned amax, float, float) { return amax; }
+  static __device__ __forceinline__ bool bad_bits(unsigned) { return false; }
 };
 template <> struct RangeCheck<f16> {
   static constexpr bool on = true;
   static __device__ __forceinline__ bool bad(float v) { return !(__builtin_fabsf(v) <= 65504.f); }   // also true for NaN
+  template <bool NONNEG> static __device__ __forceinline__ unsigned track(unsigned amax, float a, float b) {
+    unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
+    if (!NONNEG) { ua &= 0x7fffffffu; ub &= 0x7fffffffu; }
+    ua = ua > ub ? ua : ub;
+    return amax > ua ? amax : ua;                                                                     // v_max3_u32
+  }
+  static __device__ __forceinline__ bool bad_bits(unsigned amax) { return amax > 0x477fe000u; }       // bits(65504.f)
 };
 __device__ __forceinline__ void raise_flag(int* flag, bool bad) {
   if (bad && flag) __atomic_store_n(flag, 1, __ATOMIC_RELAXED);
@@ -131,6 +145,16 @@ __device__ __forceinline__ unsigned short to_bits(float v) {
   return __builtin_bit_cast(unsigned short, t);
 }
 
+// the lane id from no live register (= threadIdx.x & 63 in these one-dimensional workgroups): for code that would otherwise keep a
+// lane-id register alive across a loop that has none to spare
+__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// per-half unsigned maximum of two packed pairs (v_pk_max_u16): the float maximum of 16-bit values whose sign bits are clear
+__device__ __forceinline__ unsigned pk_umax16(unsigned a, unsigned b) {
+  typedef __attribute__((ext_vector_type(2))) unsigned short u16x2;
+  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+
 // 4x4 transpose across the four lanes of a quad with DPP quad_perm moves (VALU only):
 // afterwards register j of quad lane i holds what register i of quad lane j held.
 template <int CTRL>
@@ -186,6 +210,27 @@ __device__ __forceinline__ void act_inplace(f32x4* a, int act, float slope) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) a[i][j] = a[i][j] > 0.f ? a[i][j] : a[i][j] * slope;
   }
+}
+
+// The activation for a COMPILE-TIME `ACT` (the z-march family: one kernel symbol per activation).  relu is one v_med3_f32 per value:
+// med3(v, 0, +inf) = v > 0 ? v : 0 for every v these kernels can hold -- written as the select it compiled to a canonicalising
+// v_max v, v, v in front of the v_max with 0.  What that rests on: with no NaN among the operands med3 is max(v, 0), and the
+// hardware's max orders -0 below +0, so -0 gives +0 like the select; with a NaN operand med3 returns min3, which drops a QUIET NaN and
+// gives min(0, +inf) = 0, like the select -- a SIGNALLING NaN would be quieted and returned instead, but v is an MFMA accumulator
+// (bias + products), and arithmetic results are never signalling.  tests/test_zmarch_epilogue_gpu.py holds both cases (stored bits of
+// non-positive pre-activations; NaN behind a relu stores 0 and raises nothing, as before).
+template <int V> struct Const { static constexpr int value = V; };
+template <int ACT, int N>
+__device__ __forceinline__ void act_values(f32x4* a, float slope) {
+  float pinf = __builtin_inff();                           // (opaque, in a scalar register: with a literal bound hipcc rewrites the
+  if constexpr (ACT == ACT_RELU) asm volatile("" : "+s"(pinf));   //  med3 into the canonicalise + max pair again)
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if constexpr (ACT == ACT_RELU) a[i][j] = __builtin_amdgcn_fmed3f(a[i][j], 0.f, pinf);
+      else if constexpr (ACT == ACT_LRELU) a[i][j] = a[i][j] > 0.f ? a[i][j] : a[i][j] * slope;
+    }
 }
 
 // Branch-free activation for the bandwidth-bound elementwise kernels (norm apply, BatchNorm forward / backward): k = 0 (relu),

@@ -280,6 +280,17 @@ int amx_conv3d_k3_reflect(const void* d_x0, int c0, const void* d_x1, int c1, co
                           int w, int act, float slope, int precision, void* d_wpk, void* d_out16,
                           float* d_out32, void* stream);
 
+/* Test aid (no reference counterpart): amx_conv3d_k3_reflect with the launch-side options that only amx_unet_forward sets otherwise,
+ * so that single-layer tests reach them and learn which kernel ran.  Each may be NULL: d_pool16, the fused 2x2x2 max-pool output
+ * [n][d/2][hh/2][w/2][cout] (16-bit output, a z-march layer with even extents: AMX_ERR_SHAPE otherwise); d_wmap, fp32 [d][hh][w], the
+ * fp32 planar epilogue then ACCUMULATES out32 += wmap * value into the caller's d_out32; d_oflow, a device int set to 1 when a value
+ * about to be stored in f16 lies outside the f16 range (or is NaN); kernel_name, 64 bytes on the host, the launch's name as in
+ * amx_launch_record::kernel. */
+int amx_conv3d_k3_reflect_probe(const void* d_x0, int c0, const void* d_x1, int c1, const float* d_weight, const float* d_scale,
+                                const float* d_shift, int cout, int n, int d, int hh, int w, int act, float slope, int precision,
+                                void* d_wpk, void* d_out16, float* d_out32, void* d_pool16, const float* d_wmap, int* d_oflow,
+                                char* kernel_name, void* stream);
+
 /* The same call with caller-owned scratch for the layers that split K across workgroups (deep levels with few voxels:
  * conv3d_k3_ks writes fp32 partial tensors per K slice, a second kernel sums them in slice order -- deterministic).
  * amx_conv3d_scratch_bytes returns 0 when the shape does not split; d_scratch may then be NULL. */
