@@ -140,6 +140,10 @@ SYMBOLS = {
     "amx_vit_workspace_bytes": (C.c_size_t, [_P, _I]),
     "amx_vit_forward": (_I, [_P, _P, _P, _I, _P, C.c_size_t, _I, _P]),
     "amx_vit_debug_read": (_I, [_P, C.c_char_p, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "amx_vit_windows_workspace_bytes": (C.c_size_t, [_P, _I]),
+    "amx_vit_forward_windows": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_int), _P, _P, _P, C.c_size_t, _P]),
+    "amx_vit_sliding_window_workspace_bytes": (C.c_size_t, [_P, _I]),
+    "amx_vit_sliding_window": (_I, [_P, _P, _I, _I, _I, C.c_double, _I, C.c_double, _I, _I, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _P]),
     "amx_linear": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "amx_supcon_scratch_bytes": (C.c_size_t, [_I, _I]),
     "amx_supcon_loss": (_I, [_P, _P, _I, _I, C.c_float, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),

@@ -15,7 +15,9 @@ enum GemmEpi {
   EPI_SCATTER_LN = 7, // ConvTranspose3d + channel LayerNorm + GELU: hi / lo operand rows of the next stage (Cp == 128)
   EPI_QK = 8,         // q | k projection with head-padded features (5 tiles per head): bias, per-head LayerNorm, rotary embedding,
                       // f16 operands of the attention kernel (Qp rows / K fragment tiles) -- replaces the fp32 q, k tensors + attn_prep
-  EPI_VT = 9          // v projection, token rows as the A operand: V^T fragment tiles (+ the ones row) of the attention kernel
+  EPI_VT = 9,         // v projection, token rows as the A operand: V^T fragment tiles (+ the ones row) of the attention kernel
+  EPI_PLANAR_ACC = 10 // EPI_PLANAR's values of ONE window (M = its rows) blended into the sliding-window accumulator instead of stored:
+                      // acc[c][oz + Z][oy + Y][ox + X] += wmap[Z][Y][X] * (value + bias[c] - sub[c]), plain load-add-store (one owner per element)
 };
 
 struct GemmParams {
@@ -45,6 +47,10 @@ struct GemmParams {
   float att_eps, qscale;        // LayerNorm epsilon; log2(e) / sqrt(hd)
   int T, n_prefix, heads, hd, npad, nblk_pad;   // tokens per sample, register tokens, heads, head_dim, padded tokens, key blocks
   void *Qp, *Kp, *Vt;
+  // EPI_PLANAR_ACC: `out` is the accumulator at the window's corner, fp32 [Creal][vd][vh][vw]; strides in floats
+  const float* wmap;            // window weights [2 gd][2 gh][2 gw]
+  long long acc_sc, acc_sz, acc_sy;   // channel / plane / row strides of the accumulator (vd vh vw, vh vw, vw)
+  int acc_vec;                  // 1: every quad of a row is 16-byte aligned in both the accumulator and the map (set by launch_gemm)
 };
 
 hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st);

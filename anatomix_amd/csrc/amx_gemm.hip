@@ -64,6 +64,57 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
     }
     return;
   }
+  if (EPI == EPI_PLANAR_ACC) {
+    // EPI_PLANAR's lane ownership and values for the rows of ONE window (p.M = its rows, b = 0), blended into the accumulator volume:
+    // a (channel, voxel) of the window belongs to exactly one lane, windows are launched in order on one stream -> load, add, store.
+    // The product and the sum are rounded separately (no fused multiply-add): the 16-byte and the scalar path give the same bits.
+    // Every load of a row tile is issued first, unconditionally at clamped indices (see the generic epilogue), then the stores.
+#pragma unroll
+    for (int u = 0; u < MT; ++u) {
+      const int m = m0 + u * 16 + 4 * g;
+      if (m >= p.M) continue;
+      const int x = m % p.gw, r1 = m / p.gw, y = r1 % p.gh, z = r1 / p.gh;
+      const bool even = !(li & 1);
+      float* o[NT];
+      float add[NT], cur[NT][4], w[NT][4];
+      bool live[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int nt = nt0 + t < p.ntiles ? nt0 + t : p.ntiles - 1;
+        const int n = nt * 16 + li, q = n >> 1, c = q % p.Cp, zy = q / p.Cp, cc = c < p.Creal ? c : 0;
+        live[t] = nt0 + t < p.ntiles && c < p.Creal;
+        add[t] = c < p.Creal ? p.bias[cc] - (p.sub ? p.sub[cc] : 0.f) : 0.f;
+        const int Z = 2 * z + (zy >> 1), Y = 2 * y + (zy & 1), X = 2 * x + (even ? 0 : 4);
+        const float* wm = p.wmap + ((long long)Z * 2 * p.gh + Y) * 2 * p.gw + X;
+        o[t] = (float*)p.out + cc * p.acc_sc + Z * p.acc_sz + Y * p.acc_sy + X;
+        if (p.acc_vec) {
+          const float4 w4 = *(const float4*)wm, c4 = *(const float4*)o[t];
+          w[t][0] = w4.x; w[t][1] = w4.y; w[t][2] = w4.z; w[t][3] = w4.w;
+          cur[t][0] = c4.x; cur[t][1] = c4.y; cur[t][2] = c4.z; cur[t][3] = c4.w;
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { w[t][r] = wm[r]; cur[t][r] = o[t][r]; }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const float v0 = acc[t][u][0] + add[t], v1 = acc[t][u][1] + add[t], v2 = acc[t][u][2] + add[t], v3 = acc[t][u][3] + add[t];
+        const float o0 = dpp_quad<0xB1>(even ? v2 : v0), o1 = dpp_quad<0xB1>(even ? v3 : v1);
+        if (!live[t]) continue;
+        const float val[4] = {even ? v0 : o0, even ? o0 : v2, even ? v1 : o1, even ? o1 : v3};
+        float r4[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) r4[r] = __fadd_rn(cur[t][r], __fmul_rn(w[t][r], val[r]));
+        if (p.acc_vec) {
+          *(float4*)o[t] = make_float4(r4[0], r4[1], r4[2], r4[3]);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o[t][r] = r4[r];
+        }
+      }
+    }
+    return;
+  }
   if (EPI == EPI_QK) {
     // One column block = one (q | k, head): NT = 5 tiles = the head's 80 padded features.  Lane (li, g) holds features
     // d = 16 t + 4 g .. + 3 of token row li: bias, per-head LayerNorm (sum over the lane's 20 values + the 4 lane groups),
@@ -412,7 +463,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int u = 0; u < MT; ++u) {
-        if (EPI == EPI_PLANAR || EPI == EPI_VT) {     // token rows as the A operand: a lane then owns 4 consecutive VOXELS / TOKENS of one feature
+        if (EPI == EPI_PLANAR || EPI == EPI_PLANAR_ACC || EPI == EPI_VT) {     // token rows as the A operand: a lane then owns 4 consecutive VOXELS / TOKENS of one feature
           acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[buf][u], wh[buf][t], acc[t][u], 0, 0, 0);
           if (SPLIT) {
             acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[buf][u], wh[buf][t], acc[t][u], 0, 0, 0);
@@ -534,7 +585,7 @@ __global__ __launch_bounds__(NW * 64) void wsgemm_kernel(GemmParams p, int rows_
       for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int u = 0; u < MT; ++u) {
-          if (EPI == EPI_PLANAR || EPI == EPI_VT) {
+          if (EPI == EPI_PLANAR || EPI == EPI_PLANAR_ACC || EPI == EPI_VT) {
             acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[B][u][i], wh[t], acc[t][u], 0, 0, 0);
             if (SPLIT) {
               acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[B][u][i], wh[t], acc[t][u], 0, 0, 0);
@@ -598,7 +649,7 @@ static hipError_t launch_ws(const GemmParams& p, hipStream_t st) {
   // The planar-output stage moves exactly its algorithmic bytes (0.54 GB in, 1.07 GB out: profiles/r03_vit_pmc_traffic.json) yet
   // runs at 2.7 TB/s.  Row blocks of 128 / 256 / 1024 / 5504 rows: 696 / 604 / 548 / 602 us -- 1024 it is.
   constexpr int planar_rows = 1024;
-  if (EPI == EPI_PLANAR && rows_per_wg > planar_rows) rows_per_wg = (planar_rows + unit - 1) / unit * unit;
+  if ((EPI == EPI_PLANAR || EPI == EPI_PLANAR_ACC) && rows_per_wg > planar_rows) rows_per_wg = (planar_rows + unit - 1) / unit * unit;
   nrb = (p.M + rows_per_wg - 1) / rows_per_wg;
   if (xcd_order) nrb = (nrb + 7) / 8 * 8;                          // whole groups of 8 row blocks (XCD-aware order in the kernel)
   hipLaunchKernelGGL((wsgemm_kernel<MT, NT, KC, EPI, SPLIT, NW>), dim3((unsigned)ncb * nrb), dim3(64 * nw), lds, st, p, rows_per_wg, xcd_order);
@@ -626,7 +677,7 @@ static hipError_t launch_ws_epi(const GemmParams& p, hipStream_t st) {
       // The store-bound planar stage: ONE row tile per wave (112 registers: 4 waves per SIMD).  Loads and stores share a wave's
       // in-order memory counter, so a wave's next operands wait behind the acknowledgement of its previous stores; more waves =
       // more independent queues (2 tiles per wave 547 us, 1 tile 476 us; deeper prefetch 550 -- no help).
-      if (EPI == EPI_PLANAR) return launch_ws<1, 4, 2, EPI, true>(p, st);
+      if (EPI == EPI_PLANAR || EPI == EPI_PLANAR_ACC) return launch_ws<1, 4, 2, EPI, true>(p, st);
       if (EPI == EPI_SCATTER && 4 * per_tile > 80 * 1024) return launch_ws<1, 4, 2, EPI, true, 8>(p, st);   // one workgroup per CU: 8 waves
       return launch_ws<2, 4, 2, EPI, true>(p, st);
     }
@@ -673,6 +724,14 @@ hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st) {
     case EPI_PLANAR:
       if (p.gw % 4) return hipErrorInvalidValue;
       return split ? launch_epi<EPI_PLANAR, true>(p, st) : launch_epi<EPI_PLANAR, false>(p, st);
+    case EPI_PLANAR_ACC: {
+      // one window: rows m = (z gh + y) gw + x of its half-resolution grid.  The 16-byte path needs every quad of an output row aligned
+      // in the accumulator (corner, row, plane and channel strides multiples of 4 floats) and in the map; both paths give the same bits.
+      if (p.gw % 4 || !p.wmap || !p.out || p.M != p.gd * p.gh * p.gw) return hipErrorInvalidValue;
+      GemmParams q = p;
+      q.acc_vec = !(((uintptr_t)p.out | (uintptr_t)p.wmap) & 15) && !((p.acc_sc | p.acc_sz | p.acc_sy) & 3);
+      return split ? launch_epi<EPI_PLANAR_ACC, true>(q, st) : launch_epi<EPI_PLANAR_ACC, false>(q, st);
+    }
     case EPI_QK:      // a head's 5 tiles with the whole K extent in LDS (embed_dim <= 1024); wider models stream the weights (direct kernel)
       if (split || p.Cp != 80 || p.ntiles != 2 * p.heads * 5) return hipErrorInvalidValue;
       // (4 row tiles per wave measured the same 64 us as 2: of those, ~10 us are the LDS fill, ~19 the K loop, ~34 the epilogue)

@@ -81,6 +81,11 @@ struct amx_vit {
   // workspace bookkeeping of the last forward (debug reads)
   struct Named { std::string name; char* ptr; size_t bytes; };
   std::vector<Named> dbg;
+  // amx_vit_sliding_window: the window weights of the handle's roi, cached per (mode, sigma_scale); allocated at its first call
+  float* sw_map = nullptr;
+  int sw_map_mode = -1;
+  double sw_map_sigma = 0.0;
+  hipEvent_t sw_map_ready = nullptr;
 };
 
 namespace {
@@ -224,6 +229,8 @@ int amx_vit_create(amx_vit_t** out, const amx_vit_cfg* cfg) {
 void amx_vit_destroy(amx_vit_t* h) {
   if (!h) return;
   if (h->params) (void)hipFree(h->params);
+  if (h->sw_map) (void)hipFree(h->sw_map);
+  if (h->sw_map_ready) (void)hipEventDestroy(h->sw_map_ready);
   delete h;
 }
 
@@ -402,23 +409,19 @@ Plan make_plan(const amx_vit* h, int n, char* base) {
   return P;
 }
 
-}  // namespace
+// Where the last decoder product of a forward leaves its result: the planar tensor d_y [n][C][roi] (amx_vit_forward), or -- `acc`
+// set -- sample i blended into the sliding-window accumulator at corner[i] (amx_vit_forward_windows; no [n][C][roi] tensor exists).
+struct VitOut {
+  float* y = nullptr;
+  float* acc = nullptr;                 // fp32 [C][vd][vh][vw]
+  const float* wmap = nullptr;          // fp32 [roi]
+  int vd = 0, vh = 0, vw = 0;
+  const long long* corner = nullptr;    // [n] voxel offsets (oz vh + oy) vw + ox
+};
 
-extern "C" {
-
-size_t amx_vit_workspace_bytes(const amx_vit_t* h, int n) {
-  if (!h || n < 1) return 0;
-  return make_plan(h, n, nullptr).total;
-}
-
-int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, void* stream) {
-  if (!h || !d_x || !d_y || !d_ws) return fail(AMX_ERR_INVALID, "null argument");
-  if (!h->loaded) return fail(AMX_ERR_NOT_LOADED, "vit: forward before amx_vit_load");
-  if (n < 1) return fail(AMX_ERR_INVALID, "vit: batch %d", n);
-  if ((uintptr_t)d_ws & 255) return fail(AMX_ERR_WORKSPACE, "vit: workspace must be 256-byte aligned");
-  const Plan P = make_plan(h, n, (char*)d_ws);
-  if (ws_bytes < P.total) return fail(AMX_ERR_WORKSPACE, "vit: workspace needs %zu bytes (got %zu)", P.total, ws_bytes);
-  hipStream_t st = (hipStream_t)stream;
+// The forward of n roi-sized samples d_x; every argument has been checked by the entry.
+int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& P, int n_blocks, hipStream_t st) {
+  float* const d_y = out.y;
   const amx_vit_cfg& c = h->cfg;
   const int E = h->E, Ep = h->Ep, T = h->T, V = h->V, hid = h->hidden, nreg = c.num_register_tokens;
   const int M = n * T;
@@ -527,7 +530,17 @@ int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_w
       AMX_HIP(amx::launch_colsum(P.Ad_hi[2], P.Ad_lo[2], up(d.cin, 32), d.cin, n, (int)(rows / n), kColChunks, P.colsum, st));
       AMX_HIP(amx::launch_demean(P.colsum, kColChunks, up(d.cin, 32), d.cin, rows / n, d.w_raw, d.cout, d.bias, n, P.mean, st));
     }
-    if (k == 2) {                         // planar fp32 output written by the product kernel itself
+    if (k == 2 && out.acc) {              // one product per window, in window order: overlapping windows are ordered by the stream
+      const long long wrows = rows / n, vvox = (long long)out.vd * out.vh * out.vw;
+      g.M = (int)wrows; g.wmap = out.wmap; g.acc_sc = vvox; g.acc_sz = (long long)out.vh * out.vw; g.acc_sy = out.vw;
+      for (int i = 0; i < n; ++i) {
+        g.a_hi = P.Ad_hi[2] + (size_t)i * wrows * g.lda * 2;
+        g.a_lo = P.Ad_lo[2] ? P.Ad_lo[2] + (size_t)i * wrows * g.lda * 2 : nullptr;
+        g.out = out.acc + out.corner[i];
+        g.sub = c.out_norm == 1 ? P.mean + (size_t)i * d.cout : nullptr;      // ChannelDemean stays per window
+        AMX_HIP(amx::launch_gemm(g, amx::EPI_PLANAR_ACC, st));
+      }
+    } else if (k == 2) {                  // planar fp32 output written by the product kernel itself
       g.out = d_y; g.sub = c.out_norm == 1 ? P.mean : nullptr;
       AMX_HIP(amx::launch_gemm(g, amx::EPI_PLANAR, st));
     } else if (d.cp == 128 && up(d.cout, 32) <= 128) {   // channel LayerNorm + GELU fused: the next stage's operand rows come straight out
@@ -540,6 +553,165 @@ int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_w
     }
     rows *= 8; gd *= 2; gh *= 2; gw *= 2;
   }
+  return AMX_OK;
+}
+
+// ---- sliding-window route -----------------------------------------------------------------------------------------------------
+constexpr int kVitMaxWindows = 16;
+struct VitCorners { long long off[kVitMaxWindows]; };
+
+// win[i][z][y][x] = vol[corner i + (z vh + y) vw + x]: the roi-sized batch the tokenizer reads (1 / 32 of what the decoder writes).
+// A thread moves four voxels of a row (rw is a multiple of 16); the corner may sit at any x, so the loads are scalar.
+__global__ __launch_bounds__(256) void vit_gather_windows_kernel(const float* __restrict__ vol, int vh, int vw, VitCorners c, int rd, int rh,
+                                                                 int rw, float* __restrict__ win) {
+  const long long quads = (long long)rd * rh * (rw >> 2);
+  const float* src = vol + c.off[blockIdx.y];
+  float4* dst = (float4*)(win + (long long)blockIdx.y * rd * rh * rw);
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < quads; i += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % (rw >> 2)) * 4;
+    const long long r = i / (rw >> 2);
+    const int y = (int)(r % rh), z = (int)(r / rh);
+    const float* s = src + ((long long)z * vh + y) * vw + x;
+    dst[i] = make_float4(s[0], s[1], s[2], s[3]);
+  }
+}
+
+struct VitWindowsWs {          // [gathered windows | the forward's plan]
+  size_t gather, total;
+};
+VitWindowsWs windows_ws(const amx_vit* h, int n) {
+  VitWindowsWs w;
+  w.gather = ((size_t)n * h->V * 512 * sizeof(float) + 255) & ~(size_t)255;
+  w.total = w.gather + make_plan(h, n, nullptr).total;
+  return w;
+}
+
+// every check of amx_vit_forward_windows but the offsets'
+int windows_check(const amx_vit* h, int vd, int vh, int vw, int n_windows, const void* d_ws, size_t ws_bytes) {
+  if (!h->loaded) return fail(AMX_ERR_NOT_LOADED, "vit: windows before amx_vit_load");
+  if (n_windows < 1 || n_windows > kVitMaxWindows) return fail(AMX_ERR_INVALID, "vit: 1 <= n_windows <= %d (got %d)", kVitMaxWindows, n_windows);
+  const amx_vit_cfg& c = h->cfg;
+  if (vd < c.grid_d * 8 || vh < c.grid_h * 8 || vw < c.grid_w * 8)
+    return fail(AMX_ERR_SHAPE, "vit: volume %d x %d x %d is smaller than the roi %d x %d x %d: pad it first", vd, vh, vw, c.grid_d * 8, c.grid_h * 8,
+                c.grid_w * 8);
+  if ((long long)vd * vh * vw >= (1LL << 40) / c.num_classes) return fail(AMX_ERR_SHAPE, "vit: volume %d x %d x %d is too large", vd, vh, vw);
+  if (c.out_norm != 0 && c.out_norm != 1) return fail(AMX_ERR_INVALID, "vit: out_norm %d is not applied by the engine", c.out_norm);
+  const size_t need = windows_ws(h, n_windows).total;
+  if (ws_bytes < need || ((uintptr_t)d_ws & 255))
+    return fail(AMX_ERR_WORKSPACE, "vit: workspace needs %zu bytes, 256-byte aligned (got %zu)", need, ws_bytes);
+  return AMX_OK;
+}
+
+int forward_windows(amx_vit* h, const float* d_vol, int vd, int vh, int vw, int n, const int* offsets_zyx, const float* d_wmap, float* d_acc,
+                    void* d_ws, size_t ws_bytes, hipStream_t st) {
+  if (int rc = windows_check(h, vd, vh, vw, n, d_ws, ws_bytes)) return rc;
+  const amx_vit_cfg& c = h->cfg;
+  const int rd = c.grid_d * 8, rh = c.grid_h * 8, rw = c.grid_w * 8;
+  VitCorners cn{};
+  for (int i = 0; i < n; ++i) {
+    const int oz = offsets_zyx[3 * i], oy = offsets_zyx[3 * i + 1], ox = offsets_zyx[3 * i + 2];
+    if (oz < 0 || oy < 0 || ox < 0 || oz + rd > vd || oy + rh > vh || ox + rw > vw)
+      return fail(AMX_ERR_SHAPE, "vit: window (%d,%d,%d)+(%d,%d,%d) outside volume (%d,%d,%d)", oz, oy, ox, rd, rh, rw, vd, vh, vw);
+    cn.off[i] = ((long long)oz * vh + oy) * vw + ox;
+  }
+  // ---- launches
+  float* win = (float*)d_ws;
+  const Plan P = make_plan(h, n, (char*)d_ws + windows_ws(h, n).gather);
+  const long long quads = (long long)rd * rh * (rw / 4);
+  const int blocks = (int)((quads + 255) / 256 > 2048 ? 2048 : (quads + 255) / 256);
+  hipLaunchKernelGGL(vit_gather_windows_kernel, dim3(blocks, n), dim3(256), 0, st, d_vol, vh, vw, cn, rd, rh, rw, win);
+  AMX_HIP(hipGetLastError());
+  VitOut out;
+  out.acc = d_acc; out.wmap = d_wmap; out.vd = vd; out.vh = vh; out.vw = vw; out.corner = cn.off;
+  return vit_run(h, win, out, n, P, -1, st);
+}
+
+// the window weights of (mode, sigma_scale) on the handle (the roi is the handle's): built on `st` when the key is new, else the
+// build is waited for
+int fetch_map(amx_vit* h, int mode, double sigma_scale, hipStream_t st) {
+  const amx_vit_cfg& c = h->cfg;
+  if (!h->sw_map_ready) AMX_HIP(hipEventCreateWithFlags(&h->sw_map_ready, hipEventDisableTiming));
+  if (h->sw_map && h->sw_map_mode == mode && (mode == AMX_SW_MAP_CONSTANT || h->sw_map_sigma == sigma_scale)) {
+    AMX_HIP(hipStreamWaitEvent(st, h->sw_map_ready, 0));
+    return AMX_OK;
+  }
+  if (!h->sw_map) AMX_HIP(hipMalloc((void**)&h->sw_map, (size_t)h->V * 512 * sizeof(float)));
+  else AMX_HIP(hipStreamWaitEvent(st, h->sw_map_ready, 0));
+  h->sw_map_mode = -1;
+  AMX_HIP(amx::launch_sw_importance_map(h->sw_map, c.grid_d * 8, c.grid_h * 8, c.grid_w * 8, mode, sigma_scale, st));
+  AMX_HIP(hipEventRecord(h->sw_map_ready, st));
+  h->sw_map_mode = mode, h->sw_map_sigma = sigma_scale;
+  return AMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t amx_vit_workspace_bytes(const amx_vit_t* h, int n) {
+  if (!h || n < 1) return 0;
+  return make_plan(h, n, nullptr).total;
+}
+
+int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, void* stream) {
+  if (!h || !d_x || !d_y || !d_ws) return fail(AMX_ERR_INVALID, "null argument");
+  if (!h->loaded) return fail(AMX_ERR_NOT_LOADED, "vit: forward before amx_vit_load");
+  if (n < 1) return fail(AMX_ERR_INVALID, "vit: batch %d", n);
+  if ((uintptr_t)d_ws & 255) return fail(AMX_ERR_WORKSPACE, "vit: workspace must be 256-byte aligned");
+  const Plan P = make_plan(h, n, (char*)d_ws);
+  if (ws_bytes < P.total) return fail(AMX_ERR_WORKSPACE, "vit: workspace needs %zu bytes (got %zu)", P.total, ws_bytes);
+  VitOut out;
+  out.y = d_y;
+  return vit_run(h, d_x, out, n, P, n_blocks, (hipStream_t)stream);
+}
+
+size_t amx_vit_windows_workspace_bytes(const amx_vit_t* h, int n_windows) {
+  if (!h || n_windows < 1 || n_windows > kVitMaxWindows) return 0;
+  return windows_ws(h, n_windows).total;
+}
+
+int amx_vit_forward_windows(amx_vit_t* h, const float* d_vol, int vd, int vh, int vw, int n_windows, const int* offsets_zyx,
+                            const float* d_wmap, float* d_acc, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!h || !d_vol || !offsets_zyx || !d_wmap || !d_acc || !d_ws) return fail(AMX_ERR_INVALID, "null argument");
+  return forward_windows(h, d_vol, vd, vh, vw, n_windows, offsets_zyx, d_wmap, d_acc, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t amx_vit_sliding_window_workspace_bytes(const amx_vit_t* h, int n_batch) { return amx_vit_windows_workspace_bytes(h, n_batch); }
+
+int amx_vit_sliding_window(amx_vit_t* h, const float* d_vol, int vd, int vh, int vw, double overlap, int mode, double sigma_scale, int n_batch,
+                           int out_kind, const float* d_w, const float* d_b, int classes, float* d_acc, float* d_cnt, void* d_out, void* d_ws,
+                           size_t ws_bytes, void* stream) {
+  if (!h || !d_vol || !d_acc || !d_cnt || !d_ws) return fail(AMX_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  // ---- every refusal comes before the first launch
+  const amx_vit_cfg& c = h->cfg;
+  const int rd = c.grid_d * 8, rh = c.grid_h * 8, rw = c.grid_w * 8;
+  if (n_batch < 1 || n_batch > kVitMaxWindows) return fail(AMX_ERR_INVALID, "vit: 1 <= n_batch <= %d (got %d)", kVitMaxWindows, n_batch);
+  if (mode != AMX_SW_MAP_CONSTANT && mode != AMX_SW_MAP_GAUSSIAN) return fail(AMX_ERR_INVALID, "mode: constant (0) or gaussian (1) (got %d)", mode);
+  if (mode == AMX_SW_MAP_GAUSSIAN && !(sigma_scale > 0.0)) return fail(AMX_ERR_INVALID, "sigma_scale must be positive (got %g)", sigma_scale);
+  amx::SwPlan plan;
+  if (int rc = amx::sw_make_plan(vd, vh, vw, rd, rh, rw, overlap, &plan)) return rc;
+  if (int rc = windows_check(h, vd, vh, vw, n_batch, d_ws, ws_bytes)) return rc;
+  const long long voxels = (long long)vd * vh * vw;
+  if (int rc = amx::sw_finish_check(out_kind, d_acc, d_cnt, c.num_classes, voxels, d_w, classes, d_out)) return rc;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  AMX_HIP(hipStreamIsCapturing(st, &cap));
+  // the first call allocates the cached window weights, which a capture cannot hold; amx_sliding_window has the same contract
+  if (cap != hipStreamCaptureStatusNone)
+    return fail(AMX_ERR_INVALID, "amx_vit_sliding_window cannot be captured into a graph: capture amx_sw_count_all, amx_vit_forward_windows and "
+                "amx_sw_finish, or call it outside the capture");
+  // ---- launches, all on `stream`
+  const int nwin = plan.windows(), k = n_batch < nwin ? n_batch : nwin;
+  AMX_HIP(hipMemsetAsync(d_acc, 0, (size_t)c.num_classes * voxels * sizeof(float), st));
+  if (int rc = fetch_map(h, mode, sigma_scale, st)) return rc;
+  AMX_HIP(amx::launch_sw_count_all(d_cnt, plan, h->sw_map, st));
+  for (int w0 = 0; w0 < nwin; w0 += k) {
+    int offs[kVitMaxWindows * 3];
+    const int nw = nwin - w0 < k ? nwin - w0 : k;
+    for (int i = 0; i < nw; ++i) plan.corner(w0 + i, offs + 3 * i);
+    if (int rc = forward_windows(h, d_vol, vd, vh, vw, nw, offs, h->sw_map, d_acc, d_ws, ws_bytes, st)) return rc;
+  }
+  AMX_HIP(amx::launch_sw_finish(out_kind, d_acc, d_cnt, c.num_classes, voxels, d_w, d_b, classes, d_out, st));
   return AMX_OK;
 }
 

@@ -323,40 +323,53 @@ class PrimusV2(nn.Module):
         n = lib.amx_vit_num_params(self._handle)
         return [sd[lib.amx_vit_param_name(self._handle, i).decode()] for i in range(n)]
 
+    def _engine(self, dev):
+        """The loaded engine on ``dev``: creates the handle at first use, uploads the parameters when they changed, and refuses
+        parameters that live elsewhere.  Returns ``(lib, stream)``; call it inside ``torch.cuda.device(dev)``.  The forward and the
+        sliding-window routes (registration/sliding_window.py) both start here."""
+        lib = _lib.load()
+        stream = _lib.stream(dev)
+        if self._handle is None:
+            cfg = _lib.VitCfg(**self._vit_cfg)
+            hnd = ctypes.c_void_p()
+            _lib.check(lib.amx_vit_create(ctypes.byref(hnd), ctypes.byref(cfg)))
+            self._handle = hnd
+        tensors = self._engine_tensors(lib)
+        # the engine is handed raw device pointers: a parameter still on the host (module never moved, or moved after the input)
+        # would fault the GPU instead of raising torch's device-mismatch error
+        stray = [tuple(t.shape) for t in list(tensors) + [self.rope_table] if t.device != dev]
+        if stray:
+            raise RuntimeError(f"PrimusV2.forward_hip: input on {dev} but {len(stray)} parameter / buffer tensors are elsewhere "
+                               f"(first shape {stray[0]}): move the module with .to({str(dev)!r}) first")
+        sig = tuple((t.data_ptr(), t._version) for t in tensors) + (str(dev),)
+        if sig != self._engine_sig:
+            held = [t.detach().float().contiguous() for t in tensors]
+            arr = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
+            rope = self.rope_table.detach().float().contiguous()
+            _lib.check(lib.amx_vit_load(self._handle, arr, len(held), _lib.ptr(rope), stream))
+            torch.cuda.current_stream(dev).synchronize()          # the staging copies in `held` may be temporaries
+            self._engine_sig = sig
+        return lib, stream
+
+    def _engine_workspace(self, need, dev):
+        """The engine's one device workspace, grown to ``need`` bytes (the forward and the window routes share it: they never overlap
+        on a stream)."""
+        ws = self._engine_ws
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = self._engine_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
     def forward_hip(self, x, n_blocks=-1):
         """[N, 1, D, H, W] fp32 on the GPU -> [N, num_classes, D, H, W]: ``amx_vit_forward`` + (for output norms other than none /
         demean) the torch output norm.  Raises when the configuration is outside the engine's envelope -- there is no fallback."""
-        lib = _lib.load()
         dev = x.device
         if tuple(x.shape[2:]) != tuple(8 * g for g in self.grid) or x.shape[1] != self._vit_cfg["input_channels"]:
             raise ValueError(f"PrimusV2 was built for inputs of {tuple(8 * g for g in self.grid)} (got {tuple(x.shape[1:])})")
         with torch.cuda.device(dev):
-            stream = _lib.stream(dev)
-            if self._handle is None:
-                cfg = _lib.VitCfg(**self._vit_cfg)
-                hnd = ctypes.c_void_p()
-                _lib.check(lib.amx_vit_create(ctypes.byref(hnd), ctypes.byref(cfg)))
-                self._handle = hnd
-            tensors = self._engine_tensors(lib)
-            # the engine is handed raw device pointers: a parameter still on the host (module never moved, or moved after the input)
-            # would fault the GPU instead of raising torch's device-mismatch error
-            stray = [tuple(t.shape) for t in list(tensors) + [self.rope_table] if t.device != dev]
-            if stray:
-                raise RuntimeError(f"PrimusV2.forward_hip: input on {dev} but {len(stray)} parameter / buffer tensors are elsewhere "
-                                   f"(first shape {stray[0]}): move the module with .to({str(dev)!r}) first")
-            sig = tuple((t.data_ptr(), t._version) for t in tensors) + (str(dev),)
-            if sig != self._engine_sig:
-                held = [t.detach().float().contiguous() for t in tensors]
-                arr = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
-                rope = self.rope_table.detach().float().contiguous()
-                _lib.check(lib.amx_vit_load(self._handle, arr, len(held), _lib.ptr(rope), stream))
-                torch.cuda.current_stream(dev).synchronize()          # the staging copies in `held` may be temporaries
-                self._engine_sig = sig
+            lib, stream = self._engine(dev)
             n = x.shape[0]
             need = lib.amx_vit_workspace_bytes(self._handle, n)
-            ws = self._engine_ws
-            if ws is None or ws.numel() < need or ws.device != dev:
-                ws = self._engine_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws = self._engine_workspace(need, dev)
             xin = x.detach().float().contiguous()
             y = torch.empty((n, self._vit_cfg["num_classes"]) + tuple(x.shape[2:]), dtype=torch.float32, device=dev)
             _lib.check(lib.amx_vit_forward(self._handle, _lib.ptr(xin), _lib.ptr(y), n, _lib.ptr(ws), need, int(n_blocks), stream))

@@ -17,7 +17,10 @@ Two execution paths:
   * fused   -- when the predictor is an ``anatomix_amd.Unet`` running on the HIP kernels, each window
     is ONE C-ABI call (``amx_unet_forward_window``): the first conv gathers the window straight out
     of the resident volume and the last conv's epilogue does ``acc[slice] += w * features`` in
-    place, so neither the window stack nor the per-window predictions are materialised.
+    place, so neither the window stack nor the per-window predictions are materialised.  A bare
+    ``PrimusV2`` on its engine (or ``nn.Sequential(PrimusV2, affine head)``) takes the matching route:
+    ``amx_vit_forward_windows`` gathers a batch of windows out of the resident volume and the last
+    decoder product blends every window into the accumulator in its epilogue.
 
 Multi-GPU: windows are independent, so with ``group=`` (a torch.distributed process group) they are
 dealt to ranks in contiguous z-ordered runs; each rank accumulates its own windows.  The ONE exchange
@@ -239,8 +242,12 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int,
         split = _split_unet_and_head(predictor, inputs, roi)
         if split is not None:
             (predictor, head), fused = split, True
+    vit = None if fused else _split_vit_and_head(predictor, inputs, roi)
     if fused:
         acc = _run_fused(inputs, roi, mine, wmap, predictor, cnt)
+    elif vit is not None:
+        predictor, head = vit
+        acc = _run_fused_vit(inputs, roi, mine, wmap, predictor, cnt)
     else:
         for b0 in range(0, len(mine) * B, sw_batch_size):
             idx = range(b0, min(b0 + sw_batch_size, len(mine) * B))
@@ -420,12 +427,111 @@ def _run_fused(inputs, roi, starts, wmap, model, cnt):
     return acc
 
 
+VIT_WINDOW_BATCH = 4       # windows per amx_vit_forward_windows call
+CALLS = {"vit_windows": 0, "vit_volume": 0}      # fused ViT calls: amx_vit_forward_windows / amx_vit_sliding_window (tests, diagnostics)
+
+
+def _is_vit(model) -> bool:
+    from ..model.vit3d.architectures import PrimusV2
+    return isinstance(model, PrimusV2)
+
+
+def _head_unsupported_reason(head, feat, inputs, out):
+    """Why amx_sw_finish cannot apply ``head`` to ``feat`` channels (None: it can): one 1x1x1 convolution within its sizes."""
+    from ..segmentation.losses import MAX_CLASSES, MAX_HEAD_CHANNELS, _single_conv_head
+    conv = _single_conv_head(head) if head is not None else None
+    if conv is None:
+        return f"out={out!r} needs head= made of exactly one 1x1x1 convolution"
+    if conv.in_channels != feat or not 2 <= conv.out_channels <= MAX_CLASSES or feat > MAX_HEAD_CHANNELS:
+        return (f"head of {conv.in_channels} -> {conv.out_channels} channels on {feat} features: 2 <= classes <= {MAX_CLASSES}, "
+                f"input channels == the model's output channels <= {MAX_HEAD_CHANNELS}")
+    if conv.weight.device != inputs.device:
+        return "the head and the inputs must be on one device"
+    return None
+
+
+def _vit_unsupported_reason(model, inputs, roi, head=None, out="features"):
+    """Why the fused ViT routes (amx_vit_forward_windows / amx_vit_sliding_window) cannot take this call (None: they can).  The
+    envelope: a CUDA tensor, no grad, ``use_engine``, roi equal to the model's input shape, one input channel, an output norm the
+    engine applies itself (none / demean), a configuration amx_vit_create takes, and for logits / labels a head of one 1x1x1
+    convolution within amx_sw_finish's sizes."""
+    from ..model.vit3d.architectures import ChannelDemean
+    if not inputs.is_cuda:
+        return f"there is no host path (got a {inputs.device} tensor)"
+    if torch.is_grad_enabled():
+        return "the engine runs under torch.no_grad() only"
+    if not model.use_engine:
+        return "model.use_engine is off"
+    if inputs.dim() != 5 or inputs.shape[1] != 1 or model._vit_cfg["input_channels"] != 1:
+        return f"inputs [B, 1, D, H, W] and input_channels == 1 (got {tuple(inputs.shape)}, input_channels {model._vit_cfg['input_channels']})"
+    shape = tuple(8 * g for g in model.grid)
+    if tuple(roi) != shape:
+        return f"roi must be the model's input shape {shape} (got {tuple(roi)})"
+    if not isinstance(model.out_norm, (ChannelDemean, nn.Identity)):
+        return f"out_norm must be 'none' or 'demean', which the engine applies per window (got {type(model.out_norm).__name__})"
+    if out != "features":
+        reason = _head_unsupported_reason(head, model._vit_cfg["num_classes"], inputs, out)
+        if reason is not None:
+            return reason
+    try:
+        with torch.cuda.device(inputs.device):
+            model._engine(inputs.device)
+    except _lib.AmxError as e:
+        if getattr(e, "code", None) not in (_lib.AMX_ERR_INVALID, _lib.AMX_ERR_SHAPE):
+            raise
+        return f"the HIP engine does not cover this configuration ({e})"
+    return None
+
+
+def _split_vit_and_head(predictor, inputs, roi):
+    """(PrimusV2, head or None) when the windows can run through amx_vit_forward_windows: a bare PrimusV2, or
+    nn.Sequential(PrimusV2, head) with a provably per-voxel affine head (applied once to the normalised volume, as for the Unet)."""
+    if _is_vit(predictor):
+        return (predictor, None) if _vit_unsupported_reason(predictor, inputs, roi) is None else None
+    if isinstance(predictor, nn.Sequential) and len(predictor) >= 2 and _is_vit(predictor[0]):
+        if _vit_unsupported_reason(predictor[0], inputs, roi) is not None:
+            return None
+        head = predictor[1] if len(predictor) == 2 else nn.Sequential(*list(predictor.children())[1:])
+        if _pointwise_affine(head):
+            return predictor[0], head
+    return None
+
+
+def _run_fused_vit(inputs, roi, starts, wmap, model, cnt):
+    """amx_vit_forward_windows on groups of VIT_WINDOW_BATCH windows + one amx_sw_count per window, all on the current stream
+    (overlapping windows accumulate in issue order).  ``starts`` are this rank's windows, as for ``_run_fused``."""
+    dev = inputs.device
+    B = inputs.shape[0]
+    size = tuple(inputs.shape[2:])
+    x = _lib.f32c(inputs.detach())
+    acc = torch.zeros((B, model._vit_cfg["num_classes"]) + size, dtype=torch.float32, device=dev)
+    if not starts:
+        return acc
+    wm = wmap.contiguous()
+    with torch.cuda.device(dev):
+        lib, st = model._engine(dev)
+        k = min(VIT_WINDOW_BATCH, len(starts))
+        need = lib.amx_vit_windows_workspace_bytes(model._handle, k)
+        ws = model._engine_workspace(need, dev)
+        for g0 in range(0, len(starts), k):
+            grp = starts[g0:g0 + k]
+            offs = (ctypes.c_int * (3 * len(grp)))(*[v for s3 in grp for v in s3])
+            for b in range(B):
+                _lib.check(lib.amx_vit_forward_windows(model._handle, _lib.ptr(x[b]), size[0], size[1], size[2], len(grp), offs,
+                                                       _lib.ptr(wm), _lib.ptr(acc[b]), _lib.ptr(ws), need, st))
+                CALLS["vit_windows"] += 1
+            for (z, y, xx) in grp:
+                _lib.check(lib.amx_sw_count(_lib.ptr(cnt), size[0], size[1], size[2], z, y, xx, roi[0], roi[1], roi[2], _lib.ptr(wm), st))
+    return acc
+
+
 def _volume_unsupported_reason(model, inputs, roi, head, out):
-    """Why ``sliding_window_volume`` cannot take this call (None: it can).  The envelope is amx_sliding_window's: the fused window
-    step's (``_fused_ok``), and for logits / labels a head made of one 1x1x1 convolution within amx_sw_finish's sizes."""
+    """Why ``sliding_window_volume`` cannot take this call with a Unet (None: it can).  The envelope is amx_sliding_window's: the
+    fused window step's (``_fused_ok``), and for logits / labels a head made of one 1x1x1 convolution within amx_sw_finish's sizes."""
     from ..model.network import Unet
     if not isinstance(model, Unet):
-        return f"model must be a bare anatomix_amd.Unet (got {type(model).__name__}); pass the head of a Sequential as head="
+        return (f"model must be a bare anatomix_amd.Unet or PrimusV2 (got {type(model).__name__}); pass the head of a Sequential "
+                "as head=")
     if not inputs.is_cuda:
         return f"there is no host path (got a {inputs.device} tensor)"
     if inputs.dim() != 5 or inputs.shape[1] != 1 or model._cfg["input_nc"] != 1:
@@ -439,15 +545,7 @@ def _volume_unsupported_reason(model, inputs, roi, head, out):
     if reason is not None:
         return reason
     if out != "features":
-        from ..segmentation.losses import MAX_CLASSES, MAX_HEAD_CHANNELS, _single_conv_head
-        conv = _single_conv_head(head) if head is not None else None
-        if conv is None:
-            return f"out={out!r} needs head= made of exactly one 1x1x1 convolution"
-        if conv.in_channels != cout or not 2 <= conv.out_channels <= MAX_CLASSES or cout > MAX_HEAD_CHANNELS:
-            return (f"head of {conv.in_channels} -> {conv.out_channels} channels on {cout} features: 2 <= classes <= {MAX_CLASSES}, "
-                    f"input channels == output_nc <= {MAX_HEAD_CHANNELS}")
-        if conv.weight.device != inputs.device:
-            return "the head and the inputs must be on one device"
+        return _head_unsupported_reason(head, cout, inputs, out)
     return None
 
 
@@ -455,7 +553,8 @@ def sliding_window_volume(inputs: torch.Tensor, roi_size, model, overlap: float 
                           sigma_scale: float = 0.125, head=None, out: str = "features"):
     """``sliding_window_inference(inputs, roi_size, FUSED_WINDOW_BATCH, model, overlap, mode, sigma_scale)`` as ONE C call per batch
     element (``amx_sliding_window``: schedule, window weights, count map, pipelined window batches and the finishing pass all behind
-    the C ABI).  ``model`` is a bare ``anatomix_amd.Unet``; ``out``:
+    the C ABI).  ``model`` is a bare ``anatomix_amd.Unet``, or a bare ``PrimusV2`` on its engine (``amx_vit_sliding_window``: roi equal
+    to the model's input shape, batches of VIT_WINDOW_BATCH windows, one stream); ``out``:
       * ``"features"`` -> fp32 [B, output_nc, D, H, W], the window average of the Unet's output;
       * ``"logits"``   -> fp32 [B, classes, D, H, W], ``head`` (one 1x1x1 convolution) applied to that average;
       * ``"labels"``   -> uint8 [B, 1, D, H, W], the arg-max of those logits (lowest index on ties), which are never written.
@@ -469,7 +568,8 @@ def sliding_window_volume(inputs: torch.Tensor, roi_size, model, overlap: float 
     if isinstance(roi_size, int):
         roi_size = (roi_size,) * 3
     roi = tuple(int(r) for r in roi_size)
-    reason = _volume_unsupported_reason(model, inputs, roi, head, out)
+    vit = _is_vit(model)
+    reason = _vit_unsupported_reason(model, inputs, roi, head, out) if vit else _volume_unsupported_reason(model, inputs, roi, head, out)
     if reason is not None:
         raise _lib.AmxEnvelopeError(_lib.AMX_ERR_SHAPE, "sliding_window_volume: " + reason + ".  sliding_window_inference takes any predictor.")
     B = inputs.shape[0]
@@ -485,7 +585,7 @@ def sliding_window_volume(inputs: torch.Tensor, roi_size, model, overlap: float 
     size = tuple(inputs.shape[2:])
     dev = inputs.device
     x = _lib.f32c(inputs.detach())
-    cout = model._cfg["output_nc"]
+    cout = model._vit_cfg["num_classes"] if vit else model._cfg["output_nc"]
     w = b = res = None
     classes = 0
     if out != "features":
@@ -500,6 +600,23 @@ def sliding_window_volume(inputs: torch.Tensor, roi_size, model, overlap: float 
     acc = torch.empty((B if out == "features" else 1, cout) + size, dtype=torch.float32, device=dev)
     cnt = torch.empty(size, dtype=torch.float32, device=dev)
     lib = _lib.load()
+    if vit:
+        with torch.cuda.device(dev):
+            _, st = model._engine(dev)
+            need = lib.amx_vit_sliding_window_workspace_bytes(model._handle, VIT_WINDOW_BATCH)
+            ws = model._engine_workspace(need, dev)
+            for i in range(B):
+                _lib.check_envelope(lib.amx_vit_sliding_window(
+                    model._handle, _lib.ptr(x[i]), *size, float(overlap), _lib.SW_MAP[mode], float(sigma_scale), VIT_WINDOW_BATCH,
+                    _lib.SW_OUT[out], _lib.ptr(w), _lib.ptr(b), classes, _lib.ptr(acc[i if out == "features" else 0]), _lib.ptr(cnt),
+                    _lib.ptr(res[i]) if res is not None else None, _lib.ptr(ws), need, st))
+                CALLS["vit_volume"] += 1
+        if out == "features":
+            res = acc
+        if need_pad:
+            zs, ys, xs = pads[4], pads[2], pads[0]
+            res = res[:, :, zs:zs + orig[0], ys:ys + orig[1], xs:xs + orig[2]]
+        return res
     with torch.cuda.device(dev):
         model._ensure_handle(dev)
         if model._weights_stale():

@@ -9,7 +9,7 @@ user assembles the inference by hand from MONAI's ``sliding_window_inference``, 
 and the default overlap 0.7 its validation call's; ``--ckpt`` takes what that script writes (``best_dict_epoch*.pth``: the
 state dict of ``nn.Sequential(Unet, head)``, or ``epoch*.pth`` with it under ``state_dict``).
 
-``segment_volume`` is one ``amx_sliding_window`` call (``registration.sliding_window.sliding_window_volume(out="labels")``): the
+``segment_volume`` is one ``amx_sliding_window`` call (``amx_vit_sliding_window`` for a finetuned ViT) (``registration.sliding_window.sliding_window_volume(out="labels")``): the
 windows, their average, the 1x1x1 head and the arg-max run behind the C ABI and neither the features nor the logits of the volume
 are read back.  There is no host path."""
 from __future__ import annotations
@@ -31,11 +31,11 @@ from .segmentation_utils import UnetOutBlock, get_val_transforms
 
 def segment_volume(model, image, roi=128, overlap=0.7, mode="constant"):
     """uint8 [D, H, W] labels of ``image`` (a [D, H, W] device tensor, any real dtype): ``model`` is ``nn.Sequential(Unet, head)``
-    as ``load_model`` returns it, the image is rescaled by ``get_val_transforms()`` and the windows are
+    as ``load_model`` returns it, or ``nn.Sequential(PrimusV2, head)`` with ``roi`` the ViT's input shape, the image is rescaled by ``get_val_transforms()`` and the windows are
     ``sliding_window_inference(image, roi, 4, model, overlap)``'s (train_segmentation.py:194-199), then softmax + arg-max (:84-86;
     the lowest class on ties)."""
     if not (isinstance(model, nn.Sequential) and len(model) == 2):
-        raise TypeError("segment_volume: model must be nn.Sequential(Unet, head) as load_model returns it")
+        raise TypeError("segment_volume: model must be nn.Sequential(Unet or PrimusV2, head) as load_model returns it")
     if not torch.is_tensor(image) or image.dim() != 3:
         raise ValueError(f"segment_volume: image [D, H, W] (got {tuple(getattr(image, 'shape', ()))})")
     if not image.is_cuda:

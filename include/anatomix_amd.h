@@ -509,6 +509,47 @@ size_t amx_vit_workspace_bytes(const amx_vit_t* h, int n);
  * bytes, 256-byte aligned.  n_blocks < 0: all blocks (a smaller count is a debugging aid). */
 int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, void* stream);
 int amx_vit_debug_read(amx_vit_t* h, const char* name, void* d_dst, size_t max_bytes, size_t* bytes, void* stream);
+
+/* ---- the ViT under sliding_window_inference (convex_adam_utils.py:202-219 / train_segmentation.py:194-199; the reference
+ * presents anatomix-dev-vit as "Requires 128^3 inputs, but amenable to sliding window").  The roi is the handle's input shape,
+ * 8 * grid, on every entry below. */
+
+/* Bytes of workspace amx_vit_forward_windows needs for n_windows (1 .. 16) windows: the gathered single-channel windows and the
+ * forward's own workspace.  0 for a null handle or a count out of range. */
+size_t amx_vit_windows_workspace_bytes(const amx_vit_t* h, int n_windows);
+
+/* One batch of windows of a resident volume, as sliding_window_inference hands sw_batch_size windows to the predictor and blends
+ * the predictions (convex_adam_utils.py:202-219 / train_segmentation.py:194-199): the n_windows (1 .. 16) roi-sized windows at
+ * the host array offsets_zyx [n_windows][3] are cut from d_vol fp32 [vd][vh][vw] (single channel) by a gather kernel, run as one
+ * batch through the tokenizer, blocks and decoder of amx_vit_forward, and the last decoder product runs once per window, in
+ * window order on `stream`, with an accumulating epilogue:
+ *   d_acc[c][oz + z][oy + y][ox + x] += d_wmap[z][y][x] * (value + bias[c] - mean[window][c])
+ * d_acc fp32 [num_classes][vd][vh][vw], d_wmap fp32 [roi].  ChannelDemean (out_norm == 1) stays per window.  No [n][C][roi]
+ * output tensor exists on this route.  Every (channel, voxel) of a window has one owner: plain load-add-store, no atomics,
+ * results bit-identical from run to run; rows take 16-byte accesses when ox, vw and the bases allow it and scalar ones otherwise,
+ * with identical values.  Every check comes before the first launch: null arguments (AMX_ERR_INVALID), a handle that is not
+ * loaded (AMX_ERR_NOT_LOADED), n_windows out of range (AMX_ERR_INVALID), a volume smaller than the roi or a window outside the
+ * volume (AMX_ERR_SHAPE; padding is the caller's), a workspace below amx_vit_windows_workspace_bytes(h, n_windows) or not
+ * 256-byte aligned (AMX_ERR_WORKSPACE). */
+int amx_vit_forward_windows(amx_vit_t* h, const float* d_vol, int vd, int vh, int vw, int n_windows, const int* offsets_zyx,
+                            const float* d_wmap, float* d_acc, void* d_ws, size_t ws_bytes, void* stream);
+
+/* Bytes of workspace amx_vit_sliding_window needs for batches of n_batch (1 .. 16) windows (the sw_batch_size of
+ * convex_adam_utils.py:202-219 / train_segmentation.py:194-199): one batch is in flight at a time. */
+size_t amx_vit_sliding_window_workspace_bytes(const amx_vit_t* h, int n_batch);
+
+/* sliding_window_inference(volume, roi, n_batch, vit, overlap, mode, sigma_scale) in one call (convex_adam_utils.py:202-219;
+ * with a head, train_segmentation.py:194-199): amx_sliding_window's contract with the roi implied by the handle.  The call zeroes
+ * d_acc fp32 [num_classes][vd*vh*vw], builds the window weights with amx_sw_importance_map's kernel (cached on the handle per
+ * mode and sigma_scale; the first call allocates them), writes d_cnt fp32 [vd*vh*vw] with amx_sw_count_all, runs the windows of
+ * amx_sw_plan in batches of n_batch through amx_vit_forward_windows and ends with amx_sw_finish(out_kind, ...): features in
+ * d_acc, or logits / labels in d_out (d_w, d_b, classes: the head, NULL / 0 for features).  Everything runs on `stream`, one
+ * batch at a time; no host synchronisation.  While `stream` is capturing the call is refused (AMX_ERR_INVALID).  Every check
+ * comes before the first launch and a refused call leaves all buffers untouched: those of amx_vit_forward_windows (with n_batch
+ * for n_windows), overlap / mode / sigma_scale as for amx_sliding_window, the head as for amx_sw_finish. */
+int amx_vit_sliding_window(amx_vit_t* h, const float* d_vol, int vd, int vh, int vw, double overlap, int mode, double sigma_scale,
+                           int n_batch, int out_kind, const float* d_w, const float* d_b, int classes, float* d_acc, float* d_cnt,
+                           void* d_out, void* d_ws, size_t ws_bytes, void* stream);
 /* y[m][n] = sum_k x[m][k] w[n][k] + b[n] through the ViT's MFMA product kernel (f16 operands, or hi + lo pairs when split != 0):
  * a test entry for nn.Linear-shaped products; synchronous (allocates and frees its operand buffers). */
 int amx_linear(const float* d_x, const float* d_w, const float* d_b, int m, int k, int n, int split, float* d_y, void* stream);
