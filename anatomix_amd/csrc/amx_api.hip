@@ -58,8 +58,9 @@ int amx_sw_normalize(float* d_acc, const float* d_cnt, int channels, long long v
 int amx_sw_count(float* d_cnt, int vd, int vh, int vw, int oz, int oy, int ox, int rd, int rh, int rw,
                  const float* d_wmap, void* stream) {
   if (!d_cnt || !d_wmap) return fail(AMX_ERR_INVALID, "null argument");
-  if (oz < 0 || oy < 0 || ox < 0 || oz + rd > vd || oy + rh > vh || ox + rw > vw)
-    return fail(AMX_ERR_SHAPE, "window outside volume");
+  const int corner[3] = {oz, oy, ox};
+  long long off;
+  if (int rc = amx::sw_window_offsets(vd, vh, vw, rd, rh, rw, 1, corner, &off)) return rc;
   AMX_HIP(amx::launch_sw_count(d_cnt, vd, vh, vw, oz, oy, ox, rd, rh, rw, d_wmap, (hipStream_t)stream));
   return AMX_OK;
 }
@@ -76,8 +77,7 @@ int amx_sw_plan(int vd, int vh, int vw, int rd, int rh, int rw, double overlap, 
 int amx_sw_importance_map(float* d_wmap, int rd, int rh, int rw, int mode, double sigma_scale, void* stream) {
   if (!d_wmap) return fail(AMX_ERR_INVALID, "null argument");
   if (rd < 1 || rh < 1 || rw < 1) return fail(AMX_ERR_SHAPE, "non-positive roi");
-  if (mode != AMX_SW_MAP_CONSTANT && mode != AMX_SW_MAP_GAUSSIAN) return fail(AMX_ERR_INVALID, "mode: constant (0) or gaussian (1) (got %d)", mode);
-  if (mode == AMX_SW_MAP_GAUSSIAN && !(sigma_scale > 0.0)) return fail(AMX_ERR_INVALID, "sigma_scale must be positive (got %g)", sigma_scale);
+  if (int rc = amx::sw_map_check(mode, sigma_scale)) return rc;
   AMX_HIP(amx::launch_sw_importance_map(d_wmap, rd, rh, rw, mode, sigma_scale, (hipStream_t)stream));
   return AMX_OK;
 }

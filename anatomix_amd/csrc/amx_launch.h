@@ -7,6 +7,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <functional>
+
 #include "../../include/anatomix_amd.h"
 #include "amx_common.h"
 
@@ -139,6 +141,41 @@ hipError_t launch_sw_importance_map(float* wmap, int rd, int rh, int rw, int mod
 // kind: AMX_SW_FEATURES (acc /= cnt in place, launch_sw_normalize's arithmetic), AMX_SW_LOGITS, AMX_SW_LABELS
 hipError_t launch_sw_finish(int kind, float* acc, const float* cnt, int feat, long long voxels, const float* w, const float* b, int classes,
                             void* out, hipStream_t st);
+// AMX_OK, or AMX_ERR_INVALID for a mode that is neither constant nor gaussian, or a gaussian without a positive sigma_scale
+int sw_map_check(int mode, double sigma_scale);
+// off[i] = where window i of offsets_zyx[n][3] starts in a [vd][vh][vw] volume, in voxels; AMX_ERR_SHAPE when a window leaves the volume
+int sw_window_offsets(int vd, int vh, int vw, int rd, int rh, int rw, int n, const int* offsets_zyx, long long* off);
+// The window weights of the last (roi, mode, sigma_scale) on a network handle, created at first use.  fetch: `map` holds this key's
+// weights once `st` gets there -- built on `st` when the key is new, else the build is waited for.
+struct SwMapCache {
+  float* map = nullptr;
+  int roi[3] = {0, 0, 0}, mode = -1;
+  double sigma = 0.0;
+  hipEvent_t ready = nullptr;
+  int fetch(int rd, int rh, int rw, int mode, double sigma_scale, hipStream_t st);
+  void release();
+};
+// The second lane of a call that keeps two window batches in flight (lane 0 is the caller's stream) and the events that fork it from and
+// join it to the caller's, created at first use
+struct SwLanes {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+  void release();
+};
+// A network as sw_run sees it.  check: everything the network refuses for batches of k windows, launching nothing.  run: enqueues the
+// windows offs[nw][3] on `st`; slot 0 / 1 = the lane of a two-lane call (accumulations gated on the other slot's), -1 = one lane.
+constexpr int kSwMaxBatch = 64;
+struct SwNet {
+  const char *entry, *prefix;      // the C entry's name and what the network's messages start with
+  int channels, max_batch, roi[3];
+  int lane_groups;                 // two lanes from this many window batches on (0: one stream always)
+  std::function<int(int k)> check;
+  std::function<int(int nw, const int* offs, int slot, hipStream_t st)> run;
+};
+// plan -> window weights -> count map -> window batches -> finish on `st`, every other batch on lanes->stream when the network asks for
+// two lanes (lanes may be null otherwise).  Every refusal comes before the first launch.
+int sw_run(const SwNet& net, SwMapCache& cache, SwLanes* lanes, int vd, int vh, int vw, double overlap, int mode, double sigma_scale, int n_batch,
+           int out_kind, const float* d_w, const float* d_b, int classes, float* d_acc, float* d_cnt, void* d_out, hipStream_t st);
 
 // amx_train.hip
 size_t train_scratch_bytes(int C);
@@ -271,7 +308,7 @@ inline int need_scratch(size_t need, size_t got) {
   return got < need ? fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, got) : AMX_OK;
 }
 
-// the argument check of amx_sw_finish, shared with amx_sliding_window (amx_unet.hip), which makes it before its first launch
+// the argument check of amx_sw_finish, shared with sw_run (amx_sw.hip), which makes it before its first launch
 inline int sw_finish_check(int kind, const float* acc, const float* cnt, int feat, long long voxels, const float* w, int classes,
                            const void* out) {
   if (kind != AMX_SW_FEATURES && kind != AMX_SW_LOGITS && kind != AMX_SW_LABELS)

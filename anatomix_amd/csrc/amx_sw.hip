@@ -260,4 +260,113 @@ hipError_t launch_sw_finish(int kind, float* acc, const float* cnt, int feat, lo
   return hipGetLastError();
 }
 
+// ---- checks and handle state shared by the networks' window entries ------------------------------------------------------------
+int sw_map_check(int mode, double sigma_scale) {
+  if (mode != AMX_SW_MAP_CONSTANT && mode != AMX_SW_MAP_GAUSSIAN) return fail(AMX_ERR_INVALID, "mode: constant (0) or gaussian (1) (got %d)", mode);
+  if (mode == AMX_SW_MAP_GAUSSIAN && !(sigma_scale > 0.0)) return fail(AMX_ERR_INVALID, "sigma_scale must be positive (got %g)", sigma_scale);
+  return AMX_OK;
+}
+
+int sw_window_offsets(int vd, int vh, int vw, int rd, int rh, int rw, int n, const int* offsets_zyx, long long* off) {
+  for (int i = 0; i < n; ++i) {
+    const int oz = offsets_zyx[3 * i], oy = offsets_zyx[3 * i + 1], ox = offsets_zyx[3 * i + 2];
+    if (oz < 0 || oy < 0 || ox < 0 || oz + rd > vd || oy + rh > vh || ox + rw > vw)
+      return fail(AMX_ERR_SHAPE, "window (%d,%d,%d)+(%d,%d,%d) outside volume (%d,%d,%d)", oz, oy, ox, rd, rh, rw, vd, vh, vw);
+    off[i] = ((long long)oz * vh + oy) * vw + ox;
+  }
+  return AMX_OK;
+}
+
+int SwMapCache::fetch(int rd, int rh, int rw, int mode_, double sigma_scale, hipStream_t st) {
+  if (!ready) AMX_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+  const bool same_roi = map && roi[0] == rd && roi[1] == rh && roi[2] == rw;
+  if (same_roi && mode == mode_ && (mode_ == AMX_SW_MAP_CONSTANT || sigma == sigma_scale)) {
+    AMX_HIP(hipStreamWaitEvent(st, ready, 0));
+    return AMX_OK;
+  }
+  const size_t bytes = (size_t)rd * rh * rw * sizeof(float);
+  mode = -1;
+  if (!map || (size_t)roi[0] * roi[1] * roi[2] * sizeof(float) != bytes) {
+    if (map) (void)hipFree(map);     // (waits for the device: no earlier call still reads it)
+    map = nullptr;
+    AMX_HIP(hipMalloc((void**)&map, bytes));
+  } else {
+    AMX_HIP(hipStreamWaitEvent(st, ready, 0));      // rebuilt in place: after the last build, which may be on another stream
+  }
+  AMX_HIP(launch_sw_importance_map(map, rd, rh, rw, mode_, sigma_scale, st));
+  AMX_HIP(hipEventRecord(ready, st));
+  roi[0] = rd, roi[1] = rh, roi[2] = rw, mode = mode_, sigma = sigma_scale;
+  return AMX_OK;
+}
+
+void SwMapCache::release() {
+  if (ready) (void)hipEventDestroy(ready);
+  if (map) (void)hipFree(map);
+  ready = nullptr, map = nullptr, mode = -1;
+}
+
+void SwLanes::release() {
+  if (stream) (void)hipStreamDestroy(stream);
+  if (join) (void)hipEventDestroy(join);
+  if (fork) (void)hipEventDestroy(fork);
+  stream = nullptr, join = fork = nullptr;
+}
+
+// ---- the whole-volume call ------------------------------------------------------------------------------------------------------
+int sw_run(const SwNet& net, SwMapCache& cache, SwLanes* lanes, int vd, int vh, int vw, double overlap, int mode, double sigma_scale, int n_batch,
+           int out_kind, const float* d_w, const float* d_b, int classes, float* d_acc, float* d_cnt, void* d_out, hipStream_t st) {
+  // ---- every refusal comes before the first launch
+  const int max_batch = net.max_batch < kSwMaxBatch ? net.max_batch : kSwMaxBatch;      // (kSwMaxBatch sizes the corner list of a batch)
+  if (n_batch < 1 || n_batch > max_batch) return fail(AMX_ERR_INVALID, "%s1 <= n_batch <= %d (got %d)", net.prefix, max_batch, n_batch);
+  if (int rc = sw_map_check(mode, sigma_scale)) return rc;
+  const int rd = net.roi[0], rh = net.roi[1], rw = net.roi[2];
+  SwPlan plan;
+  if (int rc = sw_make_plan(vd, vh, vw, rd, rh, rw, overlap, &plan)) return rc;
+  const int nwin = plan.windows(), k = n_batch < nwin ? n_batch : nwin, ngroups = (nwin + k - 1) / k;
+  if (int rc = net.check(k)) return rc;
+  const long long voxels = (long long)vd * vh * vw;
+  if (int rc = sw_finish_check(out_kind, d_acc, d_cnt, net.channels, voxels, d_w, classes, d_out)) return rc;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  AMX_HIP(hipStreamIsCapturing(st, &cap));
+  // Refused for now.  The first call allocates the cached window weights, which a capture cannot hold; and although the UNet's call
+  // was written to stay on the caller's stream under capture, and each piece replays correctly on its own (count map, window
+  // batches, finish), the replayed whole gave other values at every second voxel of a row when captured through
+  // sliding_window_volume, and the cause is not found.  A wrong volume is worse than a refusal.
+  if (cap != hipStreamCaptureStatusNone)
+    return fail(AMX_ERR_INVALID, "%s cannot be captured into a graph yet: capture amx_sw_count_all, the network's forward_windows entry and "
+                "amx_sw_finish, which replay correctly, or call it outside the capture", net.entry);
+  // two batches in flight, as the window loop of registration/sliding_window.py keeps them
+  const bool two = lanes && net.lane_groups > 0 && ngroups >= net.lane_groups;
+  if (two) {
+    if (!lanes->stream) AMX_HIP(hipStreamCreateWithFlags(&lanes->stream, hipStreamNonBlocking));
+    if (!lanes->fork) AMX_HIP(hipEventCreateWithFlags(&lanes->fork, hipEventDisableTiming));
+    if (!lanes->join) AMX_HIP(hipEventCreateWithFlags(&lanes->join, hipEventDisableTiming));
+  }
+  // ---- launches
+  AMX_HIP(hipMemsetAsync(d_acc, 0, (size_t)net.channels * voxels * sizeof(float), st));
+  if (int rc = cache.fetch(rd, rh, rw, mode, sigma_scale, st)) return rc;
+  // slot 0 is the caller's stream, slot 1 the handle's: one stream more than the caller already has.  (Two streams of the handle's
+  // own beside an idle caller's stream cost the overlap where a process may open four hardware queues and already uses three.)
+  if (two) {
+    AMX_HIP(hipEventRecord(lanes->fork, st));
+    AMX_HIP(hipStreamWaitEvent(lanes->stream, lanes->fork, 0));
+  }
+  // the count map does not depend on the network: it runs beside the first window batch of slot 1 (it writes every voxel of d_cnt)
+  AMX_HIP(launch_sw_count_all(d_cnt, plan, cache.map, st));
+  int rc = AMX_OK;
+  for (int g = 0; g < ngroups && rc == AMX_OK; ++g) {
+    int offs[kSwMaxBatch * 3];
+    const int w0 = g * k, nw = nwin - w0 < k ? nwin - w0 : k, slot = two ? g & 1 : -1;
+    for (int i = 0; i < nw; ++i) plan.corner(w0 + i, offs + 3 * i);
+    rc = net.run(nw, offs, slot, slot == 1 ? lanes->stream : st);
+  }
+  if (two) {    // joined also after a failed enqueue: the caller's stream must not run ahead of what was launched
+    AMX_HIP(hipEventRecord(lanes->join, lanes->stream));
+    AMX_HIP(hipStreamWaitEvent(st, lanes->join, 0));
+  }
+  if (rc != AMX_OK) return rc;
+  AMX_HIP(launch_sw_finish(out_kind, d_acc, d_cnt, net.channels, voxels, d_w, d_b, classes, d_out, st));
+  return AMX_OK;
+}
+
 }  // namespace amx

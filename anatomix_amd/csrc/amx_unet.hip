@@ -61,13 +61,9 @@ struct amx_unet {
   int* h_flag = nullptr;    // pinned host mirror, written by the last kernel of a forward when the device flag is up
   int* h_flag_dev = nullptr;   // the same memory as the device sees it
   hipEvent_t acc_done[2] = {nullptr, nullptr};   // amx_unet_forward_windows_pipelined: "slot s has finished accumulating"
-  // amx_sliding_window, all created at its first use: the stream that takes every other window batch (the caller's stream takes
-  // the rest) with the events that fork it from and join it to the caller's, and the window weights of the last (roi, mode, sigma_scale)
-  hipStream_t sw_stream = nullptr;
-  hipEvent_t sw_fork = nullptr, sw_join = nullptr, sw_map_ready = nullptr;
-  float* sw_map = nullptr;
-  int sw_map_roi[3] = {0, 0, 0}, sw_map_mode = -1;
-  double sw_map_sigma = 0.0;
+  // amx_sliding_window: the stream that takes every other window batch (the caller's stream takes the rest), and the window weights
+  amx::SwLanes sw_lanes;
+  amx::SwMapCache sw_map;
 };
 
 namespace {
@@ -1048,11 +1044,8 @@ void amx_unet_destroy(amx_unet_t* h) {
   if (h->h_flag) (void)hipHostFree(h->h_flag);
   for (int i = 0; i < 2; ++i)
     if (h->acc_done[i]) (void)hipEventDestroy(h->acc_done[i]);
-  if (h->sw_stream) (void)hipStreamDestroy(h->sw_stream);
-  if (h->sw_join) (void)hipEventDestroy(h->sw_join);
-  if (h->sw_fork) (void)hipEventDestroy(h->sw_fork);
-  if (h->sw_map_ready) (void)hipEventDestroy(h->sw_map_ready);
-  if (h->sw_map) (void)hipFree(h->sw_map);
+  h->sw_lanes.release();
+  h->sw_map.release();
   for (ConvLayer& L : h->convs) {
     if (L.wpk) (void)hipFree(L.wpk);
     if (L.wpk_up) (void)hipFree(L.wpk_up);
@@ -1188,10 +1181,10 @@ int amx_unet_forward_window(amx_unet_t* h, const float* d_vol, int vd, int vh, i
                             int ox, int rd, int rh, int rw, const float* d_wmap, float* d_acc,
                             void* d_workspace, size_t workspace_bytes, void* stream) {
   if (!h || !d_vol || !d_acc || !d_wmap || !d_workspace) return fail(AMX_ERR_INVALID, "null argument");
-  if (oz < 0 || oy < 0 || ox < 0 || oz + rd > vd || oy + rh > vh || ox + rw > vw)
-    return fail(AMX_ERR_SHAPE, "window (%d,%d,%d)+(%d,%d,%d) outside volume (%d,%d,%d)", oz, oy, ox, rd, rh, rw, vd, vh, vw);
+  const int corner[3] = {oz, oy, ox};
+  long long off;
+  if (int rc = amx::sw_window_offsets(vd, vh, vw, rd, rh, rw, 1, corner, &off)) return rc;
   const long long vvox = (long long)vd * vh * vw;
-  const long long off = ((long long)oz * vh + oy) * vw + ox;
   return run_forward(h, ForwardArgs{d_vol + off, vvox * 4, (long long)vh * vw * 4, (long long)vw * 4, d_acc + off,
                                     vvox * h->cfg.output_nc, vvox, (long long)vh * vw, vw, d_wmap, 1, rd, rh, rw,
                                     d_workspace, workspace_bytes, (hipStream_t)stream});
@@ -1204,12 +1197,7 @@ static int forward_windows(amx_unet* h, const float* d_vol, int vd, int vh, int 
   if (!h || !d_vol || !d_acc || !d_wmap || !d_workspace || !offsets_zyx) return fail(AMX_ERR_INVALID, "null argument");
   if (n_windows < 1 || n_windows > 64) return fail(AMX_ERR_INVALID, "1 <= n_windows <= 64 (got %d)", n_windows);
   long long offs[64];
-  for (int i = 0; i < n_windows; ++i) {
-    const int oz = offsets_zyx[3 * i], oy = offsets_zyx[3 * i + 1], ox = offsets_zyx[3 * i + 2];
-    if (oz < 0 || oy < 0 || ox < 0 || oz + rd > vd || oy + rh > vh || ox + rw > vw)
-      return fail(AMX_ERR_SHAPE, "window (%d,%d,%d)+(%d,%d,%d) outside volume (%d,%d,%d)", oz, oy, ox, rd, rh, rw, vd, vh, vw);
-    offs[i] = ((long long)oz * vh + oy) * vw + ox;
-  }
+  if (int rc = amx::sw_window_offsets(vd, vh, vw, rd, rh, rw, n_windows, offsets_zyx, offs)) return rc;
   const long long vvox = (long long)vd * vh * vw;
   return run_forward(h, ForwardArgs{d_vol, vvox * 4, (long long)vh * vw * 4, (long long)vw * 4, d_acc, vvox * h->cfg.output_nc, vvox,
                                     (long long)vh * vw, vw, d_wmap, n_windows, rd, rh, rw, d_workspace, workspace_bytes,
@@ -1239,102 +1227,36 @@ size_t amx_sliding_window_workspace_bytes(const amx_unet_t* h, int n_batch, int 
   return h ? 2 * align_up(layout(h, n_batch, rd, rh, rw).total, 256) : 0;
 }
 
-// the window weights of (roi, mode, sigma_scale) on the handle: built on `st` when the key is new, else the build is waited for
-static int sw_fetch_map(amx_unet* h, int rd, int rh, int rw, int mode, double sigma_scale, hipStream_t st) {
-  if (!h->sw_map_ready) AMX_HIP(hipEventCreateWithFlags(&h->sw_map_ready, hipEventDisableTiming));
-  if (h->sw_map && h->sw_map_roi[0] == rd && h->sw_map_roi[1] == rh && h->sw_map_roi[2] == rw && h->sw_map_mode == mode &&
-      (mode == AMX_SW_MAP_CONSTANT || h->sw_map_sigma == sigma_scale)) {
-    AMX_HIP(hipStreamWaitEvent(st, h->sw_map_ready, 0));
-    return AMX_OK;
-  }
-  const size_t bytes = (size_t)rd * rh * rw * sizeof(float);
-  if (!h->sw_map || (size_t)h->sw_map_roi[0] * h->sw_map_roi[1] * h->sw_map_roi[2] * sizeof(float) != bytes) {
-    if (h->sw_map) (void)hipFree(h->sw_map);     // (waits for the device: no earlier call still reads it)
-    h->sw_map = nullptr;
-    h->sw_map_mode = -1;
-    AMX_HIP(hipMalloc((void**)&h->sw_map, bytes));
-  }
-  h->sw_map_mode = -1;
-  AMX_HIP(amx::launch_sw_importance_map(h->sw_map, rd, rh, rw, mode, sigma_scale, st));
-  AMX_HIP(hipEventRecord(h->sw_map_ready, st));
-  h->sw_map_roi[0] = rd, h->sw_map_roi[1] = rh, h->sw_map_roi[2] = rw, h->sw_map_mode = mode, h->sw_map_sigma = sigma_scale;
-  return AMX_OK;
-}
-
 int amx_sliding_window(amx_unet_t* h, const float* d_vol, int vd, int vh, int vw, int rd, int rh, int rw, double overlap,
                        int mode, double sigma_scale, int n_batch, int out_kind, const float* d_w, const float* d_b,
                        int classes, float* d_acc, float* d_cnt, void* d_out, void* d_workspace, size_t workspace_bytes,
                        void* stream) {
   if (!h || !d_vol || !d_acc || !d_cnt || !d_workspace) return fail(AMX_ERR_INVALID, "null argument");
-  hipStream_t st = (hipStream_t)stream;
-  // ---- every refusal comes before the first launch
   const amx_unet_cfg& c = h->cfg;
-  if (c.input_nc != 1) return fail(AMX_ERR_SHAPE, "the sliding-window call needs input_nc == 1 (got %d)", c.input_nc);
-  if (c.output_nc % 16 || c.output_nc > 32)
-    return fail(AMX_ERR_SHAPE, "the sliding-window call accumulates output_nc = 16 or 32 channels (got %d): use the window loop of the caller", c.output_nc);
-  if (rw < 32) return fail(AMX_ERR_SHAPE, "the sliding-window call needs roi width >= 32 (got %d)", rw);
-  if (n_batch < 1 || n_batch > 64) return fail(AMX_ERR_INVALID, "1 <= n_batch <= 64 (got %d)", n_batch);
-  if (mode != AMX_SW_MAP_CONSTANT && mode != AMX_SW_MAP_GAUSSIAN) return fail(AMX_ERR_INVALID, "mode: constant (0) or gaussian (1) (got %d)", mode);
-  if (mode == AMX_SW_MAP_GAUSSIAN && !(sigma_scale > 0.0)) return fail(AMX_ERR_INVALID, "sigma_scale must be positive (got %g)", sigma_scale);
-  amx::SwPlan plan;
-  if (int rc = amx::sw_make_plan(vd, vh, vw, rd, rh, rw, overlap, &plan)) return rc;
-  const int nwin = plan.windows(), k = n_batch < nwin ? n_batch : nwin, ngroups = (nwin + k - 1) / k;
-  if (int rc = check_shape(h, k, rd, rh, rw)) return rc;
-  for (const ConvLayer& L : h->convs)
-    if (!L.loaded) return fail(AMX_ERR_NOT_LOADED, "conv model.%d has no parameters", L.module_idx);
-  const long long voxels = (long long)vd * vh * vw;
-  if (int rc = amx::sw_finish_check(out_kind, d_acc, d_cnt, c.output_nc, voxels, d_w, classes, d_out)) return rc;
-  const size_t slot_bytes = align_up(layout(h, k, rd, rh, rw).total, 256), need = amx_sliding_window_workspace_bytes(h, n_batch, rd, rh, rw);
-  if (workspace_bytes < need || ((uintptr_t)d_workspace & 255))
-    return fail(AMX_ERR_WORKSPACE, "workspace needs %zu bytes, 256-byte aligned (got %zu)", need, workspace_bytes);
-  if (int e = pending_numerics_error(h)) return e;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  AMX_HIP(hipStreamIsCapturing(st, &cap));
-  // Refused for now: the call was written to stay on the caller's stream under capture, and each piece replays correctly on its own
-  // (count map, window batches, finish), but the replayed whole gave other values at every second voxel of a row when captured through
-  // sliding_window_volume, and the cause is not found.  A wrong volume is worse than a refusal.
-  if (cap != hipStreamCaptureStatusNone)
-    return fail(AMX_ERR_INVALID, "amx_sliding_window cannot be captured into a graph yet: capture amx_sw_count_all, amx_unet_forward_windows and "
-                "amx_sw_finish, which replay correctly, or call it outside the capture");
-  // two batches in flight, as the window loop of registration/sliding_window.py keeps them
-  const bool pipelined = ngroups >= 4;
-  if (pipelined) {
-    for (int i = 0; i < 2; ++i)
-      if (!h->acc_done[i]) AMX_HIP(hipEventCreateWithFlags(&h->acc_done[i], hipEventDisableTiming));
-    if (!h->sw_stream) AMX_HIP(hipStreamCreateWithFlags(&h->sw_stream, hipStreamNonBlocking));
-    if (!h->sw_fork) AMX_HIP(hipEventCreateWithFlags(&h->sw_fork, hipEventDisableTiming));
-    if (!h->sw_join) AMX_HIP(hipEventCreateWithFlags(&h->sw_join, hipEventDisableTiming));
-  }
-  // ---- launches
-  AMX_HIP(hipMemsetAsync(d_acc, 0, (size_t)c.output_nc * voxels * sizeof(float), st));
-  if (int rc = sw_fetch_map(h, rd, rh, rw, mode, sigma_scale, st)) return rc;
-  // slot 0 is the caller's stream, slot 1 the handle's: one stream more than the caller already has.  (Two streams of the handle's
-  // own beside an idle caller's stream cost the overlap where a process may open four hardware queues and already uses three.)
-  hipStream_t lane[2] = {st, h->sw_stream};
-  if (pipelined) {
-    AMX_HIP(hipEventRecord(h->sw_fork, st));
-    AMX_HIP(hipStreamWaitEvent(lane[1], h->sw_fork, 0));
-  }
-  // the count map does not depend on the network: it runs beside the first window batch of slot 1 (it writes every voxel of d_cnt)
-  AMX_HIP(amx::launch_sw_count_all(d_cnt, plan, h->sw_map, st));
-  int rc = AMX_OK;
-  for (int g = 0; g < ngroups && rc == AMX_OK; ++g) {
-    int offs[64 * 3];
-    const int w0 = g * k, nw = nwin - w0 < k ? nwin - w0 : k, slot = g & 1;
-    for (int i = 0; i < nw; ++i) plan.corner(w0 + i, offs + 3 * i);
-    if (pipelined)
-      rc = forward_windows(h, d_vol, vd, vh, vw, nw, offs, rd, rh, rw, h->sw_map, d_acc, (char*)d_workspace + slot * slot_bytes, slot_bytes,
-                           lane[slot], h->acc_done[slot ^ 1], h->acc_done[slot]);
-    else
-      rc = forward_windows(h, d_vol, vd, vh, vw, nw, offs, rd, rh, rw, h->sw_map, d_acc, d_workspace, slot_bytes, st, nullptr, nullptr);
-  }
-  if (pipelined) {    // joined also after a failed enqueue: the caller's stream must not run ahead of what was launched
-    AMX_HIP(hipEventRecord(h->sw_join, lane[1]));
-    AMX_HIP(hipStreamWaitEvent(st, h->sw_join, 0));
-  }
-  if (rc != AMX_OK) return rc;
-  AMX_HIP(amx::launch_sw_finish(out_kind, d_acc, d_cnt, c.output_nc, voxels, d_w, d_b, classes, d_out, st));
-  return AMX_OK;
+  size_t slot_bytes = 0;      // one batch's workspace: the caller's holds two, one per slot
+  amx::SwNet net{"amx_sliding_window", "", c.output_nc, 64, {rd, rh, rw}, 4};
+  net.check = [&](int k) {
+    if (c.input_nc != 1) return fail(AMX_ERR_SHAPE, "the sliding-window call needs input_nc == 1 (got %d)", c.input_nc);
+    if (c.output_nc % 16 || c.output_nc > 32)
+      return fail(AMX_ERR_SHAPE, "the sliding-window call accumulates output_nc = 16 or 32 channels (got %d): use the window loop of the caller", c.output_nc);
+    if (rw < 32) return fail(AMX_ERR_SHAPE, "the sliding-window call needs roi width >= 32 (got %d)", rw);
+    if (int rc = check_shape(h, k, rd, rh, rw)) return rc;
+    for (const ConvLayer& L : h->convs)
+      if (!L.loaded) return fail(AMX_ERR_NOT_LOADED, "conv model.%d has no parameters", L.module_idx);
+    slot_bytes = align_up(layout(h, k, rd, rh, rw).total, 256);
+    const size_t need = amx_sliding_window_workspace_bytes(h, n_batch, rd, rh, rw);
+    if (workspace_bytes < need || ((uintptr_t)d_workspace & 255))
+      return fail(AMX_ERR_WORKSPACE, "workspace needs %zu bytes, 256-byte aligned (got %zu)", need, workspace_bytes);
+    return pending_numerics_error(h);
+  };
+  net.run = [&](int nw, const int* offs, int slot, hipStream_t st) {
+    if (slot < 0) return forward_windows(h, d_vol, vd, vh, vw, nw, offs, rd, rh, rw, h->sw_map.map, d_acc, d_workspace, slot_bytes, st, nullptr, nullptr);
+    return amx_unet_forward_windows_pipelined(h, d_vol, vd, vh, vw, nw, offs, rd, rh, rw, h->sw_map.map, d_acc,
+                                              (char*)d_workspace + slot * slot_bytes, slot_bytes, slot, st);
+  };
+  return amx::sw_run(net, h->sw_map, &h->sw_lanes, vd, vh, vw, overlap, mode, sigma_scale, n_batch, out_kind, d_w, d_b, classes, d_acc, d_cnt,
+                     d_out, (hipStream_t)stream);
 }
 
 }  // extern "C"
+

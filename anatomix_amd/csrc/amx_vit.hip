@@ -81,11 +81,7 @@ struct amx_vit {
   // workspace bookkeeping of the last forward (debug reads)
   struct Named { std::string name; char* ptr; size_t bytes; };
   std::vector<Named> dbg;
-  // amx_vit_sliding_window: the window weights of the handle's roi, cached per (mode, sigma_scale); allocated at its first call
-  float* sw_map = nullptr;
-  int sw_map_mode = -1;
-  double sw_map_sigma = 0.0;
-  hipEvent_t sw_map_ready = nullptr;
+  amx::SwMapCache sw_map;      // amx_vit_sliding_window: the window weights of the handle's roi
 };
 
 namespace {
@@ -229,8 +225,7 @@ int amx_vit_create(amx_vit_t** out, const amx_vit_cfg* cfg) {
 void amx_vit_destroy(amx_vit_t* h) {
   if (!h) return;
   if (h->params) (void)hipFree(h->params);
-  if (h->sw_map) (void)hipFree(h->sw_map);
-  if (h->sw_map_ready) (void)hipEventDestroy(h->sw_map_ready);
+  h->sw_map.release();
   delete h;
 }
 
@@ -608,12 +603,7 @@ int forward_windows(amx_vit* h, const float* d_vol, int vd, int vh, int vw, int 
   const amx_vit_cfg& c = h->cfg;
   const int rd = c.grid_d * 8, rh = c.grid_h * 8, rw = c.grid_w * 8;
   VitCorners cn{};
-  for (int i = 0; i < n; ++i) {
-    const int oz = offsets_zyx[3 * i], oy = offsets_zyx[3 * i + 1], ox = offsets_zyx[3 * i + 2];
-    if (oz < 0 || oy < 0 || ox < 0 || oz + rd > vd || oy + rh > vh || ox + rw > vw)
-      return fail(AMX_ERR_SHAPE, "vit: window (%d,%d,%d)+(%d,%d,%d) outside volume (%d,%d,%d)", oz, oy, ox, rd, rh, rw, vd, vh, vw);
-    cn.off[i] = ((long long)oz * vh + oy) * vw + ox;
-  }
+  if (int rc = amx::sw_window_offsets(vd, vh, vw, rd, rh, rw, n, offsets_zyx, cn.off)) return rc;
   // ---- launches
   float* win = (float*)d_ws;
   const Plan P = make_plan(h, n, (char*)d_ws + windows_ws(h, n).gather);
@@ -624,24 +614,6 @@ int forward_windows(amx_vit* h, const float* d_vol, int vd, int vh, int vw, int 
   VitOut out;
   out.acc = d_acc; out.wmap = d_wmap; out.vd = vd; out.vh = vh; out.vw = vw; out.corner = cn.off;
   return vit_run(h, win, out, n, P, -1, st);
-}
-
-// the window weights of (mode, sigma_scale) on the handle (the roi is the handle's): built on `st` when the key is new, else the
-// build is waited for
-int fetch_map(amx_vit* h, int mode, double sigma_scale, hipStream_t st) {
-  const amx_vit_cfg& c = h->cfg;
-  if (!h->sw_map_ready) AMX_HIP(hipEventCreateWithFlags(&h->sw_map_ready, hipEventDisableTiming));
-  if (h->sw_map && h->sw_map_mode == mode && (mode == AMX_SW_MAP_CONSTANT || h->sw_map_sigma == sigma_scale)) {
-    AMX_HIP(hipStreamWaitEvent(st, h->sw_map_ready, 0));
-    return AMX_OK;
-  }
-  if (!h->sw_map) AMX_HIP(hipMalloc((void**)&h->sw_map, (size_t)h->V * 512 * sizeof(float)));
-  else AMX_HIP(hipStreamWaitEvent(st, h->sw_map_ready, 0));
-  h->sw_map_mode = -1;
-  AMX_HIP(amx::launch_sw_importance_map(h->sw_map, c.grid_d * 8, c.grid_h * 8, c.grid_w * 8, mode, sigma_scale, st));
-  AMX_HIP(hipEventRecord(h->sw_map_ready, st));
-  h->sw_map_mode = mode, h->sw_map_sigma = sigma_scale;
-  return AMX_OK;
 }
 
 }  // namespace
@@ -682,37 +654,14 @@ int amx_vit_sliding_window(amx_vit_t* h, const float* d_vol, int vd, int vh, int
                            int out_kind, const float* d_w, const float* d_b, int classes, float* d_acc, float* d_cnt, void* d_out, void* d_ws,
                            size_t ws_bytes, void* stream) {
   if (!h || !d_vol || !d_acc || !d_cnt || !d_ws) return fail(AMX_ERR_INVALID, "null argument");
-  hipStream_t st = (hipStream_t)stream;
-  // ---- every refusal comes before the first launch
   const amx_vit_cfg& c = h->cfg;
-  const int rd = c.grid_d * 8, rh = c.grid_h * 8, rw = c.grid_w * 8;
-  if (n_batch < 1 || n_batch > kVitMaxWindows) return fail(AMX_ERR_INVALID, "vit: 1 <= n_batch <= %d (got %d)", kVitMaxWindows, n_batch);
-  if (mode != AMX_SW_MAP_CONSTANT && mode != AMX_SW_MAP_GAUSSIAN) return fail(AMX_ERR_INVALID, "mode: constant (0) or gaussian (1) (got %d)", mode);
-  if (mode == AMX_SW_MAP_GAUSSIAN && !(sigma_scale > 0.0)) return fail(AMX_ERR_INVALID, "sigma_scale must be positive (got %g)", sigma_scale);
-  amx::SwPlan plan;
-  if (int rc = amx::sw_make_plan(vd, vh, vw, rd, rh, rw, overlap, &plan)) return rc;
-  if (int rc = windows_check(h, vd, vh, vw, n_batch, d_ws, ws_bytes)) return rc;
-  const long long voxels = (long long)vd * vh * vw;
-  if (int rc = amx::sw_finish_check(out_kind, d_acc, d_cnt, c.num_classes, voxels, d_w, classes, d_out)) return rc;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  AMX_HIP(hipStreamIsCapturing(st, &cap));
-  // the first call allocates the cached window weights, which a capture cannot hold; amx_sliding_window has the same contract
-  if (cap != hipStreamCaptureStatusNone)
-    return fail(AMX_ERR_INVALID, "amx_vit_sliding_window cannot be captured into a graph: capture amx_sw_count_all, amx_vit_forward_windows and "
-                "amx_sw_finish, or call it outside the capture");
-  // ---- launches, all on `stream`
-  const int nwin = plan.windows(), k = n_batch < nwin ? n_batch : nwin;
-  AMX_HIP(hipMemsetAsync(d_acc, 0, (size_t)c.num_classes * voxels * sizeof(float), st));
-  if (int rc = fetch_map(h, mode, sigma_scale, st)) return rc;
-  AMX_HIP(amx::launch_sw_count_all(d_cnt, plan, h->sw_map, st));
-  for (int w0 = 0; w0 < nwin; w0 += k) {
-    int offs[kVitMaxWindows * 3];
-    const int nw = nwin - w0 < k ? nwin - w0 : k;
-    for (int i = 0; i < nw; ++i) plan.corner(w0 + i, offs + 3 * i);
-    if (int rc = forward_windows(h, d_vol, vd, vh, vw, nw, offs, h->sw_map, d_acc, d_ws, ws_bytes, st)) return rc;
-  }
-  AMX_HIP(amx::launch_sw_finish(out_kind, d_acc, d_cnt, c.num_classes, voxels, d_w, d_b, classes, d_out, st));
-  return AMX_OK;
+  amx::SwNet net{"amx_vit_sliding_window", "vit: ", c.num_classes, kVitMaxWindows, {c.grid_d * 8, c.grid_h * 8, c.grid_w * 8}, 0};      // one stream
+  net.check = [&](int) { return windows_check(h, vd, vh, vw, n_batch, d_ws, ws_bytes); };
+  net.run = [&](int nw, const int* offs, int, hipStream_t st) {
+    return forward_windows(h, d_vol, vd, vh, vw, nw, offs, h->sw_map.map, d_acc, d_ws, ws_bytes, st);
+  };
+  return amx::sw_run(net, h->sw_map, nullptr, vd, vh, vw, overlap, mode, sigma_scale, n_batch, out_kind, d_w, d_b, classes, d_acc, d_cnt, d_out,
+                     (hipStream_t)stream);
 }
 
 /* Copies a workspace buffer of the LAST forward on this handle (test / debugging aid): names "tokens" (after the tokenizer:

@@ -142,6 +142,7 @@ class Unet(nn.Module):
         self._weights_dirty = True
         self._workspace = None
         self._side_streams, self._side_ws = None, [None, None]
+        self._sw_streams = self._sw_ws = self._swv_ws = None      # sliding-window state: see _sw_state
         self.concurrent_chunks = 4       # batches of >= 2 chunks of this many volumes run as chunks on two streams (0: off)
         self._warned = False
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._mark_dirty())
@@ -199,7 +200,8 @@ class Unet(nn.Module):
     # nn.DataParallel replicas (which copy __dict__) must not share them: a copy starts without a handle and builds its own on
     # its first HIP forward (sharing the raw pointer would be a use-after-free on the first re-create and a double free in
     # __del__; ctypes pointers do not pickle either).
-    _PER_OBJECT_STATE = ("_handle", "_handle_key", "_workspace", "_uploaded_sig", "_sig_tensors", "_side_streams", "_side_ws", "_sw_streams", "_sw_ws")
+    _PER_OBJECT_STATE = ("_handle", "_handle_key", "_workspace", "_uploaded_sig", "_sig_tensors", "_side_streams", "_side_ws", "_sw_streams", "_sw_ws",
+                         "_swv_ws")
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -353,6 +355,21 @@ class Unet(nn.Module):
             ws = torch.empty(need, dtype=torch.uint8, device=device)
             self._workspace = ws
         return ws, need
+
+    def _sw_state(self, need, device, lanes=False):
+        """This object's sliding-window state (registration/sliding_window.py) on ``device``, its workspace grown to ``need`` bytes:
+        the workspace of the whole-volume call, or with ``lanes`` the two streams of the pipelined window route and the workspace of
+        the second one (the first uses ``_get_workspace``'s)."""
+        if not lanes:
+            if self._swv_ws is None or self._swv_ws.numel() < need or self._swv_ws.device != device:
+                self._swv_ws = torch.empty(need, dtype=torch.uint8, device=device)
+            return self._swv_ws
+        if self._sw_streams is None or self._sw_streams[0].device != device:
+            self._sw_streams = [torch.cuda.Stream(device) for _ in range(2)]
+            self._sw_ws = None
+        if self._sw_ws is None or self._sw_ws.numel() < need:
+            self._sw_ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._sw_streams, self._sw_ws
 
     def forward_hip(self, x):
         """[N,1,D,H,W] -> [N,output_nc,D,H,W] fp32, all work enqueued on the current HIP stream."""

@@ -94,14 +94,132 @@ def importance_map(roi_size: Sequence[int], mode: str = "constant", sigma_scale:
     return m.clamp_(min=floor).to(torch.float32)
 
 
-def _fused_ok(predictor, inputs, roi) -> bool:
-    """The fused window step (amx_unet_forward_windows) takes a bare Unet on the HIP path whose output conv can accumulate straight
-    into the fp32 volume: output_nc a multiple of 16 and <= 32, roi width >= 32 (include/anatomix_amd.h; other shapes leave through
-    the export pass, which the generic window loop below handles)."""
+FUSED_WINDOW_BATCH = 4     # windows per amx_unet_forward_windows call (fills the chip on the deep levels)
+PIPELINE_WINDOWS = True    # keep two window batches in flight on two HIP streams (ordered accumulation, identical results)
+VIT_WINDOW_BATCH = 4       # windows per amx_vit_forward_windows call
+CALLS = {"vit_windows": 0, "vit_volume": 0}      # fused ViT calls: amx_vit_forward_windows / amx_vit_sliding_window (tests, diagnostics)
+_F16_STORAGE = ("f16", "fp16", "float16", "f16x2", "f16x2mx", "strict_mx")
+
+
+def _unet_unsupported_reason(model, inputs, roi):
+    """Why the fused Unet routes (amx_unet_forward_windows / amx_sliding_window) cannot take this call (None: they can).  The
+    envelope: the HIP path, one input channel, and an output conv that can accumulate straight into the fp32 volume -- output_nc 16
+    or 32, roi width >= 32 (include/anatomix_amd.h; other shapes leave through the export pass, which the generic window loop handles)."""
+    if not inputs.is_cuda:
+        return f"there is no host path (got a {inputs.device} tensor)"
+    if inputs.dim() != 5 or inputs.shape[1] != 1 or model._cfg["input_nc"] != 1:
+        return f"inputs [B, 1, D, H, W] and input_nc == 1 (got {tuple(inputs.shape)}, input_nc {model._cfg['input_nc']})"
+    cout = model._cfg["output_nc"]
+    if cout % 16 or cout > 32:
+        return f"output_nc must be 16 or 32 for the in-place accumulation (got output_nc={cout})"
+    if roi[2] < 32:
+        return f"roi width >= 32 (got {roi[2]})"
+    return model.hip_unsupported_reason(inputs[:, :, :1, :1, :1].expand(-1, -1, 2, 2, 2))
+
+
+class _UnetRoute:
+    """A bare ``anatomix_amd.Unet`` as the two fused routes below see it."""
+    two_streams = True         # the window route keeps two batches in flight (PIPELINE_WINDOWS)
+    unsupported_reason = staticmethod(_unet_unsupported_reason)
+
+    def channels(self, model):
+        return model._cfg["output_nc"]
+
+    def batch(self):
+        return FUSED_WINDOW_BATCH
+
+    def prepare(self, model, dev, roi, k, whole=False):
+        """Handle and weights on ``dev`` -> (lib, workspace, its bytes) for batches of k windows, or for the whole-volume call."""
+        lib = model._ensure_handle(dev)
+        if model._weights_stale():
+            model._upload_weights(lib, dev)
+        if not whole:
+            return (lib,) + model._get_workspace(lib, k, roi[0], roi[1], roi[2], dev)
+        need = lib.amx_sliding_window_workspace_bytes(model._handle, k, *roi)
+        return lib, model._sw_state(need, dev), need
+
+    def windows(self, lib, model, x, size, grp, offs, roi, wm, acc, ws, need, st, slot=None):
+        args = (model._handle, _lib.ptr(x), *size, len(grp), offs, *roi, _lib.ptr(wm), _lib.ptr(acc), _lib.ptr(ws), need)
+        return lib.amx_unet_forward_windows(*args, st) if slot is None else lib.amx_unet_forward_windows_pipelined(*args, slot, st)
+
+    def volume(self, lib, model, x, size, roi, sw, batch, finish, ws, need, st):
+        return lib.amx_sliding_window(model._handle, _lib.ptr(x), *size, *roi, *sw, batch, *finish, _lib.ptr(ws), need, st)
+
+    def after(self, model):
+        if model.precision in _F16_STORAGE and not torch.cuda.is_current_stream_capturing():
+            # the accumulation volume leaves the library here: one synchronising range check per call (f16 storage only)
+            model.check_numerics(synchronize=True)
+
+
+def _vit_unsupported_reason(model, inputs, roi):
+    """Why the fused ViT routes (amx_vit_forward_windows / amx_vit_sliding_window) cannot take this call (None: they can).  The
+    envelope: a CUDA tensor, no grad, ``use_engine``, roi equal to the model's input shape, one input channel, an output norm the
+    engine applies itself (none / demean) and a configuration amx_vit_create takes."""
+    from ..model.vit3d.architectures import ChannelDemean
+    if not inputs.is_cuda:
+        return f"there is no host path (got a {inputs.device} tensor)"
+    if torch.is_grad_enabled():
+        return "the engine runs under torch.no_grad() only"
+    if not model.use_engine:
+        return "model.use_engine is off"
+    if inputs.dim() != 5 or inputs.shape[1] != 1 or model._vit_cfg["input_channels"] != 1:
+        return f"inputs [B, 1, D, H, W] and input_channels == 1 (got {tuple(inputs.shape)}, input_channels {model._vit_cfg['input_channels']})"
+    shape = tuple(8 * g for g in model.grid)
+    if tuple(roi) != shape:
+        return f"roi must be the model's input shape {shape} (got {tuple(roi)})"
+    if not isinstance(model.out_norm, (ChannelDemean, nn.Identity)):
+        return f"out_norm must be 'none' or 'demean', which the engine applies per window (got {type(model.out_norm).__name__})"
+    try:
+        with torch.cuda.device(inputs.device):
+            model._engine(inputs.device)
+    except _lib.AmxError as e:
+        if getattr(e, "code", None) not in (_lib.AMX_ERR_INVALID, _lib.AMX_ERR_SHAPE):
+            raise
+        return f"the HIP engine does not cover this configuration ({e})"
+    return None
+
+
+class _VitRoute:
+    """A bare ``PrimusV2`` on its engine: one stream, the roi is the model's input shape."""
+    two_streams = False
+    unsupported_reason = staticmethod(_vit_unsupported_reason)
+
+    def channels(self, model):
+        return model._vit_cfg["num_classes"]
+
+    def batch(self):
+        return VIT_WINDOW_BATCH
+
+    def prepare(self, model, dev, roi, k, whole=False):
+        lib, _ = model._engine(dev)
+        need = (lib.amx_vit_sliding_window_workspace_bytes if whole else lib.amx_vit_windows_workspace_bytes)(model._handle, k)
+        return lib, model._engine_workspace(need, dev), need
+
+    def windows(self, lib, model, x, size, grp, offs, roi, wm, acc, ws, need, st, slot=None):
+        CALLS["vit_windows"] += 1
+        return lib.amx_vit_forward_windows(model._handle, _lib.ptr(x), *size, len(grp), offs, _lib.ptr(wm), _lib.ptr(acc), _lib.ptr(ws), need, st)
+
+    def volume(self, lib, model, x, size, roi, sw, batch, finish, ws, need, st):
+        CALLS["vit_volume"] += 1
+        return lib.amx_vit_sliding_window(model._handle, _lib.ptr(x), *size, *sw, batch, *finish, _lib.ptr(ws), need, st)
+
+    def after(self, model):
+        pass
+
+
+_UNET, _VIT = _UnetRoute(), _VitRoute()
+
+
+def _route(model):
+    """The adapter of a bare network that has fused routes, else None."""
     from ..model.network import Unet
-    return (isinstance(predictor, Unet) and inputs.is_cuda and inputs.shape[1] == 1 and
-            predictor._cfg["output_nc"] % 16 == 0 and predictor._cfg["output_nc"] <= 32 and roi[2] >= 32 and
-            predictor.hip_unsupported_reason(inputs[:, :, :1, :1, :1].expand(-1, -1, 2, 2, 2)) is None)
+    from ..model.vit3d.architectures import PrimusV2
+    return _UNET if isinstance(model, Unet) else _VIT if isinstance(model, PrimusV2) else None
+
+
+def _fused_ok(predictor, inputs, roi) -> bool:
+    """True when the fused window step (amx_unet_forward_windows) takes this call: a bare Unet inside ``_unet_unsupported_reason``."""
+    return _route(predictor) is _UNET and _unet_unsupported_reason(predictor, inputs, roi) is None
 
 
 def _is_affine_leaf(m) -> bool:
@@ -174,15 +292,24 @@ def _pointwise_affine(module) -> bool:
             return False
 
 
-def _split_unet_and_head(predictor, inputs, roi):
-    """train_segmentation.py:194-199 validates with predictor = nn.Sequential(Unet, UnetOutBlock).  A per-voxel affine head commutes
-    with the window averaging -- sum_w w (A f + b) / sum_w w = A (sum_w w f / sum_w w) + b -- so the windows run through the fused
-    path up to the Unet's output and the head is applied once to the normalised volume.  Any other head: generic window loop."""
-    if isinstance(predictor, nn.Sequential) and len(predictor) >= 2 and _fused_ok(predictor[0], inputs, roi):
-        head = predictor[1] if len(predictor) == 2 else nn.Sequential(*list(predictor.children())[1:])
-        if not torch.is_grad_enabled() and _pointwise_affine(head):
-            return predictor[0], head
-    return None
+def _split_net_and_head(predictor, inputs, roi):
+    """(network, head or None) when the windows can take a fused route: a bare Unet or PrimusV2 inside its envelope, or
+    nn.Sequential(network, head) -- train_segmentation.py:194-199 validates with nn.Sequential(Unet, UnetOutBlock).  A per-voxel
+    affine head commutes with the window averaging -- sum_w w (A f + b) / sum_w w = A (sum_w w f / sum_w w) + b -- so the windows run
+    fused up to the network's output and the head is applied once to the normalised volume (under no_grad only).  Any other head,
+    any other predictor: None, the generic window loop."""
+    bare = _route(predictor) is not None
+    net = predictor if bare else predictor[0] if isinstance(predictor, nn.Sequential) and len(predictor) >= 2 else None
+    route = _route(net)
+    if route is None or route.unsupported_reason(net, inputs, roi) is not None:
+        return None
+    if bare:
+        return net, None
+    head = predictor[1] if len(predictor) == 2 else nn.Sequential(*list(predictor.children())[1:])
+    return (net, head) if not torch.is_grad_enabled() and _pointwise_affine(head) else None
+
+
+_split_unet_and_head = _split_net_and_head      # the name from before the ViT shared this function: the same function, kept callable
 
 
 def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable,
@@ -196,16 +323,7 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int,
         roi_size = (roi_size,) * 3
     roi = tuple(int(r) for r in roi_size)
     B = inputs.shape[0]
-    orig = tuple(inputs.shape[2:])
-    # pad up to the ROI (symmetric, extra voxel at the end), crop back at the end
-    pads, need_pad = [], False
-    for k in range(2, -1, -1):
-        diff = max(roi[k] - orig[k], 0)
-        half = diff // 2
-        pads += [half, diff - half]
-        need_pad |= diff > 0
-    if need_pad:
-        inputs = F.pad(inputs, pads, mode=padding_mode, value=cval)
+    inputs, crop = _pad_to_roi(inputs, roi, padding_mode, cval)
     size = tuple(inputs.shape[2:])
     starts = window_starts(size, roi, overlap)
     wmap = importance_map(roi, mode, sigma_scale, inputs.device)
@@ -237,17 +355,10 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int,
     cnt = torch.zeros(lsize, dtype=torch.float32, device=inputs.device)
     acc = None
     head = None
-    fused = _fused_ok(predictor, inputs, roi)
-    if not fused:
-        split = _split_unet_and_head(predictor, inputs, roi)
-        if split is not None:
-            (predictor, head), fused = split, True
-    vit = None if fused else _split_vit_and_head(predictor, inputs, roi)
-    if fused:
+    split = _split_net_and_head(predictor, inputs, roi)
+    if split is not None:
+        predictor, head = split
         acc = _run_fused(inputs, roi, mine, wmap, predictor, cnt)
-    elif vit is not None:
-        predictor, head = vit
-        acc = _run_fused_vit(inputs, roi, mine, wmap, predictor, cnt)
     else:
         for b0 in range(0, len(mine) * B, sw_batch_size):
             idx = range(b0, min(b0 + sw_batch_size, len(mine) * B))
@@ -269,7 +380,7 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int,
         if head is not None:
             slab = _apply_head(head, slab)
         if return_slab:
-            if need_pad:
+            if crop is not None:
                 raise ValueError("return_slab needs a volume at least as large as the roi (no padding)")
             return slab, z0, z1
         acc = _gather_slabs(slab, size[0], world, group)
@@ -277,10 +388,24 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int,
         _normalize(acc, cnt)
         if head is not None:
             acc = _apply_head(head, acc)
-    if need_pad:
-        zs, ys, xs = pads[4], pads[2], pads[0]
-        acc = acc[:, :, zs:zs + orig[0], ys:ys + orig[1], xs:xs + orig[2]]
-    return acc
+    return _crop(acc, crop)
+
+
+def _pad_to_roi(inputs, roi, mode, value):
+    """Pads a volume smaller than the ROI up to it (symmetric, the extra voxel at the end) -> (inputs, crop): what ``_crop`` needs to
+    cut the original extent back out of a result, None when nothing was padded."""
+    orig = tuple(inputs.shape[2:])
+    pads = []
+    for k in range(2, -1, -1):
+        diff = max(roi[k] - orig[k], 0)
+        pads += [diff // 2, diff - diff // 2]
+    if not any(pads):
+        return inputs, None
+    return F.pad(inputs, pads, mode=mode, value=value), tuple(slice(pads[4 - 2 * k], pads[4 - 2 * k] + orig[k]) for k in range(3))
+
+
+def _crop(t, crop):
+    return t if crop is None else t[(slice(None), slice(None)) + crop]
 
 
 def _apply_head(head, feat, planes=32):
@@ -361,79 +486,49 @@ def _gather_slabs(slab, depth, world, group):
     return torch.cat([parts[r][:, :, : bounds[r + 1] - bounds[r]] for r in range(world)], dim=2)
 
 
-FUSED_WINDOW_BATCH = 4     # windows per amx_unet_forward_windows call (fills the chip on the deep levels)
-PIPELINE_WINDOWS = True    # keep two window batches in flight on two HIP streams (ordered accumulation, identical results)
-
-
 def _run_fused(inputs, roi, starts, wmap, model, cnt):
-    """amx_unet_forward_windows on groups of FUSED_WINDOW_BATCH windows + one amx_sw_count per window, all on
-    the current stream (overlapping windows accumulate in issue order)."""
-    lib = _lib.load()
+    """The network's window entry (amx_unet_forward_windows / amx_vit_forward_windows) on groups of its window batch + one
+    amx_sw_count per window, all on the current stream (overlapping windows accumulate in issue order).  ``starts`` are this rank's
+    windows; ``model`` is a bare Unet or PrimusV2 inside its envelope (``_split_net_and_head``)."""
+    net = _route(model)
     dev = inputs.device
     B = inputs.shape[0]
     size = tuple(inputs.shape[2:])
-    x = inputs.detach()
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        x = x.float().contiguous()
-    cout = model._cfg["output_nc"]
-    acc = torch.zeros((B, cout) + size, dtype=torch.float32, device=dev)
+    x = _lib.f32c(inputs.detach())
+    acc = torch.zeros((B, net.channels(model)) + size, dtype=torch.float32, device=dev)
+    if not starts:
+        return acc
+    wm = wmap.contiguous()
     with torch.cuda.device(dev):
-        model._ensure_handle(dev)
-        if model._weights_stale():
-            model._upload_weights(lib, dev)
-        k = max(1, min(FUSED_WINDOW_BATCH, len(starts)))
-        ws, need = model._get_workspace(lib, k, roi[0], roi[1], roi[2], dev)
+        k = min(net.batch(), len(starts))
+        lib, ws, need = net.prepare(model, dev, roi, k)
         cur = torch.cuda.current_stream(dev)
-        st = ctypes.c_void_p(cur.cuda_stream)
-        wm = wmap.contiguous()
+        st = _lib.stream(dev)
         ngroups = (len(starts) + k - 1) // k
         # two window batches in flight (amx_unet_forward_windows_pipelined): batch g + 1 runs on the other stream and only its
         # accumulating launches wait for batch g -- same sums in the same order, the underfilled deep levels overlap
-        pipelined = PIPELINE_WINDOWS and B * ngroups >= 4 and not torch.cuda.is_current_stream_capturing()
-        if pipelined:
-            if getattr(model, "_sw_streams", None) is None or model._sw_streams[0].device != dev:
-                model._sw_streams = [torch.cuda.Stream(dev) for _ in range(2)]
-                model._sw_ws = None
-            if model._sw_ws is None or model._sw_ws.numel() < need:
-                model._sw_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            lanes = [(model._sw_streams[0], ws), (model._sw_streams[1], model._sw_ws)]
+        lanes = None
+        if net.two_streams and PIPELINE_WINDOWS and B * ngroups >= 4 and not torch.cuda.is_current_stream_capturing():
+            streams, ws2 = model._sw_state(need, dev, lanes=True)
+            lanes = [(ctypes.c_void_p(streams[0].cuda_stream), ws), (ctypes.c_void_p(streams[1].cuda_stream), ws2)]
             ready = cur.record_event()
-            for s_, _ in lanes:
+            for s_ in streams:
                 s_.wait_event(ready)
         call = 0
         for g0 in range(0, len(starts), k):
             grp = starts[g0:g0 + k]
             offs = (ctypes.c_int * (3 * len(grp)))(*[v for s3 in grp for v in s3])
             for b in range(B):
-                if pipelined:
-                    s_, w_ = lanes[call & 1]
-                    _lib.check(lib.amx_unet_forward_windows_pipelined(
-                        model._handle, _lib.ptr(x[b]), size[0], size[1], size[2], len(grp), offs, roi[0], roi[1], roi[2],
-                        _lib.ptr(wm), _lib.ptr(acc[b]), _lib.ptr(w_), need, call & 1, ctypes.c_void_p(s_.cuda_stream)))
-                    call += 1
-                else:
-                    _lib.check(lib.amx_unet_forward_windows(model._handle, _lib.ptr(x[b]), size[0], size[1], size[2], len(grp),
-                                                            offs, roi[0], roi[1], roi[2], _lib.ptr(wm), _lib.ptr(acc[b]),
-                                                            _lib.ptr(ws), need, st))
+                s_, w_, slot = lanes[call & 1] + (call & 1,) if lanes else (st, ws, None)
+                _lib.check(net.windows(lib, model, x[b], size, grp, offs, roi, wm, acc[b], w_, need, s_, slot))
+                call += 1
             for (z, y, xx) in grp:              # the count map is independent of the network: caller's stream
-                _lib.check(lib.amx_sw_count(_lib.ptr(cnt), size[0], size[1], size[2], z, y, xx, roi[0], roi[1], roi[2],
-                                            _lib.ptr(wm), st))
-        if pipelined:
-            for s_, _ in lanes:
+                _lib.check(lib.amx_sw_count(_lib.ptr(cnt), *size, z, y, xx, *roi, _lib.ptr(wm), st))
+        if lanes:
+            for s_ in streams:
                 cur.wait_stream(s_)
-        if model.precision in ("f16", "fp16", "float16", "f16x2", "f16x2mx", "strict_mx") and not torch.cuda.is_current_stream_capturing():
-            # the accumulation volume leaves the library here: one synchronising range check per volume (f16 storage only)
-            model.check_numerics(synchronize=True)
+        net.after(model)
     return acc
-
-
-VIT_WINDOW_BATCH = 4       # windows per amx_vit_forward_windows call
-CALLS = {"vit_windows": 0, "vit_volume": 0}      # fused ViT calls: amx_vit_forward_windows / amx_vit_sliding_window (tests, diagnostics)
-
-
-def _is_vit(model) -> bool:
-    from ..model.vit3d.architectures import PrimusV2
-    return isinstance(model, PrimusV2)
 
 
 def _head_unsupported_reason(head, feat, inputs, out):
@@ -450,117 +545,19 @@ def _head_unsupported_reason(head, feat, inputs, out):
     return None
 
 
-def _vit_unsupported_reason(model, inputs, roi, head=None, out="features"):
-    """Why the fused ViT routes (amx_vit_forward_windows / amx_vit_sliding_window) cannot take this call (None: they can).  The
-    envelope: a CUDA tensor, no grad, ``use_engine``, roi equal to the model's input shape, one input channel, an output norm the
-    engine applies itself (none / demean), a configuration amx_vit_create takes, and for logits / labels a head of one 1x1x1
-    convolution within amx_sw_finish's sizes."""
-    from ..model.vit3d.architectures import ChannelDemean
-    if not inputs.is_cuda:
-        return f"there is no host path (got a {inputs.device} tensor)"
-    if torch.is_grad_enabled():
-        return "the engine runs under torch.no_grad() only"
-    if not model.use_engine:
-        return "model.use_engine is off"
-    if inputs.dim() != 5 or inputs.shape[1] != 1 or model._vit_cfg["input_channels"] != 1:
-        return f"inputs [B, 1, D, H, W] and input_channels == 1 (got {tuple(inputs.shape)}, input_channels {model._vit_cfg['input_channels']})"
-    shape = tuple(8 * g for g in model.grid)
-    if tuple(roi) != shape:
-        return f"roi must be the model's input shape {shape} (got {tuple(roi)})"
-    if not isinstance(model.out_norm, (ChannelDemean, nn.Identity)):
-        return f"out_norm must be 'none' or 'demean', which the engine applies per window (got {type(model.out_norm).__name__})"
-    if out != "features":
-        reason = _head_unsupported_reason(head, model._vit_cfg["num_classes"], inputs, out)
-        if reason is not None:
-            return reason
-    try:
-        with torch.cuda.device(inputs.device):
-            model._engine(inputs.device)
-    except _lib.AmxError as e:
-        if getattr(e, "code", None) not in (_lib.AMX_ERR_INVALID, _lib.AMX_ERR_SHAPE):
-            raise
-        return f"the HIP engine does not cover this configuration ({e})"
-    return None
-
-
-def _split_vit_and_head(predictor, inputs, roi):
-    """(PrimusV2, head or None) when the windows can run through amx_vit_forward_windows: a bare PrimusV2, or
-    nn.Sequential(PrimusV2, head) with a provably per-voxel affine head (applied once to the normalised volume, as for the Unet)."""
-    if _is_vit(predictor):
-        return (predictor, None) if _vit_unsupported_reason(predictor, inputs, roi) is None else None
-    if isinstance(predictor, nn.Sequential) and len(predictor) >= 2 and _is_vit(predictor[0]):
-        if _vit_unsupported_reason(predictor[0], inputs, roi) is not None:
-            return None
-        head = predictor[1] if len(predictor) == 2 else nn.Sequential(*list(predictor.children())[1:])
-        if _pointwise_affine(head):
-            return predictor[0], head
-    return None
-
-
-def _run_fused_vit(inputs, roi, starts, wmap, model, cnt):
-    """amx_vit_forward_windows on groups of VIT_WINDOW_BATCH windows + one amx_sw_count per window, all on the current stream
-    (overlapping windows accumulate in issue order).  ``starts`` are this rank's windows, as for ``_run_fused``."""
-    dev = inputs.device
-    B = inputs.shape[0]
-    size = tuple(inputs.shape[2:])
-    x = _lib.f32c(inputs.detach())
-    acc = torch.zeros((B, model._vit_cfg["num_classes"]) + size, dtype=torch.float32, device=dev)
-    if not starts:
-        return acc
-    wm = wmap.contiguous()
-    with torch.cuda.device(dev):
-        lib, st = model._engine(dev)
-        k = min(VIT_WINDOW_BATCH, len(starts))
-        need = lib.amx_vit_windows_workspace_bytes(model._handle, k)
-        ws = model._engine_workspace(need, dev)
-        for g0 in range(0, len(starts), k):
-            grp = starts[g0:g0 + k]
-            offs = (ctypes.c_int * (3 * len(grp)))(*[v for s3 in grp for v in s3])
-            for b in range(B):
-                _lib.check(lib.amx_vit_forward_windows(model._handle, _lib.ptr(x[b]), size[0], size[1], size[2], len(grp), offs,
-                                                       _lib.ptr(wm), _lib.ptr(acc[b]), _lib.ptr(ws), need, st))
-                CALLS["vit_windows"] += 1
-            for (z, y, xx) in grp:
-                _lib.check(lib.amx_sw_count(_lib.ptr(cnt), size[0], size[1], size[2], z, y, xx, roi[0], roi[1], roi[2], _lib.ptr(wm), st))
-    return acc
-
-
-def _volume_unsupported_reason(model, inputs, roi, head, out):
-    """Why ``sliding_window_volume`` cannot take this call with a Unet (None: it can).  The envelope is amx_sliding_window's: the
-    fused window step's (``_fused_ok``), and for logits / labels a head made of one 1x1x1 convolution within amx_sw_finish's sizes."""
-    from ..model.network import Unet
-    if not isinstance(model, Unet):
-        return (f"model must be a bare anatomix_amd.Unet or PrimusV2 (got {type(model).__name__}); pass the head of a Sequential "
-                "as head=")
-    if not inputs.is_cuda:
-        return f"there is no host path (got a {inputs.device} tensor)"
-    if inputs.dim() != 5 or inputs.shape[1] != 1 or model._cfg["input_nc"] != 1:
-        return f"inputs [B, 1, D, H, W] and input_nc == 1 (got {tuple(inputs.shape)}, input_nc {model._cfg['input_nc']})"
-    cout = model._cfg["output_nc"]
-    if cout % 16 or cout > 32:
-        return f"output_nc must be 16 or 32 for the in-place accumulation (got output_nc={cout})"
-    if roi[2] < 32:
-        return f"roi width >= 32 (got {roi[2]})"
-    reason = model.hip_unsupported_reason(inputs[:, :, :1, :1, :1].expand(-1, -1, 2, 2, 2))
-    if reason is not None:
-        return reason
-    if out != "features":
-        return _head_unsupported_reason(head, cout, inputs, out)
-    return None
-
-
 def sliding_window_volume(inputs: torch.Tensor, roi_size, model, overlap: float = 0.25, mode: str = "constant",
                           sigma_scale: float = 0.125, head=None, out: str = "features"):
     """``sliding_window_inference(inputs, roi_size, FUSED_WINDOW_BATCH, model, overlap, mode, sigma_scale)`` as ONE C call per batch
     element (``amx_sliding_window``: schedule, window weights, count map, pipelined window batches and the finishing pass all behind
     the C ABI).  ``model`` is a bare ``anatomix_amd.Unet``, or a bare ``PrimusV2`` on its engine (``amx_vit_sliding_window``: roi equal
     to the model's input shape, batches of VIT_WINDOW_BATCH windows, one stream); ``out``:
-      * ``"features"`` -> fp32 [B, output_nc, D, H, W], the window average of the Unet's output;
+      * ``"features"`` -> fp32 [B, output_nc, D, H, W], the window average of the network's output;
       * ``"logits"``   -> fp32 [B, classes, D, H, W], ``head`` (one 1x1x1 convolution) applied to that average;
       * ``"labels"``   -> uint8 [B, 1, D, H, W], the arg-max of those logits (lowest index on ties), which are never written.
     Volumes smaller than the ROI are zero padded and cropped back like ``sliding_window_inference``.  Configurations outside the
-    call's envelope raise ``_lib.AmxEnvelopeError`` with the reason -- there is no fallback here; ``sliding_window_inference`` takes
-    any predictor.  The call cannot be captured into a graph yet (the C entry refuses while the stream is capturing)."""
+    call's envelope (the network's, and for logits / labels amx_sw_finish's head sizes) raise ``_lib.AmxEnvelopeError`` with the
+    reason -- there is no fallback here; ``sliding_window_inference`` takes any predictor.  The call cannot be captured into a graph
+    yet (the C entry refuses while the stream is capturing)."""
     if out not in _lib.SW_OUT:
         raise ValueError(f"out must be one of {sorted(_lib.SW_OUT)} (got {out!r})")
     if mode not in _lib.SW_MAP:
@@ -568,24 +565,21 @@ def sliding_window_volume(inputs: torch.Tensor, roi_size, model, overlap: float 
     if isinstance(roi_size, int):
         roi_size = (roi_size,) * 3
     roi = tuple(int(r) for r in roi_size)
-    vit = _is_vit(model)
-    reason = _vit_unsupported_reason(model, inputs, roi, head, out) if vit else _volume_unsupported_reason(model, inputs, roi, head, out)
+    net = _route(model)
+    if net is None:
+        reason = f"model must be a bare anatomix_amd.Unet or PrimusV2 (got {type(model).__name__}); pass the head of a Sequential as head="
+    else:
+        reason = net.unsupported_reason(model, inputs, roi)
+        if reason is None and out != "features":
+            reason = _head_unsupported_reason(head, net.channels(model), inputs, out)
     if reason is not None:
         raise _lib.AmxEnvelopeError(_lib.AMX_ERR_SHAPE, "sliding_window_volume: " + reason + ".  sliding_window_inference takes any predictor.")
     B = inputs.shape[0]
-    orig = tuple(inputs.shape[2:])
-    pads, need_pad = [], False
-    for k in range(2, -1, -1):
-        diff = max(roi[k] - orig[k], 0)
-        half = diff // 2
-        pads += [half, diff - half]
-        need_pad |= diff > 0
-    if need_pad:
-        inputs = F.pad(inputs, pads, mode="constant", value=0.0)
+    inputs, crop = _pad_to_roi(inputs, roi, "constant", 0.0)
     size = tuple(inputs.shape[2:])
     dev = inputs.device
     x = _lib.f32c(inputs.detach())
-    cout = model._vit_cfg["num_classes"] if vit else model._cfg["output_nc"]
+    cout = net.channels(model)
     w = b = res = None
     classes = 0
     if out != "features":
@@ -599,43 +593,13 @@ def sliding_window_volume(inputs: torch.Tensor, roi_size, model, overlap: float 
     # features: every batch element keeps its accumulator (it is the result); logits / labels: one accumulator is reused
     acc = torch.empty((B if out == "features" else 1, cout) + size, dtype=torch.float32, device=dev)
     cnt = torch.empty(size, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    if vit:
-        with torch.cuda.device(dev):
-            _, st = model._engine(dev)
-            need = lib.amx_vit_sliding_window_workspace_bytes(model._handle, VIT_WINDOW_BATCH)
-            ws = model._engine_workspace(need, dev)
-            for i in range(B):
-                _lib.check_envelope(lib.amx_vit_sliding_window(
-                    model._handle, _lib.ptr(x[i]), *size, float(overlap), _lib.SW_MAP[mode], float(sigma_scale), VIT_WINDOW_BATCH,
-                    _lib.SW_OUT[out], _lib.ptr(w), _lib.ptr(b), classes, _lib.ptr(acc[i if out == "features" else 0]), _lib.ptr(cnt),
-                    _lib.ptr(res[i]) if res is not None else None, _lib.ptr(ws), need, st))
-                CALLS["vit_volume"] += 1
-        if out == "features":
-            res = acc
-        if need_pad:
-            zs, ys, xs = pads[4], pads[2], pads[0]
-            res = res[:, :, zs:zs + orig[0], ys:ys + orig[1], xs:xs + orig[2]]
-        return res
     with torch.cuda.device(dev):
-        model._ensure_handle(dev)
-        if model._weights_stale():
-            model._upload_weights(lib, dev)
-        need = lib.amx_sliding_window_workspace_bytes(model._handle, FUSED_WINDOW_BATCH, *roi)
-        if getattr(model, "_swv_ws", None) is None or model._swv_ws.numel() < need or model._swv_ws.device != dev:
-            model._swv_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        lib, ws, need = net.prepare(model, dev, roi, net.batch(), whole=True)
         st = _lib.stream(dev)
         for i in range(B):
-            _lib.check_envelope(lib.amx_sliding_window(
-                model._handle, _lib.ptr(x[i]), *size, *roi, float(overlap), _lib.SW_MAP[mode], float(sigma_scale), FUSED_WINDOW_BATCH,
-                _lib.SW_OUT[out], _lib.ptr(w), _lib.ptr(b), classes, _lib.ptr(acc[i if out == "features" else 0]), _lib.ptr(cnt),
-                _lib.ptr(res[i]) if res is not None else None, _lib.ptr(model._swv_ws), need, st))
-        if model.precision in ("f16", "fp16", "float16", "f16x2", "f16x2mx", "strict_mx") and not torch.cuda.is_current_stream_capturing():
-            # the accumulation volume leaves the library here: one synchronising range check per call (f16 storage only)
-            model.check_numerics(synchronize=True)
-    if out == "features":
-        res = acc
-    if need_pad:
-        zs, ys, xs = pads[4], pads[2], pads[0]
-        res = res[:, :, zs:zs + orig[0], ys:ys + orig[1], xs:xs + orig[2]]
-    return res
+            finish = (_lib.SW_OUT[out], _lib.ptr(w), _lib.ptr(b), classes, _lib.ptr(acc[i if out == "features" else 0]), _lib.ptr(cnt),
+                      _lib.ptr(res[i]) if res is not None else None)
+            _lib.check_envelope(net.volume(lib, model, x[i], size, roi, (float(overlap), _lib.SW_MAP[mode], float(sigma_scale)), net.batch(),
+                                           finish, ws, need, st))
+        net.after(model)
+    return _crop(acc if out == "features" else res, crop)

@@ -154,6 +154,19 @@ def test_copies_do_not_share_the_native_handle():
         m._handle = None                                  # not a real handle: keep __del__ away from it
 
 
+def test_copies_do_not_share_the_sliding_window_state():
+    """The streams and workspaces of the sliding-window routes exist from the constructor on, belong to one module object like the
+    handle, and stay out of the pickled state."""
+    import copy
+    m = anatomix_amd.Unet(**R.VARIANTS["anatomix"])
+    names = ("_sw_streams", "_sw_ws", "_swv_ws")
+    assert all(n in m._PER_OBJECT_STATE and m.__dict__[n] is None for n in names)
+    m._sw_streams, m._sw_ws, m._swv_ws = [object(), object()], torch.zeros(4), torch.zeros(4)
+    for c in (copy.copy(m), copy.deepcopy(m), m._replicate_for_data_parallel()):
+        assert all(getattr(c, n) is None for n in names)
+    assert all(m.__getstate__()[n] is None for n in names) and m._swv_ws is not None
+
+
 def test_hip_gate_mirrors_the_library_limits():
     """Configurations the C side would refuse are refused by the Python gate with a reason (so allow_torch_path applies)."""
     dev_like = torch.zeros(1, 1, 32, 32, 32)

@@ -272,6 +272,26 @@ def test_whole_call_is_refused_while_the_stream_is_capturing(device, model):
     assert bool((t == 1.0).all()) and bool((acc == 3.0).all()) and bool((cnt == 3.0).all())
 
 
+def test_window_weights_follow_the_key(device, model):
+    """The window weights cached on the handle are rebuilt whenever (roi, mode, sigma_scale) changes, in place or reallocated: every
+    call of a sequence of keys on ONE model equals the same single call on a freshly constructed model (new handle, empty cache).
+    Roi 64 is 2 windows (one lane); roi 32 is 3 x 3 x 5 = 45 windows = 12 batches (two lanes) and another map size."""
+    size = (64, 64, 96)
+    assert len(window_starts(size, (64, 64, 64), 0.5)) == 2 and len(window_starts(size, (32, 32, 32), 0.5)) == 45
+    x = R.synthetic_input(47, 1, size).to(device)
+    sd = model.state_dict()
+    keys = [(64, dict(mode="gaussian", sigma_scale=0.25)), (64, dict(mode="constant")), (64, dict(mode="gaussian", sigma_scale=0.125)),
+            (32, dict(mode="gaussian", sigma_scale=0.125)), (64, dict(mode="gaussian", sigma_scale=0.25))]
+    with torch.no_grad():
+        for roi, kw in keys:
+            fresh = anatomix_amd.Unet(**KW)
+            fresh.load_state_dict(sd, strict=True)
+            want = sliding_window_volume(x, roi, fresh.to(device).eval(), overlap=0.5, **kw)
+            got = sliding_window_volume(x, roi, model, overlap=0.5, **kw)
+            assert got.shape == (1, 16) + size and torch.isfinite(got).all()
+            assert torch.equal(got, want), (roi, kw)
+
+
 # ---- 5. whole call, labels and logits -------------------------------------------------------------------------------------------
 def test_whole_call_labels_and_logits(device, model):
     size, roi = (64, 96, 80), (64, 64, 64)

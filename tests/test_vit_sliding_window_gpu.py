@@ -163,6 +163,23 @@ def test_vector_and_scalar_rows_give_the_same_values(device):
         assert torch.equal(res[0], wmap * model(x)[0])      # and they are the forward's values times the map
 
 
+def test_window_weights_follow_the_key(device):
+    """The window weights cached on the handle are rebuilt in place whenever (mode, sigma_scale) changes: every call of a sequence
+    of keys on ONE model equals the same single call on a fresh model loaded from the same state dict (new handle, empty cache)."""
+    roi, size, overlap, corners = CASES["A"]
+    assert len(window_starts(size, roi, overlap)) == len(corners) == 4
+    model, sd = vit(roi, device)
+    x = volume("A", device)
+    with torch.no_grad():
+        for kw in (GAUSS, dict(mode="constant"), dict(mode="gaussian", sigma_scale=0.125), GAUSS):
+            fresh = PrimusV2(**kw_of(roi))
+            fresh.load_state_dict(sd, strict=True)
+            want = sliding_window_volume(x, roi, fresh.to(device).eval(), overlap=overlap, **kw)
+            got = sliding_window_volume(x, roi, model, overlap=overlap, **kw)
+            assert got.shape == (1, 32) + size and torch.isfinite(got).all()
+            assert torch.equal(got, want), kw
+
+
 # ---- 2. float64 oracle -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", ["A", "B"])
 def test_against_the_float64_oracle(device, case):

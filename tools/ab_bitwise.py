@@ -3,12 +3,13 @@ three augmentation units, registration metrics, instance optimisation, MIND-SSC 
 shared helpers changed no summation order and no contraction.  Section ``unet``: the UNet forward (output, feature taps, encode_only,
 sliding window by window batches and as one call, the kernel names of a profiled forward) on the shipped variants and on every
 configuration tests/test_unet_gpu.py parametrises, and the single-layer conv entries, one shape per route of the conv dispatch -- the
-proof that a refactor of the launch path moved no layer to another kernel and changed no launch.  Section ``train``: the training
+proof that a refactor of the launch path moved no layer to another kernel and changed no launch.  Section ``vit``: the 3D ViT's forward
+and both of its sliding-window routes on the cases of tests/test_vit_sliding_window_gpu.py.  Section ``train``: the training
 function (model/train.py) over every configuration tests/test_train_step_gpu.py parametrises, the 6 M variant on both tap routes, and
 eager / graphed contrastive steps with FusedAdamW -- the proof that a refactor of the Python side of the training path changed no
 launch.  ``train_step`` is the step case alone, at ``--size``.
 
-    python tools/ab_bitwise.py --old PATH/libanatomix_amd.so [--new PATH/libanatomix_amd.so] [--section streams|unet|all]
+    python tools/ab_bitwise.py --old PATH/libanatomix_amd.so [--new PATH/libanatomix_amd.so] [--section streams|unet|vit|all]
     python tools/ab_bitwise.py --old-tree PATH --section train|train_step [--size 32]
 
 ``--old-tree PATH``: a directory holding another commit's ``anatomix_amd/``, ``oracle/`` and ``tests/`` (``git archive``); the old side's
@@ -89,6 +90,21 @@ def unet_section(dev, emit, tree):
                 emit(f"{tag}/profile_forward/out", y)
                 emit_names(f"{tag}/profile_forward/names", [r["kernel"] for r in recs])
 
+    # ---- the whole-volume call with a head: logits and labels of tests/test_sliding_window_call_gpu.py (6 windows: one lane)
+    from test_sliding_window_call_gpu import centred_head
+    kw = R.VARIANTS["anatomix"]
+    with contextlib.redirect_stdout(sys.stderr):
+        m = anatomix_amd.Unet(**kw)
+    m.load_state_dict(R.synthetic_state_dict(kw, 0), strict=True)
+    m = m.to(dev).eval()
+    xv = R.synthetic_input(42, 1, (64, 96, 80)).to(dev)
+    with torch.no_grad():
+        feat = sliding_window_volume(xv, 64, m, overlap=0.7)
+        emit("unet/anatomix/sliding_window_volume_64x96x80/features", feat)
+        head = centred_head(feat, 5, 3)
+        for out in ("logits", "labels"):
+            emit(f"unet/anatomix/sliding_window_volume_64x96x80/{out}", sliding_window_volume(xv, 64, m, overlap=0.7, head=head, out=out))
+
     # ---- every configuration tests/test_unet_gpu.py parametrises beside the shipped ones, at its shapes, seeds and tap lists: the
     # export-pass outputs, doubleconv=False, padded widths, ngf = 8, instance norm + Avg + trilinear, no skips, input_nc > 1
     import test_unet_gpu as T
@@ -129,6 +145,31 @@ def unet_section(dev, emit, tree):
         else:
             out = U.run_conv(dev, x0, x1, w, scale, shift, 1, precision, planar=planar)      # (offers the split-K scratch)
         emit(f"conv_layer/{route}/{c0}+up{c1}->{cout}@{s}/{precision}/out", out)
+
+
+def vit_section(dev, emit, tree):
+    """The 3D ViT on cases A, B, C of tests/test_vit_sliding_window_gpu.py, with that file's models, seeds and state dicts: the
+    forward of one window, the window-batch route (amx_vit_forward_windows) in both modes, and the whole-volume call
+    (amx_vit_sliding_window) for features, logits and labels."""
+    sys.path.insert(0, os.path.join(tree, "tests"))
+    import torch
+    import test_vit_sliding_window_gpu as T
+    from anatomix_amd.registration.sliding_window import sliding_window_inference, sliding_window_volume
+
+    for case in ("A", "B", "C"):
+        roi, size, overlap, corners = T.CASES[case]
+        model, _ = T.vit(roi, dev)
+        x = T.volume(case, dev)
+        z, y, xx = corners[-1]
+        with torch.no_grad():
+            emit(f"vit/{case}/forward", model(x[:, :, z:z + roi[0], y:y + roi[1], xx:xx + roi[2]].contiguous()))
+            for mode, kw in (("gaussian", T.GAUSS), ("constant", dict(mode="constant"))):
+                emit(f"vit/{case}/sliding_window_inference/{mode}", sliding_window_inference(x, roi, 4, model, overlap=overlap, **kw))
+                feat = sliding_window_volume(x, roi, model, overlap=overlap, **kw)
+                emit(f"vit/{case}/sliding_window_volume/features/{mode}", feat)
+            head = T.centred_head(feat, 5, T.HEAD_SEED)
+            for out in ("logits", "labels"):
+                emit(f"vit/{case}/sliding_window_volume/{out}", sliding_window_volume(x, roi, model, overlap=overlap, head=head, out=out))
 
 
 def train_section(dev, emit, size, only_step):
@@ -298,6 +339,9 @@ def child(section, tree, size, dump):
     if section in ("unet", "all"):
         unet_section(dev, emit, tree)
     if section == "unet":
+        return done()
+    if section == "vit":
+        vit_section(dev, emit, tree)
         return done()
 
     # ---- amx_seg_loss_forward / _backward / amx_seg_argmax, head mode and logits mode
@@ -511,7 +555,7 @@ def main():
     ap.add_argument("--tree", default=ROOT, help="(child) the tree this listing imports from")
     ap.add_argument("--dump", help="(child) also save every tensor to this file")
     ap.add_argument("--size", type=int, default=32, help="cube side of the contrastive steps of the train sections")
-    ap.add_argument("--section", choices=("streams", "unet", "all", "train", "train_step"), default="all")
+    ap.add_argument("--section", choices=("streams", "unet", "vit", "all", "train", "train_step"), default="all")
     ap.add_argument("--expect-different", metavar="REGEX", help="names the caller expects to differ (a repaired path): listed, not counted")
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds per child")
     ap.add_argument("--print-listings", action="store_true")
