@@ -35,6 +35,11 @@ class UnetCfg(C.Structure):
     ]
 
 
+class VitTap(C.Structure):
+    """amx_vit_tap: one request of amx_vit_forward_taps (name, device buffer or None, its capacity; out: the producing launch)."""
+    _fields_ = [("name", C.c_char_p), ("d_dst", C.c_void_p), ("bytes", C.c_size_t), ("route", C.c_char * 160)]
+
+
 class VitCfg(C.Structure):
     _fields_ = [
         ("input_channels", C.c_int32), ("num_classes", C.c_int32), ("embed_dim", C.c_int32), ("depth", C.c_int32),
@@ -140,6 +145,8 @@ SYMBOLS = {
     "amx_vit_workspace_bytes": (C.c_size_t, [_P, _I]),
     "amx_vit_forward": (_I, [_P, _P, _P, _I, _P, C.c_size_t, _I, _P]),
     "amx_vit_debug_read": (_I, [_P, C.c_char_p, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "amx_vit_tap_bytes": (C.c_size_t, [_P, _I, C.c_char_p]),
+    "amx_vit_forward_taps": (_I, [_P, _P, _P, _I, _P, C.c_size_t, _I, C.POINTER(VitTap), _I, _P]),
     "amx_vit_windows_workspace_bytes": (C.c_size_t, [_P, _I]),
     "amx_vit_forward_windows": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_int), _P, _P, _P, C.c_size_t, _P]),
     "amx_vit_sliding_window_workspace_bytes": (C.c_size_t, [_P, _I]),

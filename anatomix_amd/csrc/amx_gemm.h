@@ -1,8 +1,23 @@
 // anatomix_amd -- internal declarations of the 3D ViT kernels (amx_gemm.hip, amx_tokenizer.hip); not part of the public C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdio.h>
 
 namespace amx {
+
+// What a launcher of the ViT engine ran, for the callers that ask (null: nothing is formatted): the kernel instance as a printf-built
+// name, e.g. wsgemm<2,5,4,RESID,f16,4w> / gemm<2,5,RESID,f16,pf2> / tokconv<27,2,2,4,split> / ln_rows_vec<f32,2,gelu> / ln_rows<f16,17>.
+// No last-launch state anywhere (the ConvLaunchInfo of the conv launchers, amx_launch.h, is the model).
+struct VitLaunchInfo {
+  char name[64];
+  __attribute__((format(printf, 2, 3))) void report(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name, sizeof name, fmt, ap);
+    va_end(ap);
+  }
+};
 
 enum GemmEpi {
   EPI_F32 = 0,      // out32[m][n] = acc + bias
@@ -53,7 +68,7 @@ struct GemmParams {
   int acc_vec;                  // 1: every quad of a row is 16-byte aligned in both the accumulator and the map (set by launch_gemm)
 };
 
-hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st);
+hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st, VitLaunchInfo* info = nullptr);
 hipError_t launch_pack_gemm(const float* s0, const float* s1, const float* s2, int r0, int r1, int r2, int K, int mode, int Cp, int Creal,
                             int ntiles, int KS, void* hi, void* lo, hipStream_t st);
 hipError_t launch_vec_place(float* dst, const float* src, int n, float fill, hipStream_t st);
@@ -61,7 +76,7 @@ hipError_t launch_rope_pairs(float* dst, const float* src, int tokens, int hd, h
 hipError_t launch_headpad_vec(float* dst, const float* src, int heads, int hd, int hd_pad, hipStream_t st);   // [heads][hd] -> [heads][hd_pad], zero fill
 hipError_t launch_swiglu_bias(float* dst, const float* bg, const float* bx, int hidden, hipStream_t st);
 hipError_t launch_ln_rows(const void* in, int in_f16, long long ldi, int C, const float* w, const float* b, float eps, int M, int rows_out,
-                          int rows_in, int skip, int gelu, void* hi, void* lo, int ldo, hipStream_t st);
+                          int rows_in, int skip, int gelu, void* hi, void* lo, int ldo, hipStream_t st, VitLaunchInfo* info = nullptr);
 hipError_t launch_place_registers(const float* reg, int nreg, int E, int rows_per_b, int nb, float* tok, hipStream_t st);
 hipError_t launch_colsum(const void* hi, const void* lo, int ld, int C, int nb, int rows_per_b, int nchunk, float* out, hipStream_t st);
 hipError_t launch_demean(const float* colsum, int nchunk, int ld, int K, long long rows_per_b, const float* W, int Creal, const float* bias, int nb,
@@ -80,7 +95,7 @@ struct TokConvParams {
   float* raw;                   // fp32 channels-last [N][Do][Ho][Wo][Cout]: conv + bias
   float* stats;                 // per wave {sum, sumsq}[Cout]: [(n * waves_per_sample + w)][Cout][2]
 };
-hipError_t launch_tokconv(const TokConvParams& p, int taps, int stride, hipStream_t st);
+hipError_t launch_tokconv(const TokConvParams& p, int taps, int stride, hipStream_t st, VitLaunchInfo* info = nullptr);
 int tokconv_slots(const TokConvParams& p);      // waves per sample (= partial statistic slots per sample)
 hipError_t launch_pack_tokconv(const float* w, int Cout, int Cin, int taps, void* hi, void* lo, hipStream_t st);
 
@@ -97,7 +112,7 @@ struct TokStemParams {
   char* h_hi; char* h_lo;       // pass 1: lrelu(IN(conv)) channels-last [N][D][H][W][32] (h_lo null: no remainder plane)
   char* p_hi; char* p_lo;       //         its 2x2x2 average, [N][D/2][H/2][W/2][32]
 };
-hipError_t launch_tokstem(const TokStemParams& p, int pass, hipStream_t st);
+hipError_t launch_tokstem(const TokStemParams& p, int pass, hipStream_t st, VitLaunchInfo* info = nullptr);
 int tokstem_slots(int D, int H, int W);
 hipError_t launch_pack_tokstem(const float* w, void* hi, void* lo, hipStream_t st);
 

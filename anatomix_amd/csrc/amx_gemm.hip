@@ -625,11 +625,17 @@ __global__ __launch_bounds__(NW * 64) void wsgemm_kernel(GemmParams p, int rows_
   }
 }
 
+static const char* epi_name(int epi) {
+  static const char* const names[] = {"F32", "F16", "RESID", "SWIGLU", "SCATTER", "TOKENS", "PLANAR", "SCATTER_LN", "QK", "VT", "PLANAR_ACC"};
+  return epi >= 0 && epi < 11 ? names[epi] : "?";
+}
+
 template <int MT, int NT, int KC, int EPI, bool SPLIT, int NW = 4>
-static hipError_t launch_ws(const GemmParams& p, hipStream_t st) {
+static hipError_t launch_ws(const GemmParams& p, hipStream_t st, VitLaunchInfo* info) {
   const int ncb = (p.ntiles + NT - 1) / NT;
   const size_t lds = (size_t)NT * p.KS * 1024 * (SPLIT ? 2 : 1);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
+  if (info) info->report("wsgemm<%d,%d,%d,%s,%s,%dw>", MT, NT, KC, epi_name(EPI), SPLIT ? "split" : "f16", NW);
   static size_t attr = 0;                                          // per instantiation
   if (lds > attr) {
     hipError_t e = hipFuncSetAttribute((const void*)wsgemm_kernel<MT, NT, KC, EPI, SPLIT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -657,29 +663,30 @@ static hipError_t launch_ws(const GemmParams& p, hipStream_t st) {
 }
 
 template <int MT, int NT, int EPI, bool SPLIT, int PF>
-static hipError_t launch_one(const GemmParams& p, hipStream_t st) {
+static hipError_t launch_one(const GemmParams& p, hipStream_t st, VitLaunchInfo* info) {
+  if (info) info->report("gemm<%d,%d,%s,%s,pf%d>", MT, NT, epi_name(EPI), SPLIT ? "split" : "f16", PF);
   const int ncb = (p.ntiles + NT - 1) / NT, nrb = ((p.M + MT * 64 - 1) / (MT * 64) + 7) / 8 * 8;
   hipLaunchKernelGGL((gemm_kernel<MT, NT, EPI, SPLIT, PF>), dim3((unsigned)ncb * nrb), dim3(256), 0, st, p);
   return hipGetLastError();
 }
 
 template <int EPI, bool SPLIT>
-static hipError_t launch_epi(const GemmParams& p, hipStream_t st);
+static hipError_t launch_epi(const GemmParams& p, hipStream_t st, VitLaunchInfo* info);
 
 // weight-stationary dispatch; returns hipErrorNotSupported when the slice does not fit LDS (the caller falls back to the direct kernel)
 template <int EPI, bool SPLIT>
-static hipError_t launch_ws_epi(const GemmParams& p, hipStream_t st) {
+static hipError_t launch_ws_epi(const GemmParams& p, hipStream_t st, VitLaunchInfo* info) {
   const bool five = EPI != EPI_SWIGLU && p.ntiles % 5 == 0;
   const size_t per_tile = (size_t)p.KS * 1024 * (SPLIT ? 2 : 1);
   if (SPLIT) {
-    if (five && 5 * per_tile <= 160 * 1024) return launch_ws<2, 5, 2, EPI, true>(p, st);
+    if (five && 5 * per_tile <= 160 * 1024) return launch_ws<2, 5, 2, EPI, true>(p, st, info);
     if (!five && 4 * per_tile <= 160 * 1024) {
       // The store-bound planar stage: ONE row tile per wave (112 registers: 4 waves per SIMD).  Loads and stores share a wave's
       // in-order memory counter, so a wave's next operands wait behind the acknowledgement of its previous stores; more waves =
       // more independent queues (2 tiles per wave 547 us, 1 tile 476 us; deeper prefetch 550 -- no help).
-      if (EPI == EPI_PLANAR || EPI == EPI_PLANAR_ACC) return launch_ws<1, 4, 2, EPI, true>(p, st);
-      if (EPI == EPI_SCATTER && 4 * per_tile > 80 * 1024) return launch_ws<1, 4, 2, EPI, true, 8>(p, st);   // one workgroup per CU: 8 waves
-      return launch_ws<2, 4, 2, EPI, true>(p, st);
+      if (EPI == EPI_PLANAR || EPI == EPI_PLANAR_ACC) return launch_ws<1, 4, 2, EPI, true>(p, st, info);
+      if (EPI == EPI_SCATTER && 4 * per_tile > 80 * 1024) return launch_ws<1, 4, 2, EPI, true, 8>(p, st, info);   // one workgroup per CU: 8 waves
+      return launch_ws<2, 4, 2, EPI, true>(p, st, info);
     }
     return hipErrorNotSupported;
   }
@@ -688,64 +695,64 @@ static hipError_t launch_ws_epi(const GemmParams& p, hipStream_t st) {
   // (a plain `if`: both row-tile variants stay instantiated for every epilogue -- dropping the unused ones changes how the shared
   //  epilogue is inlined into the direct kernels of the same tile shape, i.e. their code)
   if (EPI != EPI_F32) {
-    if (five && 5 * per_tile <= 160 * 1024) return launch_ws<2, 5, 4, EPI, false>(p, st);
-    if (!five && 4 * per_tile <= 160 * 1024) return launch_ws<2, 4, 4, EPI, false>(p, st);
+    if (five && 5 * per_tile <= 160 * 1024) return launch_ws<2, 5, 4, EPI, false>(p, st, info);
+    if (!five && 4 * per_tile <= 160 * 1024) return launch_ws<2, 4, 4, EPI, false>(p, st, info);
     return hipErrorNotSupported;
   }
-  if (five && 5 * per_tile <= 160 * 1024) return launch_ws<4, 5, 3, EPI, false>(p, st);
-  if (!five && 4 * per_tile <= 160 * 1024) return launch_ws<4, 4, 4, EPI, false>(p, st);
+  if (five && 5 * per_tile <= 160 * 1024) return launch_ws<4, 5, 3, EPI, false>(p, st, info);
+  if (!five && 4 * per_tile <= 160 * 1024) return launch_ws<4, 4, 4, EPI, false>(p, st, info);
   return hipErrorNotSupported;
 }
 
 template <int EPI, bool SPLIT>
-static hipError_t launch_epi(const GemmParams& p, hipStream_t st) {
+static hipError_t launch_epi(const GemmParams& p, hipStream_t st, VitLaunchInfo* info) {
   {
-    const hipError_t e = launch_ws_epi<EPI, SPLIT>(p, st);
+    const hipError_t e = launch_ws_epi<EPI, SPLIT>(p, st, info);
     if (e != hipErrorNotSupported) return e;
   }
   // NT = 5 where the tile count is a multiple of 5 (396 -> 25 tiles, 3 x 396 -> 75): no idle column tiles.  SwiGLU pairs need an even NT.
   const bool five = EPI != EPI_SWIGLU && p.ntiles % 5 == 0;
   const bool small = (long long)((p.M + 255) / 256) * ((p.ntiles + (five ? 4 : 3)) / (five ? 5 : 4)) < 512;   // < 2 workgroups per CU: halve the row block
-  if (SPLIT) return five ? launch_one<2, 5, EPI, true, 1>(p, st) : launch_one<2, 4, EPI, true, 1>(p, st);
-  if (five) return small ? launch_one<2, 5, EPI, false, 2>(p, st) : launch_one<4, 5, EPI, false, 2>(p, st);
-  return small ? launch_one<2, 4, EPI, false, 2>(p, st) : launch_one<4, 4, EPI, false, 2>(p, st);
+  if (SPLIT) return five ? launch_one<2, 5, EPI, true, 1>(p, st, info) : launch_one<2, 4, EPI, true, 1>(p, st, info);
+  if (five) return small ? launch_one<2, 5, EPI, false, 2>(p, st, info) : launch_one<4, 5, EPI, false, 2>(p, st, info);
+  return small ? launch_one<2, 4, EPI, false, 2>(p, st, info) : launch_one<4, 4, EPI, false, 2>(p, st, info);
 }
 
-hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st) {
+hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st, VitLaunchInfo* info) {
   const bool split = p.a_lo != nullptr;
   if (split != (p.w_lo != nullptr)) return hipErrorInvalidValue;
   switch (epi) {
-    case EPI_F32: return split ? launch_epi<EPI_F32, true>(p, st) : launch_epi<EPI_F32, false>(p, st);
-    case EPI_F16: return split ? hipErrorInvalidValue : launch_epi<EPI_F16, false>(p, st);
-    case EPI_RESID: return split ? hipErrorInvalidValue : launch_epi<EPI_RESID, false>(p, st);
-    case EPI_SWIGLU: return split ? hipErrorInvalidValue : launch_epi<EPI_SWIGLU, false>(p, st);
-    case EPI_SCATTER: return split ? launch_epi<EPI_SCATTER, true>(p, st) : launch_epi<EPI_SCATTER, false>(p, st);
-    case EPI_TOKENS: return split ? launch_epi<EPI_TOKENS, true>(p, st) : launch_epi<EPI_TOKENS, false>(p, st);
+    case EPI_F32: return split ? launch_epi<EPI_F32, true>(p, st, info) : launch_epi<EPI_F32, false>(p, st, info);
+    case EPI_F16: return split ? hipErrorInvalidValue : launch_epi<EPI_F16, false>(p, st, info);
+    case EPI_RESID: return split ? hipErrorInvalidValue : launch_epi<EPI_RESID, false>(p, st, info);
+    case EPI_SWIGLU: return split ? hipErrorInvalidValue : launch_epi<EPI_SWIGLU, false>(p, st, info);
+    case EPI_SCATTER: return split ? launch_epi<EPI_SCATTER, true>(p, st, info) : launch_epi<EPI_SCATTER, false>(p, st, info);
+    case EPI_TOKENS: return split ? launch_epi<EPI_TOKENS, true>(p, st, info) : launch_epi<EPI_TOKENS, false>(p, st, info);
     case EPI_PLANAR:
       if (p.gw % 4) return hipErrorInvalidValue;
-      return split ? launch_epi<EPI_PLANAR, true>(p, st) : launch_epi<EPI_PLANAR, false>(p, st);
+      return split ? launch_epi<EPI_PLANAR, true>(p, st, info) : launch_epi<EPI_PLANAR, false>(p, st, info);
     case EPI_PLANAR_ACC: {
       // one window: rows m = (z gh + y) gw + x of its half-resolution grid.  The 16-byte path needs every quad of an output row aligned
       // in the accumulator (corner, row, plane and channel strides multiples of 4 floats) and in the map; both paths give the same bits.
       if (p.gw % 4 || !p.wmap || !p.out || p.M != p.gd * p.gh * p.gw) return hipErrorInvalidValue;
       GemmParams q = p;
       q.acc_vec = !(((uintptr_t)p.out | (uintptr_t)p.wmap) & 15) && !((p.acc_sc | p.acc_sz | p.acc_sy) & 3);
-      return split ? launch_epi<EPI_PLANAR_ACC, true>(q, st) : launch_epi<EPI_PLANAR_ACC, false>(q, st);
+      return split ? launch_epi<EPI_PLANAR_ACC, true>(q, st, info) : launch_epi<EPI_PLANAR_ACC, false>(q, st, info);
     }
     case EPI_QK:      // a head's 5 tiles with the whole K extent in LDS (embed_dim <= 1024); wider models stream the weights (direct kernel)
       if (split || p.Cp != 80 || p.ntiles != 2 * p.heads * 5) return hipErrorInvalidValue;
       // (4 row tiles per wave measured the same 64 us as 2: of those, ~10 us are the LDS fill, ~19 the K loop, ~34 the epilogue)
       // eight waves of ONE row tile (the epilogue is long: more waves hide it; 64 -> 56 us; the residual / SwiGLU products measured no gain)
-      return (size_t)5 * p.KS * 1024 <= 160 * 1024 ? launch_ws<1, 5, 4, EPI_QK, false, 8>(p, st) : launch_one<2, 5, EPI_QK, false, 2>(p, st);
+      return (size_t)5 * p.KS * 1024 <= 160 * 1024 ? launch_ws<1, 5, 4, EPI_QK, false, 8>(p, st, info) : launch_one<2, 5, EPI_QK, false, 2>(p, st, info);
     case EPI_VT:
       if (split || p.Cp != 80 || p.ntiles != p.heads * 5) return hipErrorInvalidValue;
-      return (size_t)5 * p.KS * 1024 <= 160 * 1024 ? launch_ws<1, 5, 4, EPI_VT, false, 8>(p, st) : launch_one<2, 5, EPI_VT, false, 2>(p, st);
+      return (size_t)5 * p.KS * 1024 <= 160 * 1024 ? launch_ws<1, 5, 4, EPI_VT, false, 8>(p, st, info) : launch_one<2, 5, EPI_VT, false, 2>(p, st, info);
     case EPI_SCATTER_LN:
       if (p.Cp != 128 || p.ntiles != 64 || p.ldo > 128) return hipErrorInvalidValue;
       if ((size_t)8 * p.KS * 1024 * (split ? 2 : 1) <= 160 * 1024)
         // the 112 KiB slice leaves one workgroup per CU: 8 waves of one row tile each (442 -> 369 us against 4 waves of two)
-        return split ? launch_ws<1, 8, 2, EPI_SCATTER_LN, true, 8>(p, st) : launch_ws<2, 8, 4, EPI_SCATTER_LN, false>(p, st);
-      return split ? launch_one<2, 8, EPI_SCATTER_LN, true, 1>(p, st) : launch_one<2, 8, EPI_SCATTER_LN, false, 1>(p, st);
+        return split ? launch_ws<1, 8, 2, EPI_SCATTER_LN, true, 8>(p, st, info) : launch_ws<2, 8, 4, EPI_SCATTER_LN, false>(p, st, info);
+      return split ? launch_one<2, 8, EPI_SCATTER_LN, true, 1>(p, st, info) : launch_one<2, 8, EPI_SCATTER_LN, false, 1>(p, st, info);
   }
   return hipErrorInvalidValue;
 }
@@ -968,12 +975,16 @@ __global__ __launch_bounds__(256) void ln_rows_vec_kernel(const TIN* __restrict_
 }
 
 hipError_t launch_ln_rows(const void* in, int in_f16, long long ldi, int C, const float* w, const float* b, float eps, int M, int rows_out,
-                          int rows_in, int skip, int gelu, void* hi, void* lo, int ldo, hipStream_t st) {
+                          int rows_in, int skip, int gelu, void* hi, void* lo, int ldo, hipStream_t st, VitLaunchInfo* info) {
   if (ldo < C) return hipErrorInvalidValue;
   const dim3 grid((M + 3) / 4), block(256);
   if (C % 4 == 0 && ldi % 4 == 0 && ldo % 4 == 0 && (ldo + 255) / 256 <= 12 && !(in_f16 && gelu)) {
-#define AMX_LNV(TIN, PERV, G) \
-  hipLaunchKernelGGL((ln_rows_vec_kernel<TIN, PERV, G>), grid, block, 0, st, (const TIN*)in, ldi, C, w, b, eps, M, rows_out, rows_in, skip, (f16*)hi, (f16*)lo, ldo)
+#define AMX_LNV(TIN, PERV, G)                                                                                                                  \
+  do {                                                                                                                                         \
+    if (info) info->report("ln_rows_vec<%s,%d%s%s>", sizeof(TIN) == 4 ? "f32" : "f16", PERV, G ? ",gelu" : "", lo ? ",split" : "");             \
+    hipLaunchKernelGGL((ln_rows_vec_kernel<TIN, PERV, G>), grid, block, 0, st, (const TIN*)in, ldi, C, w, b, eps, M, rows_out, rows_in, skip, \
+                       (f16*)hi, (f16*)lo, ldo);                                                                                               \
+  } while (0)
     const int perv = (ldo + 255) / 256;
     if (in_f16) { if (perv <= 2) AMX_LNV(f16, 2, false); else if (perv <= 5) AMX_LNV(f16, 5, false); else AMX_LNV(f16, 12, false); }
     else if (gelu) { if (perv <= 1) AMX_LNV(float, 1, true); else if (perv <= 2) AMX_LNV(float, 2, true); else AMX_LNV(float, 5, true); }
@@ -982,8 +993,12 @@ hipError_t launch_ln_rows(const void* in, int in_f16, long long ldi, int C, cons
     return hipGetLastError();
   }
   if (C > 64 * 17 || ldo > 64 * 17) return hipErrorInvalidValue;      // scalar fallback: rows of up to 1088 columns
-#define AMX_LN(TIN, PER, G) \
-  hipLaunchKernelGGL((ln_rows_kernel<TIN, PER, G>), grid, block, 0, st, (const TIN*)in, ldi, C, w, b, eps, M, rows_out, rows_in, skip, (f16*)hi, (f16*)lo, ldo)
+#define AMX_LN(TIN, PER, G)                                                                                                               \
+  do {                                                                                                                                    \
+    if (info) info->report("ln_rows<%s,%d%s%s>", sizeof(TIN) == 4 ? "f32" : "f16", PER, G ? ",gelu" : "", lo ? ",split" : "");             \
+    hipLaunchKernelGGL((ln_rows_kernel<TIN, PER, G>), grid, block, 0, st, (const TIN*)in, ldi, C, w, b, eps, M, rows_out, rows_in, skip, \
+                       (f16*)hi, (f16*)lo, ldo);                                                                                          \
+  } while (0)
   const int per = (ldo + 63) / 64;
   if (in_f16) {
     if (gelu) return hipErrorInvalidValue;

@@ -195,8 +195,9 @@ static int tokconv_mt(const TokConvParams& p) {          // 64 voxels per wave w
 int tokconv_slots(const TokConvParams& p) { return (int)((long long)p.Do * p.Ho * p.Wo / (16 * tokconv_mt(p))); }
 
 template <int TAPS, int STRIDE>
-static hipError_t launch_tokconv_ts(const TokConvParams& p, hipStream_t st) {
+static hipError_t launch_tokconv_ts(const TokConvParams& p, hipStream_t st, VitLaunchInfo* info) {
   const int mt = tokconv_mt(p), nt = p.Cout >= 64 ? 4 : 2;
+  if (info) info->report("tokconv<%d,%d,%d,%d,%s>", TAPS, STRIDE, mt, nt, p.x_lo ? "split" : "f16");
   const long long waves = (long long)p.N * p.Do * p.Ho * p.Wo / (16 * mt);
   const dim3 grid((unsigned)(((waves + 3) / 4 + 7) / 8 * 8), p.Cout / (16 * nt)), block(256);      // a multiple of 8 workgroups (XCD-aware order)
 #define AMX_TC(M_, N_)                                                                                        \
@@ -212,11 +213,11 @@ static hipError_t launch_tokconv_ts(const TokConvParams& p, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_tokconv(const TokConvParams& p, int taps, int stride, hipStream_t st) {
+hipError_t launch_tokconv(const TokConvParams& p, int taps, int stride, hipStream_t st, VitLaunchInfo* info) {
   if (p.Cin % 32 || p.Cout % 32 || ((long long)p.Do * p.Ho * p.Wo) % 64) return hipErrorInvalidValue;   // a wave never straddles two samples
-  if (taps == 27 && stride == 2) return launch_tokconv_ts<27, 2>(p, st);
-  if (taps == 27 && stride == 1) return launch_tokconv_ts<27, 1>(p, st);
-  if (taps == 1 && stride == 1) return launch_tokconv_ts<1, 1>(p, st);
+  if (taps == 27 && stride == 2) return launch_tokconv_ts<27, 2>(p, st, info);
+  if (taps == 27 && stride == 1) return launch_tokconv_ts<27, 1>(p, st, info);
+  if (taps == 1 && stride == 1) return launch_tokconv_ts<1, 1>(p, st, info);
   return hipErrorInvalidValue;
 }
 
@@ -370,8 +371,9 @@ __global__ __launch_bounds__(256) void tokstem_kernel(TokStemParams p) {
 
 int tokstem_slots(int D, int H, int W) { return (D / 2) * (H / 2); }
 
-hipError_t launch_tokstem(const TokStemParams& p, int pass, hipStream_t st) {
+hipError_t launch_tokstem(const TokStemParams& p, int pass, hipStream_t st, VitLaunchInfo* info) {
   if (p.W % 16 || (p.D & 1) || (p.H & 1)) return hipErrorInvalidValue;
+  if (info) info->report("tokstem<%d,%s>", pass, p.h_lo ? "split" : "f16");
   const int waves = p.N * (p.D / 2) * (p.H / 2);
   if (pass == 0) hipLaunchKernelGGL(tokstem_kernel<0>, dim3((waves + 3) / 4), dim3(256), 0, st, p);
   else hipLaunchKernelGGL(tokstem_kernel<1>, dim3((waves + 3) / 4), dim3(256), 0, st, p);

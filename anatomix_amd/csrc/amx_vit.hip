@@ -414,8 +414,87 @@ struct VitOut {
   const long long* corner = nullptr;    // [n] voxel offsets (oz vh + oy) vw + ox
 };
 
-// The forward of n roi-sized samples d_x; every argument has been checked by the entry.
-int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& P, int n_blocks, hipStream_t st) {
+// decoder stage k (0, 1) runs channel LayerNorm + GELU inside the product's epilogue: no fp32 tensor between the two stages
+bool dec_fused(const DecStage& d) { return d.cp == 128 && up(d.cout, 32) <= 128; }
+
+// ---- taps (amx_vit_forward_taps): where every named intermediate of a forward at batch n lives while it is valid.  A tap is one byte
+// range, or two that are handed out back to back ([hi plane | lo plane], [scale | shift]); nb == 0: one range.  (The size query builds
+// the table on a plan without a base: only the sizes mean anything there.)
+struct TapSrc {
+  std::string name;
+  const void* a;
+  size_t na;
+  const void* b;
+  size_t nb;
+  size_t bytes() const { return na + nb; }
+};
+struct TapSet {
+  std::vector<TapSrc> table;
+  amx_vit_tap* req;
+  int nreq;
+};
+
+std::vector<TapSrc> tap_table(const amx_vit* h, int n, const Plan& P, int nb, const float* d_y) {
+  std::vector<TapSrc> t;
+  const amx_vit_cfg& c = h->cfg;
+  const int E = h->E, Ep = h->Ep, T = h->T, V = h->V, hid = h->hidden;
+  const size_t M = (size_t)n * T;
+  auto one = [&](const std::string& name, const void* a, size_t na) { t.push_back({name, a, na, nullptr, 0}); };
+  auto two = [&](const std::string& name, const void* a, const void* b, size_t each, bool pair = true) {
+    t.push_back({name, a, each, pair ? b : nullptr, pair ? each : 0});
+  };
+  size_t vox = (size_t)V * 512;
+  two("h0", P.h_hi[0], P.h_lo[0], n * vox * 32 * 2, c.stem_split != 0);
+  two("p0", P.p_hi[0], P.p_lo[0], n * (vox / 8) * 32 * 2);
+  for (int k = 0; k < 3; ++k) {
+    const std::string s = "s" + std::to_string(k);
+    const size_t C = kStageC[k + 1], vo = vox / 8;
+    one(s + ".raw1", P.raw1, n * vo * C * 4);
+    two(s + ".ss1", P.sc[0], P.sh[0], n * C * 4);
+    two(s + ".a1", P.a1_hi, P.a1_lo, n * vo * C * 2);
+    one(s + ".raw2", P.raw2, n * vo * C * 4);
+    two(s + ".ss2", P.sc[1], P.sh[1], n * C * 4);
+    one(s + ".raws", P.raws, n * vo * C * 4);
+    two(s + ".sss", P.sc[2], P.sh[2], n * C * 4);
+    two(s + ".h", P.h_hi[k + 1], P.h_lo[k + 1], n * vo * C * 2);
+    if (k < 2) two(s + ".p", P.p_hi[k + 1], P.p_lo[k + 1], n * (vo / 8) * C * 2);
+    vox = vo;
+  }
+  one("tokens", P.tok, M * E * 4);
+  for (int b = 0; b < nb; ++b) {
+    const std::string s = "b" + std::to_string(b);
+    one(s + ".ln1", P.A1, M * Ep * 2);
+    one(s + ".attn", P.AO, M * E * 4);
+    one(s + ".ln_attn", P.A1, M * Ep * 2);
+    one(s + ".tok1", P.tok, M * E * 4);
+    one(s + ".ln2", P.A1, M * Ep * 2);
+    one(s + ".hd", P.Hd, M * up(hid, 16) * 2);
+    one(s + ".ln_mlp", P.A2, M * up(hid, 32) * 2);
+    one(s + ".tok2", P.tok, M * E * 4);
+  }
+  size_t rows = (size_t)n * V;
+  two("d.ln", P.Ad_hi[0], P.Ad_lo[0], rows * Ep * 2, c.decoder_split != 0);
+  for (int k = 0; k < 2; ++k) {
+    const DecStage& d = h->dec[k];
+    rows *= 8;
+    if (!dec_fused(d)) one("d" + std::to_string(k) + ".raw", P.rawd[k], rows * d.cout * 4);
+    two("d" + std::to_string(k + 1) + ".in", P.Ad_hi[k + 1], P.Ad_lo[k + 1], rows * up(d.cout, 32) * 2, c.decoder_split != 0);
+  }
+  if (c.out_norm == 1) one("d.mean", P.mean, (size_t)n * c.num_classes * 4);
+  one("y", d_y, rows * 8 * c.num_classes * 4);
+  return t;
+}
+
+const TapSrc* tap_find(const std::vector<TapSrc>& t, const char* name) {
+  for (const auto& e : t)
+    if (e.name == name) return &e;
+  return nullptr;
+}
+
+// The forward of n roi-sized samples d_x; every argument has been checked by the entry.  `ts` (amx_vit_forward_taps): after the launch that
+// produces a named buffer, the requested copies of it are enqueued on the same stream and the launch's instance name is written into the
+// request -- no launch is added, moved or routed differently.
+int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& P, int n_blocks, hipStream_t st, TapSet* ts = nullptr) {
   float* const d_y = out.y;
   const amx_vit_cfg& c = h->cfg;
   const int E = h->E, Ep = h->Ep, T = h->T, V = h->V, hid = h->hidden, nreg = c.num_register_tokens;
@@ -423,6 +502,23 @@ int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& 
   const int D0 = c.grid_d * 8, H0 = c.grid_h * 8, W0 = c.grid_w * 8;
   h->dbg.clear();
   auto note = [&](const char* name, const void* p, size_t bytes) { h->dbg.push_back({name, (char*)p, bytes}); };
+  amx::VitLaunchInfo li0{}, li1{};
+  amx::VitLaunchInfo *const i0 = ts ? &li0 : nullptr, *const i1 = ts ? &li1 : nullptr;
+  auto tap = [&](const std::string& name, const std::string& route) -> hipError_t {
+    if (!ts) return hipSuccess;
+    for (int i = 0; i < ts->nreq; ++i) {
+      amx_vit_tap& r = ts->req[i];
+      if (name != r.name) continue;
+      snprintf(r.route, sizeof r.route, "%s", route.c_str());
+      if (!r.d_dst) continue;
+      const TapSrc* s = tap_find(ts->table, r.name);
+      if (!s) return hipErrorInvalidValue;
+      hipError_t e = hipMemcpyAsync(r.d_dst, s->a, s->na, hipMemcpyDeviceToDevice, st);
+      if (e == hipSuccess && s->nb) e = hipMemcpyAsync((char*)r.d_dst + s->na, s->b, s->nb, hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  };
 
   // ------------------------------------------------------------------ tokenizer
   {
@@ -433,9 +529,11 @@ int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& 
     sp.h_hi = P.h_hi[0]; sp.h_lo = c.stem_split ? P.h_lo[0] : nullptr; sp.p_hi = P.p_hi[0]; sp.p_lo = P.p_lo[0];
     AMX_HIP(amx::launch_tokstem(sp, 0, st));
     AMX_HIP(amx::launch_tok_finalize(P.stats, n, amx::tokstem_slots(D0, H0, W0), 32, (long long)D0 * H0 * W0, h->stem_nw, h->stem_nb, c.in_eps, P.sc[0], P.sh[0], st));
-    AMX_HIP(amx::launch_tokstem(sp, 1, st));
+    AMX_HIP(amx::launch_tokstem(sp, 1, st, i0));
     note("h0_hi", P.h_hi[0], (size_t)n * D0 * H0 * W0 * 32 * 2);
     note("p0_hi", P.p_hi[0], (size_t)n * D0 * H0 * W0 * 4 * 2);
+    AMX_HIP(tap("h0", li0.name));
+    AMX_HIP(tap("p0", li0.name));
   }
   int Dk = D0, Hk = H0, Wk = W0;
   for (int k = 0; k < 3; ++k) {
@@ -447,21 +545,31 @@ int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& 
     // conv1: stride 2 from the stage input
     cp.x_hi = P.h_hi[k]; cp.x_lo = (k == 0 && !c.stem_split) ? nullptr : P.h_lo[k]; cp.D = Dk; cp.H = Hk; cp.W = Wk; cp.Cin = s.cin;
     cp.w_hi = s.c1.hi; cp.w_lo = s.c1.lo; cp.bias = s.c1b; cp.raw = P.raw1;
-    AMX_HIP(amx::launch_tokconv(cp, 27, 2, st));
+    const std::string sk = "s" + std::to_string(k);
+    AMX_HIP(amx::launch_tokconv(cp, 27, 2, st, i0));
+    AMX_HIP(tap(sk + ".raw1", li0.name));
     AMX_HIP(amx::launch_tok_finalize(P.stats, n, amx::tokconv_slots(cp), s.cout, vo, s.n1w, s.n1b, c.in_eps, P.sc[0], P.sh[0], st));
+    AMX_HIP(tap(sk + ".ss1", "tok_finalize"));
     AMX_HIP(amx::launch_tok_apply(P.raw1, n, vo, s.cout, P.sc[0], P.sh[0], 0.01f, P.a1_hi, P.a1_lo, st));
+    AMX_HIP(tap(sk + ".a1", "tok_apply"));
     // conv2
     cp.x_hi = P.a1_hi; cp.x_lo = P.a1_lo; cp.D = Do; cp.H = Ho; cp.W = Wo; cp.Cin = s.cout;
     cp.w_hi = s.c2.hi; cp.w_lo = s.c2.lo; cp.bias = s.c2b; cp.raw = P.raw2;
-    AMX_HIP(amx::launch_tokconv(cp, 27, 1, st));
+    AMX_HIP(amx::launch_tokconv(cp, 27, 1, st, i0));
+    AMX_HIP(tap(sk + ".raw2", li0.name));
     AMX_HIP(amx::launch_tok_finalize(P.stats, n, amx::tokconv_slots(cp), s.cout, vo, s.n2w, s.n2b, c.in_eps, P.sc[1], P.sh[1], st));
+    AMX_HIP(tap(sk + ".ss2", "tok_finalize"));
     // skip: 1x1x1 conv of the average-pooled stage input (no bias)
     cp.x_hi = P.p_hi[k]; cp.x_lo = P.p_lo[k]; cp.Cin = s.cin;
     cp.w_hi = s.sk.hi; cp.w_lo = s.sk.lo; cp.bias = nullptr; cp.raw = P.raws;
-    AMX_HIP(amx::launch_tokconv(cp, 1, 1, st));
+    AMX_HIP(amx::launch_tokconv(cp, 1, 1, st, i0));
+    AMX_HIP(tap(sk + ".raws", li0.name));
     AMX_HIP(amx::launch_tok_finalize(P.stats, n, amx::tokconv_slots(cp), s.cout, vo, s.snw, s.snb, c.in_eps, P.sc[2], P.sh[2], st));
+    AMX_HIP(tap(sk + ".sss", "tok_finalize"));
     AMX_HIP(amx::launch_tok_combine(P.raw2, P.raws, n, Do, Ho, Wo, s.cout, P.sc[1], P.sh[1], P.sc[2], P.sh[2], 0.01f, P.h_hi[k + 1], P.h_lo[k + 1],
                                     k < 2 ? P.p_hi[k + 1] : nullptr, k < 2 ? P.p_lo[k + 1] : nullptr, st));
+    AMX_HIP(tap(sk + ".h", "tok_combine"));
+    if (k < 2) AMX_HIP(tap(sk + ".p", "tok_combine"));
     if (k == 0) { note("raw1_s0", P.raw1, (size_t)n * vo * s.cout * 4); }
     Dk = Do; Hk = Ho; Wk = Wo;
   }
@@ -470,10 +578,11 @@ int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& 
     g.a_hi = P.h_hi[3]; g.a_lo = P.h_lo[3]; g.lda = kStageC[3]; g.M = n * V; g.KS = h->tokproj.KS;
     g.w_hi = h->tokproj.hi; g.w_lo = h->tokproj.lo; g.ntiles = h->tokproj.ntiles; g.Nreal = E; g.bias = h->tokproj_b;
     g.out = P.tok; g.ldo = E; g.V = V; g.nreg = nreg; g.pos = h->pos;
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_TOKENS, st));
+    AMX_HIP(amx::launch_gemm(g, amx::EPI_TOKENS, st, i0));
     AMX_HIP(amx::launch_place_registers(h->regs, nreg, E, T, n, P.tok, st));
   }
   note("tokens", P.tok, (size_t)M * E * 4);
+  AMX_HIP(tap("tokens", li0.name));
 
   // ------------------------------------------------------------------ EVA blocks
   const int nb = n_blocks < 0 || n_blocks > c.depth ? c.depth : n_blocks;
@@ -486,33 +595,43 @@ int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& 
     const Block& b = h->blk[bi];
     amx::GemmParams g{};
     g.a_hi = P.A1; g.lda = Ep; g.M = M;
-    AMX_HIP(amx::launch_ln_rows(P.tok, 0, E, E, b.n1w, b.n1b, 1e-6f, M, M, M, 0, 0, P.A1, nullptr, Ep, st));
+    const std::string bk = "b" + std::to_string(bi);
+    AMX_HIP(amx::launch_ln_rows(P.tok, 0, E, E, b.n1w, b.n1b, 1e-6f, M, M, M, 0, 0, P.A1, nullptr, Ep, st, i0));
+    AMX_HIP(tap(bk + ".ln1", li0.name));
     // q | k and v projections write the attention kernel's f16 operands themselves (bias, per-head LayerNorm, rotary embedding,
     // fragment layouts in the epilogue): no fp32 q / k / v tensors, no separate preparation pass
     g.att_eps = 1e-5f; g.qscale = 1.4426950408889634f / sqrtf((float)h->hd); g.rope = h->rope; g.T = T; g.n_prefix = nreg; g.heads = c.heads;
     g.hd = h->hd; g.npad = att_npad; g.nblk_pad = att_nblk; g.Qp = Qp; g.Kp = Kp; g.Vt = Vt; g.Cp = 80;
     g.qnw = c.qk_norm ? b.qnw : nullptr; g.qnb = b.qnb; g.knw = c.qk_norm ? b.knw : nullptr; g.knb = b.knb;
     g.KS = b.qk.KS; g.w_hi = b.qk.hi; g.ntiles = b.qk.ntiles; g.Nreal = b.qk.ntiles * 16; g.bias = b.qkb; g.out = Qp; g.ldo = 0;
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_QK, st));
+    AMX_HIP(amx::launch_gemm(g, amx::EPI_QK, st, i0));
     g.KS = b.v.KS; g.w_hi = b.v.hi; g.ntiles = b.v.ntiles; g.Nreal = b.v.ntiles * 16; g.bias = b.vb; g.out = Vt;
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_VT, st));
+    AMX_HIP(amx::launch_gemm(g, amx::EPI_VT, st, i1));
     AMX_HIP(amx::launch_attention_fwd(Qp, Kp, Vt, n, T, c.heads, h->hd, P.AO, st));
-    AMX_HIP(amx::launch_ln_rows(P.AO, 0, E, E, c.scale_attn_inner ? b.anw : nullptr, b.anb, 1e-5f, M, M, M, 0, 0, P.A1, nullptr, Ep, st));
+    AMX_HIP(tap(bk + ".attn", std::string(li0.name) + " + " + li1.name + " + attn_fwd"));      // the operand buffers are not tapped: one group
+    AMX_HIP(amx::launch_ln_rows(P.AO, 0, E, E, c.scale_attn_inner ? b.anw : nullptr, b.anb, 1e-5f, M, M, M, 0, 0, P.A1, nullptr, Ep, st, i0));
+    AMX_HIP(tap(bk + ".ln_attn", li0.name));
     g.KS = b.proj.KS; g.w_hi = b.proj.hi; g.ntiles = b.proj.ntiles; g.Nreal = E; g.bias = b.projb; g.gamma = b.g1; g.out = P.tok; g.ldo = E;
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_RESID, st));
-    AMX_HIP(amx::launch_ln_rows(P.tok, 0, E, E, b.n2w, b.n2b, 1e-6f, M, M, M, 0, 0, P.A1, nullptr, Ep, st));
+    AMX_HIP(amx::launch_gemm(g, amx::EPI_RESID, st, i0));
+    AMX_HIP(tap(bk + ".tok1", li0.name));
+    AMX_HIP(amx::launch_ln_rows(P.tok, 0, E, E, b.n2w, b.n2b, 1e-6f, M, M, M, 0, 0, P.A1, nullptr, Ep, st, i0));
+    AMX_HIP(tap(bk + ".ln2", li0.name));
     g.KS = b.fc1.KS; g.w_hi = b.fc1.hi; g.ntiles = b.fc1.ntiles; g.Nreal = 2 * up(hid, 16); g.bias = b.fc1b; g.gamma = nullptr; g.out = P.Hd; g.ldo = up(hid, 16);
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_SWIGLU, st));
-    AMX_HIP(amx::launch_ln_rows(P.Hd, 1, up(hid, 16), hid, b.mnw, b.mnb, 1e-6f, M, M, M, 0, 0, P.A2, nullptr, up(hid, 32), st));
+    AMX_HIP(amx::launch_gemm(g, amx::EPI_SWIGLU, st, i0));
+    AMX_HIP(tap(bk + ".hd", li0.name));
+    AMX_HIP(amx::launch_ln_rows(P.Hd, 1, up(hid, 16), hid, b.mnw, b.mnb, 1e-6f, M, M, M, 0, 0, P.A2, nullptr, up(hid, 32), st, i0));
+    AMX_HIP(tap(bk + ".ln_mlp", li0.name));
     g.a_hi = P.A2; g.lda = up(hid, 32);
     g.KS = b.fc2.KS; g.w_hi = b.fc2.hi; g.ntiles = b.fc2.ntiles; g.Nreal = E; g.bias = b.fc2b; g.gamma = b.g2; g.out = P.tok; g.ldo = E;
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_RESID, st));
+    AMX_HIP(amx::launch_gemm(g, amx::EPI_RESID, st, i0));
+    AMX_HIP(tap(bk + ".tok2", li0.name));
   }
   note("tokens_out", P.tok, (size_t)M * E * 4);
 
   // ------------------------------------------------------------------ final norm (drops the register tokens) + decoder
   const int Mv = n * V;
-  AMX_HIP(amx::launch_ln_rows(P.tok, 0, E, E, h->fnw, h->fnb, 1e-6f, Mv, V, T, nreg, 0, P.Ad_hi[0], P.Ad_lo[0], Ep, st));
+  AMX_HIP(amx::launch_ln_rows(P.tok, 0, E, E, h->fnw, h->fnb, 1e-6f, Mv, V, T, nreg, 0, P.Ad_hi[0], P.Ad_lo[0], Ep, st, i0));
+  AMX_HIP(tap("d.ln", li0.name));
   int gd = c.grid_d, gh = c.grid_h, gw = c.grid_w;
   long long rows = Mv;
   for (int k = 0; k < 3; ++k) {
@@ -524,6 +643,7 @@ int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& 
     if (k == 2 && c.out_norm == 1) {      // ChannelDemean: the mean of every output channel follows from the column means of this stage's input
       AMX_HIP(amx::launch_colsum(P.Ad_hi[2], P.Ad_lo[2], up(d.cin, 32), d.cin, n, (int)(rows / n), kColChunks, P.colsum, st));
       AMX_HIP(amx::launch_demean(P.colsum, kColChunks, up(d.cin, 32), d.cin, rows / n, d.w_raw, d.cout, d.bias, n, P.mean, st));
+      AMX_HIP(tap("d.mean", "colsum + demean"));
     }
     if (k == 2 && out.acc) {              // one product per window, in window order: overlapping windows are ordered by the stream
       const long long wrows = rows / n, vvox = (long long)out.vd * out.vh * out.vw;
@@ -537,14 +657,18 @@ int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& 
       }
     } else if (k == 2) {                  // planar fp32 output written by the product kernel itself
       g.out = d_y; g.sub = c.out_norm == 1 ? P.mean : nullptr;
-      AMX_HIP(amx::launch_gemm(g, amx::EPI_PLANAR, st));
-    } else if (d.cp == 128 && up(d.cout, 32) <= 128) {   // channel LayerNorm + GELU fused: the next stage's operand rows come straight out
+      AMX_HIP(amx::launch_gemm(g, amx::EPI_PLANAR, st, i0));
+      AMX_HIP(tap("y", li0.name));
+    } else if (dec_fused(d)) {            // channel LayerNorm + GELU fused: the next stage's operand rows come straight out
       g.out = P.Ad_hi[k + 1]; g.out_lo = P.Ad_lo[k + 1]; g.ldo = up(d.cout, 32); g.lnw = d.lnw; g.lnb = d.lnb; g.eps = 1e-6f;
-      AMX_HIP(amx::launch_gemm(g, amx::EPI_SCATTER_LN, st));
+      AMX_HIP(amx::launch_gemm(g, amx::EPI_SCATTER_LN, st, i0));
+      AMX_HIP(tap("d" + std::to_string(k + 1) + ".in", li0.name));
     } else {
-      AMX_HIP(amx::launch_gemm(g, amx::EPI_SCATTER, st));
+      AMX_HIP(amx::launch_gemm(g, amx::EPI_SCATTER, st, i0));
+      AMX_HIP(tap("d" + std::to_string(k) + ".raw", li0.name));
       AMX_HIP(amx::launch_ln_rows(P.rawd[k], 0, d.cout, d.cout, d.lnw, d.lnb, 1e-6f, (int)(rows * 8), (int)(rows * 8), (int)(rows * 8), 0, 1, P.Ad_hi[k + 1],
-                                  P.Ad_lo[k + 1], up(d.cout, 32), st));
+                                  P.Ad_lo[k + 1], up(d.cout, 32), st, i0));
+      AMX_HIP(tap("d" + std::to_string(k + 1) + ".in", li0.name));
     }
     rows *= 8; gd *= 2; gh *= 2; gw *= 2;
   }
@@ -635,6 +759,36 @@ int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_w
   VitOut out;
   out.y = d_y;
   return vit_run(h, d_x, out, n, P, n_blocks, (hipStream_t)stream);
+}
+
+size_t amx_vit_tap_bytes(const amx_vit_t* h, int n, const char* name) {
+  if (!h || n < 1 || !name) return 0;
+  const std::vector<TapSrc> t = tap_table(h, n, make_plan(h, n, nullptr), h->cfg.depth, nullptr);
+  const TapSrc* s = tap_find(t, name);
+  return s ? s->bytes() : 0;
+}
+
+int amx_vit_forward_taps(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, amx_vit_tap* taps,
+                         int n_taps, void* stream) {
+  if (!h || !d_x || !d_y || !d_ws || n_taps < 0 || (n_taps && !taps)) return fail(AMX_ERR_INVALID, "null argument");
+  if (!h->loaded) return fail(AMX_ERR_NOT_LOADED, "vit: forward before amx_vit_load");
+  if (n < 1) return fail(AMX_ERR_INVALID, "vit: batch %d", n);
+  if ((uintptr_t)d_ws & 255) return fail(AMX_ERR_WORKSPACE, "vit: workspace must be 256-byte aligned");
+  const Plan P = make_plan(h, n, (char*)d_ws);
+  if (ws_bytes < P.total) return fail(AMX_ERR_WORKSPACE, "vit: workspace needs %zu bytes (got %zu)", P.total, ws_bytes);
+  const int nb = n_blocks < 0 || n_blocks > h->cfg.depth ? h->cfg.depth : n_blocks;
+  TapSet ts{tap_table(h, n, P, nb, d_y), taps, n_taps};
+  for (int i = 0; i < n_taps; ++i) {            // every refusal comes before the first launch
+    if (!taps[i].name) return fail(AMX_ERR_INVALID, "vit: tap %d has no name", i);
+    const TapSrc* s = tap_find(ts.table, taps[i].name);
+    if (!s) return fail(AMX_ERR_INVALID, "vit: no tap named %s in this forward (%d blocks)", taps[i].name, nb);
+    if (taps[i].d_dst && taps[i].bytes < s->bytes())
+      return fail(AMX_ERR_WORKSPACE, "vit: tap %s needs %zu bytes (got %zu)", taps[i].name, s->bytes(), taps[i].bytes);
+    taps[i].route[0] = 0;
+  }
+  VitOut out;
+  out.y = d_y;
+  return vit_run(h, d_x, out, n, P, n_blocks, (hipStream_t)stream, &ts);
 }
 
 size_t amx_vit_windows_workspace_bytes(const amx_vit_t* h, int n_windows) {

@@ -359,9 +359,14 @@ class PrimusV2(nn.Module):
             ws = self._engine_ws = torch.empty(need, dtype=torch.uint8, device=dev)
         return ws
 
-    def forward_hip(self, x, n_blocks=-1):
+    def forward_hip(self, x, n_blocks=-1, taps=None):
         """[N, 1, D, H, W] fp32 on the GPU -> [N, num_classes, D, H, W]: ``amx_vit_forward`` + (for output norms other than none /
-        demean) the torch output norm.  Raises when the configuration is outside the engine's envelope -- there is no fallback."""
+        demean) the torch output norm.  Raises when the configuration is outside the engine's envelope -- there is no fallback.
+
+        ``taps`` (test aid): names of intermediates (``amx_vit_forward_taps``, include/anatomix_amd.h lists them), or a dict
+        name -> bool (False: only the route, nothing is copied).  Returns ``(y, {name: (data, route)})``: ``data`` is the flat byte
+        buffer viewed as the tap's type -- one tensor, a ``(first, second)`` pair for the two-range taps (hi | lo planes, scale |
+        shift), or None -- and ``route`` the instance name of the launch that produced it.  ``y`` has the bits of a plain forward."""
         dev = x.device
         if tuple(x.shape[2:]) != tuple(8 * g for g in self.grid) or x.shape[1] != self._vit_cfg["input_channels"]:
             raise ValueError(f"PrimusV2 was built for inputs of {tuple(8 * g for g in self.grid)} (got {tuple(x.shape[1:])})")
@@ -372,10 +377,39 @@ class PrimusV2(nn.Module):
             ws = self._engine_workspace(need, dev)
             xin = x.detach().float().contiguous()
             y = torch.empty((n, self._vit_cfg["num_classes"]) + tuple(x.shape[2:]), dtype=torch.float32, device=dev)
-            _lib.check(lib.amx_vit_forward(self._handle, _lib.ptr(xin), _lib.ptr(y), n, _lib.ptr(ws), need, int(n_blocks), stream))
+            if taps is None:
+                _lib.check(lib.amx_vit_forward(self._handle, _lib.ptr(xin), _lib.ptr(y), n, _lib.ptr(ws), need, int(n_blocks), stream))
+            else:
+                want = dict(taps) if isinstance(taps, dict) else {name: True for name in taps}
+                req = (_lib.VitTap * max(1, len(want)))()
+                bufs = {}
+                for r, (name, copy) in zip(req, want.items()):
+                    r.name = name.encode()
+                    if copy:
+                        nbytes = lib.amx_vit_tap_bytes(self._handle, n, r.name)
+                        bufs[name] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                        r.d_dst, r.bytes = bufs[name].data_ptr(), nbytes
+                _lib.check(lib.amx_vit_forward_taps(self._handle, _lib.ptr(xin), _lib.ptr(y), n, _lib.ptr(ws), need, int(n_blocks), req,
+                                                    len(want), stream))
+                got = {name: (self._tap_view(name, bufs.get(name)), r.route.decode()) for r, name in zip(req, want)}
         if not isinstance(self.out_norm, (ChannelDemean, nn.Identity)):
             y = self.out_norm(y)
-        return y
+        return y if taps is None else (y, got)
+
+    def _tap_view(self, name, buf):
+        """A tap's bytes as tensors of its type: fp32 for the raw conv outputs, (scale, shift), the token stream, the attention
+        output, the demean constants and the output; f16 for the operand rows; a pair for the two-range taps."""
+        if buf is None:
+            return None
+        leaf = name.split(".")[-1]
+        if leaf in ("ss1", "ss2", "sss"):
+            return tuple(buf.view(torch.float32).chunk(2))
+        if leaf in ("raw1", "raw2", "raws", "tokens", "attn", "tok1", "tok2", "raw", "mean", "y"):
+            return buf.view(torch.float32)
+        split = self._vit_cfg["stem_split"] if name == "h0" else (self._vit_cfg["decoder_split"] if name[0] == "d" else 1)
+        if leaf in ("h0", "p0", "a1", "h", "p", "in") or name == "d.ln":
+            return tuple(buf.view(torch.float16).chunk(2)) if split else (buf.view(torch.float16), None)
+        return buf.view(torch.float16)
 
     def debug_read(self, name, dtype=torch.float32):
         """A workspace buffer of the last ``forward_hip`` (tests): flat tensor of ``dtype``."""

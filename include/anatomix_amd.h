@@ -510,6 +510,32 @@ size_t amx_vit_workspace_bytes(const amx_vit_t* h, int n);
 int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, void* stream);
 int amx_vit_debug_read(amx_vit_t* h, const char* name, void* d_dst, size_t max_bytes, size_t* bytes, void* stream);
 
+/* amx_vit_forward with taps (test aid; the stage-by-stage walk of tests/_vit_walk.py).  The workspace regions of tokenizer, blocks and
+ * decoder alias each other and the token stream is updated in place, so an intermediate can only be read while the forward runs: for every
+ * request, the named buffer is copied to d_dst (`bytes` = its capacity) by a device-to-device copy enqueued on `stream` right after the
+ * launch that produces it, and `route` receives that launch's instance name (e.g. wsgemm<2,5,4,RESID,f16,4w>, tokconv<27,2,2,4,split>,
+ * ln_rows_vec<f32,2>).  d_dst NULL: the route only.  No launch is added, moved or routed differently: d_y has the bits of amx_vit_forward.
+ * Names (k = 0..2 tokenizer stage, b = block; "x | y" = two ranges back to back, each half of amx_vit_tap_bytes):
+ *   h0, p0                 stem output and its 2x2x2 average: f16 channels-last [n][D][H][W][32], hi | lo (hi alone when stem_split == 0)
+ *   s{k}.raw1 .raw2 .raws  fp32 channels-last conv outputs (conv1, conv2, skip);  s{k}.ss1 .ss2 .sss  InstanceNorm scale | shift, fp32 [n][C]
+ *   s{k}.a1, s{k}.h, s{k}.p   f16 hi | lo: activation behind conv1, stage output, its average (no s2.p)
+ *   tokens                 fp32 [n][T][E] behind the tokenizer (registers in front)
+ *   b{b}.ln1 .ln_attn .ln2 f16 [n T][Ep] operand rows;  b{b}.attn fp32 [n T][E];  b{b}.tok1 .tok2 fp32 [n T][E] token stream
+ *   b{b}.hd                f16 [n T][hidden up to 16];  b{b}.ln_mlp f16 [n T][hidden up to 32]
+ *   d.ln, d1.in, d2.in     f16 hi | lo decoder operand rows [rows][channels up to 32] (hi alone when decoder_split == 0)
+ *   d0.raw, d1.raw         fp32 [8 rows][C] -- absent when the stage's LayerNorm + GELU is fused into the product (Cp == 128)
+ *   d.mean                 fp32 [n][num_classes] (out_norm == 1);  y  the output itself
+ * Unknown names (or a block >= n_blocks) fail with AMX_ERR_INVALID, short buffers with AMX_ERR_WORKSPACE, before the first launch. */
+typedef struct amx_vit_tap {
+  const char* name;
+  void* d_dst;       /* device buffer, or NULL */
+  size_t bytes;      /* its capacity */
+  char route[160];   /* out: the producing launch */
+} amx_vit_tap;
+size_t amx_vit_tap_bytes(const amx_vit_t* h, int n, const char* name);   /* 0 for an unknown name */
+int amx_vit_forward_taps(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, amx_vit_tap* taps,
+                         int n_taps, void* stream);
+
 /* ---- the ViT under sliding_window_inference (convex_adam_utils.py:202-219 / train_segmentation.py:194-199; the reference
  * presents anatomix-dev-vit as "Requires 128^3 inputs, but amenable to sliding window").  The roi is the handle's input shape,
  * 8 * grid, on every entry below. */

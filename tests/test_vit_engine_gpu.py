@@ -1,7 +1,10 @@
 """GPU: the ViT engine (amx_vit_forward: own kernels for the conv tokenizer, the token-matrix products, the attention and the
 decoder) against the oracle restatement, stage by stage: the MFMA product kernel alone (amx_linear), the tokenizer's tokens, the
 decoder with no blocks in between, a few blocks, and the whole network at reduced and odd sizes.  (The 128^3 operating point is
-tests/test_vit_gpu.py.)  Parity with the upstream package is UNPINNED (oracle/vit_ref.py)."""
+tests/test_vit_gpu.py.)  Parity with the upstream package is UNPINNED (oracle/vit_ref.py).
+
+A failure here says that the network is off, not where: tests/test_vit_walk_gpu.py compares every stage of the same forward with a
+float64 reference of the tensors stored in front of it and names the stage, the kernel instance and the element."""
 import ctypes
 
 import numpy as np
