@@ -505,6 +505,54 @@ int amx_attention_prepared(const void* d_scratch, size_t scratch_bytes, int b, i
   return AMX_OK;
 }
 
+namespace {
+// the envelope shared by the attention entries: AMX_OK or the refusal, before any launch
+int attention_args_ok(const float* d_qn_w, const float* d_qn_b, const float* d_kn_w, const float* d_kn_b, int n_prefix, int b, int n,
+                      int heads, int head_dim) {
+  if (b < 1 || n < 1 || heads < 1 || head_dim < 2 || head_dim > 80 || (head_dim & 1))
+    return fail(AMX_ERR_INVALID, "attention: head_dim must be even and <= 80 (got %d), b, n, heads >= 1", head_dim);
+  if ((!d_qn_w) != (!d_qn_b) || (!d_kn_w) != (!d_kn_b)) return fail(AMX_ERR_INVALID, "attention: norm weight and bias go together");
+  if (n_prefix < 0 || n_prefix > n) return fail(AMX_ERR_INVALID, "attention: 0 <= n_prefix <= n");
+  return AMX_OK;
+}
+}  // namespace
+
+size_t amx_attention_train_scratch_bytes(int b, int heads, int n, int head_dim) {
+  if (b < 1 || heads < 1 || n < 1 || head_dim < 2 || head_dim > 80 || (head_dim & 1)) return 0;
+  return amx::attention_train_scratch_bytes(b, heads, n, head_dim);
+}
+
+int amx_attention_qknorm_rope_train(const float* d_q, const float* d_k, const float* d_v, const float* d_qn_w, const float* d_qn_b,
+                                    const float* d_kn_w, const float* d_kn_b, float norm_eps, const float* d_rope, int n_prefix, int b,
+                                    int n, int heads, int head_dim, float* d_out, float* d_lse, void* d_scratch, size_t scratch_bytes,
+                                    void* stream) {
+  if (!d_q || !d_k || !d_v || !d_out || !d_lse || !d_scratch) return fail(AMX_ERR_INVALID, "attention: null argument");
+  if (int rc = attention_args_ok(d_qn_w, d_qn_b, d_kn_w, d_kn_b, n_prefix, b, n, heads, head_dim)) return rc;
+  if (scratch_bytes < amx::attention_scratch_bytes(b, heads, n) || ((uintptr_t)d_scratch & 15))
+    return fail(AMX_ERR_WORKSPACE, "attention scratch needs %zu bytes, 16-byte aligned", amx::attention_scratch_bytes(b, heads, n));
+  AMX_HIP(amx::launch_attention(d_q, d_k, d_v, d_qn_w, d_qn_b, d_kn_w, d_kn_b, norm_eps, d_rope, n_prefix, b, n, heads, head_dim, d_out,
+                                d_scratch, (hipStream_t)stream, d_lse));
+  return AMX_OK;
+}
+
+int amx_attention_backward(const float* d_q, const float* d_k, const float* d_v, const float* d_qn_w, const float* d_qn_b,
+                           const float* d_kn_w, const float* d_kn_b, float norm_eps, const float* d_rope, int n_prefix, int b, int n,
+                           int heads, int head_dim, const float* d_out, const float* d_lse, const float* d_dout, float* d_dq, float* d_dk,
+                           float* d_dv, float* d_dqn_w, float* d_dqn_b, float* d_dkn_w, float* d_dkn_b, void* d_scratch,
+                           size_t scratch_bytes, void* stream) {
+  if (!d_q || !d_k || !d_v || !d_out || !d_lse || !d_dout || !d_scratch) return fail(AMX_ERR_INVALID, "attention backward: null argument");
+  if (int rc = attention_args_ok(d_qn_w, d_qn_b, d_kn_w, d_kn_b, n_prefix, b, n, heads, head_dim)) return rc;
+  if ((!d_qn_w && (d_dqn_w || d_dqn_b)) || (!d_kn_w && (d_dkn_w || d_dkn_b)))
+    return fail(AMX_ERR_INVALID, "attention backward: a norm gradient was asked for a norm that is absent");
+  const size_t need = amx::attention_train_scratch_bytes(b, heads, n, head_dim);
+  if (scratch_bytes < need || ((uintptr_t)d_scratch & 15))
+    return fail(AMX_ERR_WORKSPACE, "attention backward scratch needs %zu bytes, 16-byte aligned", need);
+  AMX_HIP(amx::launch_attention_backward(d_q, d_k, d_v, d_qn_w, d_qn_b, d_kn_w, d_kn_b, norm_eps, d_rope, n_prefix, b, n, heads, head_dim,
+                                         d_out, d_lse, d_dout, d_dq, d_dk, d_dv, d_dqn_w, d_dqn_b, d_dkn_w, d_dkn_b, d_scratch,
+                                         (hipStream_t)stream));
+  return AMX_OK;
+}
+
 size_t amx_supcon_scratch_bytes(int n, int c) { return amx::supcon_scratch_bytes(n, c); }
 
 int amx_supcon_loss(const float* d_feat, const int* d_labels, int n, int c, float temperature, int weigh_rarity,

@@ -23,24 +23,11 @@
 
 #include <type_traits>
 
+#include "amx_attention.h"
 #include "amx_device.h"
 #include "amx_launch.h"
 
 namespace amx {
-
-
-constexpr int kAttKRow = 104;         // halves per Qp / Kp row (208 B)
-constexpr int kAttDV = 80;            // head_dim padded to 5 output tiles of 16
-constexpr int kAttBN = 64;            // keys per block
-constexpr int kAttQT = 2;             // 16-query tiles per wave (measured: QT = 1 halves the work per staged K / V tile and is slower at batch 2)
-constexpr int kAttBM = 4 * 16 * kAttQT;  // queries per workgroup (4 waves)
-constexpr int kAttPad = 128;          // token padding of the operand buffers
-constexpr int kAttNLW = 2;            // loader waves
-constexpr int kAttNBUF = 3;           // ring depth (key blocks in flight); 5 measured the same: the MFMA waves, not the loaders, set the pace
-constexpr int kAttKFrag = 12;         // K fragments per key block: 4 key tiles x 3 K steps (96 padded dims), 1 KiB each
-constexpr int kAttVFrag = 10;         // V^T fragments per key block: 5 output tiles x 2 K steps (64 keys)
-
-__host__ __device__ inline int att_npad(int n) { return (n + kAttPad - 1) / kAttPad * kAttPad; }
 
 // grid (n_pad / 64, heads, b), block 256 = 4 waves x 16 tokens: one workgroup = one key block of one head.  One wave handles a
 // token at a time, lane d < hd holds channel d (and d + 64).  q rows go straight to global memory (a row is contiguous); the K
@@ -48,20 +35,31 @@ __host__ __device__ inline int att_npad(int n) { return (n + kAttPad - 1) / kAtt
 // per-token 2-byte stores at a 144-byte stride of the first version were 2/3 of this kernel's time).
 // Row `hd` of the V^T tile is set to ONE for real tokens: the PV product then accumulates the softmax row sum in output row hd
 // for free (attn_fwd, ONES) -- head_dim 80 has no spare row and keeps the VALU sum.
+// TRAIN: the backward's re-run (amx_attention_bwd.hip) -- the same arithmetic, and three more images of the same f16 values: V as a
+// ROW image, K-hat and Q-hat as COL images (amx_attention.h).
+template <bool TRAIN>
 __global__ __launch_bounds__(256) void attn_prep_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                         const float* __restrict__ v, const float* __restrict__ qn_w,
                                                         const float* __restrict__ qn_b, const float* __restrict__ kn_w,
                                                         const float* __restrict__ kn_b, float eps, const float* __restrict__ rope,
                                                         int n_prefix, int n, int heads, int hd, int ld, f16* __restrict__ Qp,
-                                                        f16* __restrict__ Kp, f16* __restrict__ Vt) {
+                                                        f16* __restrict__ Kp, f16* __restrict__ Vt, f16* __restrict__ Vr,
+                                                        f16* __restrict__ Kt, f16* __restrict__ Qt) {
   // K and V^T tiles of the block in MFMA FRAGMENT order ([fragment][lane][8 halves], the order attn_fwd reads them with one
   // conflict-free ds_read_b128 per fragment): assembled here, written out linearly.
   __shared__ __attribute__((aligned(16))) f16 ktile[kAttKFrag * 512];
   __shared__ __attribute__((aligned(16))) f16 vt[kAttVFrag * 512];
+  __shared__ __attribute__((aligned(16))) f16 vrow[TRAIN ? kAttKFrag * 512 : 8];
+  __shared__ __attribute__((aligned(16))) f16 kcol[TRAIN ? kAttVFrag * 512 : 8];
+  __shared__ __attribute__((aligned(16))) f16 qcol[TRAIN ? kAttVFrag * 512 : 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int h = blockIdx.y, b = blockIdx.z, npad = att_npad(n);
   for (int i = threadIdx.x; i < kAttKFrag * 64; i += 256) ((uint4*)ktile)[i] = make_uint4(0u, 0u, 0u, 0u);
   for (int i = threadIdx.x; i < kAttVFrag * 64; i += 256) ((uint4*)vt)[i] = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (TRAIN) {
+    for (int i = threadIdx.x; i < kAttKFrag * 64; i += 256) ((uint4*)vrow)[i] = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = threadIdx.x; i < kAttVFrag * 64; i += 256) ((uint4*)kcol)[i] = ((uint4*)qcol)[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
   __syncthreads();
   const bool a0 = lane < hd, a1 = lane + 64 < hd;
   // wave-wide sum on the VALU (DPP row shifts + row broadcasts, total read from lane 63): the ds_bpermute butterflies of
@@ -138,10 +136,18 @@ __global__ __launch_bounds__(256) void attn_prep_kernel(const float* __restrict_
       if (s == 0) {
         qo[lane] = (f16)(y0 * qpost);
         if (lane + 64 < kAttKRow) qo[lane + 64] = (f16)(a1 ? y1 * qpost : 0.f);
+        if constexpr (TRAIN) {
+          if (a0) qcol[att_col_idx(tib, lane)] = (f16)(y0 * qpost);
+          if (a1) qcol[att_col_idx(tib, lane + 64)] = (f16)(y1 * qpost);
+        }
       } else {                           // key (tile tib / 16, row tib % 16): dim d -> fragment (tile, d / 32), lane ((d % 32) / 8, row), element d % 8
         auto kidx = [&](int d) { return (((tib >> 4) * 3 + (d >> 5)) * 64 + ((d & 31) >> 3) * 16 + (tib & 15)) * 8 + (d & 7); };
         if (a0) ktile[kidx(lane)] = (f16)y0;
         if (a1) ktile[kidx(lane + 64)] = (f16)y1;
+        if constexpr (TRAIN) {
+          if (a0) kcol[att_col_idx(tib, lane)] = (f16)y0;
+          if (a1) kcol[att_col_idx(tib, lane + 64)] = (f16)y1;
+        }
       }
     }
     // V^T: dv row d, key tib -> fragment (d / 16, tib / 32), lane (g, d % 16); the 32 keys of a K step are taken in the order
@@ -153,6 +159,10 @@ __global__ __launch_bounds__(256) void attn_prep_kernel(const float* __restrict_
     if (a0) vt[vidx(lane)] = (f16)v0;
     if (a1) vt[vidx(lane + 64)] = (f16)v1;
     if (lane == 0 && hd < kAttDV) vt[vidx(hd)] = (f16)1.f;
+    if constexpr (TRAIN) {
+      if (a0) vrow[att_row_idx(tib, lane)] = (f16)v0;
+      if (a1) vrow[att_row_idx(tib, lane + 64)] = (f16)v1;
+    }
   }
   }
   __syncthreads();
@@ -161,6 +171,13 @@ __global__ __launch_bounds__(256) void attn_prep_kernel(const float* __restrict_
   uint4* vd = (uint4*)(Vt + blk * (kAttVFrag * 512));
   for (int i = threadIdx.x; i < kAttKFrag * 64; i += 256) kd[i] = ((const uint4*)ktile)[i];
   for (int i = threadIdx.x; i < kAttVFrag * 64; i += 256) vd[i] = ((const uint4*)vt)[i];
+  if constexpr (TRAIN) {
+    uint4* vr = (uint4*)(Vr + blk * (kAttKFrag * 512));
+    uint4* kt = (uint4*)(Kt + blk * (kAttVFrag * 512));
+    uint4* qt = (uint4*)(Qt + blk * (kAttVFrag * 512));
+    for (int i = threadIdx.x; i < kAttKFrag * 64; i += 256) vr[i] = ((const uint4*)vrow)[i];
+    for (int i = threadIdx.x; i < kAttVFrag * 64; i += 256) { kt[i] = ((const uint4*)kcol)[i]; qt[i] = ((const uint4*)qcol)[i]; }
+  }
 }
 
 typedef __attribute__((address_space(1))) const void* att_gptr_t;
@@ -173,7 +190,8 @@ typedef __attribute__((address_space(3))) void* att_lptr_t;
 // (amx_device.h) -- no workgroup barrier in the loop.
 template <bool ONES>
 __global__ __launch_bounds__((4 + kAttNLW) * 64) void attn_fwd_kernel(const f16* __restrict__ Qp, const f16* __restrict__ Kp,
-                                                       const f16* __restrict__ Vt, int n, int heads, int hd, float* __restrict__ out) {
+                                                       const f16* __restrict__ Vt, int n, int heads, int hd, float* __restrict__ out,
+                                                       float* __restrict__ lse) {
   constexpr int QT = kAttQT, KB = kAttKFrag * 1024, VB = kAttVFrag * 1024, BUF = KB + VB, NBUF = kAttNBUF;
   constexpr int NDMA = (BUF + 1023) / 1024, NLW = kAttNLW;  // 1 KiB pieces per key block (the last one partial)
   constexpr int PER = (NDMA + NLW - 1) / NLW;               // pieces per loader wave and block (waves without a last piece pad the count)
@@ -384,6 +402,8 @@ __global__ __launch_bounds__((4 + kAttNLW) * 64) void attn_fwd_kernel(const f16*
     const float inv = 1.f / l;
     const int qi = q0 + qt * 16 + li;
     if (qi >= n) continue;
+    // training: the row's log-sum-exp in the exp2 domain, [b][heads][n] (the backward recomputes P = exp2(S - lse) from it)
+    if (lse != nullptr && g == 0) lse[bh * n + qi] = m_ref[qt] + __builtin_log2f(l);
     float* o = out + ((long long)b * n + qi) * heads * hd + (long long)h * hd;
 #pragma unroll
     for (int dt = 0; dt < 5; ++dt)
@@ -412,7 +432,8 @@ void attention_operands(void* scratch, int b, int heads, int n, void** Qp, void*
 }
 
 // softmax(q k^T) v on prepared operands
-hipError_t launch_attention_fwd(const void* Qp, const void* Kp, const void* Vt, int b, int n, int heads, int hd, float* out, hipStream_t st) {
+hipError_t launch_attention_fwd(const void* Qp, const void* Kp, const void* Vt, int b, int n, int heads, int hd, float* out, hipStream_t st,
+                                float* lse) {
   const int npad = att_npad(n);
   constexpr int LDS = kAttNBUF * (kAttKFrag + kAttVFrag) * 1024 + 64;
   static amx::DeviceOnce attr_once;
@@ -424,28 +445,37 @@ hipError_t launch_attention_fwd(const void* Qp, const void* Kp, const void* Vt, 
   }
   if (hd < kAttDV)
     hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(npad / kAttBM, heads, b), dim3((4 + kAttNLW) * 64), LDS, st, (const f16*)Qp, (const f16*)Kp,
-                       (const f16*)Vt, n, heads, hd, out);
+                       (const f16*)Vt, n, heads, hd, out, lse);
   else
     hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(npad / kAttBM, heads, b), dim3((4 + kAttNLW) * 64), LDS, st, (const f16*)Qp, (const f16*)Kp,
-                       (const f16*)Vt, n, heads, hd, out);
+                       (const f16*)Vt, n, heads, hd, out, lse);
   return hipGetLastError();
 }
 
 hipError_t launch_attention_ld(const float* q, const float* k, const float* v, int ld, const float* qn_w, const float* qn_b, const float* kn_w,
                                const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
-                               float* out, void* scratch, hipStream_t st) {
+                               float* out, void* scratch, hipStream_t st, float* lse) {
   void *Qp, *Kp, *Vt;
   int npad;
   attention_operands(scratch, b, heads, n, &Qp, &Kp, &Vt, &npad, nullptr);
-  hipLaunchKernelGGL(attn_prep_kernel, dim3(npad / kAttBN, heads, b), dim3(256), 0, st, q, k, v, qn_w, qn_b, kn_w, kn_b, eps, rope,
-                     n_prefix, n, heads, hd, ld, (f16*)Qp, (f16*)Kp, (f16*)Vt);
-  return launch_attention_fwd(Qp, Kp, Vt, b, n, heads, hd, out, st);
+  hipLaunchKernelGGL(attn_prep_kernel<false>, dim3(npad / kAttBN, heads, b), dim3(256), 0, st, q, k, v, qn_w, qn_b, kn_w, kn_b, eps, rope,
+                     n_prefix, n, heads, hd, ld, (f16*)Qp, (f16*)Kp, (f16*)Vt, (f16*)nullptr, (f16*)nullptr, (f16*)nullptr);
+  return launch_attention_fwd(Qp, Kp, Vt, b, n, heads, hd, out, st, lse);
+}
+
+// the backward's re-run of the preparation: every operand image of q-hat, k-hat and v (amx_attention_bwd.hip)
+hipError_t launch_attention_prep_train(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b,
+                                       const float* kn_w, const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n,
+                                       int heads, int hd, const AttTrainScratch& S, hipStream_t st) {
+  hipLaunchKernelGGL(attn_prep_kernel<true>, dim3(att_npad(n) / kAttBN, heads, b), dim3(256), 0, st, q, k, v, qn_w, qn_b, kn_w, kn_b, eps,
+                     rope, n_prefix, n, heads, hd, heads * hd, S.Qp, S.Kp, S.Vt, S.Vr, S.Kt, S.Qt);
+  return hipGetLastError();
 }
 
 hipError_t launch_attention(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
                             const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
-                            float* out, void* scratch, hipStream_t st) {
-  return launch_attention_ld(q, k, v, heads * hd, qn_w, qn_b, kn_w, kn_b, eps, rope, n_prefix, b, n, heads, hd, out, scratch, st);
+                            float* out, void* scratch, hipStream_t st, float* lse) {
+  return launch_attention_ld(q, k, v, heads * hd, qn_w, qn_b, kn_w, kn_b, eps, rope, n_prefix, b, n, heads, hd, out, scratch, st, lse);
 }
 
 }  // namespace amx

@@ -296,10 +296,18 @@ hipError_t launch_minmax_finalize(const void* scratch, int n, long long V, float
 // amx_attention.hip
 size_t attention_scratch_bytes(int b, int heads, int n);
 void attention_operands(void* scratch, int b, int heads, int n, void** Qp, void** Kp, void** Vt, int* npad_out, int* nblk_pad_out);
-hipError_t launch_attention_fwd(const void* Qp, const void* Kp, const void* Vt, int b, int n, int heads, int hd, float* out, hipStream_t st);
+hipError_t launch_attention_fwd(const void* Qp, const void* Kp, const void* Vt, int b, int n, int heads, int hd, float* out, hipStream_t st,
+                                float* lse = nullptr);     // lse: [b][heads][n] log-sum-exp (exp2 domain) for the backward, or null
 hipError_t launch_attention(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
                             const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
-                            float* out, void* scratch, hipStream_t st);
+                            float* out, void* scratch, hipStream_t st, float* lse = nullptr);
+
+// amx_attention_bwd.hip
+size_t attention_train_scratch_bytes(int b, int heads, int n, int hd);
+hipError_t launch_attention_backward(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
+                                     const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
+                                     const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv, float* dqn_w,
+                                     float* dqn_b, float* dkn_w, float* dkn_b, void* scratch, hipStream_t st);
 
 // amx_api.hip: stores the thread-local message that amx_last_error() returns, and gives `code` back
 int fail(int code, const char* fmt, ...);

@@ -15,9 +15,11 @@ tokens, every EVA block (LayerNorms, q / k / v, QK-LayerNorm + rotary embedding 
 LayerScale residuals, SwiGLU MLP), final norm, transposed-conv decoder, ChannelDemean -- is ONE call into libanatomix_amd.so
 (``amx_vit_forward``, csrc/amx_vit.hip: own MFMA kernels for the convolutions, the token-matrix products and the attention;
 no vendor GEMM / conv library).  Output norms other than none / demean are applied on the engine's output by their torch module.
-Under autograd or on the CPU the torch modules below compute the same network (training the ViT is not part of the accelerated
-path); ``PrimusV2.use_engine = False`` forces that composition on the GPU too (its attention core then still runs through
-``amx_attention_qknorm_rope``).
+Under autograd or on the CPU the torch modules below compute the same network; ``PrimusV2.use_engine = False`` forces that
+composition on the GPU too (its attention core then still runs through ``amx_attention_qknorm_rope``).  Of training, the attention
+core alone is on the accelerated path: ``PrimusV2.train_attention = "hip"`` runs it forward and backward on the library's kernels
+(``_AttentionCoreFn``: amx_attention_qknorm_rope_train / amx_attention_backward); the default ``"torch"`` keeps
+F.scaled_dot_product_attention, and everything around the core is torch autograd either way.
 """
 from __future__ import annotations
 
@@ -181,6 +183,67 @@ def _rope(x, table):
     return x * table[:, hd:] + rot * table[:, :hd]
 
 
+TRAIN_CORES = ("torch", "hip")
+_train_scratch_cache = {}
+
+
+def _train_scratch(nb, dev):
+    """One scratch buffer per device for every block's training calls: a call leaves nothing in it that a later call reads (the
+    backward re-runs the preparation), and the calls of one autograd pass are ordered on the stream."""
+    buf = _train_scratch_cache.get(dev)
+    if buf is None or buf.numel() < nb:
+        buf = _train_scratch_cache[dev] = torch.empty(nb, dtype=torch.uint8, device=dev)
+    return buf
+
+
+class _AttentionCoreFn(torch.autograd.Function):
+    """The attention core under autograd on the library's own kernels: ``amx_attention_qknorm_rope_train`` forward (the no-grad
+    core's output bit for bit, plus the log-sum-exp), ``amx_attention_backward`` backward (csrc/amx_attention_bwd.hip).  Saved:
+    q, k, v, the output, the log-sum-exp [B, heads, N], the norm parameters and the rotary table -- no N x N tensor."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qn_w, qn_b, kn_w, kn_b, table, n_prefix, heads, eps):
+        lib = _lib.load()
+        B, N, E = q.shape
+        hd, dev = E // heads, q.device
+        out = torch.empty_like(q)
+        lse = torch.empty(B, heads, N, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            nb = lib.amx_attention_train_scratch_bytes(B, heads, N, hd)
+            if nb == 0:
+                raise _lib.AmxError(f"attention: unsupported shape (heads {heads}, head_dim {hd})")
+            scratch = _train_scratch(nb, dev)
+            _lib.check(lib.amx_attention_qknorm_rope_train(
+                _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(qn_w), _lib.ptr(qn_b), _lib.ptr(kn_w), _lib.ptr(kn_b), float(eps),
+                _lib.ptr(table), int(n_prefix), B, N, heads, hd, _lib.ptr(out), _lib.ptr(lse), _lib.ptr(scratch), nb,
+                _lib.stream(dev)))
+        ctx.save_for_backward(q, k, v, out, lse, qn_w, qn_b, kn_w, kn_b, table)
+        ctx.cfg = (int(n_prefix), int(heads), float(eps))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q, k, v, out, lse, qn_w, qn_b, kn_w, kn_b, table = ctx.saved_tensors
+        n_prefix, heads, eps = ctx.cfg
+        lib = _lib.load()
+        B, N, E = q.shape
+        hd, dev = E // heads, q.device
+        dout = _lib.f32c(dout)
+        need = ctx.needs_input_grad
+        new = lambda like, on: torch.empty_like(like) if on else None
+        dq, dk, dv = new(q, need[0]), new(k, need[1]), new(v, need[2])
+        dnorm = [new(p, p is not None and need[3 + i]) for i, p in enumerate((qn_w, qn_b, kn_w, kn_b))]
+        with torch.cuda.device(dev):
+            nb = lib.amx_attention_train_scratch_bytes(B, heads, N, hd)
+            scratch = _train_scratch(nb, dev)
+            _lib.check(lib.amx_attention_backward(
+                _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(qn_w), _lib.ptr(qn_b), _lib.ptr(kn_w), _lib.ptr(kn_b), eps,
+                _lib.ptr(table), n_prefix, B, N, heads, hd, _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout), _lib.ptr(dq), _lib.ptr(dk),
+                _lib.ptr(dv), *[_lib.ptr(t) for t in dnorm], _lib.ptr(scratch), nb, _lib.stream(dev)))
+        return (dq, dk, dv, *dnorm, None, None, None, None)
+
+
 class EvaAttention(nn.Module):
     def __init__(self, dim, num_heads, qk_norm, scale_attn_inner):
         super().__init__()
@@ -191,6 +254,14 @@ class EvaAttention(nn.Module):
         self.norm = nn.LayerNorm(dim) if scale_attn_inner else nn.Identity()
         self.proj = nn.Linear(dim, dim)
         self._scratch = None
+        # the core under autograd on a GPU: "torch" (F.scaled_dot_product_attention and torch's autograd) or "hip" (_AttentionCoreFn)
+        self.train_core = "torch"
+
+    def core_hip_train(self, q, k, v, table, n_prefix):
+        """``core_hip`` as a differentiable function of q, k, v and the norm parameters (fp32 contiguous CUDA tensors)."""
+        qn, kn = self.q_norm, self.k_norm
+        return _AttentionCoreFn.apply(q, k, v, qn.weight if qn else None, qn.bias if qn else None, kn.weight if qn else None,
+                                      kn.bias if qn else None, table, n_prefix, self.num_heads, qn.eps if qn else 1e-5)
 
     def core_hip(self, q, k, v, table, n_prefix):
         """q, k, v fp32 [B, N, E] -> attention output [B, N, E]: one C-ABI call."""
@@ -228,6 +299,8 @@ class EvaAttention(nn.Module):
         q, k, v = self.q_proj(x), self.k_proj(x), self.v_proj(x)
         if x.is_cuda and not torch.is_grad_enabled():          # the kernel takes fp32 (under the f16 mode the linears hand over halves)
             y = self.core_hip(q.float().contiguous(), k.float().contiguous(), v.float().contiguous(), table, n_prefix)
+        elif x.is_cuda and self.train_core == "hip":
+            y = self.core_hip_train(q.float().contiguous(), k.float().contiguous(), v.float().contiguous(), table, n_prefix)
         else:
             y = self.core_torch(q, k, v, table, n_prefix)
         return self.proj(self.norm(y))
@@ -312,9 +385,25 @@ class PrimusV2(nn.Module):
         dec = [m for m in self.up_projection.decode.modules() if isinstance(m, nn.ConvTranspose3d)]
         self._vit_cfg["dec1"], self._vit_cfg["dec2"] = (dec[0].out_channels, dec[1].out_channels) if len(dec) == 3 else (0, 0)
         self.use_engine = True
+        self._train_attention = "torch"
         self._handle = None
         self._engine_sig = None
         self._engine_ws = None
+
+    @property
+    def train_attention(self):
+        """Who runs the attention core when autograd is on and the input is on a GPU: ``"torch"`` (the default:
+        F.scaled_dot_product_attention) or ``"hip"`` (the library's flash forward + backward, ``_AttentionCoreFn``).  The linears,
+        LayerNorms, tokenizer and decoder are torch autograd either way."""
+        return self._train_attention
+
+    @train_attention.setter
+    def train_attention(self, value):
+        if value not in TRAIN_CORES:
+            raise ValueError(f"train_attention must be one of {TRAIN_CORES}, got {value!r}")
+        self._train_attention = value
+        for blk in self.eva.blocks:
+            blk.attn.train_core = value
 
     # ------------------------------------------------------------------------------------------------------------------
     # HIP engine (one C-ABI call per forward)

@@ -466,6 +466,35 @@ int amx_attention_qknorm_rope(const float* d_q, const float* d_k, const float* d
  * launches after its q | k and v projections; bench.py times it as the ViT's dominant kernel). */
 int amx_attention_prepared(const void* d_scratch, size_t scratch_bytes, int b, int n, int heads, int head_dim, float* d_out, void* stream);
 
+/* ---- The attention core under autograd ---------------------------------------------------------------------------------------
+ * Training the ViT (the reference trains it: pretraining/models/pretraining_networks.py:107-145, options/primus_options.py) needs
+ * the gradient of the sequence above.  These entries replace what torch autograd records and replays for
+ * q_norm / k_norm -> rope -> F.scaled_dot_product_attention: the forward that also saves the log-sum-exp, and one backward call.
+ *
+ * amx_attention_train_scratch_bytes: bytes of d_scratch for amx_attention_backward (0 outside the envelope: head_dim even and <= 80,
+ * b, n, heads >= 1); the forward entry below needs only amx_attention_scratch_bytes of it. */
+size_t amx_attention_train_scratch_bytes(int b, int heads, int n, int head_dim);
+/* amx_attention_qknorm_rope (same arguments, bit-identical d_out) that also stores d_lse: fp32 [b][heads][n], the log-sum-exp of every
+ * score row in the exp2 domain (scores already multiplied by log2(e) / sqrt(head_dim)) -- what autograd's SDPA node saves instead of
+ * the probabilities. */
+int amx_attention_qknorm_rope_train(const float* d_q, const float* d_k, const float* d_v, const float* d_qn_w, const float* d_qn_b,
+                                    const float* d_kn_w, const float* d_kn_b, float norm_eps, const float* d_rope, int n_prefix, int b,
+                                    int n, int heads, int head_dim, float* d_out, float* d_lse, void* d_scratch, size_t scratch_bytes,
+                                    void* stream);
+/* Backward of the call above (replaces the autograd nodes of F.scaled_dot_product_attention, the rotation and the two per-head
+ * nn.LayerNorm): from the saved fp32 d_q / d_k / d_v, d_out, d_lse and the incoming gradient d_dout (fp32, contiguous, the layout of
+ * d_out) it writes d_dq / d_dk / d_dv (the layout of d_q) and the gradients of the norm parameters d_dqn_w / d_dqn_b / d_dkn_w /
+ * d_dkn_b (fp32 [head_dim], written, not accumulated).  Any gradient output may be NULL and is then skipped; the norm-gradient
+ * pointers must be NULL when the norms are absent.  The probabilities are recomputed (f16 MFMA operands, fp32 accumulation,
+ * softmax and dP - D in fp32); d_dout is normalised by one power of two per (batch, head), found on the device, before it is
+ * rounded to f16, so gradients far below f16's range keep their precision and an all-zero d_dout gives zeros.  No atomics:
+ * bit-identical results run to run. */
+int amx_attention_backward(const float* d_q, const float* d_k, const float* d_v, const float* d_qn_w, const float* d_qn_b,
+                           const float* d_kn_w, const float* d_kn_b, float norm_eps, const float* d_rope, int n_prefix, int b, int n,
+                           int heads, int head_dim, const float* d_out, const float* d_lse, const float* d_dout, float* d_dq, float* d_dk,
+                           float* d_dv, float* d_dqn_w, float* d_dqn_b, float* d_dkn_w, float* d_dkn_b, void* d_scratch,
+                           size_t scratch_bytes, void* stream);
+
 /* ---- The whole 3D ViT variant `anatomix-dev-vit` (PrimusV2-S) as one forward ------------------------------------------------
  * Replaces PrimusV2.forward (anatomix/model/vit3d/architectures.py:231-260 with the wrapper's extensions :89-165, tokenizer
  * deep_tokenizer.py:12-68, registry entry load_from_hf.py:25-35): conv tokenizer (stem + three stride-2 residual stages + 1x1x1
