@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "amx_gemm.h"
 #include "amx_launch.h"
 
 static thread_local std::string g_err;
@@ -550,6 +551,41 @@ int amx_attention_backward(const float* d_q, const float* d_k, const float* d_v,
   AMX_HIP(amx::launch_attention_backward(d_q, d_k, d_v, d_qn_w, d_qn_b, d_kn_w, d_kn_b, norm_eps, d_rope, n_prefix, b, n, heads, head_dim,
                                          d_out, d_lse, d_dout, d_dq, d_dk, d_dv, d_dqn_w, d_dqn_b, d_dkn_w, d_dkn_b, d_scratch,
                                          (hipStream_t)stream));
+  return AMX_OK;
+}
+
+size_t amx_linear_train_scratch_bytes(long long m, int k, int n) { return amx::linear_train_scratch_bytes(m, k, n); }
+
+namespace {
+// the envelope and the scratch of the two linear entries: AMX_OK or the refusal, before any launch
+int linear_args_ok(const char* what, long long m, int k, int n, const void* d_scratch, size_t scratch_bytes) {
+  const size_t need = amx::linear_train_scratch_bytes(m, k, n);
+  if (need == 0)
+    return fail(AMX_ERR_INVALID, "%s: (M, K, N) = (%lld, %d, %d) is outside the envelope (K, N multiples of 4 up to 2^20, M * max(K, N) < 2^31)",
+                what, m, k, n);
+  if (!d_scratch || scratch_bytes < need || ((uintptr_t)d_scratch & 15)) return fail(AMX_ERR_WORKSPACE, "%s scratch needs %zu bytes, 16-byte aligned", what, need);
+  return AMX_OK;
+}
+bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return !(((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15);
+}
+}  // namespace
+
+int amx_linear_forward(const float* d_x, const float* d_w, const float* d_bias, long long m, int k, int n, float* d_y, void* d_scratch,
+                       size_t scratch_bytes, void* stream) {
+  if (!d_x || !d_w || !d_y) return fail(AMX_ERR_INVALID, "linear forward: null argument");
+  if (int rc = linear_args_ok("linear forward", m, k, n, d_scratch, scratch_bytes)) return rc;
+  if (!aligned16(d_x, d_y)) return fail(AMX_ERR_INVALID, "linear forward: d_x and d_y must be 16-byte aligned");
+  AMX_HIP(amx::launch_linear_forward(d_x, d_w, d_bias, m, k, n, d_y, d_scratch, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_linear_backward(const float* d_x, const float* d_w, const float* d_dy, long long m, int k, int n, float* d_dx, float* d_dw,
+                        float* d_dbias, void* d_scratch, size_t scratch_bytes, void* stream) {
+  if (!d_x || !d_w || !d_dy) return fail(AMX_ERR_INVALID, "linear backward: null argument");
+  if (int rc = linear_args_ok("linear backward", m, k, n, d_scratch, scratch_bytes)) return rc;
+  if (!aligned16(d_x, d_dy, d_dx, d_dw)) return fail(AMX_ERR_INVALID, "linear backward: d_x, d_dy, d_dx and d_dw must be 16-byte aligned");
+  AMX_HIP(amx::launch_linear_backward(d_x, d_w, d_dy, m, k, n, d_dx, d_dw, d_dbias, d_scratch, (hipStream_t)stream));
   return AMX_OK;
 }
 

@@ -31,8 +31,10 @@ enum GemmEpi {
   EPI_QK = 8,         // q | k projection with head-padded features (5 tiles per head): bias, per-head LayerNorm, rotary embedding,
                       // f16 operands of the attention kernel (Qp rows / K fragment tiles) -- replaces the fp32 q, k tensors + attn_prep
   EPI_VT = 9,         // v projection, token rows as the A operand: V^T fragment tiles (+ the ones row) of the attention kernel
-  EPI_PLANAR_ACC = 10 // EPI_PLANAR's values of ONE window (M = its rows) blended into the sliding-window accumulator instead of stored:
+  EPI_PLANAR_ACC = 10, // EPI_PLANAR's values of ONE window (M = its rows) blended into the sliding-window accumulator instead of stored:
                       // acc[c][oz + Z][oy + Y][ox + X] += wmap[Z][Y][X] * (value + bias[c] - sub[c]), plain load-add-store (one owner per element)
+  EPI_F32_SCALED = 11 // out32[m][n] = acc * *scale: the data gradient of a linear layer (amx_linear_bwd.hip), whose dy rows were divided by
+                      // a power of two found on the device
 };
 
 struct GemmParams {
@@ -66,6 +68,7 @@ struct GemmParams {
   const float* wmap;            // window weights [2 gd][2 gh][2 gw]
   long long acc_sc, acc_sz, acc_sy;   // channel / plane / row strides of the accumulator (vd vh vw, vh vw, vw)
   int acc_vec;                  // 1: every quad of a row is 16-byte aligned in both the accumulator and the map (set by launch_gemm)
+  const float* scale;           // EPI_F32_SCALED: one device float, the factor of every output
 };
 
 hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st, VitLaunchInfo* info = nullptr);
@@ -82,6 +85,14 @@ hipError_t launch_colsum(const void* hi, const void* lo, int ld, int C, int nb, 
 hipError_t launch_demean(const float* colsum, int nchunk, int ld, int K, long long rows_per_b, const float* W, int Creal, const float* bias, int nb,
                          float* mean, hipStream_t st);
 hipError_t launch_export_planar(const float* in, int C, long long vox, int nb, const float* sub, float* out, hipStream_t st);
+
+// ---- linear layers under autograd (amx_linear_bwd.hip) ----------------------------------------------------------------
+// y = x W^T + b and its three gradients for fp32 x [M][K], W [N][K], dy [M][N]; operands rounded once to f16, fp32 sums.
+size_t linear_train_scratch_bytes(long long M, int K, int N);   // 0 outside the envelope (K % 4, N % 4, M * max(K, N) beyond int)
+hipError_t launch_linear_forward(const float* x, const float* w, const float* bias, long long M, int K, int N, float* y, void* scratch,
+                                 hipStream_t st);
+hipError_t launch_linear_backward(const float* x, const float* w, const float* dy, long long M, int K, int N, float* dx, float* dw,
+                                  float* dbias, void* scratch, hipStream_t st);
 
 // ---- tokenizer (amx_tokenizer.hip) ----------------------------------------------------------------------------------
 struct TokConvParams {

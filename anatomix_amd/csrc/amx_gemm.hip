@@ -335,6 +335,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
   // EVERY global load of the epilogue is issued first, unconditionally (clamped indices), into registers: loads placed under the
   // per-tile conditions below were each followed by a full wait -- ten to twenty exposed memory latencies per row group.
   float4 bias4[NT], gam4[NT], extra[NT][MT];
+  float out_scale = 1.f;
+  if (EPI == EPI_F32_SCALED) out_scale = *p.scale;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int nt = nt0 + t < p.ntiles ? nt0 + t : p.ntiles - 1, n = nt * 16 + 4 * g;
@@ -397,6 +399,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
       float r[4] = {v[0] + b4.x, v[1] + b4.y, v[2] + b4.z, v[3] + b4.w};
       if (EPI == EPI_F32) {
         *(float4*)((float*)p.out + (long long)m * p.ldo + n) = make_float4(r[0], r[1], r[2], r[3]);
+      } else if (EPI == EPI_F32_SCALED) {                           // a power of two: exact
+        *(float4*)((float*)p.out + (long long)m * p.ldo + n) = make_float4(r[0] * out_scale, r[1] * out_scale, r[2] * out_scale, r[3] * out_scale);
       } else if (EPI == EPI_F16) {
         *(uint2*)((f16*)p.out + (long long)m * p.ldo + n) =
             make_uint2(to_bits<f16>(r[0]) | ((unsigned)to_bits<f16>(r[1]) << 16), to_bits<f16>(r[2]) | ((unsigned)to_bits<f16>(r[3]) << 16));
@@ -626,8 +630,8 @@ __global__ __launch_bounds__(NW * 64) void wsgemm_kernel(GemmParams p, int rows_
 }
 
 static const char* epi_name(int epi) {
-  static const char* const names[] = {"F32", "F16", "RESID", "SWIGLU", "SCATTER", "TOKENS", "PLANAR", "SCATTER_LN", "QK", "VT", "PLANAR_ACC"};
-  return epi >= 0 && epi < 11 ? names[epi] : "?";
+  static const char* const names[] = {"F32", "F16", "RESID", "SWIGLU", "SCATTER", "TOKENS", "PLANAR", "SCATTER_LN", "QK", "VT", "PLANAR_ACC", "F32_SCALED"};
+  return epi >= 0 && epi < 12 ? names[epi] : "?";
 }
 
 template <int MT, int NT, int KC, int EPI, bool SPLIT, int NW = 4>
@@ -723,6 +727,7 @@ hipError_t launch_gemm(const GemmParams& p, int epi, hipStream_t st, VitLaunchIn
   if (split != (p.w_lo != nullptr)) return hipErrorInvalidValue;
   switch (epi) {
     case EPI_F32: return split ? launch_epi<EPI_F32, true>(p, st, info) : launch_epi<EPI_F32, false>(p, st, info);
+    case EPI_F32_SCALED: return split || !p.scale ? hipErrorInvalidValue : launch_epi<EPI_F32_SCALED, false>(p, st, info);
     case EPI_F16: return split ? hipErrorInvalidValue : launch_epi<EPI_F16, false>(p, st, info);
     case EPI_RESID: return split ? hipErrorInvalidValue : launch_epi<EPI_RESID, false>(p, st, info);
     case EPI_SWIGLU: return split ? hipErrorInvalidValue : launch_epi<EPI_SWIGLU, false>(p, st, info);

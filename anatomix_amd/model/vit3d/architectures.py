@@ -16,10 +16,12 @@ LayerScale residuals, SwiGLU MLP), final norm, transposed-conv decoder, ChannelD
 (``amx_vit_forward``, csrc/amx_vit.hip: own MFMA kernels for the convolutions, the token-matrix products and the attention;
 no vendor GEMM / conv library).  Output norms other than none / demean are applied on the engine's output by their torch module.
 Under autograd or on the CPU the torch modules below compute the same network; ``PrimusV2.use_engine = False`` forces that
-composition on the GPU too (its attention core then still runs through ``amx_attention_qknorm_rope``).  Of training, the attention
-core alone is on the accelerated path: ``PrimusV2.train_attention = "hip"`` runs it forward and backward on the library's kernels
-(``_AttentionCoreFn``: amx_attention_qknorm_rope_train / amx_attention_backward); the default ``"torch"`` keeps
-F.scaled_dot_product_attention, and everything around the core is torch autograd either way.
+composition on the GPU too (its attention core then still runs through ``amx_attention_qknorm_rope``).  Of training, two parts
+are on the accelerated path, each behind its own switch with the default ``"torch"``: ``PrimusV2.train_attention = "hip"`` runs
+the attention core forward and backward on the library's kernels (``_AttentionCoreFn``: amx_attention_qknorm_rope_train /
+amx_attention_backward) instead of F.scaled_dot_product_attention, and ``PrimusV2.train_linear = "hip"`` runs the blocks' seven
+nn.Linear the same way (``_LinearFn``: amx_linear_forward / amx_linear_backward, f16 operands and fp32 sums).  The LayerNorms,
+LayerScale, the SwiGLU product, the tokenizer and the decoder are torch autograd either way.
 """
 from __future__ import annotations
 
@@ -244,6 +246,61 @@ class _AttentionCoreFn(torch.autograd.Function):
         return (dq, dk, dv, *dnorm, None, None, None, None)
 
 
+class _LinearFn(torch.autograd.Function):
+    """``F.linear(x, weight, bias)`` under autograd on the library's own kernels (csrc/amx_linear_bwd.hip): ``amx_linear_forward``
+    forward, ``amx_linear_backward`` backward (dx, dW and db in one call; gradients nobody needs are passed as null).  Every
+    operand is rounded once to f16, every sum is fp32.  Saved: the fp32 ``x`` and ``weight`` -- no f16 copy is kept."""
+
+    @staticmethod
+    def _scratch(lib, M, K, N, dev):
+        nb = lib.amx_linear_train_scratch_bytes(M, K, N)
+        if nb == 0:
+            raise _lib.AmxError(f"linear: (M, K, N) = ({M}, {K}, {N}) is outside the envelope of amx_linear_forward "
+                                "(K and N multiples of 4, M * max(K, N) < 2^31)")
+        return _train_scratch(nb, dev), nb
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        lib = _lib.load()
+        N, K = weight.shape
+        dev = x.device
+        xc, w, b = _lib.f32c(x), _lib.f32c(weight), None if bias is None else _lib.f32c(bias)
+        M = xc.numel() // K
+        y = torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            scratch, nb = _LinearFn._scratch(lib, M, K, N, dev)
+            _lib.check(lib.amx_linear_forward(_lib.ptr(xc), _lib.ptr(w), _lib.ptr(b), M, K, N, _lib.ptr(y), _lib.ptr(scratch), nb,
+                                              _lib.stream(dev)))
+        ctx.save_for_backward(xc, w)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        lib = _lib.load()
+        N, K = w.shape
+        M, dev = x.numel() // K, x.device
+        dy = _lib.f32c(dy)
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x) if need[0] else None
+        dw = torch.empty_like(w) if need[1] else None
+        db = torch.empty(N, dtype=torch.float32, device=dev) if ctx.has_bias and need[2] else None
+        with torch.cuda.device(dev):
+            scratch, nb = _LinearFn._scratch(lib, M, K, N, dev)
+            _lib.check(lib.amx_linear_backward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(dy), M, K, N, _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
+                                               _lib.ptr(scratch), nb, _lib.stream(dev)))
+        return dx, dw, db
+
+
+def _linear(layer, x, route):
+    """``layer(x)`` for an nn.Linear: through ``_LinearFn`` when the route is "hip", the input is on a GPU and autograd is on."""
+    if route == "hip" and x.is_cuda and torch.is_grad_enabled():
+        return _LinearFn.apply(x, layer.weight, layer.bias)
+    return layer(x)
+
+
 class EvaAttention(nn.Module):
     def __init__(self, dim, num_heads, qk_norm, scale_attn_inner):
         super().__init__()
@@ -256,6 +313,8 @@ class EvaAttention(nn.Module):
         self._scratch = None
         # the core under autograd on a GPU: "torch" (F.scaled_dot_product_attention and torch's autograd) or "hip" (_AttentionCoreFn)
         self.train_core = "torch"
+        # the four linears under autograd on a GPU: "torch" (nn.Linear) or "hip" (_LinearFn)
+        self.train_linear = "torch"
 
     def core_hip_train(self, q, k, v, table, n_prefix):
         """``core_hip`` as a differentiable function of q, k, v and the norm parameters (fp32 contiguous CUDA tensors)."""
@@ -296,14 +355,15 @@ class EvaAttention(nn.Module):
         return F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, N, E)
 
     def forward(self, x, table, n_prefix):
-        q, k, v = self.q_proj(x), self.k_proj(x), self.v_proj(x)
+        lin = self.train_linear
+        q, k, v = _linear(self.q_proj, x, lin), _linear(self.k_proj, x, lin), _linear(self.v_proj, x, lin)
         if x.is_cuda and not torch.is_grad_enabled():          # the kernel takes fp32 (under the f16 mode the linears hand over halves)
             y = self.core_hip(q.float().contiguous(), k.float().contiguous(), v.float().contiguous(), table, n_prefix)
         elif x.is_cuda and self.train_core == "hip":
             y = self.core_hip_train(q.float().contiguous(), k.float().contiguous(), v.float().contiguous(), table, n_prefix)
         else:
             y = self.core_torch(q, k, v, table, n_prefix)
-        return self.proj(self.norm(y))
+        return _linear(self.proj, self.norm(y), lin)
 
 
 class SwiGLU(nn.Module):
@@ -312,9 +372,11 @@ class SwiGLU(nn.Module):
         self.fc1_g, self.fc1_x = nn.Linear(dim, hidden), nn.Linear(dim, hidden)
         self.norm = nn.LayerNorm(hidden, eps=1e-6)
         self.fc2 = nn.Linear(hidden, dim)
+        self.train_linear = "torch"          # as EvaAttention.train_linear
 
     def forward(self, x):
-        return self.fc2(self.norm(F.silu(self.fc1_g(x)) * self.fc1_x(x)))
+        lin = self.train_linear
+        return _linear(self.fc2, self.norm(F.silu(_linear(self.fc1_g, x, lin)) * _linear(self.fc1_x, x, lin)), lin)
 
 
 class EvaBlock(nn.Module):
@@ -386,6 +448,7 @@ class PrimusV2(nn.Module):
         self._vit_cfg["dec1"], self._vit_cfg["dec2"] = (dec[0].out_channels, dec[1].out_channels) if len(dec) == 3 else (0, 0)
         self.use_engine = True
         self._train_attention = "torch"
+        self._train_linear = "torch"
         self._handle = None
         self._engine_sig = None
         self._engine_ws = None
@@ -393,8 +456,8 @@ class PrimusV2(nn.Module):
     @property
     def train_attention(self):
         """Who runs the attention core when autograd is on and the input is on a GPU: ``"torch"`` (the default:
-        F.scaled_dot_product_attention) or ``"hip"`` (the library's flash forward + backward, ``_AttentionCoreFn``).  The linears,
-        LayerNorms, tokenizer and decoder are torch autograd either way."""
+        F.scaled_dot_product_attention) or ``"hip"`` (the library's flash forward + backward, ``_AttentionCoreFn``).  The
+        LayerNorms, tokenizer and decoder are torch autograd either way; the linears have their own switch, ``train_linear``."""
         return self._train_attention
 
     @train_attention.setter
@@ -404,6 +467,21 @@ class PrimusV2(nn.Module):
         self._train_attention = value
         for blk in self.eva.blocks:
             blk.attn.train_core = value
+
+    @property
+    def train_linear(self):
+        """Who runs the seven nn.Linear of every EVA block when autograd is on and the input is on a GPU: ``"torch"`` (the default:
+        fp32 vendor GEMMs under torch autograd) or ``"hip"`` (``_LinearFn``: f16 operands, fp32 sums, forward and both gradients on
+        the library's kernels).  CPU tensors and ``torch.no_grad()`` keep their paths either way."""
+        return self._train_linear
+
+    @train_linear.setter
+    def train_linear(self, value):
+        if value not in TRAIN_CORES:
+            raise ValueError(f"train_linear must be one of {TRAIN_CORES}, got {value!r}")
+        self._train_linear = value
+        for blk in self.eva.blocks:
+            blk.attn.train_linear = blk.mlp.train_linear = value
 
     # ------------------------------------------------------------------------------------------------------------------
     # HIP engine (one C-ABI call per forward)

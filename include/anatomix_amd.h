@@ -495,6 +495,24 @@ int amx_attention_backward(const float* d_q, const float* d_k, const float* d_v,
                            float* d_dv, float* d_dqn_w, float* d_dqn_b, float* d_dkn_w, float* d_dkn_b, void* d_scratch,
                            size_t scratch_bytes, void* stream);
 
+/* ---- The blocks' linear layers under autograd ---------------------------------------------------------------------------------
+ * y = x W^T + b for fp32 d_x [m][k], d_w [n][k], d_bias [n] or NULL, and its gradients: what torch autograd runs as fp32 vendor
+ * GEMMs for the seven nn.Linear of an EVA block.  Every operand is rounded ONCE to f16 (x, W, and dy divided by one power of two per
+ * call, 2^e <= max |dy| / 8 < 2^(e+1), found on the device; f16 subnormals are kept) and every sum is fp32
+ * (v_mfma_f32_16x16x32_f16).  Nothing is cached across calls: the weights are packed per call into d_scratch, the backward
+ * re-converts the saved fp32 d_x.  No allocation, no synchronisation (capture-safe); no atomics: bit-identical results run to run.
+ *
+ * amx_linear_train_scratch_bytes: bytes of d_scratch for either entry (0 outside the envelope: k % 4 == 0, n % 4 == 0, both at most
+ * 2^20, m >= 1, m * max(k, n) within int range).  d_x, d_y, d_dy, d_dx, d_dw and d_scratch are 16-byte aligned. */
+size_t amx_linear_train_scratch_bytes(long long m, int k, int n);
+int amx_linear_forward(const float* d_x, const float* d_w, const float* d_bias, long long m, int k, int n, float* d_y, void* d_scratch,
+                       size_t scratch_bytes, void* stream);
+/* d_dx [m][k] = dy W, d_dw [n][k] = dy^T x, d_dbias [n] = the fp32 column sums of the UNROUNDED d_dy [m][n] (contiguous); each
+ * output is written, not accumulated, and may be NULL: it is then skipped and the others are unchanged bit for bit.  An all-zero
+ * d_dy gives exact zeros. */
+int amx_linear_backward(const float* d_x, const float* d_w, const float* d_dy, long long m, int k, int n, float* d_dx, float* d_dw,
+                        float* d_dbias, void* d_scratch, size_t scratch_bytes, void* stream);
+
 /* ---- The whole 3D ViT variant `anatomix-dev-vit` (PrimusV2-S) as one forward ------------------------------------------------
  * Replaces PrimusV2.forward (anatomix/model/vit3d/architectures.py:231-260 with the wrapper's extensions :89-165, tokenizer
  * deep_tokenizer.py:12-68, registry entry load_from_hf.py:25-35): conv tokenizer (stem + three stride-2 residual stages + 1x1x1
