@@ -151,7 +151,6 @@ SYMBOLS = {
     "amx_vit_load": (_I, [_P, C.POINTER(_P), _I, _P, _P]),
     "amx_vit_workspace_bytes": (C.c_size_t, [_P, _I]),
     "amx_vit_forward": (_I, [_P, _P, _P, _I, _P, C.c_size_t, _I, _P]),
-    "amx_vit_debug_read": (_I, [_P, C.c_char_p, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "amx_vit_tap_bytes": (C.c_size_t, [_P, _I, C.c_char_p]),
     "amx_vit_forward_taps": (_I, [_P, _P, _P, _I, _P, C.c_size_t, _I, C.POINTER(VitTap), _I, _P]),
     "amx_vit_windows_workspace_bytes": (C.c_size_t, [_P, _I]),

@@ -571,6 +571,34 @@ bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, 
 }
 }  // namespace
 
+int amx_linear(const float* d_x, const float* d_w, const float* d_b, int m, int k, int n, int split, float* d_y, void* stream) {
+  if (!d_x || !d_w || !d_y) return fail(AMX_ERR_INVALID, "null argument");
+  if (m < 1 || k < 1 || n < 4 || (n % 4) || k > 64 * 17) return fail(AMX_ERR_INVALID, "linear: m >= 1, 1 <= k <= 1088, n a multiple of 4 (got %d %d %d)", m, k, n);
+  hipStream_t st = (hipStream_t)stream;
+  auto up = [](int v, int mult) { return (v + mult - 1) / mult * mult; };
+  const int kp = up(k, 32), ntiles = up(n, 16) / 16, KS = kp / 32;
+  const size_t abytes = (size_t)m * kp * 2, wbytes = (size_t)ntiles * KS * 1024, bbytes = (size_t)ntiles * 16 * 4;
+  char* buf = nullptr;
+  AMX_HIP(hipMalloc((void**)&buf, 2 * abytes + 2 * wbytes + bbytes + 1024));
+  char *a_hi = buf, *a_lo = buf + abytes, *w_hi = buf + 2 * abytes, *w_lo = w_hi + wbytes;
+  float* bias = (float*)(w_lo + wbytes);
+  int rc = AMX_OK;
+  hipError_t e = amx::launch_ln_rows(d_x, 0, k, k, nullptr, nullptr, 0.f, m, m, m, 0, 0, a_hi, split ? a_lo : nullptr, kp, st);
+  if (e == hipSuccess) e = amx::launch_pack_gemm(d_w, nullptr, nullptr, n, 0, 0, k, 0, 0, 0, ntiles, KS, w_hi, split ? w_lo : nullptr, st);
+  if (e == hipSuccess) e = amx::launch_vec_place(bias, d_b, n, 0.f, st);
+  if (e == hipSuccess && ntiles * 16 > n) e = amx::launch_vec_place(bias + n, nullptr, ntiles * 16 - n, 0.f, st);
+  if (e == hipSuccess) {
+    amx::GemmParams g{};
+    g.a_hi = a_hi; g.a_lo = split ? a_lo : nullptr; g.lda = kp; g.M = m; g.KS = KS; g.w_hi = w_hi; g.w_lo = split ? w_lo : nullptr;
+    g.ntiles = ntiles; g.Nreal = n; g.bias = bias; g.out = d_y; g.ldo = n;
+    e = amx::launch_gemm(g, amx::EPI_F32, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) rc = fail(AMX_ERR_HIP, "linear: %s", hipGetErrorString(e));
+  (void)hipFree(buf);
+  return rc;
+}
+
 int amx_linear_forward(const float* d_x, const float* d_w, const float* d_bias, long long m, int k, int n, float* d_y, void* d_scratch,
                        size_t scratch_bytes, void* stream) {
   if (!d_x || !d_w || !d_y) return fail(AMX_ERR_INVALID, "linear forward: null argument");

@@ -10,8 +10,6 @@
 //   decoder        hi + lo operands (cfg.decoder_split), fp32 raw outputs, LayerNorm + GELU in fp32.
 #include <math.h>
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <string>
@@ -78,9 +76,6 @@ struct amx_vit {
   std::vector<Block> blk;
   float *fnw, *fnb;
   DecStage dec[3];
-  // workspace bookkeeping of the last forward (debug reads)
-  struct Named { std::string name; char* ptr; size_t bytes; };
-  std::vector<Named> dbg;
   amx::SwMapCache sw_map;      // amx_vit_sliding_window: the window weights of the handle's roi
 };
 
@@ -419,69 +414,74 @@ bool dec_fused(const DecStage& d) { return d.cp == 128 && up(d.cout, 32) <= 128;
 
 // ---- taps (amx_vit_forward_taps): where every named intermediate of a forward at batch n lives while it is valid.  A tap is one byte
 // range, or two that are handed out back to back ([hi plane | lo plane], [scale | shift]); nb == 0: one range.  (The size query builds
-// the table on a plan without a base: only the sizes mean anything there.)
+// the table on a plan without a base: only the sizes mean anything there.)  The forward states a tap as (kind, index); its name is
+// written here alone, %d = the tokenizer stage, block or decoder stage.
+enum TapKind {
+  T_H0, T_P0, T_RAW1, T_SS1, T_A1, T_RAW2, T_SS2, T_RAWS, T_SSS, T_H, T_P, T_TOKENS,
+  T_LN1, T_ATTN, T_LN_ATTN, T_TOK1, T_LN2, T_HD, T_LN_MLP, T_TOK2,
+  T_DLN, T_DRAW, T_DIN, T_DMEAN, T_Y
+};
+const char* const kTapName[] = {"h0", "p0", "s%d.raw1", "s%d.ss1", "s%d.a1", "s%d.raw2", "s%d.ss2", "s%d.raws", "s%d.sss", "s%d.h", "s%d.p", "tokens",
+                                "b%d.ln1", "b%d.attn", "b%d.ln_attn", "b%d.tok1", "b%d.ln2", "b%d.hd", "b%d.ln_mlp", "b%d.tok2",
+                                "d.ln", "d%d.raw", "d%d.in", "d.mean", "y"};
 struct TapSrc {
+  int kind, idx;
   std::string name;
-  const void* a;
-  size_t na;
-  const void* b;
-  size_t nb;
+  const void *a, *b;      // the range(s)
+  size_t na, nb;
   size_t bytes() const { return na + nb; }
 };
-struct TapSet {
-  std::vector<TapSrc> table;
-  amx_vit_tap* req;
-  int nreq;
-};
+struct TapReq { amx_vit_tap* req; TapSrc src; };      // a request and the table entry it names, resolved before the first launch
+typedef std::vector<TapReq> TapSet;
 
 std::vector<TapSrc> tap_table(const amx_vit* h, int n, const Plan& P, int nb, const float* d_y) {
   std::vector<TapSrc> t;
   const amx_vit_cfg& c = h->cfg;
   const int E = h->E, Ep = h->Ep, T = h->T, V = h->V, hid = h->hidden;
   const size_t M = (size_t)n * T;
-  auto one = [&](const std::string& name, const void* a, size_t na) { t.push_back({name, a, na, nullptr, 0}); };
-  auto two = [&](const std::string& name, const void* a, const void* b, size_t each, bool pair = true) {
-    t.push_back({name, a, each, pair ? b : nullptr, pair ? each : 0});
+  auto two = [&](int kind, int idx, const void* a, const void* b, size_t each, bool pair = true) {
+    char name[32];
+    snprintf(name, sizeof name, kTapName[kind], idx);
+    t.push_back({kind, idx, name, a, pair ? b : nullptr, each, pair ? each : 0});
   };
+  auto one = [&](int kind, int idx, const void* a, size_t na) { two(kind, idx, a, nullptr, na, false); };
   size_t vox = (size_t)V * 512;
-  two("h0", P.h_hi[0], P.h_lo[0], n * vox * 32 * 2, c.stem_split != 0);
-  two("p0", P.p_hi[0], P.p_lo[0], n * (vox / 8) * 32 * 2);
+  two(T_H0, 0, P.h_hi[0], P.h_lo[0], n * vox * 32 * 2, c.stem_split != 0);
+  two(T_P0, 0, P.p_hi[0], P.p_lo[0], n * (vox / 8) * 32 * 2);
   for (int k = 0; k < 3; ++k) {
-    const std::string s = "s" + std::to_string(k);
     const size_t C = kStageC[k + 1], vo = vox / 8;
-    one(s + ".raw1", P.raw1, n * vo * C * 4);
-    two(s + ".ss1", P.sc[0], P.sh[0], n * C * 4);
-    two(s + ".a1", P.a1_hi, P.a1_lo, n * vo * C * 2);
-    one(s + ".raw2", P.raw2, n * vo * C * 4);
-    two(s + ".ss2", P.sc[1], P.sh[1], n * C * 4);
-    one(s + ".raws", P.raws, n * vo * C * 4);
-    two(s + ".sss", P.sc[2], P.sh[2], n * C * 4);
-    two(s + ".h", P.h_hi[k + 1], P.h_lo[k + 1], n * vo * C * 2);
-    if (k < 2) two(s + ".p", P.p_hi[k + 1], P.p_lo[k + 1], n * (vo / 8) * C * 2);
+    one(T_RAW1, k, P.raw1, n * vo * C * 4);
+    two(T_SS1, k, P.sc[0], P.sh[0], n * C * 4);
+    two(T_A1, k, P.a1_hi, P.a1_lo, n * vo * C * 2);
+    one(T_RAW2, k, P.raw2, n * vo * C * 4);
+    two(T_SS2, k, P.sc[1], P.sh[1], n * C * 4);
+    one(T_RAWS, k, P.raws, n * vo * C * 4);
+    two(T_SSS, k, P.sc[2], P.sh[2], n * C * 4);
+    two(T_H, k, P.h_hi[k + 1], P.h_lo[k + 1], n * vo * C * 2);
+    if (k < 2) two(T_P, k, P.p_hi[k + 1], P.p_lo[k + 1], n * (vo / 8) * C * 2);
     vox = vo;
   }
-  one("tokens", P.tok, M * E * 4);
+  one(T_TOKENS, 0, P.tok, M * E * 4);
   for (int b = 0; b < nb; ++b) {
-    const std::string s = "b" + std::to_string(b);
-    one(s + ".ln1", P.A1, M * Ep * 2);
-    one(s + ".attn", P.AO, M * E * 4);
-    one(s + ".ln_attn", P.A1, M * Ep * 2);
-    one(s + ".tok1", P.tok, M * E * 4);
-    one(s + ".ln2", P.A1, M * Ep * 2);
-    one(s + ".hd", P.Hd, M * up(hid, 16) * 2);
-    one(s + ".ln_mlp", P.A2, M * up(hid, 32) * 2);
-    one(s + ".tok2", P.tok, M * E * 4);
+    one(T_LN1, b, P.A1, M * Ep * 2);
+    one(T_ATTN, b, P.AO, M * E * 4);
+    one(T_LN_ATTN, b, P.A1, M * Ep * 2);
+    one(T_TOK1, b, P.tok, M * E * 4);
+    one(T_LN2, b, P.A1, M * Ep * 2);
+    one(T_HD, b, P.Hd, M * up(hid, 16) * 2);
+    one(T_LN_MLP, b, P.A2, M * up(hid, 32) * 2);
+    one(T_TOK2, b, P.tok, M * E * 4);
   }
   size_t rows = (size_t)n * V;
-  two("d.ln", P.Ad_hi[0], P.Ad_lo[0], rows * Ep * 2, c.decoder_split != 0);
+  two(T_DLN, 0, P.Ad_hi[0], P.Ad_lo[0], rows * Ep * 2, c.decoder_split != 0);
   for (int k = 0; k < 2; ++k) {
     const DecStage& d = h->dec[k];
     rows *= 8;
-    if (!dec_fused(d)) one("d" + std::to_string(k) + ".raw", P.rawd[k], rows * d.cout * 4);
-    two("d" + std::to_string(k + 1) + ".in", P.Ad_hi[k + 1], P.Ad_lo[k + 1], rows * up(d.cout, 32) * 2, c.decoder_split != 0);
+    if (!dec_fused(d)) one(T_DRAW, k, P.rawd[k], rows * d.cout * 4);
+    two(T_DIN, k + 1, P.Ad_hi[k + 1], P.Ad_lo[k + 1], rows * up(d.cout, 32) * 2, c.decoder_split != 0);
   }
-  if (c.out_norm == 1) one("d.mean", P.mean, (size_t)n * c.num_classes * 4);
-  one("y", d_y, rows * 8 * c.num_classes * 4);
+  if (c.out_norm == 1) one(T_DMEAN, 0, P.mean, (size_t)n * c.num_classes * 4);
+  one(T_Y, 0, d_y, rows * 8 * c.num_classes * 4);
   return t;
 }
 
@@ -491,189 +491,233 @@ const TapSrc* tap_find(const std::vector<TapSrc>& t, const char* name) {
   return nullptr;
 }
 
-// The forward of n roi-sized samples d_x; every argument has been checked by the entry.  `ts` (amx_vit_forward_taps): after the launch that
-// produces a named buffer, the requested copies of it are enqueued on the same stream and the launch's instance name is written into the
-// request -- no launch is added, moved or routed differently.
-int vit_run(amx_vit* h, const float* d_x, const VitOut& out, int n, const Plan& P, int n_blocks, hipStream_t st, TapSet* ts = nullptr) {
-  float* const d_y = out.y;
-  const amx_vit_cfg& c = h->cfg;
-  const int E = h->E, Ep = h->Ep, T = h->T, V = h->V, hid = h->hidden, nreg = c.num_register_tokens;
-  const int M = n * T;
-  const int D0 = c.grid_d * 8, H0 = c.grid_h * 8, W0 = c.grid_w * 8;
-  h->dbg.clear();
-  auto note = [&](const char* name, const void* p, size_t bytes) { h->dbg.push_back({name, (char*)p, bytes}); };
+// The launch schedule of one forward of n roi-sized samples, one method per step; every argument has been checked by the entry.  `ts`
+// (amx_vit_forward_taps): after the launch that produces a named buffer, the requested copies of it are enqueued on the same stream and the
+// launch's instance name is written into the request -- no launch is added, moved or routed differently.  Null: no name is formatted at all.
+struct VitForward {
+  const amx_vit* const h;
+  const amx_vit_cfg& c;
+  const Plan& P;
+  const VitOut& out;
+  const TapSet* const ts;
+  const hipStream_t st;
+  const int n, E, Ep, T, V, hid, M, nreg;       // M: token rows of the batch
+  void *Qp, *Kp, *Vt;                           // the attention kernel's f16 operands inside P.att, and their padded extents
+  int att_npad, att_nblk;
   amx::VitLaunchInfo li0{}, li1{};
-  amx::VitLaunchInfo *const i0 = ts ? &li0 : nullptr, *const i1 = ts ? &li1 : nullptr;
-  auto tap = [&](const std::string& name, const std::string& route) -> hipError_t {
+  amx::VitLaunchInfo *const i0, *const i1;      // what a launcher reports into: null without taps
+
+  VitForward(const amx_vit* h_, const Plan& P_, int n_, hipStream_t st_, const VitOut& out_, const TapSet* ts_)
+      : h(h_), c(h_->cfg), P(P_), out(out_), ts(ts_), st(st_), n(n_), E(h_->E), Ep(h_->Ep), T(h_->T), V(h_->V), hid(h_->hidden), M(n_ * h_->T),
+        nreg(h_->cfg.num_register_tokens), i0(ts_ ? &li0 : nullptr), i1(ts_ ? &li1 : nullptr) {
+    amx::attention_operands(P.att, n, c.heads, T, &Qp, &Kp, &Vt, &att_npad, &att_nblk);
+  }
+
+  int run(const float* d_x, int n_blocks) {      // n_blocks: 0 .. depth
+    int e = stem(d_x);
+    for (int k = 0; k < 3 && !e; ++k) e = stage(k);
+    if (!e) e = embed();
+    if (!e && n_blocks > 0) e = clear_attention_operands();
+    for (int b = 0; b < n_blocks && !e; ++b) e = block(b);
+    if (!e) e = final_norm();
+    for (int k = 0; k < 3 && !e; ++k) e = decoder_stage(k);
+    return e;
+  }
+  // the buffer of tap (kind, idx) has just been produced by `route`
+  hipError_t tap(int kind, int idx, const char* route) const {
     if (!ts) return hipSuccess;
-    for (int i = 0; i < ts->nreq; ++i) {
-      amx_vit_tap& r = ts->req[i];
-      if (name != r.name) continue;
-      snprintf(r.route, sizeof r.route, "%s", route.c_str());
-      if (!r.d_dst) continue;
-      const TapSrc* s = tap_find(ts->table, r.name);
-      if (!s) return hipErrorInvalidValue;
-      hipError_t e = hipMemcpyAsync(r.d_dst, s->a, s->na, hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess && s->nb) e = hipMemcpyAsync((char*)r.d_dst + s->na, s->b, s->nb, hipMemcpyDeviceToDevice, st);
+    for (const TapReq& q : *ts) {
+      const TapSrc& s = q.src;
+      if (s.kind != kind || s.idx != idx) continue;
+      snprintf(q.req->route, sizeof q.req->route, "%s", route);
+      if (!q.req->d_dst) continue;
+      hipError_t e = hipMemcpyAsync(q.req->d_dst, s.a, s.na, hipMemcpyDeviceToDevice, st);
+      if (e == hipSuccess && s.nb) e = hipMemcpyAsync((char*)q.req->d_dst + s.na, s.b, s.nb, hipMemcpyDeviceToDevice, st);
       if (e != hipSuccess) return e;
     }
     return hipSuccess;
-  };
-
-  // ------------------------------------------------------------------ tokenizer
-  {
-    amx::TokStemParams sp{};
+  }
+  // a launch, then the tap of what it produced (route null: the instance the launcher reported)
+  hipError_t tapped(hipError_t launched, int kind, int idx, const char* route = nullptr) const {
+    return launched != hipSuccess ? launched : tap(kind, idx, route ? route : li0.name);
+  }
+  // ---- parameter builders.  A product's operand and packed-weight fields: M rows of A (hi [+ lo], lda halves each) times W; the epilogue's are the caller's
+  static amx::GemmParams product(const char* a_hi, const char* a_lo, int lda, int M, const Packed& w) {
+    amx::GemmParams g{};
+    g.a_hi = a_hi; g.a_lo = a_lo; g.lda = lda; g.M = M;
+    g.w_hi = w.hi; g.w_lo = w.lo; g.ntiles = w.ntiles; g.KS = w.KS;
+    return g;
+  }
+  // a conv of the tokenizer: input planes [n][D][H][W][Cin] -> raw [n][D / stride]...[Cout] (+ bias), partial statistics into P.stats
+  amx::TokConvParams conv(const char* x_hi, const char* x_lo, int D, int H, int W, int Cin, int stride, int Cout, const Packed& w, const float* bias,
+                          float* raw) const {
+    amx::TokConvParams cp{};
+    cp.x_hi = x_hi; cp.x_lo = x_lo; cp.N = n; cp.D = D; cp.H = H; cp.W = W; cp.Cin = Cin;
+    cp.Do = D / stride; cp.Ho = H / stride; cp.Wo = W / stride; cp.Cout = Cout;
+    cp.w_hi = w.hi; cp.w_lo = w.lo; cp.bias = bias; cp.raw = raw; cp.stats = P.stats;
+    return cp;
+  }
+  struct LnIn { const void* p; int f16, ld, C; };      // the rows to normalise: fp32 or f16, ld elements apart, C columns
+  struct LnOut { char *hi, *lo; int ld; };             // f16 operand rows, ld halves each (lo null: no remainder plane)
+  // LayerNorm (w null: a plain conversion) [+ GELU] of `rows` whole rows
+  hipError_t ln_whole_rows(LnIn in, const float* w, const float* b, float eps, int rows, int gelu, LnOut o) {
+    return amx::launch_ln_rows(in.p, in.f16, in.ld, in.C, w, b, eps, rows, rows, rows, 0, gelu, o.hi, o.lo, o.ld, st, i0);
+  }
+  // ---- tokenizer
+  int stem(const float* d_x) {
+    const int D0 = c.grid_d * 8, H0 = c.grid_h * 8, W0 = c.grid_w * 8;
+    amx::TokStemParams sp{};         // pass 0: statistics; pass 1: normalised output and its average
     sp.x = d_x; sp.N = n; sp.D = D0; sp.H = H0; sp.W = W0;
     sp.w_hi = h->stem_w.hi; sp.w_lo = h->stem_w.lo; sp.bias = h->stem_b; sp.stats = P.stats;
     sp.scale = P.sc[0]; sp.shift = P.sh[0]; sp.slope = 0.01f;
     sp.h_hi = P.h_hi[0]; sp.h_lo = c.stem_split ? P.h_lo[0] : nullptr; sp.p_hi = P.p_hi[0]; sp.p_lo = P.p_lo[0];
     AMX_HIP(amx::launch_tokstem(sp, 0, st));
     AMX_HIP(amx::launch_tok_finalize(P.stats, n, amx::tokstem_slots(D0, H0, W0), 32, (long long)D0 * H0 * W0, h->stem_nw, h->stem_nb, c.in_eps, P.sc[0], P.sh[0], st));
-    AMX_HIP(amx::launch_tokstem(sp, 1, st, i0));
-    note("h0_hi", P.h_hi[0], (size_t)n * D0 * H0 * W0 * 32 * 2);
-    note("p0_hi", P.p_hi[0], (size_t)n * D0 * H0 * W0 * 4 * 2);
-    AMX_HIP(tap("h0", li0.name));
-    AMX_HIP(tap("p0", li0.name));
+    AMX_HIP(tapped(amx::launch_tokstem(sp, 1, st, i0), T_H0, 0));
+    AMX_HIP(tap(T_P0, 0, li0.name));
+    return AMX_OK;
   }
-  int Dk = D0, Hk = H0, Wk = W0;
-  for (int k = 0; k < 3; ++k) {
+  // InstanceNorm statistics of the conv that `cp` just ran -> (scale, shift) set `set`
+  hipError_t finalize(const amx::TokConvParams& cp, const float* gamma, const float* beta, int set) {
+    return amx::launch_tok_finalize(P.stats, n, amx::tokconv_slots(cp), cp.Cout, (long long)cp.Do * cp.Ho * cp.Wo, gamma, beta, c.in_eps, P.sc[set], P.sh[set], st);
+  }
+  // stage k: lrelu(IN(conv2(lrelu(IN(conv1(x))))) + IN(skip(avgpool(x)))) at half the input's extent, and its average for the next stage
+  int stage(int k) {
     const Stage& s = h->st[k];
-    const int Do = Dk / 2, Ho = Hk / 2, Wo = Wk / 2;
-    const long long vo = (long long)Do * Ho * Wo;
-    amx::TokConvParams cp{};
-    cp.N = n; cp.Do = Do; cp.Ho = Ho; cp.Wo = Wo; cp.Cout = s.cout; cp.stats = P.stats;
+    const int Dk = c.grid_d * 8 >> k, Hk = c.grid_h * 8 >> k, Wk = c.grid_w * 8 >> k, Do = Dk / 2, Ho = Hk / 2, Wo = Wk / 2;
     // conv1: stride 2 from the stage input
-    cp.x_hi = P.h_hi[k]; cp.x_lo = (k == 0 && !c.stem_split) ? nullptr : P.h_lo[k]; cp.D = Dk; cp.H = Hk; cp.W = Wk; cp.Cin = s.cin;
-    cp.w_hi = s.c1.hi; cp.w_lo = s.c1.lo; cp.bias = s.c1b; cp.raw = P.raw1;
-    const std::string sk = "s" + std::to_string(k);
-    AMX_HIP(amx::launch_tokconv(cp, 27, 2, st, i0));
-    AMX_HIP(tap(sk + ".raw1", li0.name));
-    AMX_HIP(amx::launch_tok_finalize(P.stats, n, amx::tokconv_slots(cp), s.cout, vo, s.n1w, s.n1b, c.in_eps, P.sc[0], P.sh[0], st));
-    AMX_HIP(tap(sk + ".ss1", "tok_finalize"));
-    AMX_HIP(amx::launch_tok_apply(P.raw1, n, vo, s.cout, P.sc[0], P.sh[0], 0.01f, P.a1_hi, P.a1_lo, st));
-    AMX_HIP(tap(sk + ".a1", "tok_apply"));
-    // conv2
-    cp.x_hi = P.a1_hi; cp.x_lo = P.a1_lo; cp.D = Do; cp.H = Ho; cp.W = Wo; cp.Cin = s.cout;
-    cp.w_hi = s.c2.hi; cp.w_lo = s.c2.lo; cp.bias = s.c2b; cp.raw = P.raw2;
-    AMX_HIP(amx::launch_tokconv(cp, 27, 1, st, i0));
-    AMX_HIP(tap(sk + ".raw2", li0.name));
-    AMX_HIP(amx::launch_tok_finalize(P.stats, n, amx::tokconv_slots(cp), s.cout, vo, s.n2w, s.n2b, c.in_eps, P.sc[1], P.sh[1], st));
-    AMX_HIP(tap(sk + ".ss2", "tok_finalize"));
+    const amx::TokConvParams c1 = conv(P.h_hi[k], (k == 0 && !c.stem_split) ? nullptr : P.h_lo[k], Dk, Hk, Wk, s.cin, 2, s.cout, s.c1, s.c1b, P.raw1);
+    AMX_HIP(tapped(amx::launch_tokconv(c1, 27, 2, st, i0), T_RAW1, k));
+    AMX_HIP(tapped(finalize(c1, s.n1w, s.n1b, 0), T_SS1, k, "tok_finalize"));
+    AMX_HIP(tapped(amx::launch_tok_apply(P.raw1, n, (long long)Do * Ho * Wo, s.cout, P.sc[0], P.sh[0], 0.01f, P.a1_hi, P.a1_lo, st), T_A1, k, "tok_apply"));
+    const amx::TokConvParams c2 = conv(P.a1_hi, P.a1_lo, Do, Ho, Wo, s.cout, 1, s.cout, s.c2, s.c2b, P.raw2);
+    AMX_HIP(tapped(amx::launch_tokconv(c2, 27, 1, st, i0), T_RAW2, k));
+    AMX_HIP(tapped(finalize(c2, s.n2w, s.n2b, 1), T_SS2, k, "tok_finalize"));
     // skip: 1x1x1 conv of the average-pooled stage input (no bias)
-    cp.x_hi = P.p_hi[k]; cp.x_lo = P.p_lo[k]; cp.Cin = s.cin;
-    cp.w_hi = s.sk.hi; cp.w_lo = s.sk.lo; cp.bias = nullptr; cp.raw = P.raws;
-    AMX_HIP(amx::launch_tokconv(cp, 1, 1, st, i0));
-    AMX_HIP(tap(sk + ".raws", li0.name));
-    AMX_HIP(amx::launch_tok_finalize(P.stats, n, amx::tokconv_slots(cp), s.cout, vo, s.snw, s.snb, c.in_eps, P.sc[2], P.sh[2], st));
-    AMX_HIP(tap(sk + ".sss", "tok_finalize"));
+    const amx::TokConvParams sk = conv(P.p_hi[k], P.p_lo[k], Do, Ho, Wo, s.cin, 1, s.cout, s.sk, nullptr, P.raws);
+    AMX_HIP(tapped(amx::launch_tokconv(sk, 1, 1, st, i0), T_RAWS, k));
+    AMX_HIP(tapped(finalize(sk, s.snw, s.snb, 2), T_SSS, k, "tok_finalize"));
     AMX_HIP(amx::launch_tok_combine(P.raw2, P.raws, n, Do, Ho, Wo, s.cout, P.sc[1], P.sh[1], P.sc[2], P.sh[2], 0.01f, P.h_hi[k + 1], P.h_lo[k + 1],
                                     k < 2 ? P.p_hi[k + 1] : nullptr, k < 2 ? P.p_lo[k + 1] : nullptr, st));
-    AMX_HIP(tap(sk + ".h", "tok_combine"));
-    if (k < 2) AMX_HIP(tap(sk + ".p", "tok_combine"));
-    if (k == 0) { note("raw1_s0", P.raw1, (size_t)n * vo * s.cout * 4); }
-    Dk = Do; Hk = Ho; Wk = Wo;
+    AMX_HIP(tap(T_H, k, "tok_combine"));
+    if (k < 2) AMX_HIP(tap(T_P, k, "tok_combine"));
+    return AMX_OK;
   }
-  {
-    amx::GemmParams g{};
-    g.a_hi = P.h_hi[3]; g.a_lo = P.h_lo[3]; g.lda = kStageC[3]; g.M = n * V; g.KS = h->tokproj.KS;
-    g.w_hi = h->tokproj.hi; g.w_lo = h->tokproj.lo; g.ntiles = h->tokproj.ntiles; g.Nreal = E; g.bias = h->tokproj_b;
-    g.out = P.tok; g.ldo = E; g.V = V; g.nreg = nreg; g.pos = h->pos;
+  // token projection (+ bias + position embedding) behind the register tokens of every sample
+  int embed() {
+    amx::GemmParams g = product(P.h_hi[3], P.h_lo[3], kStageC[3], n * V, h->tokproj);
+    g.Nreal = E; g.bias = h->tokproj_b; g.out = P.tok; g.ldo = E; g.V = V; g.nreg = nreg; g.pos = h->pos;
     AMX_HIP(amx::launch_gemm(g, amx::EPI_TOKENS, st, i0));
-    AMX_HIP(amx::launch_place_registers(h->regs, nreg, E, T, n, P.tok, st));
+    AMX_HIP(tapped(amx::launch_place_registers(h->regs, nreg, E, T, n, P.tok, st), T_TOKENS, 0));
+    return AMX_OK;
   }
-  note("tokens", P.tok, (size_t)M * E * 4);
-  AMX_HIP(tap("tokens", li0.name));
-
-  // ------------------------------------------------------------------ EVA blocks
-  const int nb = n_blocks < 0 || n_blocks > c.depth ? c.depth : n_blocks;
-  void *Qp, *Kp, *Vt;
-  int att_npad, att_nblk;
-  amx::attention_operands(P.att, n, c.heads, T, &Qp, &Kp, &Vt, &att_npad, &att_nblk);
+  // ---- EVA blocks
   // padding of the operand buffers (token rows / keys beyond T, feature columns beyond head_dim) is zero and never written again
-  if (nb > 0) AMX_HIP(hipMemsetAsync(P.att, 0, amx::attention_scratch_bytes(n, c.heads, T), st));
-  for (int bi = 0; bi < nb; ++bi) {
-    const Block& b = h->blk[bi];
-    amx::GemmParams g{};
-    g.a_hi = P.A1; g.lda = Ep; g.M = M;
-    const std::string bk = "b" + std::to_string(bi);
-    AMX_HIP(amx::launch_ln_rows(P.tok, 0, E, E, b.n1w, b.n1b, 1e-6f, M, M, M, 0, 0, P.A1, nullptr, Ep, st, i0));
-    AMX_HIP(tap(bk + ".ln1", li0.name));
-    // q | k and v projections write the attention kernel's f16 operands themselves (bias, per-head LayerNorm, rotary embedding,
-    // fragment layouts in the epilogue): no fp32 q / k / v tensors, no separate preparation pass
+  int clear_attention_operands() {
+    AMX_HIP(hipMemsetAsync(P.att, 0, amx::attention_scratch_bytes(n, c.heads, T), st));
+    return AMX_OK;
+  }
+  // The q | k (EPI_QK) or v (EPI_VT) projection of the rows in P.A1.  It writes the attention kernel's f16 operands itself (bias, per-head
+  // LayerNorm, rotary embedding, fragment layouts in the epilogue): no fp32 q / k / v tensors, no separate preparation pass
+  amx::GemmParams attention_operand(const Block& b, const Packed& w, const float* bias, void* dst) const {
+    amx::GemmParams g = product(P.A1, nullptr, Ep, M, w);
+    g.Nreal = w.ntiles * 16; g.bias = bias; g.out = dst; g.ldo = 0;
     g.att_eps = 1e-5f; g.qscale = 1.4426950408889634f / sqrtf((float)h->hd); g.rope = h->rope; g.T = T; g.n_prefix = nreg; g.heads = c.heads;
     g.hd = h->hd; g.npad = att_npad; g.nblk_pad = att_nblk; g.Qp = Qp; g.Kp = Kp; g.Vt = Vt; g.Cp = 80;
     g.qnw = c.qk_norm ? b.qnw : nullptr; g.qnb = b.qnb; g.knw = c.qk_norm ? b.knw : nullptr; g.knb = b.knb;
-    g.KS = b.qk.KS; g.w_hi = b.qk.hi; g.ntiles = b.qk.ntiles; g.Nreal = b.qk.ntiles * 16; g.bias = b.qkb; g.out = Qp; g.ldo = 0;
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_QK, st, i0));
-    g.KS = b.v.KS; g.w_hi = b.v.hi; g.ntiles = b.v.ntiles; g.Nreal = b.v.ntiles * 16; g.bias = b.vb; g.out = Vt;
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_VT, st, i1));
-    AMX_HIP(amx::launch_attention_fwd(Qp, Kp, Vt, n, T, c.heads, h->hd, P.AO, st));
-    AMX_HIP(tap(bk + ".attn", std::string(li0.name) + " + " + li1.name + " + attn_fwd"));      // the operand buffers are not tapped: one group
-    AMX_HIP(amx::launch_ln_rows(P.AO, 0, E, E, c.scale_attn_inner ? b.anw : nullptr, b.anb, 1e-5f, M, M, M, 0, 0, P.A1, nullptr, Ep, st, i0));
-    AMX_HIP(tap(bk + ".ln_attn", li0.name));
-    g.KS = b.proj.KS; g.w_hi = b.proj.hi; g.ntiles = b.proj.ntiles; g.Nreal = E; g.bias = b.projb; g.gamma = b.g1; g.out = P.tok; g.ldo = E;
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_RESID, st, i0));
-    AMX_HIP(tap(bk + ".tok1", li0.name));
-    AMX_HIP(amx::launch_ln_rows(P.tok, 0, E, E, b.n2w, b.n2b, 1e-6f, M, M, M, 0, 0, P.A1, nullptr, Ep, st, i0));
-    AMX_HIP(tap(bk + ".ln2", li0.name));
-    g.KS = b.fc1.KS; g.w_hi = b.fc1.hi; g.ntiles = b.fc1.ntiles; g.Nreal = 2 * up(hid, 16); g.bias = b.fc1b; g.gamma = nullptr; g.out = P.Hd; g.ldo = up(hid, 16);
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_SWIGLU, st, i0));
-    AMX_HIP(tap(bk + ".hd", li0.name));
-    AMX_HIP(amx::launch_ln_rows(P.Hd, 1, up(hid, 16), hid, b.mnw, b.mnb, 1e-6f, M, M, M, 0, 0, P.A2, nullptr, up(hid, 32), st, i0));
-    AMX_HIP(tap(bk + ".ln_mlp", li0.name));
-    g.a_hi = P.A2; g.lda = up(hid, 32);
-    g.KS = b.fc2.KS; g.w_hi = b.fc2.hi; g.ntiles = b.fc2.ntiles; g.Nreal = E; g.bias = b.fc2b; g.gamma = b.g2; g.out = P.tok; g.ldo = E;
-    AMX_HIP(amx::launch_gemm(g, amx::EPI_RESID, st, i0));
-    AMX_HIP(tap(bk + ".tok2", li0.name));
+    return g;
   }
-  note("tokens_out", P.tok, (size_t)M * E * 4);
-
-  // ------------------------------------------------------------------ final norm (drops the register tokens) + decoder
-  const int Mv = n * V;
-  AMX_HIP(amx::launch_ln_rows(P.tok, 0, E, E, h->fnw, h->fnb, 1e-6f, Mv, V, T, nreg, 0, P.Ad_hi[0], P.Ad_lo[0], Ep, st, i0));
-  AMX_HIP(tap("d.ln", li0.name));
-  int gd = c.grid_d, gh = c.grid_h, gw = c.grid_w;
-  long long rows = Mv;
-  for (int k = 0; k < 3; ++k) {
+  // tok += gamma * (rows x W + bias): the residual products behind attention and MLP
+  hipError_t residual(const char* rows, int lda, const Packed& w, const float* bias, const float* gamma) {
+    amx::GemmParams g = product(rows, nullptr, lda, M, w);
+    g.Nreal = E; g.bias = bias; g.gamma = gamma; g.out = P.tok; g.ldo = E;
+    return amx::launch_gemm(g, amx::EPI_RESID, st, i0);
+  }
+  int block(int bi) {
+    const Block& b = h->blk[bi];
+    // ---- attention
+    AMX_HIP(tapped(ln_whole_rows({P.tok, 0, E, E}, b.n1w, b.n1b, 1e-6f, M, 0, {P.A1, nullptr, Ep}), T_LN1, bi));
+    AMX_HIP(amx::launch_gemm(attention_operand(b, b.qk, b.qkb, Qp), amx::EPI_QK, st, i0));
+    AMX_HIP(amx::launch_gemm(attention_operand(b, b.v, b.vb, Vt), amx::EPI_VT, st, i1));
+    char group[sizeof li0.name + sizeof li1.name + 16] = "";      // the operand buffers are not tapped: one group
+    if (ts) snprintf(group, sizeof group, "%s + %s + attn_fwd", li0.name, li1.name);
+    AMX_HIP(tapped(amx::launch_attention_fwd(Qp, Kp, Vt, n, T, c.heads, h->hd, P.AO, st), T_ATTN, bi, group));
+    AMX_HIP(tapped(ln_whole_rows({P.AO, 0, E, E}, c.scale_attn_inner ? b.anw : nullptr, b.anb, 1e-5f, M, 0, {P.A1, nullptr, Ep}), T_LN_ATTN, bi));
+    AMX_HIP(tapped(residual(P.A1, Ep, b.proj, b.projb, b.g1), T_TOK1, bi));
+    // ---- SwiGLU MLP
+    AMX_HIP(tapped(ln_whole_rows({P.tok, 0, E, E}, b.n2w, b.n2b, 1e-6f, M, 0, {P.A1, nullptr, Ep}), T_LN2, bi));
+    amx::GemmParams g = product(P.A1, nullptr, Ep, M, b.fc1);
+    g.Nreal = 2 * up(hid, 16); g.bias = b.fc1b; g.out = P.Hd; g.ldo = up(hid, 16);
+    AMX_HIP(tapped(amx::launch_gemm(g, amx::EPI_SWIGLU, st, i0), T_HD, bi));
+    AMX_HIP(tapped(ln_whole_rows({P.Hd, 1, up(hid, 16), hid}, b.mnw, b.mnb, 1e-6f, M, 0, {P.A2, nullptr, up(hid, 32)}), T_LN_MLP, bi));
+    AMX_HIP(tapped(residual(P.A2, up(hid, 32), b.fc2, b.fc2b, b.g2), T_TOK2, bi));
+    return AMX_OK;
+  }
+  // ---- final norm + decoder
+  // the final norm drops the register tokens: output row r of sample s is token row s T + nreg + r
+  int final_norm() {
+    AMX_HIP(tapped(amx::launch_ln_rows(P.tok, 0, E, E, h->fnw, h->fnb, 1e-6f, /* M */ n * V, /* rows_out */ V, /* rows_in */ T, /* skip */ nreg,
+                                       /* gelu */ 0, P.Ad_hi[0], P.Ad_lo[0], Ep, st, i0), T_DLN, 0));
+    return AMX_OK;
+  }
+  // the product of decoder stage k (ConvTranspose3d, kernel 2, stride 2) on `rows` of its operand rows from row0; where the result goes is the caller's
+  amx::GemmParams dec_product(int k, long long row0, long long rows) const {
     const DecStage& d = h->dec[k];
-    amx::GemmParams g{};
-    g.a_hi = P.Ad_hi[k]; g.a_lo = P.Ad_lo[k]; g.lda = up(d.cin, 32); g.M = (int)rows; g.KS = d.w.KS;
-    g.w_hi = d.w.hi; g.w_lo = d.w.lo; g.ntiles = d.w.ntiles; g.Nreal = 8 * d.cp; g.bias = d.bias;
-    g.out = P.rawd[k]; g.ldo = d.cout; g.gd = gd; g.gh = gh; g.gw = gw; g.Cp = d.cp; g.Creal = d.cout;
-    if (k == 2 && c.out_norm == 1) {      // ChannelDemean: the mean of every output channel follows from the column means of this stage's input
-      AMX_HIP(amx::launch_colsum(P.Ad_hi[2], P.Ad_lo[2], up(d.cin, 32), d.cin, n, (int)(rows / n), kColChunks, P.colsum, st));
-      AMX_HIP(amx::launch_demean(P.colsum, kColChunks, up(d.cin, 32), d.cin, rows / n, d.w_raw, d.cout, d.bias, n, P.mean, st));
-      AMX_HIP(tap("d.mean", "colsum + demean"));
-    }
-    if (k == 2 && out.acc) {              // one product per window, in window order: overlapping windows are ordered by the stream
-      const long long wrows = rows / n, vvox = (long long)out.vd * out.vh * out.vw;
-      g.M = (int)wrows; g.wmap = out.wmap; g.acc_sc = vvox; g.acc_sz = (long long)out.vh * out.vw; g.acc_sy = out.vw;
-      for (int i = 0; i < n; ++i) {
-        g.a_hi = P.Ad_hi[2] + (size_t)i * wrows * g.lda * 2;
-        g.a_lo = P.Ad_lo[2] ? P.Ad_lo[2] + (size_t)i * wrows * g.lda * 2 : nullptr;
-        g.out = out.acc + out.corner[i];
-        g.sub = c.out_norm == 1 ? P.mean + (size_t)i * d.cout : nullptr;      // ChannelDemean stays per window
-        AMX_HIP(amx::launch_gemm(g, amx::EPI_PLANAR_ACC, st));
-      }
-    } else if (k == 2) {                  // planar fp32 output written by the product kernel itself
-      g.out = d_y; g.sub = c.out_norm == 1 ? P.mean : nullptr;
-      AMX_HIP(amx::launch_gemm(g, amx::EPI_PLANAR, st, i0));
-      AMX_HIP(tap("y", li0.name));
-    } else if (dec_fused(d)) {            // channel LayerNorm + GELU fused: the next stage's operand rows come straight out
-      g.out = P.Ad_hi[k + 1]; g.out_lo = P.Ad_lo[k + 1]; g.ldo = up(d.cout, 32); g.lnw = d.lnw; g.lnb = d.lnb; g.eps = 1e-6f;
-      AMX_HIP(amx::launch_gemm(g, amx::EPI_SCATTER_LN, st, i0));
-      AMX_HIP(tap("d" + std::to_string(k + 1) + ".in", li0.name));
-    } else {
-      AMX_HIP(amx::launch_gemm(g, amx::EPI_SCATTER, st, i0));
-      AMX_HIP(tap("d" + std::to_string(k) + ".raw", li0.name));
-      AMX_HIP(amx::launch_ln_rows(P.rawd[k], 0, d.cout, d.cout, d.lnw, d.lnb, 1e-6f, (int)(rows * 8), (int)(rows * 8), (int)(rows * 8), 0, 1, P.Ad_hi[k + 1],
-                                  P.Ad_lo[k + 1], up(d.cout, 32), st, i0));
-      AMX_HIP(tap("d" + std::to_string(k + 1) + ".in", li0.name));
-    }
-    rows *= 8; gd *= 2; gh *= 2; gw *= 2;
+    const int lda = up(d.cin, 32);
+    amx::GemmParams g = product(P.Ad_hi[k] + row0 * lda * 2, P.Ad_lo[k] ? P.Ad_lo[k] + row0 * lda * 2 : nullptr, lda, (int)rows, d.w);
+    g.Nreal = 8 * d.cp; g.bias = d.bias; g.ldo = d.cout; g.Cp = d.cp; g.Creal = d.cout;
+    g.gd = c.grid_d << k; g.gh = c.grid_h << k; g.gw = c.grid_w << k;
+    return g;
   }
-  return AMX_OK;
-}
+  int decoder_stage(int k) {
+    const long long rows = ((long long)n * V) << (3 * k);      // operand rows of the stage; it writes 8 times as many
+    if (k < 2) return dec_fused(h->dec[k]) ? scatter_ln(k, rows) : scatter_then_ln(k, rows);
+    if (c.out_norm == 1)
+      if (int e = demean(rows)) return e;
+    return out.acc ? planar_acc(rows) : planar(rows);
+  }
+  // channel LayerNorm + GELU fused into the product: the next stage's operand rows come straight out, no fp32 tensor between the two
+  int scatter_ln(int k, long long rows) {
+    const DecStage& d = h->dec[k];
+    amx::GemmParams g = dec_product(k, 0, rows);
+    g.out = P.Ad_hi[k + 1]; g.out_lo = P.Ad_lo[k + 1]; g.ldo = up(d.cout, 32); g.lnw = d.lnw; g.lnb = d.lnb; g.eps = 1e-6f;
+    AMX_HIP(tapped(amx::launch_gemm(g, amx::EPI_SCATTER_LN, st, i0), T_DIN, k + 1));
+    return AMX_OK;
+  }
+  int scatter_then_ln(int k, long long rows) {
+    const DecStage& d = h->dec[k];
+    amx::GemmParams g = dec_product(k, 0, rows);
+    g.out = P.rawd[k];
+    AMX_HIP(tapped(amx::launch_gemm(g, amx::EPI_SCATTER, st, i0), T_DRAW, k));
+    AMX_HIP(tapped(ln_whole_rows({P.rawd[k], 0, d.cout, d.cout}, d.lnw, d.lnb, 1e-6f, (int)(rows * 8), 1, {P.Ad_hi[k + 1], P.Ad_lo[k + 1], up(d.cout, 32)}), T_DIN, k + 1));
+    return AMX_OK;
+  }
+  // ChannelDemean: the mean of every output channel follows from the column means of the last stage's input
+  int demean(long long rows) {
+    const DecStage& d = h->dec[2];
+    AMX_HIP(amx::launch_colsum(P.Ad_hi[2], P.Ad_lo[2], up(d.cin, 32), d.cin, n, (int)(rows / n), kColChunks, P.colsum, st));
+    AMX_HIP(tapped(amx::launch_demean(P.colsum, kColChunks, up(d.cin, 32), d.cin, rows / n, d.w_raw, d.cout, d.bias, n, P.mean, st), T_DMEAN, 0, "colsum + demean"));
+    return AMX_OK;
+  }
+  // planar fp32 output written by the product kernel itself
+  int planar(long long rows) {
+    amx::GemmParams g = dec_product(2, 0, rows);
+    g.out = out.y; g.sub = c.out_norm == 1 ? P.mean : nullptr;
+    AMX_HIP(tapped(amx::launch_gemm(g, amx::EPI_PLANAR, st, i0), T_Y, 0));
+    return AMX_OK;
+  }
+  // sliding window: one product per window, in window order (overlapping windows are ordered by the stream), blended into the accumulator
+  int planar_acc(long long rows) {
+    const long long wrows = rows / n;
+    for (int i = 0; i < n; ++i) {
+      amx::GemmParams g = dec_product(2, i * wrows, wrows);
+      g.wmap = out.wmap; g.acc_sc = (long long)out.vd * out.vh * out.vw; g.acc_sz = (long long)out.vh * out.vw; g.acc_sy = out.vw;
+      g.out = out.acc + out.corner[i]; g.sub = c.out_norm == 1 ? P.mean + (size_t)i * h->dec[2].cout : nullptr;      // ChannelDemean stays per window
+      AMX_HIP(amx::launch_gemm(g, amx::EPI_PLANAR_ACC, st));
+    }
+    return AMX_OK;
+  }
+};
 
 // ---- sliding-window route -----------------------------------------------------------------------------------------------------
 constexpr int kVitMaxWindows = 16;
@@ -721,7 +765,7 @@ int windows_check(const amx_vit* h, int vd, int vh, int vw, int n_windows, const
   return AMX_OK;
 }
 
-int forward_windows(amx_vit* h, const float* d_vol, int vd, int vh, int vw, int n, const int* offsets_zyx, const float* d_wmap, float* d_acc,
+int forward_windows(const amx_vit* h, const float* d_vol, int vd, int vh, int vw, int n, const int* offsets_zyx, const float* d_wmap, float* d_acc,
                     void* d_ws, size_t ws_bytes, hipStream_t st) {
   if (int rc = windows_check(h, vd, vh, vw, n, d_ws, ws_bytes)) return rc;
   const amx_vit_cfg& c = h->cfg;
@@ -737,7 +781,32 @@ int forward_windows(amx_vit* h, const float* d_vol, int vd, int vh, int vw, int 
   AMX_HIP(hipGetLastError());
   VitOut out;
   out.acc = d_acc; out.wmap = d_wmap; out.vd = vd; out.vh = vh; out.vw = vw; out.corner = cn.off;
-  return vit_run(h, win, out, n, P, -1, st);
+  return VitForward(h, P, n, st, out, nullptr).run(win, c.depth);
+}
+
+// amx_vit_forward and amx_vit_forward_taps: a plain forward is a forward with zero taps.  Every refusal comes before the first launch.
+int forward_checked(const amx_vit* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, amx_vit_tap* taps, int n_taps,
+                    hipStream_t st) {
+  if (!h || !d_x || !d_y || !d_ws || n_taps < 0 || (n_taps && !taps)) return fail(AMX_ERR_INVALID, "null argument");
+  if (!h->loaded) return fail(AMX_ERR_NOT_LOADED, "vit: forward before amx_vit_load");
+  if (n < 1) return fail(AMX_ERR_INVALID, "vit: batch %d", n);
+  if ((uintptr_t)d_ws & 255) return fail(AMX_ERR_WORKSPACE, "vit: workspace must be 256-byte aligned");
+  const Plan P = make_plan(h, n, (char*)d_ws);
+  if (ws_bytes < P.total) return fail(AMX_ERR_WORKSPACE, "vit: workspace needs %zu bytes (got %zu)", P.total, ws_bytes);
+  const int nb = n_blocks < 0 || n_blocks > h->cfg.depth ? h->cfg.depth : n_blocks;
+  TapSet ts;
+  const std::vector<TapSrc> table = n_taps ? tap_table(h, n, P, nb, d_y) : std::vector<TapSrc>();
+  for (int i = 0; i < n_taps; ++i) {
+    if (!taps[i].name) return fail(AMX_ERR_INVALID, "vit: tap %d has no name", i);
+    const TapSrc* s = tap_find(table, taps[i].name);
+    if (!s) return fail(AMX_ERR_INVALID, "vit: no tap named %s in this forward (%d blocks)", taps[i].name, nb);
+    if (taps[i].d_dst && taps[i].bytes < s->bytes())
+      return fail(AMX_ERR_WORKSPACE, "vit: tap %s needs %zu bytes (got %zu)", taps[i].name, s->bytes(), taps[i].bytes);
+    taps[i].route[0] = 0;
+    ts.push_back({&taps[i], *s});
+  }
+  const VitOut out{d_y};
+  return VitForward(h, P, n, st, out, n_taps ? &ts : nullptr).run(d_x, nb);
 }
 
 }  // namespace
@@ -750,15 +819,7 @@ size_t amx_vit_workspace_bytes(const amx_vit_t* h, int n) {
 }
 
 int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, void* stream) {
-  if (!h || !d_x || !d_y || !d_ws) return fail(AMX_ERR_INVALID, "null argument");
-  if (!h->loaded) return fail(AMX_ERR_NOT_LOADED, "vit: forward before amx_vit_load");
-  if (n < 1) return fail(AMX_ERR_INVALID, "vit: batch %d", n);
-  if ((uintptr_t)d_ws & 255) return fail(AMX_ERR_WORKSPACE, "vit: workspace must be 256-byte aligned");
-  const Plan P = make_plan(h, n, (char*)d_ws);
-  if (ws_bytes < P.total) return fail(AMX_ERR_WORKSPACE, "vit: workspace needs %zu bytes (got %zu)", P.total, ws_bytes);
-  VitOut out;
-  out.y = d_y;
-  return vit_run(h, d_x, out, n, P, n_blocks, (hipStream_t)stream);
+  return forward_checked(h, d_x, d_y, n, d_ws, ws_bytes, n_blocks, nullptr, 0, (hipStream_t)stream);
 }
 
 size_t amx_vit_tap_bytes(const amx_vit_t* h, int n, const char* name) {
@@ -770,25 +831,7 @@ size_t amx_vit_tap_bytes(const amx_vit_t* h, int n, const char* name) {
 
 int amx_vit_forward_taps(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, amx_vit_tap* taps,
                          int n_taps, void* stream) {
-  if (!h || !d_x || !d_y || !d_ws || n_taps < 0 || (n_taps && !taps)) return fail(AMX_ERR_INVALID, "null argument");
-  if (!h->loaded) return fail(AMX_ERR_NOT_LOADED, "vit: forward before amx_vit_load");
-  if (n < 1) return fail(AMX_ERR_INVALID, "vit: batch %d", n);
-  if ((uintptr_t)d_ws & 255) return fail(AMX_ERR_WORKSPACE, "vit: workspace must be 256-byte aligned");
-  const Plan P = make_plan(h, n, (char*)d_ws);
-  if (ws_bytes < P.total) return fail(AMX_ERR_WORKSPACE, "vit: workspace needs %zu bytes (got %zu)", P.total, ws_bytes);
-  const int nb = n_blocks < 0 || n_blocks > h->cfg.depth ? h->cfg.depth : n_blocks;
-  TapSet ts{tap_table(h, n, P, nb, d_y), taps, n_taps};
-  for (int i = 0; i < n_taps; ++i) {            // every refusal comes before the first launch
-    if (!taps[i].name) return fail(AMX_ERR_INVALID, "vit: tap %d has no name", i);
-    const TapSrc* s = tap_find(ts.table, taps[i].name);
-    if (!s) return fail(AMX_ERR_INVALID, "vit: no tap named %s in this forward (%d blocks)", taps[i].name, nb);
-    if (taps[i].d_dst && taps[i].bytes < s->bytes())
-      return fail(AMX_ERR_WORKSPACE, "vit: tap %s needs %zu bytes (got %zu)", taps[i].name, s->bytes(), taps[i].bytes);
-    taps[i].route[0] = 0;
-  }
-  VitOut out;
-  out.y = d_y;
-  return vit_run(h, d_x, out, n, P, n_blocks, (hipStream_t)stream, &ts);
+  return forward_checked(h, d_x, d_y, n, d_ws, ws_bytes, n_blocks, taps, n_taps, (hipStream_t)stream);
 }
 
 size_t amx_vit_windows_workspace_bytes(const amx_vit_t* h, int n_windows) {
@@ -816,49 +859,6 @@ int amx_vit_sliding_window(amx_vit_t* h, const float* d_vol, int vd, int vh, int
   };
   return amx::sw_run(net, h->sw_map, nullptr, vd, vh, vw, overlap, mode, sigma_scale, n_batch, out_kind, d_w, d_b, classes, d_acc, d_cnt, d_out,
                      (hipStream_t)stream);
-}
-
-/* Copies a workspace buffer of the LAST forward on this handle (test / debugging aid): names "tokens" (after the tokenizer:
- * fp32 [n][T][E]), "tokens_out" (after the blocks), "h0_hi", "p0_hi", "raw1_s0". */
-int amx_vit_debug_read(amx_vit_t* h, const char* name, void* d_dst, size_t max_bytes, size_t* bytes, void* stream) {
-  if (!h || !name) return fail(AMX_ERR_INVALID, "null argument");
-  for (const auto& e : h->dbg)
-    if (e.name == name) {
-      if (bytes) *bytes = e.bytes;
-      if (d_dst) {
-        if (max_bytes < e.bytes) return fail(AMX_ERR_WORKSPACE, "debug_read %s: %zu bytes needed", name, e.bytes);
-        AMX_HIP(hipMemcpyAsync(d_dst, e.ptr, e.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-      }
-      return AMX_OK;
-    }
-  return fail(AMX_ERR_INVALID, "debug_read: no buffer named %s", name);
-}
-
-int amx_linear(const float* d_x, const float* d_w, const float* d_b, int m, int k, int n, int split, float* d_y, void* stream) {
-  if (!d_x || !d_w || !d_y) return fail(AMX_ERR_INVALID, "null argument");
-  if (m < 1 || k < 1 || n < 4 || (n % 4) || k > 64 * 17) return fail(AMX_ERR_INVALID, "linear: m >= 1, 1 <= k <= 1088, n a multiple of 4 (got %d %d %d)", m, k, n);
-  hipStream_t st = (hipStream_t)stream;
-  const int kp = up(k, 32), ntiles = up(n, 16) / 16, KS = kp / 32;
-  const size_t abytes = (size_t)m * kp * 2, wbytes = (size_t)ntiles * KS * 1024, bbytes = (size_t)ntiles * 16 * 4;
-  char* buf = nullptr;
-  AMX_HIP(hipMalloc((void**)&buf, 2 * abytes + 2 * wbytes + bbytes + 1024));
-  char *a_hi = buf, *a_lo = buf + abytes, *w_hi = buf + 2 * abytes, *w_lo = w_hi + wbytes;
-  float* bias = (float*)(w_lo + wbytes);
-  int rc = AMX_OK;
-  hipError_t e = amx::launch_ln_rows(d_x, 0, k, k, nullptr, nullptr, 0.f, m, m, m, 0, 0, a_hi, split ? a_lo : nullptr, kp, st);
-  if (e == hipSuccess) e = amx::launch_pack_gemm(d_w, nullptr, nullptr, n, 0, 0, k, 0, 0, 0, ntiles, KS, w_hi, split ? w_lo : nullptr, st);
-  if (e == hipSuccess) e = amx::launch_vec_place(bias, d_b, n, 0.f, st);
-  if (e == hipSuccess && ntiles * 16 > n) e = amx::launch_vec_place(bias + n, nullptr, ntiles * 16 - n, 0.f, st);
-  if (e == hipSuccess) {
-    amx::GemmParams g{};
-    g.a_hi = a_hi; g.a_lo = split ? a_lo : nullptr; g.lda = kp; g.M = m; g.KS = KS; g.w_hi = w_hi; g.w_lo = split ? w_lo : nullptr;
-    g.ntiles = ntiles; g.Nreal = n; g.bias = bias; g.out = d_y; g.ldo = n;
-    e = amx::launch_gemm(g, amx::EPI_F32, st);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) rc = fail(AMX_ERR_HIP, "linear: %s", hipGetErrorString(e));
-  (void)hipFree(buf);
-  return rc;
 }
 
 }  // extern "C"

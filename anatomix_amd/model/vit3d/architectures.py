@@ -578,17 +578,6 @@ class PrimusV2(nn.Module):
             return tuple(buf.view(torch.float16).chunk(2)) if split else (buf.view(torch.float16), None)
         return buf.view(torch.float16)
 
-    def debug_read(self, name, dtype=torch.float32):
-        """A workspace buffer of the last ``forward_hip`` (tests): flat tensor of ``dtype``."""
-        lib = _lib.load()
-        nbytes = ctypes.c_size_t()
-        _lib.check(lib.amx_vit_debug_read(self._handle, name.encode(), None, 0, ctypes.byref(nbytes), None))
-        out = torch.empty(nbytes.value, dtype=torch.uint8, device=self._engine_ws.device)
-        with torch.cuda.device(out.device):
-            _lib.check(lib.amx_vit_debug_read(self._handle, name.encode(), _lib.ptr(out), nbytes.value, None,
-                                              _lib.stream(out.device)))
-        return out.view(dtype)
-
     def _drop_engine(self):
         """The engine's packed parameters live on the device it was created on: a move / copy / replica starts over."""
         hnd, self._handle = self.__dict__.get("_handle"), None

@@ -555,7 +555,6 @@ size_t amx_vit_workspace_bytes(const amx_vit_t* h, int n);
 /* d_x: fp32 [n][1][8 grid_d][8 grid_h][8 grid_w]; d_y: fp32 [n][num_classes][same volume].  d_ws: amx_vit_workspace_bytes(h, n)
  * bytes, 256-byte aligned.  n_blocks < 0: all blocks (a smaller count is a debugging aid). */
 int amx_vit_forward(amx_vit_t* h, const float* d_x, float* d_y, int n, void* d_ws, size_t ws_bytes, int n_blocks, void* stream);
-int amx_vit_debug_read(amx_vit_t* h, const char* name, void* d_dst, size_t max_bytes, size_t* bytes, void* stream);
 
 /* amx_vit_forward with taps (test aid; the stage-by-stage walk of tests/_vit_walk.py).  The workspace regions of tokenizer, blocks and
  * decoder alias each other and the token stream is updated in place, so an intermediate can only be read while the forward runs: for every

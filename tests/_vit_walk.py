@@ -1,4 +1,4 @@
-"""The ViT stage walk: every stage of the engine forward (amx_vit.hip ``vit_run``) checked on its own, teacher-forced with the tensors
+"""The ViT stage walk: every stage of the engine forward (amx_vit.hip ``VitForward``) checked on its own, teacher-forced with the tensors
 the forward itself stored (``PrimusV2.forward_hip(x, taps=...)``, names in include/anatomix_amd.h).
 
 ``walk(sd, kw, x, taps, only=None, samples=None, routes=None) -> [Rec]``: one record per stage.  The input of a stage is the tap in

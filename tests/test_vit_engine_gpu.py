@@ -62,8 +62,8 @@ def test_tokenizer_tokens_match_the_oracle(device, size, batch):
     m, sd = _model(kw, 3, device)
     x = V.synthetic_input(11, batch, size)
     with torch.no_grad():
-        m.forward_hip(x.to(device), n_blocks=0)
-        got = m.debug_read("tokens").view(batch, -1, kw["embed_dim"]).cpu()
+        _, taps = m.forward_hip(x.to(device), n_blocks=0, taps=["tokens"])
+        got = taps["tokens"][0].view(batch, -1, kw["embed_dim"]).cpu()
     ref = _oracle_tokens(x.double(), {k: v.double() for k, v in sd.items()}, kw).float()
     assert got.shape == ref.shape and torch.isfinite(got).all()
     e = rel_l2(got, ref)
