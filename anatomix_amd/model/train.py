@@ -596,6 +596,25 @@ def _norm_adjoint(bw, blk):
     return fr
 
 
+def _stem_weight_grad(fr, x0, cout):
+    """The stem's weight gradient, on the image with its mean taken out.  An image is one-signed and the gradient of the stem's raw
+    output has zero channel sums (the norm adjoint removes them), so sum dY x cancels to 1/500 of its terms while the 32 products
+    of every MFMA step share a sign: at 2 x (32, 48, 80) in f16 the kernel on x itself stood at rel-L2 1.01e-5 of float64, and at
+    6.6e-7 on x - 0.5 (tests/test_backward_walk_gpu.py).  So: dW = sum dY (x - c) + c sum dY with c the image's mean; x - c goes
+    into two of the sixteen stored channels the kernel reads anyway (its 16-bit rounding and what that leaves), the sum of dY is
+    taken in double.  Inline: the stem is the last block and normally has no data gradient to run beside."""
+    d = x0[..., 0].float()
+    c = d.mean()
+    d = d - c
+    hi = d.to(x0.dtype)
+    xs = torch.zeros_like(x0)
+    xs[..., 0] = hi
+    xs[..., 1] = (d - hi.float()).to(x0.dtype)
+    dw = T.conv_wgrad(fr, xs, None, 2, cout)
+    total = T.interior(fr)[..., :cout].sum((0, 1, 2, 3), dtype=torch.float64)
+    return dw[:, :1] + dw[:, 1:] + (c.double() * total).float().view(-1, 1, 1, 1, 1)
+
+
 def _weight_grad(bw, blk, fr, x0, x1):
     # The weight gradient and the data gradient of a block both read `fr` and nothing else of each other: the weight
     # gradient goes to a side stream (result and scratch preallocated / cached on this one) and is joined before the next
@@ -603,7 +622,9 @@ def _weight_grad(bw, blk, fr, x0, x1):
     # adjoint (second frame per shape + events) measured slower: 11.4 vs 10.7 ms per step in round 2, and again 9.04 vs 8.71 ms in
     # round 3 with the one-round weight-gradient launches (the two MFMA kernels contend; the adjoint passes lose more than the join costs).
     conv, cin, cout = blk.conv, blk.conv.in_channels, blk.conv.out_channels
-    if x0.is_cuda and x0.shape[3] >= OVERLAP_WGRAD_MIN_W:
+    if blk.inputs[0] == "x" and cin == 1 and x1 is None:
+        bw.pgrads[id(conv.weight)] = _stem_weight_grad(fr, x0, cout)
+    elif x0.is_cuda and x0.shape[3] >= OVERLAP_WGRAD_MIN_W:
         dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x0.device)
         T.wgrad_scratch(x0, x1, cout)                                    # make sure the cached scratch exists (allocated here)
         side = _side_stream(x0.device)
