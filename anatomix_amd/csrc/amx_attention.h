@@ -1,9 +1,10 @@
-// anatomix_amd -- constants and operand layouts shared by the attention core's forward (amx_attention.hip) and backward
-// (amx_attention_bwd.hip).
+// anatomix_amd -- constants, operand layouts and argument checks shared by the attention core's forward (amx_attention.hip) and
+// backward (amx_attention_bwd.hip).
 #pragma once
 #include <stddef.h>
 
 #include "amx_common.h"
+#include "amx_launch.h"
 
 namespace amx {
 
@@ -51,5 +52,21 @@ AttTrainScratch attention_train_layout(void* scratch, int b, int heads, int n, i
 hipError_t launch_attention_prep_train(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b,
                                        const float* kn_w, const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n,
                                        int heads, int hd, const AttTrainScratch& S, hipStream_t st);
+
+// the envelope shared by the attention entries: AMX_OK or the refusal, before any launch
+inline int attention_args_ok(const float* d_qn_w, const float* d_qn_b, const float* d_kn_w, const float* d_kn_b, int n_prefix, int b, int n,
+                             int heads, int head_dim) {
+  if (b < 1 || n < 1 || heads < 1 || head_dim < 2 || head_dim > 80 || (head_dim & 1))
+    return fail(AMX_ERR_INVALID, "attention: head_dim must be even and <= 80 (got %d), b, n, heads >= 1", head_dim);
+  if ((!d_qn_w) != (!d_qn_b) || (!d_kn_w) != (!d_kn_b)) return fail(AMX_ERR_INVALID, "attention: norm weight and bias go together");
+  if (n_prefix < 0 || n_prefix > n) return fail(AMX_ERR_INVALID, "attention: 0 <= n_prefix <= n");
+  return AMX_OK;
+}
+// the forward's scratch (attention_scratch_bytes), as every entry that runs the forward checks it
+inline int attention_scratch_ok(const void* d_scratch, size_t scratch_bytes, int b, int heads, int n) {
+  if (scratch_bytes < attention_scratch_bytes(b, heads, n) || ((uintptr_t)d_scratch & 15))
+    return fail(AMX_ERR_WORKSPACE, "attention scratch needs %zu bytes, 16-byte aligned", attention_scratch_bytes(b, heads, n));
+  return AMX_OK;
+}
 
 }  // namespace amx

@@ -472,10 +472,54 @@ hipError_t launch_attention_prep_train(const float* q, const float* k, const flo
   return hipGetLastError();
 }
 
-hipError_t launch_attention(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
-                            const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
-                            float* out, void* scratch, hipStream_t st, float* lse) {
+static hipError_t launch_attention(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
+                                   const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
+                                   float* out, void* scratch, hipStream_t st, float* lse = nullptr) {
   return launch_attention_ld(q, k, v, heads * hd, qn_w, qn_b, kn_w, kn_b, eps, rope, n_prefix, b, n, heads, hd, out, scratch, st, lse);
 }
 
 }  // namespace amx
+
+using amx::fail;
+
+extern "C" {
+
+size_t amx_attention_scratch_bytes(int b, int heads, int n, int head_dim) {
+  if (b < 1 || heads < 1 || n < 1 || head_dim < 2 || head_dim > 80) return 0;
+  return amx::attention_scratch_bytes(b, heads, n);
+}
+
+int amx_attention_qknorm_rope(const float* d_q, const float* d_k, const float* d_v, const float* d_qn_w, const float* d_qn_b,
+                              const float* d_kn_w, const float* d_kn_b, float norm_eps, const float* d_rope, int n_prefix, int b,
+                              int n, int heads, int head_dim, float* d_out, void* d_scratch, size_t scratch_bytes, void* stream) {
+  if (!d_q || !d_k || !d_v || !d_out || !d_scratch) return fail(AMX_ERR_INVALID, "null argument");
+  if (int rc = amx::attention_args_ok(d_qn_w, d_qn_b, d_kn_w, d_kn_b, n_prefix, b, n, heads, head_dim)) return rc;
+  if (int rc = amx::attention_scratch_ok(d_scratch, scratch_bytes, b, heads, n)) return rc;
+  AMX_HIP(amx::launch_attention(d_q, d_k, d_v, d_qn_w, d_qn_b, d_kn_w, d_kn_b, norm_eps, d_rope, n_prefix, b, n, heads, head_dim, d_out,
+                                d_scratch, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_attention_prepared(const void* d_scratch, size_t scratch_bytes, int b, int n, int heads, int head_dim, float* d_out, void* stream) {
+  if (!d_scratch || !d_out) return fail(AMX_ERR_INVALID, "null argument");
+  if (int rc = amx::attention_args_ok(nullptr, nullptr, nullptr, nullptr, 0, b, n, heads, head_dim)) return rc;
+  if (int rc = amx::attention_scratch_ok(d_scratch, scratch_bytes, b, heads, n)) return rc;
+  void *Qp, *Kp, *Vt;
+  amx::attention_operands((void*)d_scratch, b, heads, n, &Qp, &Kp, &Vt, nullptr, nullptr);
+  AMX_HIP(amx::launch_attention_fwd(Qp, Kp, Vt, b, n, heads, head_dim, d_out, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_attention_qknorm_rope_train(const float* d_q, const float* d_k, const float* d_v, const float* d_qn_w, const float* d_qn_b,
+                                    const float* d_kn_w, const float* d_kn_b, float norm_eps, const float* d_rope, int n_prefix, int b,
+                                    int n, int heads, int head_dim, float* d_out, float* d_lse, void* d_scratch, size_t scratch_bytes,
+                                    void* stream) {
+  if (!d_q || !d_k || !d_v || !d_out || !d_lse || !d_scratch) return fail(AMX_ERR_INVALID, "attention: null argument");
+  if (int rc = amx::attention_args_ok(d_qn_w, d_qn_b, d_kn_w, d_kn_b, n_prefix, b, n, heads, head_dim)) return rc;
+  if (int rc = amx::attention_scratch_ok(d_scratch, scratch_bytes, b, heads, n)) return rc;
+  AMX_HIP(amx::launch_attention(d_q, d_k, d_v, d_qn_w, d_qn_b, d_kn_w, d_kn_b, norm_eps, d_rope, n_prefix, b, n, heads, head_dim, d_out,
+                                d_scratch, (hipStream_t)stream, d_lse));
+  return AMX_OK;
+}
+
+}  // extern "C"

@@ -531,12 +531,12 @@ AttTrainScratch attention_train_layout(void* scratch, int b, int heads, int n, i
   return S;
 }
 
-size_t attention_train_scratch_bytes(int b, int heads, int n, int hd) { return attention_train_layout(nullptr, b, heads, n, hd).bytes; }
+static size_t attention_train_scratch_bytes(int b, int heads, int n, int hd) { return attention_train_layout(nullptr, b, heads, n, hd).bytes; }
 
-hipError_t launch_attention_backward(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
-                                     const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
-                                     const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv, float* dqn_w,
-                                     float* dqn_b, float* dkn_w, float* dkn_b, void* scratch, hipStream_t st) {
+static hipError_t launch_attention_backward(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
+                                            const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
+                                            const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv, float* dqn_w,
+                                            float* dqn_b, float* dkn_w, float* dkn_b, void* scratch, hipStream_t st) {
   const AttTrainScratch S = attention_train_layout(scratch, b, heads, n, hd);
   const int npad = att_npad(n), nblk = (n + kAttBN - 1) / kAttBN;
   static amx::DeviceOnce attr_once;
@@ -569,3 +569,32 @@ hipError_t launch_attention_backward(const float* q, const float* k, const float
 }
 
 }  // namespace amx
+
+using amx::fail;
+
+extern "C" {
+
+size_t amx_attention_train_scratch_bytes(int b, int heads, int n, int head_dim) {
+  if (b < 1 || heads < 1 || n < 1 || head_dim < 2 || head_dim > 80 || (head_dim & 1)) return 0;
+  return amx::attention_train_scratch_bytes(b, heads, n, head_dim);
+}
+
+int amx_attention_backward(const float* d_q, const float* d_k, const float* d_v, const float* d_qn_w, const float* d_qn_b,
+                           const float* d_kn_w, const float* d_kn_b, float norm_eps, const float* d_rope, int n_prefix, int b, int n,
+                           int heads, int head_dim, const float* d_out, const float* d_lse, const float* d_dout, float* d_dq, float* d_dk,
+                           float* d_dv, float* d_dqn_w, float* d_dqn_b, float* d_dkn_w, float* d_dkn_b, void* d_scratch,
+                           size_t scratch_bytes, void* stream) {
+  if (!d_q || !d_k || !d_v || !d_out || !d_lse || !d_dout || !d_scratch) return fail(AMX_ERR_INVALID, "attention backward: null argument");
+  if (int rc = amx::attention_args_ok(d_qn_w, d_qn_b, d_kn_w, d_kn_b, n_prefix, b, n, heads, head_dim)) return rc;
+  if ((!d_qn_w && (d_dqn_w || d_dqn_b)) || (!d_kn_w && (d_dkn_w || d_dkn_b)))
+    return fail(AMX_ERR_INVALID, "attention backward: a norm gradient was asked for a norm that is absent");
+  const size_t need = amx::attention_train_scratch_bytes(b, heads, n, head_dim);
+  if (scratch_bytes < need || ((uintptr_t)d_scratch & 15))
+    return fail(AMX_ERR_WORKSPACE, "attention backward scratch needs %zu bytes, 16-byte aligned", need);
+  AMX_HIP(amx::launch_attention_backward(d_q, d_k, d_v, d_qn_w, d_qn_b, d_kn_w, d_kn_b, norm_eps, d_rope, n_prefix, b, n, heads, head_dim,
+                                         d_out, d_lse, d_dout, d_dq, d_dk, d_dv, d_dqn_w, d_dqn_b, d_dkn_w, d_dkn_b, d_scratch,
+                                         (hipStream_t)stream));
+  return AMX_OK;
+}
+
+}  // extern "C"

@@ -520,8 +520,6 @@ bool conv_zx_shape_eligible(const ConvParams& p) {
   return !p.src0_f32c1 && p.C0 == 32 && p.C1 == 0 && p.Cout == 32 && out_ok && p.mxs &&
          ((p.W % 32 == 0 && p.H % 2 == 0) || (p.W % 16 == 0 && p.H % 4 == 0)) && p.D % 2 == 0 && p.D >= 4 && p.s0x == 32;
 }
-bool conv_zx_eligible(const ConvParams& p) { return (p.out32 || p.out) && conv_zx_shape_eligible(p); }
-int conv_zx_stats_slots(int H, int W) { return H * W / 32; }       // one per (tile, half tile), whichever tile shape runs
 
 template <typename C>
 static hipError_t launch_conv_zx_t(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st,
@@ -535,7 +533,7 @@ static hipError_t launch_conv_zx_t(ConvParams p, const float* in_ab, int in_act,
   }
   p.nby = p.H / C::TY;
   p.nbx = p.W / C::TX;
-  if (info)                                                  // slots: one per (tile, x half), as conv_zx_stats_slots
+  if (info)                                                  // slots: one per (tile, x half) = H * W / 32, whichever tile shape runs
     info->report(p.stats ? p.nby * p.nbx * 2 : 0, "conv3d_k3_zx<f16x2mx,32->32,%dx%dx%d,m4+x4+cv4,r%d%s%s>", C::TZ, C::TY, C::TX, C::R,
                  in_ab ? ",norm-in" : "", p.out32 ? ",o1" : "");
   ZxExtra e;
@@ -545,7 +543,7 @@ static hipError_t launch_conv_zx_t(ConvParams p, const float* in_ab, int in_act,
 }
 
 hipError_t launch_conv_zx(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st, ConvLaunchInfo* info) {
-  // 4x16 tiles wherever they fit, 2x32 otherwise (conv_zx_eligible admits nothing else)
+  // 4x16 tiles wherever they fit, 2x32 otherwise (conv_zx_shape_eligible admits nothing else)
   const bool tall_ok = p.W % 16 == 0 && p.H % 4 == 0;
   // (a ring of 8 planes instead of 6 for the 4x16 tiles: 1016 / 1067 -> 1015 / 1037 us, inside the noise -- not instantiated)
   // (two mailbox sets -- NBOX = 2, an mx wave one step ahead of its main waves: 1030 / 1014 -> 1036 / 1015 us, nothing -- not instantiated)

@@ -84,15 +84,6 @@ hipError_t launch_place_registers(const float* reg, int nreg, int E, int rows_pe
 hipError_t launch_colsum(const void* hi, const void* lo, int ld, int C, int nb, int rows_per_b, int nchunk, float* out, hipStream_t st);
 hipError_t launch_demean(const float* colsum, int nchunk, int ld, int K, long long rows_per_b, const float* W, int Creal, const float* bias, int nb,
                          float* mean, hipStream_t st);
-hipError_t launch_export_planar(const float* in, int C, long long vox, int nb, const float* sub, float* out, hipStream_t st);
-
-// ---- linear layers under autograd (amx_linear_bwd.hip) ----------------------------------------------------------------
-// y = x W^T + b and its three gradients for fp32 x [M][K], W [N][K], dy [M][N]; operands rounded once to f16, fp32 sums.
-size_t linear_train_scratch_bytes(long long M, int K, int N);   // 0 outside the envelope (K % 4, N % 4, M * max(K, N) beyond int)
-hipError_t launch_linear_forward(const float* x, const float* w, const float* bias, long long M, int K, int N, float* y, void* scratch,
-                                 hipStream_t st);
-hipError_t launch_linear_backward(const float* x, const float* w, const float* dy, long long M, int K, int N, float* dx, float* dw,
-                                  float* dbias, void* scratch, hipStream_t st);
 
 // ---- tokenizer (amx_tokenizer.hip) ----------------------------------------------------------------------------------
 struct TokConvParams {

@@ -1119,7 +1119,7 @@ __global__ __launch_bounds__(256) void export_planar_kernel(const float* __restr
     out[((long long)b * C + c) * vox + v0 + v] = tile[v * (C + 1) + c] - (sub ? sub[b * C + c] : 0.f);
   }
 }
-hipError_t launch_export_planar(const float* in, int C, long long vox, int nb, const float* sub, float* out, hipStream_t st) {
+static hipError_t launch_export_planar(const float* in, int C, long long vox, int nb, const float* sub, float* out, hipStream_t st) {
   if (vox % 64 || C > 128) return hipErrorInvalidValue;
   hipLaunchKernelGGL(export_planar_kernel, dim3((unsigned)(vox / 64), nb), dim3(256), 64 * (C + 1) * sizeof(float), st, in, C, vox, sub, out);
   return hipGetLastError();

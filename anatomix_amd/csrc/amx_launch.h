@@ -1,7 +1,10 @@
-// anatomix_amd -- host-side declarations shared between translation units: every amx:: function that one .hip file defines and
-// another calls, with its default arguments (stated here and nowhere else), plus the error helper of the C ABI entries, the cached CU
-// count of a device and the one statement of the stored tensor layouts (the stride setters at the end).  The conv launchers keep no
-// state between calls: what a launch ran, and how many statistics slots it wrote, comes back through the caller's ConvLaunchInfo.
+// anatomix_amd -- host-side declarations shared between translation units: the amx:: functions that one .hip file defines and
+// ANOTHER calls, with their default arguments.  A C ABI entry lives in the file that defines the launcher it calls;
+// a launcher that only its own file calls is `static` there, carries its default arguments at its definition and is not declared
+// here (tests/test_launch_header.py holds this header and amx_gemm.h to that).  Also here: the error helper of the C ABI entries, their
+// shared checks, the cached CU count of a device and the one statement of the stored tensor layouts (the stride setters at the end).
+// The conv launchers keep no state between calls: what a launch ran, and how many statistics slots it wrote, comes back through the
+// caller's ConvLaunchInfo.
 // Not part of the public C ABI (that is include/anatomix_amd.h).  The ViT engine's launchers and parameter structs are in amx_gemm.h.
 #pragma once
 #include <stdarg.h>
@@ -66,9 +69,7 @@ bool conv_zmarch_eligible_split(const ConvParams& p);
 hipError_t launch_conv_zmarch(const ConvParams& p, int precision, hipStream_t st, ConvLaunchInfo* info = nullptr);
 
 // amx_conv3d_zx.hip
-bool conv_zx_eligible(const ConvParams& p);
-bool conv_zx_shape_eligible(const ConvParams& p);     // the same, less "the 16-bit output has memory"
-int conv_zx_stats_slots(int H, int W);
+bool conv_zx_shape_eligible(const ConvParams& p);     // shapes only: p.out is not asked, its strides are
 size_t conv_zx_packed_bytes();
 hipError_t launch_pack_weights_zx(const float* w, const float* scale, void* wx, const int* mxs, int CoutReal, hipStream_t st);
 hipError_t launch_conv_zx(ConvParams p, const float* in_ab, int in_act, float in_slope, const void* wx, hipStream_t st, ConvLaunchInfo* info = nullptr);
@@ -108,15 +109,8 @@ hipError_t launch_affine_act(void* x, const float* scale, const float* shift, in
 hipError_t launch_export_ncdhw(const void* src0, int C0, const void* src1, int C1, int up_shift, int N, int D, int H, int W,
                                float* out, int precision, hipStream_t st, int S0 = 0, int S1 = 0);
 hipError_t launch_import_input(const float* src, void* dst, int N, int Cin, long long vox, int precision, hipStream_t st);
-hipError_t launch_import_ncdhw(const float* src, void* dst, int N, int C, int D, int H, int W, long long dn, long long dz,
-                               long long dy, long long dx, int accumulate, int precision, hipStream_t st);
-hipError_t launch_upsample2_trilinear_backward(const void* gout, void* gin, int N, int D, int H, int W, int C, int precision,
-                                               hipStream_t st);
 
 // amx_sw.hip
-hipError_t launch_sw_normalize(float* acc, const float* cnt, int channels, long long voxels, hipStream_t st);
-hipError_t launch_sw_count(float* cnt, int vd, int vh, int vw, int oz, int oy, int ox, int rd, int rh,
-                           int rw, const float* wmap, hipStream_t st);
 // The window schedule of one axis (registration/sliding_window.py window_starts): start i = min(i * interval, size - roi) for
 // i in [0, count).  The one statement of that arithmetic: amx_sw_plan lists the corners from it, the count-map kernel walks it.
 struct SwAxis {
@@ -132,17 +126,8 @@ struct SwPlan {
     zyx[0] = ax[0].start(i / (ax[2].count * ax[1].count));
   }
 };
-constexpr int kSwMaxWindows = 1 << 20;
-// AMX_OK and the plan, or AMX_ERR_SHAPE (a volume smaller than the roi, a non-positive size, more than kSwMaxWindows windows)
-int sw_make_plan(int vd, int vh, int vw, int rd, int rh, int rw, double overlap, SwPlan* plan);
+constexpr int kSwMaxWindows = 1 << 20;         // a plan holds no more windows than this
 constexpr int kSwMaxF = 64, kSwMaxC = 32;      // the head envelope of sw_finish: amx_seg_argmax's (amx_segloss.hip)
-hipError_t launch_sw_count_all(float* cnt, const SwPlan& plan, const float* wmap, hipStream_t st);
-hipError_t launch_sw_importance_map(float* wmap, int rd, int rh, int rw, int mode, double sigma_scale, hipStream_t st);
-// kind: AMX_SW_FEATURES (acc /= cnt in place, launch_sw_normalize's arithmetic), AMX_SW_LOGITS, AMX_SW_LABELS
-hipError_t launch_sw_finish(int kind, float* acc, const float* cnt, int feat, long long voxels, const float* w, const float* b, int classes,
-                            void* out, hipStream_t st);
-// AMX_OK, or AMX_ERR_INVALID for a mode that is neither constant nor gaussian, or a gaussian without a positive sigma_scale
-int sw_map_check(int mode, double sigma_scale);
 // off[i] = where window i of offsets_zyx[n][3] starts in a [vd][vh][vw] volume, in voxels; AMX_ERR_SHAPE when a window leaves the volume
 int sw_window_offsets(int vd, int vh, int vw, int rd, int rh, int rw, int n, const int* offsets_zyx, long long* off);
 // The window weights of the last (roi, mode, sigma_scale) on a network handle, created at first use.  fetch: `map` holds this key's
@@ -177,84 +162,11 @@ struct SwNet {
 int sw_run(const SwNet& net, SwMapCache& cache, SwLanes* lanes, int vd, int vh, int vw, double overlap, int mode, double sigma_scale, int n_batch,
            int out_kind, const float* d_w, const float* d_b, int classes, float* d_acc, float* d_cnt, void* d_out, hipStream_t st);
 
-// amx_train.hip
-size_t train_scratch_bytes(int C);
-hipError_t launch_bn_train_forward(const void* x, void* y, const float* gamma, const float* beta, float eps, long long rows, int C,
-                                   int act, float slope, void* scratch, float* save_mean, float* save_rstd, float* running_mean,
-                                   float* running_var, float momentum, int precision, hipStream_t st);
-hipError_t launch_bn_act_backward(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
-                                  const float* gamma, const float* beta, float* dgamma, float* dbeta, void* dx_framed, int N, int D,
-                                  int H, int W, int C, int act, float slope, void* scratch, int precision, hipStream_t st);
-hipError_t launch_pad_fold(const void* g_framed, void* din, int N, int D, int H, int W, int C, int accumulate, int precision,
-                           hipStream_t st);
-hipError_t launch_dgrad_fold_shell(const void* dy, long long yn, long long yz, long long yy, long long yx, int cdy, const float* w,
-                                   int co_real, int ci_real, void* dx, int cdx, int N, int D, int H, int W, int precision, void* scratch,
-                                   hipStream_t st);
-size_t dgrad_shell_scratch_bytes();
-hipError_t launch_pool2_max_backward(const void* dp, const void* in, void* din, int N, int Do, int Ho, int Wo, int C,
-                                     int accumulate, int precision, hipStream_t st);
-hipError_t launch_upcat_split(const void* dcat, void* dskip, void* dlow, int N, int Dl, int Hl, int Wl, int c0, int c1,
-                              int acc_skip, int framed, int precision, hipStream_t st);
-
-// amx_wgrad.hip
-size_t wgrad_scratch_bytes(int N, int D, int H, int W, int Cout, int CinPad);
-hipError_t launch_wgrad(WgradParams p, int CinReal, float* dw, int accumulate, void* scratch, int precision, hipStream_t st);
-
-// amx_optim.hip
-hipError_t launch_adamw(const long long* table, int count, double lr, double b1, double b2, double eps, double wd, int maximize,
-                        hipStream_t st, const double* d_hyper = nullptr, const float* d_norm = nullptr, double max_norm = 0.0);
-size_t grad_norms_scratch_bytes(const long long* table, int count, int groups);
-hipError_t launch_grad_norms(const long long* table, int count, int groups, float* out, void* scratch, size_t scratch_bytes,
-                             hipStream_t st);
-
-// amx_supcon.hip
-size_t supcon_scratch_bytes(int N, int C);
-hipError_t launch_supcon(const float* feat, const int* labels, int N, int C, float temperature, int rarity, int balance,
-                         int sqrt_mode, float* loss, float* grad, void* scratch, hipStream_t st);
-hipError_t launch_supcon_batch(int nb, const float* const* feat, const int* const* labels, int N, int C, float temperature, int rarity,
-                               int balance, int sqrt_mode, float* const* loss, float* const* grad, void* scratch, hipStream_t st);
-
 // amx_mlp.hip
-hipError_t launch_mlp_layer_forward(const float* x, int n, int k, const float* w, int m, const float* gamma, const float* beta,
-                                    float eps, int act, float slope, float* z, float* y, float* mean, float* rstd, float* rmean,
-                                    float* rvar, float momentum, hipStream_t st);
-hipError_t launch_mlp_layer_backward(const float* dy, const float* y, const float* z, const float* mean, const float* rstd,
-                                     const float* gamma, int act, float slope, const float* x, const float* w, int n, int k,
-                                     int m, float* dz, float* dgamma, float* dbeta, float* dw, float* dx, float* wpart,
-                                     hipStream_t st);
-size_t mlp_backward_scratch_floats(int n, int cin, int width);
-hipError_t launch_mlp_heads_layer_forward(int nb, const float* const* x, int n, const int* k, const float* const* w, int m,
-                                          const float* const* gamma, const float* const* beta, float eps, int act, float slope,
-                                          float* const* z, float* const* y, float* const* mean, float* const* rstd,
-                                          float* const* rmean, float* const* rvar, float momentum, hipStream_t st);
-hipError_t launch_mlp_heads_layer_backward(int nb, const float* const* dy, const float* const* y, const float* const* z,
-                                           const float* const* mean, const float* const* rstd, const float* const* gamma, int act,
-                                           float slope, const float* const* x, const float* const* w, int n, const int* k, int m,
-                                           float* const* dz, float* const* dgamma, float* const* dbeta, float* const* dw,
-                                           float* const* dx, float* const* wpart, hipStream_t st);
 hipError_t launch_small_gemm_batch(int nb, bool ta, bool tb, const float* const* A, const float* const* B, float* const* Cm, int M,
                                    int N, int R, int splits, float scale, hipStream_t st);
 
-// amx_sample.hip
-hipError_t launch_gather_labels_batch(const float* seg, int D, int H, int W, int nb, const long long* const* coords, int P, const int* dims,
-                                      int views, int* const* out, hipStream_t st);
-hipError_t launch_sample_coords(const long long* draws, int n, int num, int d0, int d1, int d2, long long* coords, hipStream_t st);
-hipError_t launch_sample_perm(const long long* keys, int nvox, int num, int d1, int d2, long long* coords, hipStream_t st);
-hipError_t launch_gather_labels(const float* seg, int D, int H, int W, const long long* coords, int P, int d, int h, int w, int views,
-                                int* out, hipStream_t st);
-hipError_t launch_gather_rows(const void* src, int dtype, long long sn, long long sz, long long sy, long long sx, long long sc,
-                              const long long* coords, int N, int P, int C, float* rows, hipStream_t st);
-hipError_t launch_sampled_conv_backward(const float* g, const long long* coords, const void* x, int xc, const float* w, int N, int P, int D,
-                                        int H, int W, int Cout, int Cin, float* dw, void* din, int dc, void* scratch, int precision,
-                                        hipStream_t st);
-size_t sampled_conv_backward_scratch_bytes(int P);
-hipError_t launch_scatter_rows(const float* rows, const long long* coords, void* dst, int dtype, long long dn, long long dz, long long dy,
-                               long long dx, int N, int P, int C, int accumulate, hipStream_t st);
-
 // amx_regfeat.hip
-size_t mindssc_scratch_bytes(int H, int W, int D);
-hipError_t launch_mindssc(const float* img, int H, int W, int D, int radius, int dilation, float* out, void* scratch,
-                          hipStream_t st);
 hipError_t launch_pool_cat(const float* a, int ca, float sa, const float* b, int cb, float sb, int H, int W, int D, int g,
                            float* out, hipStream_t st);
 hipError_t launch_box_filter(const float* in, float* out, int C, int H, int W, int D, int k, hipStream_t st);
@@ -266,67 +178,22 @@ hipError_t launch_correlate(const float* fix, const float* mov, int C, int h, in
 hipError_t launch_resize_trilinear(const float* in, int C, int h, int w, int d, float* out, int H, int W, int D,
                                    const float* scale, int flip, hipStream_t st);
 
-// amx_reginstopt.hip
-hipError_t launch_instopt_smooth3(const float* in, float* out, int h, int w, int d, hipStream_t st);
-size_t instopt_scratch_bytes(int h, int w, int d);
-hipError_t launch_instopt_grad(const float* weight, const float* fix, const float* mov, int c, int h, int w, int d, float lambda,
-                               float* grad_weight, float* disp_sample, float* loss2, void* scratch, hipStream_t st);
-hipError_t launch_instopt_adam(float* weight, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr, int t,
-                               hipStream_t st, bool zero_moments = false);
-hipError_t launch_instopt(float* weight, const float* fix, const float* mov, int c, int h, int w, int d, float lambda, double lr,
-                          int niter, float* fitted, void* scratch, hipStream_t st);
-size_t run_instopt_scratch_bytes(int c, int H, int W, int D, int g, int smooth);
-hipError_t launch_run_instopt(const float* disp_hr, const float* feat_fix, const float* feat_mov, int c, int H, int W, int D, int g,
-                              float lambda, int niter, int smooth, double lr, float* out, void* scratch, hipStream_t st);
-hipError_t launch_warp3d(const float* vol, int c, const float* disp, int H, int W, int D, int nearest, float* out, hipStream_t st);
-
-// amx_regmetrics.hip
-hipError_t launch_label_overlap(const void* a, int lt_a, const void* b, int lt_b, long long voxels, int bins, long long* counts,
-                                long long* bad, hipStream_t st);
-size_t jacobian_det_scratch_bytes(int H, int W, int D);
-hipError_t launch_jacobian_det(const float* disp, int H, int W, int D, int add_identity, float* jdet, float* stats, void* scratch,
-                               hipStream_t st);
-
 // amx_segaug.hip: the min / max of n rows of V floats (CLIP: of max(x, 0)) as per-workgroup partial pairs in `scratch`
-// (minmax_bytes), and their reduction to minmax[n][2]
+// (minmax_bytes)
 size_t minmax_bytes(int n, long long V);
 hipError_t launch_minmax_partials(const float* x, int n, long long V, bool clip, void* scratch, hipStream_t st);
-hipError_t launch_minmax_finalize(const void* scratch, int n, long long V, float* minmax, hipStream_t st);
 
 // amx_attention.hip
 size_t attention_scratch_bytes(int b, int heads, int n);
 void attention_operands(void* scratch, int b, int heads, int n, void** Qp, void** Kp, void** Vt, int* npad_out, int* nblk_pad_out);
 hipError_t launch_attention_fwd(const void* Qp, const void* Kp, const void* Vt, int b, int n, int heads, int hd, float* out, hipStream_t st,
                                 float* lse = nullptr);     // lse: [b][heads][n] log-sum-exp (exp2 domain) for the backward, or null
-hipError_t launch_attention(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
-                            const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
-                            float* out, void* scratch, hipStream_t st, float* lse = nullptr);
-
-// amx_attention_bwd.hip
-size_t attention_train_scratch_bytes(int b, int heads, int n, int hd);
-hipError_t launch_attention_backward(const float* q, const float* k, const float* v, const float* qn_w, const float* qn_b, const float* kn_w,
-                                     const float* kn_b, float eps, const float* rope, int n_prefix, int b, int n, int heads, int hd,
-                                     const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv, float* dqn_w,
-                                     float* dqn_b, float* dkn_w, float* dkn_b, void* scratch, hipStream_t st);
 
 // amx_api.hip: stores the thread-local message that amx_last_error() returns, and gives `code` back
 int fail(int code, const char* fmt, ...);
 // the scratch check of the C ABI entries: AMX_OK, or AMX_ERR_WORKSPACE when the caller's `got` bytes are fewer than `need`
 inline int need_scratch(size_t need, size_t got) {
   return got < need ? fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes (got %zu)", need, got) : AMX_OK;
-}
-
-// the argument check of amx_sw_finish, shared with sw_run (amx_sw.hip), which makes it before its first launch
-inline int sw_finish_check(int kind, const float* acc, const float* cnt, int feat, long long voxels, const float* w, int classes,
-                           const void* out) {
-  if (kind != AMX_SW_FEATURES && kind != AMX_SW_LOGITS && kind != AMX_SW_LABELS)
-    return fail(AMX_ERR_INVALID, "output kind: features (0), logits (1) or labels (2) (got %d)", kind);
-  if (!acc || !cnt || feat < 1 || voxels < 1 || voxels >= (1LL << 40)) return fail(AMX_ERR_INVALID, "bad argument");
-  if (kind == AMX_SW_FEATURES) return AMX_OK;
-  if (classes < 2 || classes > kSwMaxC) return fail(AMX_ERR_INVALID, "2 <= classes <= %d (got %d)", kSwMaxC, classes);
-  if (feat > kSwMaxF) return fail(AMX_ERR_INVALID, "1 <= feat <= %d head input channels (got %d)", kSwMaxF, feat);
-  if (!w || !out) return fail(AMX_ERR_INVALID, "logits and labels need the head's weight and an output buffer");
-  return AMX_OK;
 }
 
 // the checks of the row-streaming C ABI units (amx_segaug.hip, amx_preaug.hip, amx_synth.hip).  A unit names its rows: `count` is

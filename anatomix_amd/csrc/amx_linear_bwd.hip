@@ -24,6 +24,7 @@
 
 #include "amx_device.h"
 #include "amx_gemm.h"
+#include "amx_launch.h"
 
 namespace amx {
 
@@ -37,7 +38,6 @@ constexpr int kLinMinSteps = 16;        // token steps per chunk, at least
 constexpr int kLinWantWg = 512;         // workgroups a wgrad launch aims for (2 per CU)
 
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 struct LinPlan {
   int ldk, ldn, KT, NT, KS, NS, MS;     // padded row lengths (halves); 16-feature tiles; 32-column steps of K / N; 32-token steps
@@ -286,13 +286,13 @@ hipError_t launch_image(const float* src, long long M, int C, int ld, int CT, in
 
 }  // namespace
 
-size_t linear_train_scratch_bytes(long long M, int K, int N) {
+static size_t linear_train_scratch_bytes(long long M, int K, int N) {
   LinPlan p;
   return linear_plan(M, K, N, &p) ? p.bytes : 0;
 }
 
-hipError_t launch_linear_forward(const float* x, const float* w, const float* bias, long long M, int K, int N, float* y, void* scratch,
-                                 hipStream_t st) {
+static hipError_t launch_linear_forward(const float* x, const float* w, const float* bias, long long M, int K, int N, float* y, void* scratch,
+                                        hipStream_t st) {
   LinPlan p;
   if (!linear_plan(M, K, N, &p)) return hipErrorInvalidValue;
   char* sc = (char*)scratch;
@@ -308,8 +308,8 @@ hipError_t launch_linear_forward(const float* x, const float* w, const float* bi
   return launch_gemm(g, EPI_F32, st);
 }
 
-hipError_t launch_linear_backward(const float* x, const float* w, const float* dy, long long M, int K, int N, float* dx, float* dw,
-                                  float* dbias, void* scratch, hipStream_t st) {
+static hipError_t launch_linear_backward(const float* x, const float* w, const float* dy, long long M, int K, int N, float* dx, float* dw,
+                                         float* dbias, void* scratch, hipStream_t st) {
   LinPlan p;
   if (!linear_plan(M, K, N, &p)) return hipErrorInvalidValue;
   char* sc = (char*)scratch;
@@ -350,3 +350,72 @@ hipError_t launch_linear_backward(const float* x, const float* w, const float* d
 }
 
 }  // namespace amx
+
+namespace {
+using amx::fail;
+
+// the envelope and the scratch of the two linear entries: AMX_OK or the refusal, before any launch
+int linear_args_ok(const char* what, long long m, int k, int n, const void* d_scratch, size_t scratch_bytes) {
+  const size_t need = amx::linear_train_scratch_bytes(m, k, n);
+  if (need == 0)
+    return fail(AMX_ERR_INVALID, "%s: (M, K, N) = (%lld, %d, %d) is outside the envelope (K, N multiples of 4 up to 2^20, M * max(K, N) < 2^31)",
+                what, m, k, n);
+  if (!d_scratch || scratch_bytes < need || ((uintptr_t)d_scratch & 15)) return fail(AMX_ERR_WORKSPACE, "%s scratch needs %zu bytes, 16-byte aligned", what, need);
+  return AMX_OK;
+}
+bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return !(((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15);
+}
+}  // namespace
+
+extern "C" {
+
+size_t amx_linear_train_scratch_bytes(long long m, int k, int n) { return amx::linear_train_scratch_bytes(m, k, n); }
+
+int amx_linear(const float* d_x, const float* d_w, const float* d_b, int m, int k, int n, int split, float* d_y, void* stream) {
+  if (!d_x || !d_w || !d_y) return fail(AMX_ERR_INVALID, "null argument");
+  if (m < 1 || k < 1 || n < 4 || (n % 4) || k > 64 * 17) return fail(AMX_ERR_INVALID, "linear: m >= 1, 1 <= k <= 1088, n a multiple of 4 (got %d %d %d)", m, k, n);
+  hipStream_t st = (hipStream_t)stream;
+  auto up = [](int v, int mult) { return (v + mult - 1) / mult * mult; };
+  const int kp = up(k, 32), ntiles = up(n, 16) / 16, KS = kp / 32;
+  const size_t abytes = (size_t)m * kp * 2, wbytes = (size_t)ntiles * KS * 1024, bbytes = (size_t)ntiles * 16 * 4;
+  char* buf = nullptr;
+  AMX_HIP(hipMalloc((void**)&buf, 2 * abytes + 2 * wbytes + bbytes + 1024));
+  char *a_hi = buf, *a_lo = buf + abytes, *w_hi = buf + 2 * abytes, *w_lo = w_hi + wbytes;
+  float* bias = (float*)(w_lo + wbytes);
+  int rc = AMX_OK;
+  hipError_t e = amx::launch_ln_rows(d_x, 0, k, k, nullptr, nullptr, 0.f, m, m, m, 0, 0, a_hi, split ? a_lo : nullptr, kp, st);
+  if (e == hipSuccess) e = amx::launch_pack_gemm(d_w, nullptr, nullptr, n, 0, 0, k, 0, 0, 0, ntiles, KS, w_hi, split ? w_lo : nullptr, st);
+  if (e == hipSuccess) e = amx::launch_vec_place(bias, d_b, n, 0.f, st);
+  if (e == hipSuccess && ntiles * 16 > n) e = amx::launch_vec_place(bias + n, nullptr, ntiles * 16 - n, 0.f, st);
+  if (e == hipSuccess) {
+    amx::GemmParams g{};
+    g.a_hi = a_hi; g.a_lo = split ? a_lo : nullptr; g.lda = kp; g.M = m; g.KS = KS; g.w_hi = w_hi; g.w_lo = split ? w_lo : nullptr;
+    g.ntiles = ntiles; g.Nreal = n; g.bias = bias; g.out = d_y; g.ldo = n;
+    e = amx::launch_gemm(g, amx::EPI_F32, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) rc = fail(AMX_ERR_HIP, "linear: %s", hipGetErrorString(e));
+  (void)hipFree(buf);
+  return rc;
+}
+
+int amx_linear_forward(const float* d_x, const float* d_w, const float* d_bias, long long m, int k, int n, float* d_y, void* d_scratch,
+                       size_t scratch_bytes, void* stream) {
+  if (!d_x || !d_w || !d_y) return fail(AMX_ERR_INVALID, "linear forward: null argument");
+  if (int rc = linear_args_ok("linear forward", m, k, n, d_scratch, scratch_bytes)) return rc;
+  if (!aligned16(d_x, d_y)) return fail(AMX_ERR_INVALID, "linear forward: d_x and d_y must be 16-byte aligned");
+  AMX_HIP(amx::launch_linear_forward(d_x, d_w, d_bias, m, k, n, d_y, d_scratch, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_linear_backward(const float* d_x, const float* d_w, const float* d_dy, long long m, int k, int n, float* d_dx, float* d_dw,
+                        float* d_dbias, void* d_scratch, size_t scratch_bytes, void* stream) {
+  if (!d_x || !d_w || !d_dy) return fail(AMX_ERR_INVALID, "linear backward: null argument");
+  if (int rc = linear_args_ok("linear backward", m, k, n, d_scratch, scratch_bytes)) return rc;
+  if (!aligned16(d_x, d_dy, d_dx, d_dw)) return fail(AMX_ERR_INVALID, "linear backward: d_x, d_dy, d_dx and d_dw must be 16-byte aligned");
+  AMX_HIP(amx::launch_linear_backward(d_x, d_w, d_dy, m, k, n, d_dx, d_dw, d_dbias, d_scratch, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+}  // extern "C"

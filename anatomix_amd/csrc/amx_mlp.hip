@@ -432,10 +432,10 @@ static void gemm_dispatch(const float* A, const float* B, float* Cm, int M, int 
 static inline int rows_per_thread(int n) { return n <= 256 ? 1 : n <= 512 ? 2 : n <= 1024 ? 4 : 8; }
 
 // One layer of nb heads (same rows n and width m, own input widths k[b]): z = x w^T, then BatchNorm1d(train) + activation.
-hipError_t launch_mlp_heads_layer_forward(int nb, const float* const* x, int n, const int* k, const float* const* w, int m,
-                                          const float* const* gamma, const float* const* beta, float eps, int act, float slope,
-                                          float* const* z, float* const* y, float* const* mean, float* const* rstd,
-                                          float* const* rmean, float* const* rvar, float momentum, hipStream_t st) {
+static hipError_t launch_mlp_heads_layer_forward(int nb, const float* const* x, int n, const int* k, const float* const* w, int m,
+                                                 const float* const* gamma, const float* const* beta, float eps, int act, float slope,
+                                                 float* const* z, float* const* y, float* const* mean, float* const* rstd,
+                                                 float* const* rmean, float* const* rvar, float momentum, hipStream_t st) {
   GemmBatch g;
   g.nb = nb; g.splits = 1; g.scale = 1.f;
   BnFwdBatch bt;
@@ -457,23 +457,23 @@ hipError_t launch_mlp_heads_layer_forward(int nb, const float* const* x, int n, 
   return hipGetLastError();
 }
 
-hipError_t launch_mlp_layer_forward(const float* x, int n, int k, const float* w, int m, const float* gamma, const float* beta,
-                                    float eps, int act, float slope, float* z, float* y, float* mean, float* rstd, float* rmean,
-                                    float* rvar, float momentum, hipStream_t st) {
+static hipError_t launch_mlp_layer_forward(const float* x, int n, int k, const float* w, int m, const float* gamma, const float* beta,
+                                           float eps, int act, float slope, float* z, float* y, float* mean, float* rstd, float* rmean,
+                                           float* rvar, float momentum, hipStream_t st) {
   return launch_mlp_heads_layer_forward(1, &x, n, &k, &w, m, &gamma, &beta, eps, act, slope, &z, &y, &mean, &rstd, &rmean, &rvar,
                                         momentum, st);
 }
 
-size_t mlp_backward_scratch_floats(int n, int cin, int width) {
+static size_t mlp_backward_scratch_floats(int n, int cin, int width) {
   return 2 * (size_t)n * width + (size_t)MLP_WSPLIT * width * (cin > width ? cin : width);
 }
 
 // Adjoint of one layer of nb heads: dz (activation + BatchNorm adjoint), dW = dZ^T X (row-split + ordered sum), dX = dZ W (where asked).
-hipError_t launch_mlp_heads_layer_backward(int nb, const float* const* dy, const float* const* y, const float* const* z,
-                                           const float* const* mean, const float* const* rstd, const float* const* gamma, int act,
-                                           float slope, const float* const* x, const float* const* w, int n, const int* k, int m,
-                                           float* const* dz, float* const* dgamma, float* const* dbeta, float* const* dw,
-                                           float* const* dx, float* const* wpart, hipStream_t st) {
+static hipError_t launch_mlp_heads_layer_backward(int nb, const float* const* dy, const float* const* y, const float* const* z,
+                                                  const float* const* mean, const float* const* rstd, const float* const* gamma, int act,
+                                                  float slope, const float* const* x, const float* const* w, int n, const int* k, int m,
+                                                  float* const* dz, float* const* dgamma, float* const* dbeta, float* const* dw,
+                                                  float* const* dx, float* const* wpart, hipStream_t st) {
   BnBwdBatch bt;
   for (int b = 0; b < nb; ++b) {
     bt.dy[b] = dy[b]; bt.y[b] = y[b]; bt.z[b] = z[b]; bt.mean[b] = mean[b]; bt.rstd[b] = rstd[b]; bt.gamma[b] = gamma[b];
@@ -514,10 +514,10 @@ hipError_t launch_mlp_heads_layer_backward(int nb, const float* const* dy, const
   return hipGetLastError();
 }
 
-hipError_t launch_mlp_layer_backward(const float* dy, const float* y, const float* z, const float* mean, const float* rstd,
-                                     const float* gamma, int act, float slope, const float* x, const float* w, int n, int k,
-                                     int m, float* dz, float* dgamma, float* dbeta, float* dw, float* dx, float* wpart,
-                                     hipStream_t st) {
+static hipError_t launch_mlp_layer_backward(const float* dy, const float* y, const float* z, const float* mean, const float* rstd,
+                                            const float* gamma, int act, float slope, const float* x, const float* w, int n, int k,
+                                            int m, float* dz, float* dgamma, float* dbeta, float* dw, float* dx, float* wpart,
+                                            hipStream_t st) {
   return launch_mlp_heads_layer_backward(1, &dy, &y, &z, &mean, &rstd, &gamma, act, slope, &x, &w, n, &k, m, &dz, &dgamma, &dbeta,
                                          &dw, &dx, &wpart, st);
 }
@@ -546,3 +546,136 @@ hipError_t launch_small_gemm(bool ta, bool tb, const float* A, const float* B, f
 }
 
 }  // namespace amx
+
+using amx::fail;
+
+static int mlp_check(int n, int cin, int width, int n_layers) {
+  if (n < 1 || n > 2048) return fail(AMX_ERR_SHAPE, "mlp head: 1 <= n <= 2048 rows (got %d)", n);
+  if (cin < 4 || cin % 4 || width < 8 || width % 8) return fail(AMX_ERR_SHAPE, "mlp head: cin %% 4 == 0 and width %% 8 == 0 (got %d, %d)", cin, width);
+  if (cin > 4096 || width > 4096) return fail(AMX_ERR_SHAPE, "mlp head: at most 4096 features per layer (got %d, %d)", cin, width);
+  if (n_layers < 1 || n_layers > 8) return fail(AMX_ERR_INVALID, "mlp head: 1 <= n_layers <= 8 (got %d)", n_layers);
+  return AMX_OK;
+}
+
+extern "C" {
+
+int amx_mlp_head_forward(const float* d_x, int n, int cin, int width, int n_layers, const float* const* w,
+                         const float* const* gamma, const float* const* beta, float* const* running_mean,
+                         float* const* running_var, float eps, float momentum, int act, float slope, float* d_z, float* d_y,
+                         float* d_mean, float* d_rstd, void* stream) {
+  if (!d_x || !w || !gamma || !beta || !running_mean || !running_var || !d_z || !d_y || !d_mean || !d_rstd)
+    return fail(AMX_ERR_INVALID, "null argument");
+  if (int rc = mlp_check(n, cin, width, n_layers)) return rc;
+  if (act != AMX_ACT_NONE && act != AMX_ACT_RELU && act != AMX_ACT_LRELU) return fail(AMX_ERR_INVALID, "unsupported activation");
+  const size_t plane = (size_t)n * width;
+  for (int l = 0; l < n_layers; ++l) {
+    if (!w[l] || (!gamma[l] != !beta[l]) || (!running_mean[l] != !running_var[l])) return fail(AMX_ERR_INVALID, "layer %d: bad parameter pointers", l);
+    AMX_HIP(amx::launch_mlp_layer_forward(l ? d_y + (l - 1) * plane : d_x, n, l ? width : cin, w[l], width, gamma[l], beta[l], eps,
+                                          l + 1 < n_layers ? act : AMX_ACT_NONE, slope, d_z + l * plane, d_y + l * plane,
+                                          d_mean + (size_t)l * width, d_rstd + (size_t)l * width, running_mean[l], running_var[l],
+                                          momentum, (hipStream_t)stream));
+  }
+  return AMX_OK;
+}
+
+size_t amx_mlp_head_scratch_bytes(int n, int cin, int width) { return amx::mlp_backward_scratch_floats(n, cin, width) * sizeof(float); }
+
+int amx_mlp_head_backward(const float* d_dy, const float* d_x, int n, int cin, int width, int n_layers,
+                          const float* const* w, const float* const* gamma, int act, float slope, const float* d_z,
+                          const float* d_y, const float* d_mean, const float* d_rstd, float* const* dw, float* const* dgamma,
+                          float* const* dbeta, float* d_dx, void* d_scratch, size_t scratch_bytes, void* stream) {
+  if (!d_dy || !d_x || !w || !gamma || !d_z || !d_y || !d_mean || !d_rstd || !dw || !dgamma || !dbeta || !d_scratch)
+    return fail(AMX_ERR_INVALID, "null argument");
+  if (int rc = mlp_check(n, cin, width, n_layers)) return rc;
+  if (int rc = amx::need_scratch(amx_mlp_head_scratch_bytes(n, cin, width), scratch_bytes)) return rc;
+  const size_t plane = (size_t)n * width;
+  float* dz = (float*)d_scratch;
+  float* dprev = dz + plane;
+  for (int l = n_layers - 1; l >= 0; --l) {
+    if (!w[l] || !dw[l] || (gamma[l] && (!dgamma[l] || !dbeta[l]))) return fail(AMX_ERR_INVALID, "layer %d: bad parameter pointers", l);
+    AMX_HIP(amx::launch_mlp_layer_backward(l + 1 < n_layers ? dprev : d_dy, d_y + l * plane, d_z + l * plane,
+                                           d_mean + (size_t)l * width, d_rstd + (size_t)l * width, gamma[l],
+                                           l + 1 < n_layers ? act : AMX_ACT_NONE, slope, l ? d_y + (l - 1) * plane : d_x, w[l], n,
+                                           l ? width : cin, width, dz, gamma[l] ? dgamma[l] : nullptr, gamma[l] ? dbeta[l] : nullptr,
+                                           dw[l], l ? dprev : d_dx, dprev + plane, (hipStream_t)stream));
+  }
+  return AMX_OK;
+}
+
+// ---- the heads of ONE contrastive step as batches: n_heads chains of the same length run as one chain of launches
+int amx_mlp_heads_forward(int n_heads, const float* const* d_x, int n, const int* cin, int width, int n_layers, const float* const* w,
+                          const float* const* gamma, const float* const* beta, float* const* running_mean, float* const* running_var,
+                          float eps, float momentum, int act, float slope, float* const* d_z, float* const* d_y, float* const* d_mean,
+                          float* const* d_rstd, void* stream) {
+  if (!d_x || !cin || !w || !gamma || !beta || !running_mean || !running_var || !d_z || !d_y || !d_mean || !d_rstd)
+    return fail(AMX_ERR_INVALID, "null argument");
+  if (n_heads < 1 || n_heads > amx::MLP_MAXB) return fail(AMX_ERR_INVALID, "1 <= heads <= %d (got %d)", amx::MLP_MAXB, n_heads);
+  if (act != AMX_ACT_NONE && act != AMX_ACT_RELU && act != AMX_ACT_LRELU) return fail(AMX_ERR_INVALID, "unsupported activation");
+  const size_t plane = (size_t)n * width;
+  for (int h = 0; h < n_heads; ++h) {
+    if (int rc = mlp_check(n, cin[h], width, n_layers)) return rc;
+    if (!d_x[h] || !d_z[h] || !d_y[h] || !d_mean[h] || !d_rstd[h]) return fail(AMX_ERR_INVALID, "head %d: null buffer", h);
+    for (int l = 0; l < n_layers; ++l) {
+      const int i = h * n_layers + l;
+      if (!w[i] || (!gamma[i] != !beta[i]) || (!running_mean[i] != !running_var[i]))
+        return fail(AMX_ERR_INVALID, "head %d layer %d: bad parameter pointers", h, l);
+    }
+  }
+  for (int l = 0; l < n_layers; ++l) {
+    const float *x[amx::MLP_MAXB], *wl[amx::MLP_MAXB], *gl[amx::MLP_MAXB], *bl[amx::MLP_MAXB];
+    float *z[amx::MLP_MAXB], *y[amx::MLP_MAXB], *mu[amx::MLP_MAXB], *rs[amx::MLP_MAXB], *rm[amx::MLP_MAXB], *rv[amx::MLP_MAXB];
+    int k[amx::MLP_MAXB];
+    for (int h = 0; h < n_heads; ++h) {
+      const int i = h * n_layers + l;
+      x[h] = l ? d_y[h] + (l - 1) * plane : d_x[h];
+      k[h] = l ? width : cin[h];
+      wl[h] = w[i]; gl[h] = gamma[i]; bl[h] = beta[i]; rm[h] = running_mean[i]; rv[h] = running_var[i];
+      z[h] = d_z[h] + l * plane; y[h] = d_y[h] + l * plane; mu[h] = d_mean[h] + (size_t)l * width; rs[h] = d_rstd[h] + (size_t)l * width;
+    }
+    AMX_HIP(amx::launch_mlp_heads_layer_forward(n_heads, x, n, k, wl, width, gl, bl, eps, l + 1 < n_layers ? act : AMX_ACT_NONE, slope,
+                                                z, y, mu, rs, rm, rv, momentum, (hipStream_t)stream));
+  }
+  return AMX_OK;
+}
+
+int amx_mlp_heads_backward(int n_heads, const float* const* d_dy, const float* const* d_x, int n, const int* cin, int width, int n_layers,
+                           const float* const* w, const float* const* gamma, int act, float slope, const float* const* d_z,
+                           const float* const* d_y, const float* const* d_mean, const float* const* d_rstd, float* const* dw,
+                           float* const* dgamma, float* const* dbeta, float* const* d_dx, void* const* d_scratch, size_t scratch_bytes,
+                           void* stream) {
+  if (!d_dy || !d_x || !cin || !w || !gamma || !d_z || !d_y || !d_mean || !d_rstd || !dw || !dgamma || !dbeta || !d_dx || !d_scratch)
+    return fail(AMX_ERR_INVALID, "null argument");
+  if (n_heads < 1 || n_heads > amx::MLP_MAXB) return fail(AMX_ERR_INVALID, "1 <= heads <= %d (got %d)", amx::MLP_MAXB, n_heads);
+  const size_t plane = (size_t)n * width;
+  for (int h = 0; h < n_heads; ++h) {
+    if (int rc = mlp_check(n, cin[h], width, n_layers)) return rc;
+    if (scratch_bytes < amx_mlp_head_scratch_bytes(n, cin[h], width))
+      return fail(AMX_ERR_WORKSPACE, "head %d: scratch needs %zu bytes (got %zu)", h, amx_mlp_head_scratch_bytes(n, cin[h], width), scratch_bytes);
+    if (!d_dy[h] || !d_x[h] || !d_z[h] || !d_y[h] || !d_mean[h] || !d_rstd[h] || !d_scratch[h]) return fail(AMX_ERR_INVALID, "head %d: null buffer", h);
+    for (int l = 0; l < n_layers; ++l) {
+      const int i = h * n_layers + l;
+      if (!w[i] || !dw[i] || (gamma[i] && (!dgamma[i] || !dbeta[i]))) return fail(AMX_ERR_INVALID, "head %d layer %d: bad parameter pointers", h, l);
+    }
+  }
+  for (int l = n_layers - 1; l >= 0; --l) {
+    const float *dy[amx::MLP_MAXB], *y[amx::MLP_MAXB], *z[amx::MLP_MAXB], *mu[amx::MLP_MAXB], *rs[amx::MLP_MAXB], *gl[amx::MLP_MAXB];
+    const float *x[amx::MLP_MAXB], *wl[amx::MLP_MAXB];
+    float *dz[amx::MLP_MAXB], *dg[amx::MLP_MAXB], *db[amx::MLP_MAXB], *dwl[amx::MLP_MAXB], *dx[amx::MLP_MAXB], *wpart[amx::MLP_MAXB];
+    int k[amx::MLP_MAXB];
+    for (int h = 0; h < n_heads; ++h) {
+      const int i = h * n_layers + l;
+      float* dzb = (float*)d_scratch[h];
+      float* dprev = dzb + plane;
+      dy[h] = l + 1 < n_layers ? dprev : d_dy[h];
+      y[h] = d_y[h] + l * plane; z[h] = d_z[h] + l * plane; mu[h] = d_mean[h] + (size_t)l * width; rs[h] = d_rstd[h] + (size_t)l * width;
+      gl[h] = gamma[i]; x[h] = l ? d_y[h] + (l - 1) * plane : d_x[h]; wl[h] = w[i]; k[h] = l ? width : cin[h];
+      dz[h] = dzb; dg[h] = gamma[i] ? dgamma[i] : nullptr; db[h] = gamma[i] ? dbeta[i] : nullptr; dwl[h] = dw[i];
+      dx[h] = l ? dprev : d_dx[h]; wpart[h] = dprev + plane;
+    }
+    AMX_HIP(amx::launch_mlp_heads_layer_backward(n_heads, dy, y, z, mu, rs, gl, l + 1 < n_layers ? act : AMX_ACT_NONE, slope, x, wl, n, k,
+                                                 width, dz, dg, db, dwl, dx, wpart, (hipStream_t)stream));
+  }
+  return AMX_OK;
+}
+
+}  // extern "C"

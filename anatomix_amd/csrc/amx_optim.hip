@@ -109,8 +109,8 @@ __global__ __launch_bounds__(256) void adamw_clip_kernel(AdamArgs a, const float
 }
 
 // table: count rows of 6 x 64-bit {p, g, m, v, step, numel} on the HOST.  d_norm non-null: the clipping step
-hipError_t launch_adamw(const long long* table, int count, double lr, double b1, double b2, double eps, double wd, int maximize,
-                        hipStream_t st, const double* d_hyper, const float* d_norm, double max_norm) {
+static hipError_t launch_adamw(const long long* table, int count, double lr, double b1, double b2, double eps, double wd, int maximize,
+                               hipStream_t st, const double* d_hyper = nullptr, const float* d_norm = nullptr, double max_norm = 0.0) {
   for (int t0 = 0; t0 < count; t0 += kAdamTensors) {
     AdamArgs a;
     const long long blocks = fill_adam_args(a, table, t0, count - t0 < kAdamTensors ? count - t0 : kAdamTensors);
@@ -171,14 +171,14 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
   if (threadIdx.x == 0) out[blockIdx.x] = (float)sqrt(acc);
 }
 
-size_t grad_norms_scratch_bytes(const long long* table, int count, int groups) {
+static size_t grad_norms_scratch_bytes(const long long* table, int count, int groups) {
   const long long blocks = norm_total_blocks(table, count, groups);
   return blocks < 0 ? 0 : norm_scratch_bytes(blocks);
 }
 
 // table: count rows of 3 x 64-bit {grad, numel, group} on the HOST
-hipError_t launch_grad_norms(const long long* table, int count, int groups, float* out, void* scratch, size_t scratch_bytes,
-                             hipStream_t st) {
+static hipError_t launch_grad_norms(const long long* table, int count, int groups, float* out, void* scratch, size_t scratch_bytes,
+                                    hipStream_t st) {
   const long long total = norm_total_blocks(table, count, groups);
   if (total < 0 || scratch_bytes < norm_scratch_bytes(total)) return hipErrorInvalidValue;
   if (groups == 0) return hipSuccess;
@@ -198,3 +198,66 @@ hipError_t launch_grad_norms(const long long* table, int count, int groups, floa
 }
 
 }  // namespace amx
+
+namespace {
+using amx::fail;
+
+// every row of an AdamW table: AMX_OK, or the first tensor with a null pointer or a negative size
+int adamw_tensors_ok(const amx_adamw_tensor* tensors, int count) {
+  for (int t = 0; t < count; ++t) {
+    const amx_adamw_tensor& r = tensors[t];
+    if (!r.param || !r.grad || !r.exp_avg || !r.exp_avg_sq || !r.step || r.numel < 0)
+      return fail(AMX_ERR_INVALID, "adamw: tensor %d has a null pointer or a negative size", t);
+  }
+  return AMX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int amx_adamw_step(const amx_adamw_tensor* tensors, int count, double lr, double beta1, double beta2, double eps, double weight_decay,
+                   int maximize, void* stream) {
+  static_assert(sizeof(amx_adamw_tensor) == 48, "six 64-bit fields");
+  if (count < 0 || (count && !tensors)) return fail(AMX_ERR_INVALID, "bad argument");
+  if (!(lr >= 0.0) || !(eps >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(weight_decay >= 0.0))
+    return fail(AMX_ERR_INVALID, "adamw: lr %g, betas (%g, %g), eps %g, weight_decay %g out of range", lr, beta1, beta2, eps, weight_decay);
+  if (int rc = adamw_tensors_ok(tensors, count)) return rc;
+  AMX_HIP(amx::launch_adamw((const long long*)tensors, count, lr, beta1, beta2, eps, weight_decay, maximize, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_adamw_step_dev(const amx_adamw_tensor* tensors, int count, const double* d_hyper, int maximize, void* stream) {
+  if (count < 0 || (count && !tensors) || !d_hyper) return fail(AMX_ERR_INVALID, "bad argument");
+  if (int rc = adamw_tensors_ok(tensors, count)) return rc;
+  AMX_HIP(amx::launch_adamw((const long long*)tensors, count, 0.0, 0.0, 0.0, 0.0, 0.0, maximize, (hipStream_t)stream, d_hyper));
+  return AMX_OK;
+}
+
+int amx_adamw_step_clip_dev(const amx_adamw_tensor* tensors, int count, const double* d_hyper, int maximize, const float* d_total_norm,
+                            double max_norm, void* stream) {
+  if (count < 0 || (count && !tensors) || !d_hyper || !d_total_norm || !(max_norm >= 0.0))
+    return fail(AMX_ERR_INVALID, "adamw: bad argument (max_norm %g)", max_norm);
+  if (int rc = adamw_tensors_ok(tensors, count)) return rc;
+  AMX_HIP(amx::launch_adamw((const long long*)tensors, count, 0.0, 0.0, 0.0, 0.0, 0.0, maximize, (hipStream_t)stream, d_hyper, d_total_norm,
+                            max_norm));
+  return AMX_OK;
+}
+
+size_t amx_grad_norms_scratch_bytes(const amx_grad_tensor* tensors, int count, int groups) {
+  static_assert(sizeof(amx_grad_tensor) == 24, "three 64-bit fields");
+  if (count < 0 || groups < 0 || (count && !tensors)) return 0;
+  return amx::grad_norms_scratch_bytes((const long long*)tensors, count, groups);
+}
+
+int amx_grad_norms(const amx_grad_tensor* tensors, int count, int groups, float* d_out, void* d_scratch, size_t scratch_bytes,
+                   void* stream) {
+  if (count < 0 || groups < 0 || (count && !tensors) || (groups && !d_out) || !d_scratch) return fail(AMX_ERR_INVALID, "bad argument");
+  for (int t = 0; t < count; ++t)
+    if (!tensors[t].grad && tensors[t].numel) return fail(AMX_ERR_INVALID, "grad_norms: tensor %d has a null pointer", t);
+  if (amx_grad_norms_scratch_bytes(tensors, count, groups) == 0 || scratch_bytes < amx_grad_norms_scratch_bytes(tensors, count, groups))
+    return fail(AMX_ERR_INVALID, "grad_norms: a negative size, a group outside [0, %d), too many blocks, or too little scratch", groups);
+  AMX_HIP(amx::launch_grad_norms((const long long*)tensors, count, groups, d_out, d_scratch, scratch_bytes, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+}  // extern "C"

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void warp3d_kernel(const float* __restrict__ v
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------
-hipError_t launch_instopt_smooth3(const float* in, float* out, int h, int w, int d, hipStream_t st) {
+static hipError_t launch_instopt_smooth3(const float* in, float* out, int h, int w, int d, hipStream_t st) {
   const dim3 grid(cdiv(d, kSmX) * cdiv(w, kSmY) * cdiv(h, kSmZ), 3);
   instopt_smooth3_kernel<<<grid, 256, 0, st>>>(in, out, h, w, d);
   return hipGetLastError();
@@ -299,11 +299,11 @@ static InstoptLayout instopt_layout(int h, int w, int d) {
   L.total = o;
   return L;
 }
-size_t instopt_scratch_bytes(int h, int w, int d) { return instopt_layout(h, w, d).total; }
+static size_t instopt_scratch_bytes(int h, int w, int d) { return instopt_layout(h, w, d).total; }
 
 // one iteration's forward and backward from a given weight: smooth, sample + gradient, smooth (3 launches, 4 with the loss)
-hipError_t launch_instopt_grad(const float* weight, const float* fix, const float* mov, int c, int h, int w, int d, float lambda,
-                               float* grad_weight, float* disp_sample, float* loss2, void* scratch, hipStream_t st) {
+static hipError_t launch_instopt_grad(const float* weight, const float* fix, const float* mov, int c, int h, int w, int d, float lambda,
+                                      float* grad_weight, float* disp_sample, float* loss2, void* scratch, hipStream_t st) {
   const InstoptLayout L = instopt_layout(h, w, d);
   char* base = (char*)scratch;
   float* ds = disp_sample ? disp_sample : (float*)(base + L.ds);
@@ -317,8 +317,8 @@ hipError_t launch_instopt_grad(const float* weight, const float* fix, const floa
 
 // step t (1-based) of torch.optim.Adam(lr, betas (0.9, 0.999), eps 1e-8): 1 - beta^t, lr / (1 - beta1^t) and sqrt(1 - beta2^t)
 // are formed in double, as torch forms them from Python floats, and rounded once
-hipError_t launch_instopt_adam(float* weight, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr, int t,
-                               hipStream_t st, bool zero_moments) {
+static hipError_t launch_instopt_adam(float* weight, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr, int t,
+                                      hipStream_t st, bool zero_moments = false) {
   const double b1 = 0.9, b2 = 0.999;
   const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
   const AdamStep a = {(float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(lr / bc1), (float)sqrt(bc2), 1e-8f, zero_moments ? 1 : 0};
@@ -328,8 +328,8 @@ hipError_t launch_instopt_adam(float* weight, const float* grad, float* exp_avg,
 
 // `niter` iterations; the field returned is the disp_sample of the LAST iteration's forward (weights after niter - 1 updates):
 // the reference's last backward and step do not reach its output and are not run.  4 launches per iteration.
-hipError_t launch_instopt(float* weight, const float* fix, const float* mov, int c, int h, int w, int d, float lambda, double lr,
-                          int niter, float* fitted, void* scratch, hipStream_t st) {
+static hipError_t launch_instopt(float* weight, const float* fix, const float* mov, int c, int h, int w, int d, float lambda, double lr,
+                                 int niter, float* fitted, void* scratch, hipStream_t st) {
   const InstoptLayout L = instopt_layout(h, w, d);
   char* base = (char*)scratch;
   float *gs = (float*)(base + L.gs), *gw = (float*)(base + L.gw), *m = (float*)(base + L.m), *v = (float*)(base + L.v);
@@ -365,10 +365,10 @@ static RunLayout run_layout(int c, int H, int W, int D, int g, int smooth) {
   L.total = o;
   return L;
 }
-size_t run_instopt_scratch_bytes(int c, int H, int W, int D, int g, int smooth) { return run_layout(c, H, W, D, g, smooth).total; }
+static size_t run_instopt_scratch_bytes(int c, int H, int W, int D, int g, int smooth) { return run_layout(c, H, W, D, g, smooth).total; }
 
-hipError_t launch_run_instopt(const float* disp_hr, const float* feat_fix, const float* feat_mov, int c, int H, int W, int D, int g,
-                              float lambda, int niter, int smooth, double lr, float* out, void* scratch, hipStream_t st) {
+static hipError_t launch_run_instopt(const float* disp_hr, const float* feat_fix, const float* feat_mov, int c, int H, int W, int D, int g,
+                                     float lambda, int niter, int smooth, double lr, float* out, void* scratch, hipStream_t st) {
   const RunLayout L = run_layout(c, H, W, D, g, smooth);
   const int h = H / g, w = W / g, d = D / g;
   char* base = (char*)scratch;
@@ -389,7 +389,7 @@ hipError_t launch_run_instopt(const float* disp_hr, const float* feat_fix, const
   return e;
 }
 
-hipError_t launch_warp3d(const float* vol, int c, const float* disp, int H, int W, int D, int nearest, float* out, hipStream_t st) {
+static hipError_t launch_warp3d(const float* vol, int c, const float* disp, int H, int W, int D, int nearest, float* out, hipStream_t st) {
   const int grid = cdiv((long long)H * W * D, 256);
   if (nearest) warp3d_kernel<true><<<grid, 256, 0, st>>>(vol, c, disp, H, W, D, out);
   else warp3d_kernel<false><<<grid, 256, 0, st>>>(vol, c, disp, H, W, D, out);

@@ -174,8 +174,8 @@ static inline bool lov_aligned_dyn(int lt, const void* p, long long head) {
     else LOV_LAUNCH(LA, RM_LABEL_U8);                         \
   } while (0)
 
-hipError_t launch_label_overlap(const void* a, int lt_a, const void* b, int lt_b, long long voxels, int bins, long long* counts,
-                                long long* bad, hipStream_t st) {
+static hipError_t launch_label_overlap(const void* a, int lt_a, const void* b, int lt_b, long long voxels, int bins, long long* counts,
+                                       long long* bad, hipStream_t st) {
   unsigned long long* cnt = (unsigned long long*)counts;
   unsigned long long* badp = (unsigned long long*)bad;
   label_overlap_zero_kernel<<<(3 * bins + kRmThreads - 1) / kRmThreads, kRmThreads, 0, st>>>(cnt, 3 * bins, badp);
@@ -363,13 +363,13 @@ static inline int jac_blocks(const float* u, int H, int W, int D) {
   const long long units = (long long)(H - 1) * (W - 1) * ((D - 1 + vpt - 1) / vpt), need = (units + kRmThreads - 1) / kRmThreads;
   return (int)(need < kStreamMaxBlocks ? need : kStreamMaxBlocks);
 }
-size_t jacobian_det_scratch_bytes(int H, int W, int D) {
+static size_t jacobian_det_scratch_bytes(int H, int W, int D) {
   const long long need = ((long long)(H - 1) * (W - 1) * (D - 1) + kRmThreads - 1) / kRmThreads;       // covers both mappings
   return (size_t)(need < kStreamMaxBlocks ? need : kStreamMaxBlocks) * kJacRec * sizeof(double);
 }
 
-hipError_t launch_jacobian_det(const float* disp, int H, int W, int D, int add_identity, float* jdet, float* stats, void* scratch,
-                               hipStream_t st) {
+static hipError_t launch_jacobian_det(const float* disp, int H, int W, int D, int add_identity, float* jdet, float* stats, void* scratch,
+                                      hipStream_t st) {
   const int grid = jac_blocks(disp, H, W, D), vec = jac_vpt(disp, D) == 4;
   double* part = (double*)scratch;
   if (stats) {

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(1024) void sample_perm_kernel(const long long* __re
   }
 }
 
-hipError_t launch_sample_perm(const long long* keys, int nvox, int num, int d1, int d2, long long* coords, hipStream_t st) {
+static hipError_t launch_sample_perm(const long long* keys, int nvox, int num, int d1, int d2, long long* coords, hipStream_t st) {
   sample_perm_kernel<<<1, 1024, 0, st>>>(keys, nvox, num, d1, d2, coords);
   return hipGetLastError();
 }
@@ -154,8 +154,8 @@ __global__ void gather_labels_kernel(const float* __restrict__ seg, int D, int H
   for (int v = 0; v < views; ++v) out[v * P + i] = lab;
 }
 
-hipError_t launch_gather_labels(const float* seg, int D, int H, int W, const long long* coords, int P, int d, int h, int w, int views,
-                                int* out, hipStream_t st) {
+static hipError_t launch_gather_labels(const float* seg, int D, int H, int W, const long long* coords, int P, int d, int h, int w, int views,
+                                       int* out, hipStream_t st) {
   gather_labels_kernel<<<(P + 255) / 256, 256, 0, st>>>(seg, D, H, W, coords, P, d, h, w, views, out);
   return hipGetLastError();
 }
@@ -182,8 +182,8 @@ __global__ void gather_labels_batch_kernel(const float* __restrict__ seg, int D,
   for (int v = 0; v < views; ++v) out[v * P + i] = lab;
 }
 
-hipError_t launch_gather_labels_batch(const float* seg, int D, int H, int W, int nb, const long long* const* coords, int P, const int* dims,
-                                      int views, int* const* out, hipStream_t st) {
+static hipError_t launch_gather_labels_batch(const float* seg, int D, int H, int W, int nb, const long long* const* coords, int P, const int* dims,
+                                             int views, int* const* out, hipStream_t st) {
   GatherLabelsBatch bt;
   for (int b = 0; b < nb; ++b) {
     bt.coords[b] = coords[b]; bt.out[b] = out[b]; bt.d[b] = dims[3 * b]; bt.h[b] = dims[3 * b + 1]; bt.w[b] = dims[3 * b + 2];
@@ -233,8 +233,8 @@ __global__ void scatter_rows_kernel(const float* __restrict__ rows, const long l
   }
 }
 
-hipError_t launch_gather_rows(const void* src, int dtype, long long sn, long long sz, long long sy, long long sx, long long sc,
-                              const long long* coords, int N, int P, int C, float* rows, hipStream_t st) {
+static hipError_t launch_gather_rows(const void* src, int dtype, long long sn, long long sz, long long sy, long long sx, long long sc,
+                                     const long long* coords, int N, int P, int C, float* rows, hipStream_t st) {
   const long long total = (long long)N * P * C;
   const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
   if (dtype == 0) gather_rows_kernel<0><<<blocks, 256, 0, st>>>((const char*)src, sn, sz, sy, sx, sc, coords, N, P, C, rows);
@@ -358,11 +358,11 @@ __global__ __launch_bounds__(256) void sampled_conv_dgrad_kernel(const float* __
   if (ci < Cin) ((T*)din)[((((size_t)n * D + uz) * H + uy) * W + ux) * dc + ci] = (T)acc;
 }
 
-size_t sampled_conv_backward_scratch_bytes(int P) { return (size_t)P * ((P + 31) / 32) * sizeof(unsigned) + (size_t)SWG * 27 * 256 * sizeof(float); }
+static size_t sampled_conv_backward_scratch_bytes(int P) { return (size_t)P * ((P + 31) / 32) * sizeof(unsigned) + (size_t)SWG * 27 * 256 * sizeof(float); }
 
-hipError_t launch_sampled_conv_backward(const float* g, const long long* coords, const void* x, int xc, const float* w, int N, int P, int D,
-                                        int H, int W, int Cout, int Cin, float* dw, void* din, int dc, void* scratch, int precision,
-                                        hipStream_t st) {
+static hipError_t launch_sampled_conv_backward(const float* g, const long long* coords, const void* x, int xc, const float* w, int N, int P, int D,
+                                               int H, int W, int Cout, int Cin, float* dw, void* din, int dc, void* scratch, int precision,
+                                               hipStream_t st) {
   const dim3 dgrid((P * 27 + 15) / 16, N);
   const int nchunk = (P + 31) / 32;
   unsigned* mask = (unsigned*)scratch;
@@ -380,8 +380,8 @@ hipError_t launch_sampled_conv_backward(const float* g, const long long* coords,
   return hipGetLastError();
 }
 
-hipError_t launch_scatter_rows(const float* rows, const long long* coords, void* dst, int dtype, long long dn, long long dz, long long dy,
-                               long long dx, int N, int P, int C, int accumulate, hipStream_t st) {
+static hipError_t launch_scatter_rows(const float* rows, const long long* coords, void* dst, int dtype, long long dn, long long dz, long long dy,
+                                      long long dx, int N, int P, int C, int accumulate, hipStream_t st) {
   const long long total = (long long)N * P * C;
   const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
   if (dtype == 0) scatter_rows_kernel<f16><<<blocks, 256, 0, st>>>(rows, coords, (char*)dst, dn, dz, dy, dx, N, P, C, accumulate);
@@ -390,7 +390,7 @@ hipError_t launch_scatter_rows(const float* rows, const long long* coords, void*
   return hipGetLastError();
 }
 
-hipError_t launch_sample_coords(const long long* draws, int n, int num, int d0, int d1, int d2, long long* coords, hipStream_t st) {
+static hipError_t launch_sample_coords(const long long* draws, int n, int num, int d0, int d1, int d2, long long* coords, hipStream_t st) {
   int tsize = 1024;
   while (tsize < 2 * n) tsize <<= 1;                         // load factor <= 1/2 (n <= 4096: at most 8192 slots)
   const bool small = (long long)d0 * d1 * d2 < (1ll << 31);
@@ -414,3 +414,78 @@ hipError_t launch_sample_coords(const long long* draws, int n, int num, int d0, 
 }
 
 }  // namespace amx
+
+using amx::fail;
+
+extern "C" {
+
+int amx_gather_labels(const float* d_seg, int sd, int sh, int sw, const long long* d_coords, int p, int d, int hh, int w, int views,
+                      int* d_labels, void* stream) {
+  if (!d_seg || !d_coords || !d_labels || p < 1 || views < 1) return fail(AMX_ERR_INVALID, "gather_labels: bad arguments");
+  if (sd < 1 || sh < 1 || sw < 1 || d < 1 || hh < 1 || w < 1) return fail(AMX_ERR_SHAPE, "gather_labels: non-positive shape");
+  AMX_HIP(amx::launch_gather_labels(d_seg, sd, sh, sw, d_coords, p, d, hh, w, views, d_labels, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_gather_labels_batch(const float* d_seg, int sd, int sh, int sw, int n_maps, const long long* const* d_coords, int p, const int* dims,
+                            int views, int* const* d_labels, void* stream) {
+  if (!d_seg || !d_coords || !dims || !d_labels || p < 1 || views < 1) return fail(AMX_ERR_INVALID, "gather_labels: bad arguments");
+  if (n_maps < 1 || n_maps > amx::MLP_MAXB) return fail(AMX_ERR_INVALID, "1 <= maps <= %d (got %d)", amx::MLP_MAXB, n_maps);
+  if (sd < 1 || sh < 1 || sw < 1) return fail(AMX_ERR_SHAPE, "gather_labels: non-positive shape");
+  for (int b = 0; b < n_maps; ++b)
+    if (!d_coords[b] || !d_labels[b] || dims[3 * b] < 1 || dims[3 * b + 1] < 1 || dims[3 * b + 2] < 1)
+      return fail(AMX_ERR_SHAPE, "gather_labels: map %d: bad arguments", b);
+  AMX_HIP(amx::launch_gather_labels_batch(d_seg, sd, sh, sw, n_maps, d_coords, p, dims, views, d_labels, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_sample_coords(const long long* d_draws, int n_draws, int num, int d0, int d1, int d2, long long* d_coords, void* stream) {
+  if (!d_draws || !d_coords) return fail(AMX_ERR_INVALID, "null argument");
+  if (num < 1 || n_draws < num || n_draws > 4096) return fail(AMX_ERR_INVALID, "1 <= num <= n_draws <= 4096 (got %d, %d)", num, n_draws);
+  if (d0 < 1 || d1 < 1 || d2 < 1) return fail(AMX_ERR_SHAPE, "non-positive shape");
+  AMX_HIP(amx::launch_sample_coords(d_draws, n_draws, num, d0, d1, d2, d_coords, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_sample_perm(const long long* d_keys, int d0, int d1, int d2, int num, long long* d_coords, void* stream) {
+  if (!d_keys || !d_coords) return fail(AMX_ERR_INVALID, "null argument");
+  if (d0 < 1 || d1 < 1 || d2 < 1) return fail(AMX_ERR_SHAPE, "non-positive shape");
+  const long long nvox = (long long)d0 * d1 * d2;
+  if (nvox > 4096 || num < 1 || num > nvox) return fail(AMX_ERR_INVALID, "sample_perm: 1 <= num <= d0 d1 d2 <= 4096 (got %d of %lld)", num, nvox);
+  AMX_HIP(amx::launch_sample_perm(d_keys, (int)nvox, num, d1, d2, d_coords, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_gather_rows(const void* d_src, int dtype, long long src_sn, long long src_sz, long long src_sy, long long src_sx, long long src_sc,
+                    const long long* d_coords, int n, int p, int c, float* d_rows, void* stream) {
+  if (!d_src || !d_coords || !d_rows || n < 1 || p < 1 || c < 1 || dtype < 0 || dtype > 2) return fail(AMX_ERR_INVALID, "gather_rows: bad arguments");
+  AMX_HIP(amx::launch_gather_rows(d_src, dtype, src_sn, src_sz, src_sy, src_sx, src_sc, d_coords, n, p, c, d_rows, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_scatter_rows(const float* d_rows, const long long* d_coords, void* d_dst, int precision, long long dst_sn, long long dst_sz,
+                     long long dst_sy, long long dst_sx, int n, int p, int c, int accumulate, void* stream) {
+  if (!d_rows || !d_coords || !d_dst || n < 1 || p < 1 || c < 1 || (precision != AMX_PREC_F16 && precision != AMX_PREC_BF16))
+    return fail(AMX_ERR_INVALID, "scatter_rows: bad arguments");
+  AMX_HIP(amx::launch_scatter_rows(d_rows, d_coords, d_dst, precision, dst_sn, dst_sz, dst_sy, dst_sx, n, p, c, accumulate, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+size_t amx_conv3d_backward_sampled_scratch_bytes(int p) { return amx::sampled_conv_backward_scratch_bytes(p); }
+
+int amx_conv3d_backward_sampled(const float* d_grows, const long long* d_coords, const void* d_x, int x_channels, const float* d_w, int n,
+                                int p, int d, int hh, int w, int cout, int cin, float* d_dw, void* d_din, int din_channels, void* d_scratch,
+                                size_t scratch_bytes, int precision, void* stream) {
+  if (!d_scratch || scratch_bytes < amx::sampled_conv_backward_scratch_bytes(p))
+    return fail(AMX_ERR_WORKSPACE, "conv3d_backward_sampled: scratch needs %zu bytes", amx::sampled_conv_backward_scratch_bytes(p));
+  if (!d_grows || !d_coords || !d_x || !d_w || !d_dw || n < 1 || p < 1) return fail(AMX_ERR_INVALID, "conv3d_backward_sampled: bad arguments");
+  if (precision != AMX_PREC_F16 && precision != AMX_PREC_BF16) return fail(AMX_ERR_INVALID, "conv3d_backward_sampled: f16 / bf16 storage");
+  if (cout < 1 || cout > 16 || cin < 1 || cin > 16 || x_channels < cin || (d_din && din_channels < cin))
+    return fail(AMX_ERR_SHAPE, "conv3d_backward_sampled: 1 <= cout, cin <= 16 (got %d, %d)", cout, cin);
+  if (d < 2 || hh < 2 || w < 2 || p > 1024) return fail(AMX_ERR_SHAPE, "conv3d_backward_sampled: sizes >= 2, at most 1024 sampled voxels");
+  AMX_HIP(amx::launch_sampled_conv_backward(d_grows, d_coords, d_x, x_channels, d_w, n, p, d, hh, w, cout, cin, d_dw, d_din, din_channels,
+                                            d_scratch, precision, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+}  // extern "C"

@@ -242,7 +242,7 @@ hipError_t launch_minmax_partials(const float* x, int n, long long V, bool clip,
   return hipGetLastError();
 }
 
-hipError_t launch_minmax_finalize(const void* scratch, int n, long long V, float* minmax, hipStream_t st) {
+static hipError_t launch_minmax_finalize(const void* scratch, int n, long long V, float* minmax, hipStream_t st) {
   minmax_finalize_kernel<<<n, Aug::kThreads, 0, st>>>((const float*)scratch, Aug::chunks(n, V), minmax);
   return hipGetLastError();
 }

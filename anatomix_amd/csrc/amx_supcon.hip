@@ -296,14 +296,14 @@ __global__ __launch_bounds__(256) void sc_dnorm_kernel(const ScBatch bt, int C, 
   }
 }
 
-size_t supcon_scratch_bytes(int N, int C) {
+static size_t supcon_scratch_bytes(int N, int C) {
   return ((size_t)(1 + SC_KSPLIT) * N * C + (size_t)N * N + (size_t)4 * N + 64) * sizeof(float);
 }
 
 // nb losses of one shape: feat[b] [N][C], labels[b] [N] -> loss[b], grad[b] (nullptr for every b: no gradients); scratch: nb slices of
 // supcon_scratch_bytes(N, C).
-hipError_t launch_supcon_batch(int nb, const float* const* feat, const int* const* labels, int N, int C, float temperature, int rarity,
-                               int balance, int sqrt_mode, float* const* loss, float* const* grad, void* scratch, hipStream_t st) {
+static hipError_t launch_supcon_batch(int nb, const float* const* feat, const int* const* labels, int N, int C, float temperature, int rarity,
+                                      int balance, int sqrt_mode, float* const* loss, float* const* grad, void* scratch, hipStream_t st) {
   ScBatch bt;
   bt.scratch = (char*)scratch;
   bt.stride = supcon_scratch_bytes(N, C);
@@ -351,9 +351,44 @@ hipError_t launch_supcon_batch(int nb, const float* const* feat, const int* cons
   return hipGetLastError();
 }
 
-hipError_t launch_supcon(const float* feat, const int* labels, int N, int C, float temperature, int rarity, int balance,
-                         int sqrt_mode, float* loss, float* grad, void* scratch, hipStream_t st) {
+static hipError_t launch_supcon(const float* feat, const int* labels, int N, int C, float temperature, int rarity, int balance,
+                                int sqrt_mode, float* loss, float* grad, void* scratch, hipStream_t st) {
   return launch_supcon_batch(1, &feat, &labels, N, C, temperature, rarity, balance, sqrt_mode, &loss, &grad, scratch, st);
 }
 
 }  // namespace amx
+
+using amx::fail;
+
+extern "C" {
+
+size_t amx_supcon_scratch_bytes(int n, int c) { return amx::supcon_scratch_bytes(n, c); }
+
+int amx_supcon_loss(const float* d_feat, const int* d_labels, int n, int c, float temperature, int weigh_rarity,
+                    int balance_denominator, int sqrt_mode, float* d_loss, float* d_grad, void* d_scratch,
+                    size_t scratch_bytes, void* stream) {
+  if (!d_feat || !d_labels || !d_loss || !d_scratch) return fail(AMX_ERR_INVALID, "null argument");
+  if (n < 2 || n > 16384 || c < 1 || !(temperature > 0.f)) return fail(AMX_ERR_INVALID, "bad sizes (n=%d c=%d T=%g)", n, c, temperature);
+  if (int rc = amx::need_scratch(amx::supcon_scratch_bytes(n, c), scratch_bytes)) return rc;
+  AMX_HIP(amx::launch_supcon(d_feat, d_labels, n, c, temperature, weigh_rarity, balance_denominator, sqrt_mode, d_loss,
+                             d_grad, d_scratch, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_supcon_loss_batch(int n_losses, const float* const* d_feat, const int* const* d_labels, int n, int c, float temperature,
+                          int weigh_rarity, int balance_denominator, int sqrt_mode, float* const* d_loss, float* const* d_grad,
+                          void* d_scratch, size_t scratch_bytes, void* stream) {
+  if (!d_feat || !d_labels || !d_loss || !d_scratch) return fail(AMX_ERR_INVALID, "null argument");
+  if (n_losses < 1 || n_losses > amx::MLP_MAXB) return fail(AMX_ERR_INVALID, "1 <= losses <= %d (got %d)", amx::MLP_MAXB, n_losses);
+  if (n < 2 || n > 16384 || c < 1 || !(temperature > 0.f)) return fail(AMX_ERR_INVALID, "bad sizes (n=%d c=%d T=%g)", n, c, temperature);
+  if (int rc = amx::need_scratch(n_losses * amx::supcon_scratch_bytes(n, c), scratch_bytes)) return rc;
+  for (int b = 0; b < n_losses; ++b) {
+    if (!d_feat[b] || !d_labels[b] || !d_loss[b]) return fail(AMX_ERR_INVALID, "loss %d: null buffer", b);
+    if (d_grad && (!d_grad[b] != !d_grad[0])) return fail(AMX_ERR_INVALID, "gradients for all losses or for none");
+  }
+  AMX_HIP(amx::launch_supcon_batch(n_losses, d_feat, d_labels, n, c, temperature, weigh_rarity, balance_denominator, sqrt_mode, d_loss,
+                                   d_grad, d_scratch, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+}  // extern "C"

@@ -42,7 +42,7 @@ __global__ void sw_count_kernel(float* __restrict__ cnt, int vh, int vw, int oz,
   }
 }
 
-hipError_t launch_sw_normalize(float* acc, const float* cnt, int channels, long long voxels, hipStream_t st) {
+static hipError_t launch_sw_normalize(float* acc, const float* cnt, int channels, long long voxels, hipStream_t st) {
   if ((voxels & 3) && ((uintptr_t)acc & 15)) { /* alignment of channel planes is handled by the scalar tail only when voxels%4==0 */ }
   const long long v4n = voxels >> 2;
   int blocks = (int)((v4n + 255) / 256 > 4096 ? 4096 : (v4n + 255) / 256);
@@ -51,8 +51,8 @@ hipError_t launch_sw_normalize(float* acc, const float* cnt, int channels, long 
   return hipGetLastError();
 }
 
-hipError_t launch_sw_count(float* cnt, int vd, int vh, int vw, int oz, int oy, int ox, int rd, int rh, int rw,
-                           const float* wmap, hipStream_t st) {
+static hipError_t launch_sw_count(float* cnt, int vd, int vh, int vw, int oz, int oy, int ox, int rd, int rh, int rw,
+                                  const float* wmap, hipStream_t st) {
   (void)vd;
   const long long total = (long long)rd * rh * rw;
   const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
@@ -62,8 +62,9 @@ hipError_t launch_sw_count(float* cnt, int vd, int vh, int vw, int oz, int oy, i
 
 // ---- the window schedule ------------------------------------------------------------------------------------------------------
 // registration/sliding_window.py window_starts, axis by axis: scan interval int(roi * (1 - overlap)) floored at 1 (roi itself when
-// the axis equals the roi), count = 1 + the first d with d * interval + roi >= size
-int sw_make_plan(int vd, int vh, int vw, int rd, int rh, int rw, double overlap, SwPlan* plan) {
+// the axis equals the roi), count = 1 + the first d with d * interval + roi >= size.  AMX_OK and the plan, or AMX_ERR_SHAPE (a volume
+// smaller than the roi, a non-positive size, more than kSwMaxWindows windows)
+static int sw_make_plan(int vd, int vh, int vw, int rd, int rh, int rw, double overlap, SwPlan* plan) {
   const int size[3] = {vd, vh, vw}, roi[3] = {rd, rh, rw};
   long long windows = 1;
   if (!(overlap >= 0.0 && overlap < 1.0)) return fail(AMX_ERR_INVALID, "0 <= overlap < 1 (got %g)", overlap);
@@ -217,14 +218,14 @@ __global__ __launch_bounds__(SwTile::kThreads) void sw_finish_head_kernel(SwFini
   }
 }
 
-hipError_t launch_sw_count_all(float* cnt, const SwPlan& plan, const float* wmap, hipStream_t st) {
+static hipError_t launch_sw_count_all(float* cnt, const SwPlan& plan, const float* wmap, hipStream_t st) {
   const long long total = (long long)plan.ax[0].size * plan.ax[1].size * plan.ax[2].size;
   const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
   hipLaunchKernelGGL(sw_count_all_kernel, dim3(blocks), dim3(256), 0, st, cnt, plan, wmap);
   return hipGetLastError();
 }
 
-hipError_t launch_sw_importance_map(float* wmap, int rd, int rh, int rw, int mode, double sigma_scale, hipStream_t st) {
+static hipError_t launch_sw_importance_map(float* wmap, int rd, int rh, int rw, int mode, double sigma_scale, hipStream_t st) {
   const long long total = (long long)rd * rh * rw;
   const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
   const double sz = rd * sigma_scale, sy = rh * sigma_scale, sx = rw * sigma_scale;
@@ -244,8 +245,9 @@ static void sw_finish_dispatch(bool labels, bool vec, int grid, hipStream_t st, 
   }
 }
 
-hipError_t launch_sw_finish(int kind, float* acc, const float* cnt, int feat, long long voxels, const float* w, const float* b, int classes,
-                            void* out, hipStream_t st) {
+// kind: AMX_SW_FEATURES (acc /= cnt in place, launch_sw_normalize's arithmetic), AMX_SW_LOGITS, AMX_SW_LABELS
+static hipError_t launch_sw_finish(int kind, float* acc, const float* cnt, int feat, long long voxels, const float* w, const float* b, int classes,
+                                   void* out, hipStream_t st) {
   if (kind == AMX_SW_FEATURES) return launch_sw_normalize(acc, cnt, feat, voxels, st);
   const bool labels = kind == AMX_SW_LABELS;
   SwFinishArgs a;
@@ -261,7 +263,8 @@ hipError_t launch_sw_finish(int kind, float* acc, const float* cnt, int feat, lo
 }
 
 // ---- checks and handle state shared by the networks' window entries ------------------------------------------------------------
-int sw_map_check(int mode, double sigma_scale) {
+// AMX_OK, or AMX_ERR_INVALID for a mode that is neither constant nor gaussian, or a gaussian without a positive sigma_scale
+static int sw_map_check(int mode, double sigma_scale) {
   if (mode != AMX_SW_MAP_CONSTANT && mode != AMX_SW_MAP_GAUSSIAN) return fail(AMX_ERR_INVALID, "mode: constant (0) or gaussian (1) (got %d)", mode);
   if (mode == AMX_SW_MAP_GAUSSIAN && !(sigma_scale > 0.0)) return fail(AMX_ERR_INVALID, "sigma_scale must be positive (got %g)", sigma_scale);
   return AMX_OK;
@@ -310,6 +313,19 @@ void SwLanes::release() {
   if (join) (void)hipEventDestroy(join);
   if (fork) (void)hipEventDestroy(fork);
   stream = nullptr, join = fork = nullptr;
+}
+
+// the argument check of amx_sw_finish, which sw_run makes before its first launch
+static int sw_finish_check(int kind, const float* acc, const float* cnt, int feat, long long voxels, const float* w, int classes,
+                           const void* out) {
+  if (kind != AMX_SW_FEATURES && kind != AMX_SW_LOGITS && kind != AMX_SW_LABELS)
+    return fail(AMX_ERR_INVALID, "output kind: features (0), logits (1) or labels (2) (got %d)", kind);
+  if (!acc || !cnt || feat < 1 || voxels < 1 || voxels >= (1LL << 40)) return fail(AMX_ERR_INVALID, "bad argument");
+  if (kind == AMX_SW_FEATURES) return AMX_OK;
+  if (classes < 2 || classes > kSwMaxC) return fail(AMX_ERR_INVALID, "2 <= classes <= %d (got %d)", kSwMaxC, classes);
+  if (feat > kSwMaxF) return fail(AMX_ERR_INVALID, "1 <= feat <= %d head input channels (got %d)", kSwMaxF, feat);
+  if (!w || !out) return fail(AMX_ERR_INVALID, "logits and labels need the head's weight and an output buffer");
+  return AMX_OK;
 }
 
 // ---- the whole-volume call ------------------------------------------------------------------------------------------------------
@@ -370,3 +386,58 @@ int sw_run(const SwNet& net, SwMapCache& cache, SwLanes* lanes, int vd, int vh, 
 }
 
 }  // namespace amx
+
+using amx::fail;
+
+extern "C" {
+
+int amx_sw_normalize(float* d_acc, const float* d_cnt, int channels, long long voxels, void* stream) {
+  if (!d_acc || !d_cnt || channels < 1 || voxels < 1) return fail(AMX_ERR_INVALID, "bad argument");
+  AMX_HIP(amx::launch_sw_normalize(d_acc, d_cnt, channels, voxels, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_sw_count(float* d_cnt, int vd, int vh, int vw, int oz, int oy, int ox, int rd, int rh, int rw,
+                 const float* d_wmap, void* stream) {
+  if (!d_cnt || !d_wmap) return fail(AMX_ERR_INVALID, "null argument");
+  const int corner[3] = {oz, oy, ox};
+  long long off;
+  if (int rc = amx::sw_window_offsets(vd, vh, vw, rd, rh, rw, 1, corner, &off)) return rc;
+  AMX_HIP(amx::launch_sw_count(d_cnt, vd, vh, vw, oz, oy, ox, rd, rh, rw, d_wmap, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_sw_plan(int vd, int vh, int vw, int rd, int rh, int rw, double overlap, int* offsets_zyx, int capacity) {
+  if (capacity < 0 || (capacity > 0 && !offsets_zyx)) return fail(AMX_ERR_INVALID, "bad offsets buffer");
+  amx::SwPlan plan;
+  if (int rc = amx::sw_make_plan(vd, vh, vw, rd, rh, rw, overlap, &plan)) return rc;
+  const int n = plan.windows();
+  for (int i = 0; i < n && i < capacity; ++i) plan.corner(i, offsets_zyx + 3 * i);
+  return n;
+}
+
+int amx_sw_importance_map(float* d_wmap, int rd, int rh, int rw, int mode, double sigma_scale, void* stream) {
+  if (!d_wmap) return fail(AMX_ERR_INVALID, "null argument");
+  if (rd < 1 || rh < 1 || rw < 1) return fail(AMX_ERR_SHAPE, "non-positive roi");
+  if (int rc = amx::sw_map_check(mode, sigma_scale)) return rc;
+  AMX_HIP(amx::launch_sw_importance_map(d_wmap, rd, rh, rw, mode, sigma_scale, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_sw_count_all(float* d_cnt, int vd, int vh, int vw, int rd, int rh, int rw, double overlap, const float* d_wmap,
+                     void* stream) {
+  if (!d_cnt || !d_wmap) return fail(AMX_ERR_INVALID, "null argument");
+  amx::SwPlan plan;
+  if (int rc = amx::sw_make_plan(vd, vh, vw, rd, rh, rw, overlap, &plan)) return rc;
+  AMX_HIP(amx::launch_sw_count_all(d_cnt, plan, d_wmap, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_sw_finish(int kind, float* d_acc, const float* d_cnt, int feat, long long voxels, const float* d_w, const float* d_b,
+                  int classes, void* d_out, void* stream) {
+  if (int rc = amx::sw_finish_check(kind, d_acc, d_cnt, feat, voxels, d_w, classes, d_out)) return rc;
+  AMX_HIP(amx::launch_sw_finish(kind, d_acc, d_cnt, feat, voxels, d_w, d_b, classes, d_out, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+}  // extern "C"

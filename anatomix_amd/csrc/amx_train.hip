@@ -705,11 +705,11 @@ __global__ __launch_bounds__(256) void dgrad_shell_kernel(const char* __restrict
   }
 }
 
-size_t dgrad_shell_scratch_bytes() { return (size_t)shell_base(27, 1) * 2 * 1024; }     // the largest fragment table (one tap per step, two m tiles)
+static size_t dgrad_shell_scratch_bytes() { return (size_t)shell_base(27, 1) * 2 * 1024; }     // the largest fragment table (one tap per step, two m tiles)
 
-hipError_t launch_dgrad_fold_shell(const void* dy, long long yn, long long yz, long long yy, long long yx, int cdy, const float* w,
-                                   int co_real, int ci_real, void* dx, int cdx, int N, int D, int H, int W, int precision, void* scratch,
-                                   hipStream_t st) {
+static hipError_t launch_dgrad_fold_shell(const void* dy, long long yn, long long yz, long long yy, long long yx, int cdy, const float* w,
+                                          int co_real, int ci_real, void* dx, int cdx, int N, int D, int H, int W, int precision, void* scratch,
+                                          hipStream_t st) {
   if ((cdy != 16 && cdy != 32) || (cdx != 16 && cdx != 32) || precision > 1 || !scratch) return hipErrorInvalidValue;
   long long mx = (long long)H * W;
   if ((long long)D * W > mx) mx = (long long)D * W;
@@ -739,13 +739,13 @@ hipError_t launch_dgrad_fold_shell(const void* dy, long long yn, long long yz, l
 }
 
 // ------------------------------------------------------------------------------------------- launchers
-size_t train_scratch_bytes(int C) { return ((size_t)65536 * 2 + (size_t)C * 2) * sizeof(float); }
+static size_t train_scratch_bytes(int C) { return ((size_t)65536 * 2 + (size_t)C * 2) * sizeof(float); }
 
 static int grid_for(long long total) { return (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256); }
 
-hipError_t launch_bn_train_forward(const void* x, void* y, const float* gamma, const float* beta, float eps, long long rows, int C,
-                                   int act, float slope, void* scratch, float* save_mean, float* save_rstd, float* running_mean,
-                                   float* running_var, float momentum, int precision, hipStream_t st) {
+static hipError_t launch_bn_train_forward(const void* x, void* y, const float* gamma, const float* beta, float eps, long long rows, int C,
+                                          int act, float slope, void* scratch, float* save_mean, float* save_rstd, float* running_mean,
+                                          float* running_var, float momentum, int precision, hipStream_t st) {
   if (C % 8 || C > 2048 || rows < 1) return hipErrorInvalidValue;
   float* partial = (float*)scratch;
   float* ab = partial + (size_t)65536 * 2;
@@ -765,9 +765,9 @@ hipError_t launch_bn_train_forward(const void* x, void* y, const float* gamma, c
   return hipGetLastError();
 }
 
-hipError_t launch_bn_act_backward(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
-                                  const float* gamma, const float* beta, float* dgamma, float* dbeta, void* dx_framed, int N, int D,
-                                  int H, int W, int C, int act, float slope, void* scratch, int precision, hipStream_t st) {
+static hipError_t launch_bn_act_backward(const void* dy, const void* y, const void* x, const float* mean, const float* rstd,
+                                         const float* gamma, const float* beta, float* dgamma, float* dbeta, void* dx_framed, int N, int D,
+                                         int H, int W, int C, int act, float slope, void* scratch, int precision, hipStream_t st) {
   if (!y && !mean) return hipErrorInvalidValue;             // the activation's argument is either read (y) or recomputed from x
   if (C % 8 || C > 2048 || (long long)N * D * H * W * (C / 8) >= (1ll << 31)) return hipErrorInvalidValue;
   const long long rows = (long long)N * D * H * W;
@@ -788,8 +788,8 @@ hipError_t launch_bn_act_backward(const void* dy, const void* y, const void* x, 
   return hipGetLastError();
 }
 
-hipError_t launch_pad_fold(const void* g_framed, void* din, int N, int D, int H, int W, int C, int accumulate, int precision,
-                           hipStream_t st) {
+static hipError_t launch_pad_fold(const void* g_framed, void* din, int N, int D, int H, int W, int C, int accumulate, int precision,
+                                  hipStream_t st) {
   if (C % 8 || D < 2 || H < 2 || W < 2 || (long long)N * D * H * W * (C / 8) >= (1ll << 31)) return hipErrorInvalidValue;
   const unsigned blocks = (unsigned)(N * D * H);
   if (precision == 0)
@@ -799,8 +799,8 @@ hipError_t launch_pad_fold(const void* g_framed, void* din, int N, int D, int H,
   return hipGetLastError();
 }
 
-hipError_t launch_pool2_max_backward(const void* dp, const void* in, void* din, int N, int Do, int Ho, int Wo, int C,
-                                     int accumulate, int precision, hipStream_t st) {
+static hipError_t launch_pool2_max_backward(const void* dp, const void* in, void* din, int N, int Do, int Ho, int Wo, int C,
+                                            int accumulate, int precision, hipStream_t st) {
   if (C % 8) return hipErrorInvalidValue;
   const int blocks = grid_for((long long)N * Do * Ho * Wo * (C / 8));
   if (precision == 0)
@@ -812,8 +812,8 @@ hipError_t launch_pool2_max_backward(const void* dp, const void* in, void* din, 
   return hipGetLastError();
 }
 
-hipError_t launch_upcat_split(const void* dcat, void* dskip, void* dlow, int N, int Dl, int Hl, int Wl, int c0, int c1,
-                              int acc_skip, int framed, int precision, hipStream_t st) {
+static hipError_t launch_upcat_split(const void* dcat, void* dskip, void* dlow, int N, int Dl, int Hl, int Wl, int c0, int c1,
+                                     int acc_skip, int framed, int precision, hipStream_t st) {
   if (c0 % 8 || c1 % 8 || c0 < 0 || c1 < 8) return hipErrorInvalidValue;       // c0 == 0: no skip part, everything is summed over children
   const int blocks = grid_for((long long)N * Dl * Hl * Wl * ((c0 + c1) / 8));
 #define AMX_UPS(T, F)                                                                                                            \
@@ -829,3 +829,86 @@ hipError_t launch_upcat_split(const void* dcat, void* dskip, void* dlow, int N, 
 }
 
 }  // namespace amx
+
+using amx::fail;
+
+extern "C" {
+
+size_t amx_train_scratch_bytes(int c) { return amx::train_scratch_bytes(c); }
+
+int amx_bn_train_forward(const void* d_x, void* d_y, const float* d_gamma, const float* d_beta, float eps, int n,
+                         long long voxels, int c, int act, float slope, void* d_scratch, float* d_save_mean,
+                         float* d_save_rstd, float* d_running_mean, float* d_running_var, float momentum, int precision,
+                         void* stream) {
+  if (!d_x || !d_y || !d_scratch || n < 1 || voxels < 1 || c % 8 || c > 2048) return fail(AMX_ERR_INVALID, "bad argument");
+  AMX_HIP(amx::launch_bn_train_forward(d_x, d_y, d_gamma, d_beta, eps, (long long)n * voxels, c, act, slope, d_scratch, d_save_mean,
+                                       d_save_rstd, d_running_mean, d_running_var, momentum, precision, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_bn_act_backward(const void* d_dy, const void* d_y, const void* d_x, const float* d_mean, const float* d_rstd,
+                        const float* d_gamma, float* d_dgamma, float* d_dbeta, void* d_dx_framed, int n, int d, int hh, int w,
+                        int c, int act, float slope, void* d_scratch, int precision, void* stream) {
+  if (!d_dy || !d_y || !d_dx_framed || !d_scratch || c % 8 || c > 2048) return fail(AMX_ERR_INVALID, "bad argument");
+  if (d_mean && (!d_x || !d_rstd || !d_dgamma || !d_dbeta)) return fail(AMX_ERR_INVALID, "norm backward needs x, rstd, dgamma, dbeta");
+  AMX_HIP(amx::launch_bn_act_backward(d_dy, d_y, d_x ? d_x : d_y, d_mean, d_rstd, d_gamma, nullptr, d_dgamma, d_dbeta, d_dx_framed, n,
+                                      d, hh, w, c, act, slope, d_scratch, precision, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_bn_act_backward_recompute(const void* d_dy, const void* d_x, const float* d_mean, const float* d_rstd, const float* d_gamma,
+                                  const float* d_beta, float* d_dgamma, float* d_dbeta, void* d_dx_framed, int n, int d, int hh, int w,
+                                  int c, int act, float slope, void* d_scratch, int precision, void* stream) {
+  if (!d_dy || !d_x || !d_mean || !d_rstd || !d_dgamma || !d_dbeta || !d_dx_framed || !d_scratch || c % 8 || c > 2048)
+    return fail(AMX_ERR_INVALID, "bad argument");
+  AMX_HIP(amx::launch_bn_act_backward(d_dy, nullptr, d_x, d_mean, d_rstd, d_gamma, d_beta, d_dgamma, d_dbeta, d_dx_framed, n, d, hh, w,
+                                      c, act, slope, d_scratch, precision, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_pad_fold(const void* d_g_framed, void* d_din, int n, int d, int hh, int w, int c, int accumulate, int precision,
+                 void* stream) {
+  if (!d_g_framed || !d_din || c % 8 || d < 2 || hh < 2 || w < 2) return fail(AMX_ERR_INVALID, "bad argument");
+  AMX_HIP(amx::launch_pad_fold(d_g_framed, d_din, n, d, hh, w, c, accumulate, precision, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_pool2_max_backward(const void* d_dp, const void* d_in, void* d_din, int n, int dout, int hout, int wout, int c,
+                           int accumulate, int precision, void* stream) {
+  if (!d_dp || !d_in || !d_din || c % 8) return fail(AMX_ERR_INVALID, "bad argument");
+  AMX_HIP(amx::launch_pool2_max_backward(d_dp, d_in, d_din, n, dout, hout, wout, c, accumulate, precision, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+// ---- the shell terms of the data gradient; its interior launch of the forward kernel is amx_conv3d_dgrad_interior (amx_api.hip)
+size_t amx_conv3d_dgrad_shell_scratch_bytes(void) { return amx::dgrad_shell_scratch_bytes(); }
+
+int amx_conv3d_dgrad_fold_shell(const void* d_dy_framed, int c_dy, const float* d_weight, int co_real, int ci_real, void* d_dx, int c_dx, int n,
+                                int d, int hh, int w, int precision, void* d_scratch, void* stream) {
+  if (!d_dy_framed || !d_weight || !d_dx || !d_scratch || ((uintptr_t)d_scratch & 15) || co_real < 1 || co_real > c_dy || ci_real < 1 || ci_real > c_dx || d < 2 || hh < 2 || w < 2)
+    return fail(AMX_ERR_INVALID, "dgrad_fold_shell: bad arguments");
+  const long long fx = (long long)c_dy * 2, fy = fx * (w + 4), fz = fy * (hh + 4), fn = fz * (d + 4);
+  AMX_HIP(amx::launch_dgrad_fold_shell((const char*)d_dy_framed + 2 * (fz + fy + fx), fn, fz, fy, fx, c_dy, d_weight, co_real, ci_real, d_dx, c_dx,
+                                       n, d, hh, w, precision, d_scratch, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_upcat_split_backward(const void* d_dcat, void* d_dskip, void* d_dlow, int n, int dlow, int hlow, int wlow, int c0, int c1,
+                             int accumulate_skip, int precision, void* stream) {
+  if (!d_dcat || (!d_dskip && c0 > 0) || !d_dlow || n < 1 || dlow < 1 || hlow < 1 || wlow < 1 || c0 < 0 || c1 < 8 || c0 % 8 || c1 % 8)
+    return fail(AMX_ERR_INVALID, "bad argument");                       // c0 == 0: no skip part (the whole tensor is summed over children)
+  AMX_HIP(amx::launch_upcat_split(d_dcat, d_dskip, d_dlow, n, dlow, hlow, wlow, c0, c1, accumulate_skip, 0, precision,
+                                  (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_upcat_split_backward_framed(const void* d_g_framed, void* d_dskip, void* d_dlow, int n, int dlow, int hlow, int wlow, int c0,
+                                    int c1, int accumulate_skip, int precision, void* stream) {
+  if (!d_g_framed || (!d_dskip && c0 > 0) || !d_dlow || n < 1 || dlow < 1 || hlow < 1 || wlow < 1 || c0 < 0 || c1 < 8 || c0 % 8 || c1 % 8)
+    return fail(AMX_ERR_INVALID, "bad argument");                       // c0 == 0: no skip part (the whole tensor is summed over children)
+  AMX_HIP(amx::launch_upcat_split(d_g_framed, d_dskip, d_dlow, n, dlow, hlow, wlow, c0, c1, accumulate_skip, 1, precision,
+                                  (hipStream_t)stream));
+  return AMX_OK;
+}
+
+}  // extern "C"

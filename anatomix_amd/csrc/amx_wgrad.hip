@@ -16,6 +16,7 @@
 // register copy of the prefetch forced `vmcnt(0)` every item and the transposed writes cost as much LDS time as the sweep.  The form
 // below: 1028 -> 685 us over the 13 conv shapes of the 6 M UNet's step, every shape faster, tools/wgrad_layers.py.)
 #include <stdlib.h>
+#include <string.h>
 
 #include "amx_device.h"
 #include "amx_launch.h"
@@ -519,7 +520,7 @@ static WtPlan wt_plan(int N, int D, int H, int W, int Cout, int CinPad) {
   return q;
 }
 
-size_t wgrad_scratch_bytes(int N, int D, int H, int W, int Cout, int CinPad) {
+static size_t wgrad_scratch_bytes(int N, int D, int H, int W, int Cout, int CinPad) {
   const WtPlan q = wt_plan(N, D, H, W, Cout, CinPad);
   return (size_t)q.nchunk * (Cout / 16) * (CinPad / 16) * 27 * 256 * sizeof(float);
 }
@@ -536,7 +537,7 @@ static hipError_t launch_wt(const WgradParams& p, int nwg, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_wgrad(WgradParams p, int CinReal, float* dw, int accumulate, void* scratch, int precision, hipStream_t st) {
+static hipError_t launch_wgrad(WgradParams p, int CinReal, float* dw, int accumulate, void* scratch, int precision, hipStream_t st) {
   const int CinPad = p.C0 + p.C1;
   if (p.W > 128) return hipErrorInvalidValue;
   const WtPlan q = wt_plan(p.N, p.D, p.H, p.W, p.Cout, CinPad);
@@ -565,3 +566,36 @@ hipError_t launch_wgrad(WgradParams p, int CinReal, float* dw, int accumulate, v
 }
 
 }  // namespace amx
+
+using amx::fail;
+
+extern "C" {
+
+size_t amx_conv3d_wgrad_scratch_bytes(int n, int d, int hh, int w, int cout, int cin_pad) {
+  return amx::wgrad_scratch_bytes(n, d, hh, w, cout, cin_pad);
+}
+
+int amx_conv3d_wgrad(const void* d_dy, long long dy_sn, long long dy_sz, long long dy_sy, long long dy_sx, const void* d_x0,
+                     int c0, const void* d_x1, int c1, int cin_real, int cout, int n, int d, int hh, int w, float* d_dw,
+                     int accumulate, void* d_scratch, size_t scratch_bytes, int precision, void* stream) {
+  if (!d_dy || !d_x0 || !d_dw || !d_scratch) return fail(AMX_ERR_INVALID, "null argument");
+  if (c0 % 16 || c1 % 16 || c0 + c1 < 16 || cout % 16 || cout < 16 || cin_real < 1 || cin_real > c0 + c1)
+    return fail(AMX_ERR_INVALID, "channel counts must be multiples of 16 (c0=%d c1=%d cout=%d)", c0, c1, cout);
+  if (c1 && (!d_x1 || (d & 1) || (hh & 1) || (w & 1))) return fail(AMX_ERR_SHAPE, "upsampled segment needs even dims");
+  if (d < 2 || hh < 2 || w < 2 || w > 128) return fail(AMX_ERR_SHAPE, "wgrad supports 2 <= w <= 128 (got %d)", w);
+  if (scratch_bytes < amx::wgrad_scratch_bytes(n, d, hh, w, cout, c0 + c1))
+    return fail(AMX_ERR_WORKSPACE, "scratch needs %zu bytes", amx::wgrad_scratch_bytes(n, d, hh, w, cout, c0 + c1));
+  amx::WgradParams p;
+  memset(&p, 0, sizeof p);
+  p.dy = (const char*)d_dy; p.yn = dy_sn; p.yz = dy_sz; p.yy = dy_sy; p.yx = dy_sx;
+  amx::set_src0(p, d_x0, c0, d, hh, w, AMX_PREC_F16);          // 16-bit channels-last in either precision this kernel takes
+  if (c1) {
+    amx::set_src1(p, d_x1, c1, d / 2, hh / 2, w / 2, AMX_PREC_F16);
+    p.up_shift = 1;
+  }
+  p.N = n; p.D = d; p.H = hh; p.W = w; p.Cout = cout;
+  AMX_HIP(amx::launch_wgrad(p, cin_real, d_dw, accumulate, d_scratch, precision, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+}  // extern "C"

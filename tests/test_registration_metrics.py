@@ -26,8 +26,8 @@ def test_header_table_and_library_agree():
         assert name in _lib.SYMBOLS, name
         assert name + "(" in header, name
     assert "convex_adam_utils.py:226-282" in header and "run_convex_adam_with_network_feats.py:283-295" in header
-    launch = open(os.path.join(ROOT, "anatomix_amd", "csrc", "amx_launch.h")).read()
-    assert "launch_label_overlap(" in launch and "launch_jacobian_det(" in launch
+    unit = open(os.path.join(ROOT, "anatomix_amd", "csrc", "amx_regmetrics.hip")).read()
+    assert "launch_label_overlap(" in unit and "launch_jacobian_det(" in unit
     assert "amx_regmetrics" in open(os.path.join(ROOT, "anatomix_amd", "csrc", "Makefile")).read()
     integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     lib = ctypes.CDLL(_lib.LIB_PATH)
