@@ -115,6 +115,14 @@ SYMBOLS = {
     "amx_instance_norm": (_I, [_P, _P, _P, C.c_float, _I, C.c_longlong, _I, _I, C.c_float, _P, _I, _P]),
     "amx_upsample2_trilinear": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "amx_upsample2_trilinear_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "amx_conv3d_zx_probe_workspace_bytes": (C.c_size_t, []),
+    "amx_conv3d_zx_probe_stats_slots": (_I, [_I, _I]),
+    "amx_conv3d_zx_probe": (_I, [_P, _P, _P, _P, _P, _I, C.c_float, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
+    "amx_instance_norm_probe_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
+    "amx_instance_norm_probe": (_I, [_P, _P, _P, C.c_float, _I, C.c_longlong, _I, _I, _I, C.c_float, _P, C.c_size_t, _I, _I, _P, _I, _I, _P, _P,
+                                     _P]),
+    "amx_instance_norm_apply_pool_probe": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, _I, _I, _I, _I, _P, _P]),
+    "amx_upsample2_trilinear_pending": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.c_float, _P, _P]),
     "amx_upcat_split_backward": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "amx_upcat_split_backward_framed": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "amx_export_ncdhw": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),

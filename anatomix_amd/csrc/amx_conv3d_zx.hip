@@ -17,7 +17,9 @@
 //     fixed-order fold later: deterministic, no atomics) and stores the raw f16 pair, row-planar like every f16x2mx tensor.
 // Tile: 2 output planes x 2 rows x 32 x per step (one 2 x 2 x 16 block per consumer wave), marched along z through a ring of
 // R input planes; 12 waves per workgroup, one workgroup per CU.
+#include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -552,3 +554,60 @@ hipError_t launch_conv_zx(ConvParams p, const float* in_ab, int in_act, float in
 }
 
 }  // namespace amx
+
+using amx::fail;
+
+// ---- test aid: one layer of this kernel, bound the way Forward::layer_params (amx_unet.hip) binds it
+// workspace: [Wh | Wl fragments of pack_weights_mx (Q = 2)] [mxs, 2 ints] [fp8 fragments of pack_weights_zx], each 256-byte aligned
+static size_t zx_probe_wpk_bytes() { return amx::align_up((size_t)32 * 32 * 28 * 2 * 2, 256); }
+
+extern "C" {
+
+size_t amx_conv3d_zx_probe_workspace_bytes(void) { return zx_probe_wpk_bytes() + 256 + amx::conv_zx_packed_bytes(); }
+
+int amx_conv3d_zx_probe_stats_slots(int hh, int w) { return hh > 0 && w > 0 ? hh * w / 32 : 0; }
+
+int amx_conv3d_zx_probe(const void* d_x, const float* d_weight, const float* d_scale, const float* d_bias, const float* d_in_ab, int in_act,
+                        float in_slope, int n, int d, int hh, int w, int act, void* d_ws, size_t ws_bytes, void* d_out16, float* d_out32,
+                        float* d_stats, int* d_oflow, char* kernel_name, void* stream) {
+  if (!d_x || !d_weight || !d_ws || (!d_out16 == !d_out32)) return fail(AMX_ERR_INVALID, "zx probe: bad pointer arguments");
+  if (((uintptr_t)d_ws & 255) || ws_bytes < amx_conv3d_zx_probe_workspace_bytes())
+    return fail(AMX_ERR_WORKSPACE, "zx probe: workspace needs %zu bytes, 256-byte aligned (got %zu)", amx_conv3d_zx_probe_workspace_bytes(), ws_bytes);
+  if (n < 1 || d < 1 || hh < 1 || w < 1) return fail(AMX_ERR_SHAPE, "zx probe: sizes must be positive");
+  if (in_act < AMX_ACT_NONE || in_act > AMX_ACT_LRELU || act < AMX_ACT_NONE || act > AMX_ACT_LRELU) return fail(AMX_ERR_INVALID, "zx probe: unknown activation");
+  // the 16-bit epilogue stores the RAW convolution (its norm and activation are the consumer's): an activation of its own has no form
+  if (d_out16 && act != AMX_ACT_NONE) return fail(AMX_ERR_INVALID, "zx probe: the 16-bit output is stored raw, without an activation");
+  const int P = AMX_PREC_F16X2_MX;
+  hipStream_t st = (hipStream_t)stream;
+  char* wpk = (char*)d_ws;
+  int* mxs = (int*)(wpk + zx_probe_wpk_bytes());
+  char* wx = (char*)mxs + 256;
+  amx::ConvParams p;
+  memset(&p, 0, sizeof p);
+  p.N = n; p.D = d; p.H = hh; p.W = w; p.Cout = 32;
+  amx::set_src0(p, d_x, 32, d, hh, w, P);
+  p.C1 = 0;
+  p.wpk = wpk; p.bias = d_bias; p.act = act; p.slope = in_slope;
+  p.mxs = mxs;
+  p.oflow = d_oflow;
+  if (d_out32) {
+    p.out32 = d_out32;
+    p.py = w; p.pz = (long long)hh * w; p.pc = p.pz * d; p.pn = p.pc * 32;
+  } else {
+    amx::set_out(p, d_out16, 32, d, hh, w, P);
+  }
+  p.stats = d_stats;
+  if (!amx::conv_zx_shape_eligible(p)) {
+    if (d_out32 && (d_stats || act != AMX_ACT_NONE))
+      return fail(AMX_ERR_INVALID, "zx probe: the fp32 planar output carries no statistics and no activation");
+    return fail(AMX_ERR_SHAPE, "zx probe: d even and >= 4, and (w %% 32 == 0, hh even) or (w %% 16 == 0, hh %% 4 == 0) (got %d x %d x %d)", d, hh, w);
+  }
+  AMX_HIP(amx::launch_pack_weights_mx(d_weight, d_scale, wpk, mxs, 32, 32, 32, 2, st, 32));
+  AMX_HIP(amx::launch_pack_weights_zx(d_weight, d_scale, wx, mxs, 32, st));      // (after: it reads the layer's max |w|)
+  amx::ConvLaunchInfo info{};
+  AMX_HIP(amx::launch_conv_zx(p, d_in_ab, in_act, in_slope, wx, st, &info));
+  if (kernel_name) memcpy(kernel_name, info.name, sizeof info.name);
+  return AMX_OK;
+}
+
+}  // extern "C"

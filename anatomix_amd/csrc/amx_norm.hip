@@ -804,4 +804,47 @@ int amx_import_input(const float* d_src, void* d_dst, int n, int cin, int d, int
   return AMX_OK;
 }
 
+// ---- test aids: the fused forms of these launchers, which only Forward (amx_unet.hip) reaches otherwise, one launcher call each
+size_t amx_instance_norm_probe_scratch_bytes(int n, int c, int slots) {
+  return n < 1 || c < 1 || slots < 0 ? 0 : amx::instnorm_scratch_bytes(n, c, (long long)slots * c);
+}
+
+int amx_instance_norm_probe(void* d_x, const float* d_gamma, const float* d_beta, float eps, int n, long long voxels, int c, int w, int act,
+                            float slope, void* d_scratch, size_t scratch_bytes, int precision, int fused_slots, const float* d_kshift,
+                            int skip_lo, int apply, float* d_ab_out, int* d_oflow, void* stream) {
+  if (!d_scratch || c % 8 || c < 8 || c > 2048 || n < 1 || voxels < 1 || fused_slots < 0) return fail(AMX_ERR_INVALID, "norm probe: bad argument");
+  if (!d_x && (apply || fused_slots == 0)) return fail(AMX_ERR_INVALID, "norm probe: only a finalize from slots runs without the tensor");
+  if (!d_gamma != !d_beta) return fail(AMX_ERR_INVALID, "gamma and beta come together");
+  if (precision < AMX_PREC_F16 || precision > AMX_PREC_F16X2_MX) return fail(AMX_ERR_INVALID, "unsupported precision %d", precision);
+  if (precision == AMX_PREC_F16X2_MX && (w < 1 || voxels % w || c % 16 || w > (1 << 24)))
+    return fail(AMX_ERR_SHAPE, "norm probe: f16x2mx takes whole rows of w voxels and whole 16-channel chunks (voxels %lld, w %d, c %d)", voxels, w, c);
+  if (d_kshift && fused_slots == 0) return fail(AMX_ERR_INVALID, "norm probe: the shift belongs to sums a conv epilogue wrote");
+  if (act < AMX_ACT_NONE || act > AMX_ACT_LRELU) return fail(AMX_ERR_INVALID, "norm probe: unknown activation");
+  if (int e = amx::need_scratch(amx_instance_norm_probe_scratch_bytes(n, c, fused_slots), scratch_bytes)) return e;
+  AMX_HIP(amx::launch_instnorm(d_x, d_gamma, d_beta, eps, n, voxels, c, act, slope, d_scratch, precision, (hipStream_t)stream, d_oflow,
+                               fused_slots, d_kshift, w, skip_lo, apply, d_ab_out));
+  return AMX_OK;
+}
+
+int amx_instance_norm_apply_pool_probe(void* d_x, const float* d_ab, void* d_pooled, int n, int d, int hh, int w, int c, int act, float slope,
+                                       int avg, int skip_lo, int pool_skip_lo, int precision, int* d_oflow, void* stream) {
+  if (!d_x || !d_ab || !d_pooled || n < 1 || d < 1 || hh < 1 || w < 1 || c < 1) return fail(AMX_ERR_INVALID, "apply + pool probe: bad argument");
+  if (act < AMX_ACT_NONE || act > AMX_ACT_LRELU) return fail(AMX_ERR_INVALID, "apply + pool probe: unknown activation");
+  if (!amx::in_apply_pool_eligible(precision, d, hh, w, c))
+    return fail(AMX_ERR_SHAPE, "apply + pool probe: f16x2mx, even extents, c %% 16 == 0 and w * c / 8 a multiple of 64 (got %d x %d x %d, c %d)", d, hh,
+                w, c);
+  AMX_HIP(amx::launch_in_apply_pool(d_x, d_ab, d_pooled, n, d, hh, w, c, act, slope, avg, skip_lo, pool_skip_lo, d_oflow, (hipStream_t)stream));
+  return AMX_OK;
+}
+
+int amx_upsample2_trilinear_pending(const void* d_in, void* d_out, int n, int din, int hin, int win, int c, int precision, int skip_lo,
+                                    const float* d_ab, int act, float slope, int* d_oflow, void* stream) {
+  if (!d_in || !d_out || c % 8 || c < 8 || n < 1 || din < 1 || hin < 1 || win < 1) return fail(AMX_ERR_INVALID, "bad argument");
+  if (precision < AMX_PREC_F16 || precision > AMX_PREC_F16X2_MX) return fail(AMX_ERR_INVALID, "unsupported precision %d", precision);
+  if (precision == AMX_PREC_F16X2_MX && c % 16) return fail(AMX_ERR_SHAPE, "f16x2mx stores whole 16-channel chunks (c %d)", c);
+  if (act < AMX_ACT_NONE || act > AMX_ACT_LRELU) return fail(AMX_ERR_INVALID, "unknown activation");
+  AMX_HIP(amx::launch_upsample2_trilinear(d_in, d_out, n, din, hin, win, c, precision, (hipStream_t)stream, skip_lo, d_ab, act, slope, d_oflow));
+  return AMX_OK;
+}
+
 }  // extern "C"

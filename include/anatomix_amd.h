@@ -356,6 +356,47 @@ int amx_instance_norm(void* d_x, const float* d_gamma, const float* d_beta, floa
 int amx_upsample2_trilinear(const void* d_in, void* d_out, int n, int din, int hin, int win, int c,
                             int precision, void* stream);
 
+/* Test aids (no reference counterpart): the fused launches of the AMX_PREC_F16X2_MX schedule, which only amx_unet_forward makes
+ * otherwise, one launch each, so that single-launch tests reach them (tests/test_mx_fused_gpu.py).  Row-planar tensors throughout
+ * (uint8 [n][d][hh][3 c/16][w][32]); d_oflow, where given, is a device int set to 1 when a value about to be stored in f16 lies outside
+ * the f16 range (or is NaN), may be NULL.
+ *
+ * amx_conv3d_zx_probe: one 32 -> 32 layer of the normalise-on-load z-march kernel.  d_x: its input, whose InstanceNorm + activation is
+ * pending when d_in_ab, fp32 [n][32][2] (a, b), is given: the kernel reads act_in(a x + b) (in_act, in_slope).  d_weight fp32
+ * [32][32][27], d_scale / d_bias fp32 [32] or NULL.  Exactly one output: d_out16, row-planar, the RAW convolution (pair only: the copy
+ * section is not written; act must be AMX_ACT_NONE), with the InstanceNorm partial sums of (value - bias) and its square in d_stats,
+ * fp32 [n][amx_conv3d_zx_probe_stats_slots(hh, w)][32][2], when that is given; or d_out32, fp32 NCDHW, which takes no statistics and
+ * no activation (AMX_ERR_INVALID).  d even and >= 4, and w % 32 == 0 with hh even or w % 16 == 0 with hh % 4 == 0: AMX_ERR_SHAPE
+ * otherwise, before anything is launched.  d_ws: amx_conv3d_zx_probe_workspace_bytes() bytes, 256-byte aligned, for the packings.
+ * kernel_name: 64 bytes on the host, the launch's name as in amx_launch_record::kernel, or NULL. */
+size_t amx_conv3d_zx_probe_workspace_bytes(void);
+int amx_conv3d_zx_probe_stats_slots(int hh, int w);
+int amx_conv3d_zx_probe(const void* d_x, const float* d_weight, const float* d_scale, const float* d_bias, const float* d_in_ab, int in_act,
+                        float in_slope, int n, int d, int hh, int w, int act, void* d_ws, size_t ws_bytes, void* d_out16, float* d_out32,
+                        float* d_stats, int* d_oflow, char* kernel_name, void* stream);
+
+/* amx_instance_norm with every argument of its launcher: w, the row length of the row-planar layout (f16x2mx; voxels % w == 0);
+ * fused_slots > 0: the statistics pass is skipped, the head of d_scratch holds partial sums [n][fused_slots][c][2] of (x - K) and its
+ * square, K = d_kshift[c] (NULL: 0) -- a conv epilogue's, or the caller's; more than 512 slots are folded by a pre-reduction first;
+ * apply = 0: the tensor stays as it is (d_x may then be NULL when fused_slots > 0) and the pairs (a, b) with y = a x + b go to d_ab_out,
+ * fp32 [n][c][2] (NULL: they stay in the scratch); skip_lo (f16x2mx): the apply pass writes hi and the copies, not the lo planes.
+ * d_scratch: amx_instance_norm_probe_scratch_bytes(n, c, fused_slots) bytes. */
+size_t amx_instance_norm_probe_scratch_bytes(int n, int c, int slots);
+int amx_instance_norm_probe(void* d_x, const float* d_gamma, const float* d_beta, float eps, int n, long long voxels, int c, int w, int act,
+                            float slope, void* d_scratch, size_t scratch_bytes, int precision, int fused_slots, const float* d_kshift,
+                            int skip_lo, int apply, float* d_ab_out, int* d_oflow, void* stream);
+
+/* y = act(a x + b) in place on d_x [n][d][hh][w][c] with the caller's pairs d_ab fp32 [n][c][2], and its 2x2x2 average (avg) or
+ * maximum pooled copy into d_pooled [n][d/2][hh/2][w/2][c], one launch.  f16x2mx only, even extents, c % 16 == 0 and w * c / 8 a
+ * multiple of 64: AMX_ERR_SHAPE otherwise.  skip_lo / pool_skip_lo: the lo planes of the tensor / of the pooled copy are not written. */
+int amx_instance_norm_apply_pool_probe(void* d_x, const float* d_ab, void* d_pooled, int n, int d, int hh, int w, int c, int act, float slope,
+                                       int avg, int skip_lo, int pool_skip_lo, int precision, int* d_oflow, void* stream);
+
+/* amx_upsample2_trilinear of a tensor whose InstanceNorm + activation is pending: d_ab fp32 [n][c][2] (NULL: none), the eight inputs of
+ * a cell become act(a x + b) on the way in.  skip_lo (f16x2mx): the lo planes of the output are not written. */
+int amx_upsample2_trilinear_pending(const void* d_in, void* d_out, int n, int din, int hin, int win, int c, int precision, int skip_lo,
+                                    const float* d_ab, int act, float slope, int* d_oflow, void* stream);
+
 /* Adjoint of torch.cat((skip, nn.Upsample(2, 'nearest')(low)), 1) (network.py:500-502, 545) applied to the data gradient of the
  * concat conv: d_dcat 16-bit [n][2 dlow][2 hlow][2 wlow][c0 + c1] -> d_dskip [n][2 dlow][2 hlow][2 wlow][c0] (first c0
  * channels; added to the existing content when accumulate_skip) and d_dlow [n][dlow][hlow][wlow][c1] (sum of the 8 children of

@@ -57,6 +57,19 @@ def from_ndhwc_mx(raw, c, parts=False):
     return (val, x8, hi, lo) if parts else (val, x8)
 
 
+def check_copies(raw, c, what):
+    """The 2C copy bytes of every voxel equal torch's e4m3 conversion of the stored pair (hi, 2^11 lo), and the pair is a proper
+    split (lo = the f16 rounding of value - hi, |lo| <= ulp(hi) / 2).  raw: uint8 [N, D, H, 3 C/16, W, 32]; returns the values, NCDHW."""
+    val, x8, hi, lo = from_ndhwc_mx(raw, c, parts=True)
+    assert torch.isfinite(val).all()
+    assert (lo.float().abs() <= hi.float().abs() * 2.0 ** -11 + 2.0 ** -25).all(), what
+    n, d, h, w, _ = hi.shape
+    plane = lambda t: t.reshape(n, d, h, w, c // 16, 16).permute(0, 1, 2, 4, 3, 5)
+    want = torch.cat((plane(e4m3_bytes(lo.float() * 2048.0)), plane(e4m3_bytes(hi.float()))), dim=-1)
+    assert torch.equal(x8, want), f"{what}: {(x8 != want).sum().item()} of {want.numel()} copy bytes differ"
+    return val
+
+
 def split_pair(x, dtype):
     """fp32 -> (hi, lo) of the strict precisions: hi = round(x), lo = round(x - hi)."""
     hi = x.to(dtype)
@@ -143,12 +156,13 @@ def run_conv(device, x0, x1, w, scale, shift, act, precision, planar=False, slop
     return from_ndhwc_split(out) if split else from_ndhwc(out.float())
 
 
-def ref_conv_mx(x0, x1, w, scale, shift, act, slope=0.3):
+def ref_conv_mx(x0, x1, w, scale, shift, act, slope=0.3, direct_lo=False):
     """The arithmetic of AMX_PREC_F16X2_MX restated on the CPU (fp64 sums): Wh * xh exactly as the f16 MFMA multiplies it, plus the
-    two correction products from e4m3 copies under one power-of-two scale."""
+    two correction products from e4m3 copies under one power-of-two scale.  direct_lo: the operand was never stored as a pair (the
+    converter waves of amx_conv3d_zx.hip, mx_split8_direct): its lo copy is e4m3 of the fp32 residual x - hi, not of the f16 lo."""
     def parts(t):
         hi, lo = split_pair(t.float(), torch.float16)
-        return hi.float(), lo.float()
+        return hi.float(), (t.float() - hi.float()) if direct_lo else lo.float()
     xh, xl = parts(x0)
     if x1 is not None:
         uh, ul = parts(x1)

@@ -18,7 +18,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _util import (e4m3_bytes, from_ndhwc_mx, max_rel, ref_conv_fp64, ref_conv_mx, rel_l2, run_conv, split_pair, to_ndhwc_mx)
+from _util import check_copies as _check_copies
+from _util import from_ndhwc_mx, max_rel, ref_conv_fp64, ref_conv_mx, rel_l2, run_conv, to_ndhwc_mx
 import anatomix_amd
 from anatomix_amd import _lib
 from oracle import unet_ref as R
@@ -84,19 +85,6 @@ def test_conv_mx_planar_output_and_saturating_copies(device):
     got = run_conv(device, x0, None, wgt, None, shift, 0, P, planar=True)
     ref = ref_conv_mx(x0, None, wgt, None, shift, 0)
     assert torch.isfinite(got).all() and rel_l2(got, ref) < 2e-6, rel_l2(got, ref)
-
-
-def _check_copies(raw, c, what):
-    """The 2C copy bytes of every voxel equal torch's e4m3 conversion of the stored pair (hi, 2^11 lo), and the pair is a proper
-    split (lo = the f16 rounding of value - hi, |lo| <= ulp(hi) / 2)."""
-    val, x8, hi, lo = from_ndhwc_mx(raw, c, parts=True)
-    assert torch.isfinite(val).all()
-    assert (lo.float().abs() <= hi.float().abs() * 2.0 ** -11 + 2.0 ** -25).all(), what
-    n, d, h, w, _ = hi.shape
-    plane = lambda t: t.reshape(n, d, h, w, c // 16, 16).permute(0, 1, 2, 4, 3, 5)
-    want = torch.cat((plane(e4m3_bytes(lo.float() * 2048.0)), plane(e4m3_bytes(hi.float()))), dim=-1)
-    assert torch.equal(x8, want), f"{what}: {(x8 != want).sum().item()} of {want.numel()} copy bytes differ"
-    return val
 
 
 @pytest.mark.parametrize("shape", [(1, 32, 4, 6, 8), (2, 64, 3, 5, 7), (1, 256, 2, 2, 2)])
