@@ -20,8 +20,10 @@ composition on the GPU too (its attention core then still runs through ``amx_att
 are on the accelerated path, each behind its own switch with the default ``"torch"``: ``PrimusV2.train_attention = "hip"`` runs
 the attention core forward and backward on the library's kernels (``_AttentionCoreFn``: amx_attention_qknorm_rope_train /
 amx_attention_backward) instead of F.scaled_dot_product_attention, and ``PrimusV2.train_linear = "hip"`` runs the blocks' seven
-nn.Linear the same way (``_LinearFn``: amx_linear_forward / amx_linear_backward, f16 operands and fp32 sums).  The LayerNorms,
-LayerScale, the SwiGLU product, the tokenizer and the decoder are torch autograd either way.
+nn.Linear the same way (``_LinearFn``: amx_linear_forward / amx_linear_backward, f16 operands and fp32 sums).  A third part has no
+switch: ``PrimusV2.forward_train_sampled`` (what the contrastive step calls) computes the decoder and a per-voxel output norm only at
+the sampled voxels (``_DecodeRowsFn``: amx_vit_decode_rows_forward / _backward, fp32).  The LayerNorms, LayerScale, the SwiGLU
+product and the tokenizer are torch autograd either way, and so is the decoder in ``forward``.
 """
 from __future__ import annotations
 
@@ -292,6 +294,116 @@ class _LinearFn(torch.autograd.Function):
             _lib.check(lib.amx_linear_backward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(dy), M, K, N, _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
                                                _lib.ptr(scratch), nb, _lib.stream(dev)))
         return dx, dw, db
+
+
+_DECODE_ROWS_MAX_WIDTH, _DECODE_ROWS_MAX_OUT, _DECODE_ROWS_MAX_ROWS = 1056, 64, 1 << 20          # the envelope of amx_vit_decode_rows_* (include/anatomix_amd.h)
+
+
+def _decode_rows_parts(decoder, out_norm):
+    """``(tensors, ln_eps, mode, out_eps)`` of a PatchDecode + output norm as ``amx_vit_decode_rows_*`` takes them -- the twelve
+    parameter tensors {W1, b1, ln1.w, ln1.b, W2, b2, ln2.w, ln2.b, W3, b3, out.w, out.b} (None where absent) -- or a string: why the
+    rows route does not cover these modules."""
+    mods = list(decoder.decode)
+    if len(mods) != 3 or not all(isinstance(m, nn.Sequential) and len(m) == 3 for m in mods[:2]):
+        return "the decoder is not three stages (patch size 8)"
+    convs, norms = [mods[0][0], mods[1][0], mods[2]], [mods[0][1], mods[1][1]]
+    if not all(isinstance(c, nn.ConvTranspose3d) and c.kernel_size == (2, 2, 2) and c.stride == (2, 2, 2) for c in convs):
+        return "the decoder's stages are not ConvTranspose3d(kernel 2, stride 2)"
+    if not all(isinstance(n, LayerNormNd) for n in norms) or norms[0].eps != norms[1].eps:
+        return "the decoder's norms are not LayerNormNd with one eps"
+    if not all(isinstance(m[2], nn.GELU) and m[2].approximate == "none" for m in mods[:2]):
+        return "the decoder's activations are not the erf GELU"
+    if isinstance(out_norm, LayerNormNd):
+        mode, tail, out_eps = 2, [out_norm.weight, out_norm.bias], out_norm.eps
+    elif isinstance(out_norm, ChannelLayerNorm):
+        mode, tail, out_eps = 1, [None, None], out_norm.eps
+    elif out_norm is None or isinstance(out_norm, nn.Identity):
+        mode, tail, out_eps = 0, [None, None], 0.0
+    else:
+        return f"the output norm {type(out_norm).__name__} needs spatial statistics of the dense volume"
+    widths = [convs[0].in_channels] + [c.out_channels for c in convs]
+    if max(widths[:3]) > _DECODE_ROWS_MAX_WIDTH or widths[3] > _DECODE_ROWS_MAX_OUT:
+        return (f"decoder widths {widths} are outside the envelope (up to {_DECODE_ROWS_MAX_WIDTH}, output channels up to "
+                f"{_DECODE_ROWS_MAX_OUT})")
+    tensors = [convs[0].weight, convs[0].bias, norms[0].weight, norms[0].bias, convs[1].weight, convs[1].bias, norms[1].weight,
+               norms[1].bias, convs[2].weight, convs[2].bias] + tail
+    return tensors, float(norms[0].eps), mode, float(out_eps)
+
+
+class _DecodeRowsFn(torch.autograd.Function):
+    """The patch decoder (+ a per-voxel output norm) at sampled voxels under autograd on the library's own kernels
+    (csrc/amx_vit_decode_rows.hip): rows [N, P, C] from tokens [N, T, E] and coordinates [P, 3], all fp32.  Saved: the tokens, the
+    coordinates and the parameters -- the backward call re-runs the forward passes into the shared training scratch (a call leaves
+    nothing there that a later call reads)."""
+
+    @staticmethod
+    def _call(lib, entry, tokens, coords, grid, params, widths, ln_eps, mode, out_eps, extra):
+        dev = tokens.device
+        N, P = tokens.shape[0], coords.shape[0]
+        with torch.cuda.device(dev):
+            nb = lib.amx_vit_decode_rows_scratch_bytes(N, P, *widths)
+            if nb == 0:
+                raise _lib.AmxError(_lib.AMX_ERR_SHAPE, f"decode rows: views {N}, rows {P}, widths {tuple(widths)} are outside the envelope of "
+                                    f"amx_vit_decode_rows_forward (widths up to {_DECODE_ROWS_MAX_WIDTH}, output channels up to "
+                                    f"{_DECODE_ROWS_MAX_OUT}, views x rows up to 2^20)")
+            scratch = _train_scratch(nb, dev)
+            arr = (ctypes.c_void_p * 12)(*[None if t is None else t.data_ptr() for t in params])
+            _lib.check(entry(_lib.ptr(tokens), _lib.ptr(coords), arr, N, P, *grid, *widths, ln_eps, mode, out_eps, *extra, _lib.ptr(scratch), nb,
+                             _lib.stream(dev)))
+
+    @staticmethod
+    def forward(ctx, tokens, coords, grid, ln_eps, mode, out_eps, *params):
+        lib = _lib.load()
+        tok = _lib.f32c(tokens)
+        held = [None if t is None else _lib.f32c(t) for t in params]
+        widths = (held[0].shape[0], held[0].shape[1], held[4].shape[1], held[8].shape[1])
+        rows = torch.empty(tok.shape[0], coords.shape[0], widths[3], dtype=torch.float32, device=tok.device)
+        _DecodeRowsFn._call(lib, lib.amx_vit_decode_rows_forward, tok, coords, grid, held, widths, ln_eps, mode, out_eps, (_lib.ptr(rows),))
+        ctx.save_for_backward(tok, coords, *[t for t in held if t is not None])
+        ctx.present = [t is not None for t in held]
+        ctx.cfg = (tuple(grid), widths, ln_eps, mode, out_eps)
+        return rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, drows):
+        tok, coords, *rest = ctx.saved_tensors
+        it = iter(rest)
+        held = [next(it) if on else None for on in ctx.present]
+        grid, widths, ln_eps, mode, out_eps = ctx.cfg
+        need = ctx.needs_input_grad
+        dtok = torch.empty_like(tok) if need[0] else None
+        grads = [torch.empty_like(t) if t is not None and need[6 + i] else None for i, t in enumerate(held)]
+        garr = (ctypes.c_void_p * 12)(*[None if g is None else g.data_ptr() for g in grads])
+        lib = _lib.load()
+        _DecodeRowsFn._call(lib, lib.amx_vit_decode_rows_backward, tok, coords, grid, held, widths, ln_eps, mode, out_eps,
+                            (_lib.ptr(_lib.f32c(drows)), _lib.ptr(dtok), garr))
+        return (dtok, None, None, None, None, None, *grads)
+
+
+def decode_rows(tokens, coords, decoder, out_norm=None, grid=None, check_coords=True):
+    """``out_norm(decoder(tokens as a volume))[:, :, z, y, x]`` as rows [N, P, C] for the voxels ``coords`` (int64 [P, 3] as (z, y, x),
+    shared by the N views) without the volume: ``tokens`` fp32 [N, T, E] on a GPU, T = prod(grid) in C order, ``decoder`` a
+    ``PatchDecode`` of patch size 8, ``out_norm`` None / Identity / ``ChannelLayerNorm`` / ``LayerNormNd``.  Differentiable in the
+    tokens and every parameter.  ``check_coords``: refuse coordinates outside the volume here (one host read; the kernels clamp
+    whatever they are given) -- for coordinates a caller supplies."""
+    parts = _decode_rows_parts(decoder, out_norm)
+    if isinstance(parts, str):
+        raise _lib.AmxError(_lib.AMX_ERR_SHAPE, f"decode rows: {parts}")
+    tensors, ln_eps, mode, out_eps = parts
+    grid = tuple(int(g) for g in grid)
+    if not tokens.is_cuda:
+        raise RuntimeError("decode rows: the rows route runs on the GPU and has no host path")
+    if tokens.dim() != 3 or tokens.shape[1] != grid[0] * grid[1] * grid[2] or tokens.shape[2] != tensors[0].shape[0]:
+        raise ValueError(f"decode rows: tokens {tuple(tokens.shape)} do not match the grid {grid} and the width {tensors[0].shape[0]}")
+    if coords.dim() != 2 or coords.shape[1] != 3 or coords.dtype != torch.int64 or coords.shape[0] < 1:
+        raise ValueError(f"decode rows: coordinates are int64 [P, 3] (got {coords.dtype} {tuple(coords.shape)})")
+    if check_coords:
+        lo, hi = coords.amin(0).tolist(), coords.amax(0).tolist()
+        if min(lo) < 0 or any(h >= 8 * g for h, g in zip(hi, grid)):
+            raise ValueError(f"decode rows: coordinates span {lo} .. {hi}, outside the volume {tuple(8 * g for g in grid)}")
+    coords = coords.to(tokens.device).contiguous()
+    return _DecodeRowsFn.apply(tokens, coords, grid, ln_eps, mode, out_eps, *tensors)
 
 
 def _linear(layer, x, route):
@@ -578,6 +690,13 @@ class PrimusV2(nn.Module):
             return tuple(buf.view(torch.float16).chunk(2)) if split else (buf.view(torch.float16), None)
         return buf.view(torch.float16)
 
+    def train(self, mode=True):
+        """A switch of mode marks the engine's packed parameters stale: optimizers that update the parameters through raw device
+        pointers (``FusedAdamW``) do not move the tensors' version counters, which is all ``_engine`` compares (``Unet.train`` does the
+        same for its handle)."""
+        self._engine_sig = None
+        return super().train(mode)
+
     def _drop_engine(self):
         """The engine's packed parameters live on the device it was created on: a move / copy / replica starts over."""
         hnd, self._handle = self.__dict__.get("_handle"), None
@@ -627,7 +746,8 @@ class PrimusV2(nn.Module):
         except Exception:
             pass
 
-    def _body(self, x):
+    def _tokens(self, x):
+        """[N, T, E]: the tokens after the final norm, register tokens dropped."""
         feat = self.down_projection(x)
         B, E = feat.shape[:2]
         if tuple(feat.shape[2:]) != self.grid:
@@ -638,8 +758,48 @@ class PrimusV2(nn.Module):
             tok = torch.cat((self.register_tokens.expand(B, -1, -1), tok), 1)
         for blk in self.eva.blocks:
             tok = blk(tok, self.rope_table, nreg)
-        tok = self.eva.norm(tok)[:, nreg:]
-        return self.up_projection(tok.transpose(1, 2).reshape(B, E, *self.grid))
+        return self.eva.norm(tok)[:, nreg:]
+
+    def _body(self, x):
+        tok = self._tokens(x)
+        return self.up_projection(tok.transpose(1, 2).reshape(tok.shape[0], tok.shape[2], *self.grid))
+
+    def sampled_unsupported_reason(self, x, rows=None):
+        """None when ``forward_train_sampled`` covers this network and input, else why not: an output norm with spatial statistics
+        (instance, demean), a CPU tensor, a decoder or widths outside the envelope of ``amx_vit_decode_rows_*`` -- or, when the caller
+        says how many ``rows`` per view it will sample, more views x rows than the kernels take."""
+        if not x.is_cuda:
+            return "the input is a CPU tensor: the rows kernels have no host path"
+        if x.dim() != 5 or tuple(x.shape[2:]) != tuple(8 * g for g in self.grid):
+            return f"the input {tuple(x.shape)} is not [N, C, {', '.join(str(8 * g) for g in self.grid)}]"
+        parts = _decode_rows_parts(self.up_projection, self.out_norm)
+        if isinstance(parts, str):
+            return parts
+        if x.shape[0] < 1 or x.shape[0] > 65535:
+            return f"{x.shape[0]} views are outside the envelope"
+        if rows is not None and (rows < 1 or x.shape[0] * int(rows) > _DECODE_ROWS_MAX_ROWS):
+            return f"{x.shape[0]} views x {rows} rows are outside the envelope (1 .. 2^20)"
+        return None
+
+    def forward_train_sampled(self, x, layers, sampler, on_start=None):
+        """The differentiable forward with the final volume SAMPLED, the contract of ``model.train.forward_train_sampled``: returns
+        ``(None, [rows], [coords], [(D, H, W)])`` -- the fp32 rows [N, P, C] of ``out_norm(decoder(tokens))`` at the coordinates
+        ``sampler(layer id, (D, H, W))`` drew when the forward reached the decoder (called exactly once; ``on_start()`` runs right before
+        it).  The dense volume is never formed: the first result is None.  The body up to the final norm is ``forward``'s, with
+        ``train_attention`` / ``train_linear`` honoured; the decoder and a per-voxel output norm run on ``amx_vit_decode_rows_*``."""
+        layers = [int(l) for l in layers]
+        if len(layers) != 1:
+            raise ValueError(f"PrimusV2.forward_train_sampled: the ViT has one tap, the final volume (got layers {layers})")
+        reason = self.sampled_unsupported_reason(x)
+        if reason is not None:
+            raise _lib.AmxEnvelopeError(_lib.AMX_ERR_SHAPE, f"PrimusV2.forward_train_sampled: {reason}")
+        tok = self._tokens(x)
+        dims = tuple(8 * g for g in self.grid)
+        if on_start is not None:
+            on_start()
+        coords = sampler(layers[0], dims)
+        rows = decode_rows(tok, coords, self.up_projection, self.out_norm, self.grid, check_coords=False)
+        return None, [rows], [coords], [dims]
 
     def forward(self, x, layers=None, encode_only=False, verbose=False, ret_mask=False):
         """architectures.py:122-165: a nonempty ``layers`` asks for the final volume as the sole feature; a boolean ``layers`` is

@@ -24,9 +24,17 @@ What differs, on purpose:
   * TensorBoard, the visuals and the NIfTI dumps are replaced by ``log.jsonl`` (the mechanism of ``train_segmentation``): one JSON
     object per line, kinds ``train`` (total_iters, epoch, loss, per_layer, lr, grad_norm_G, grad_norm_F; every ``print_freq``)
     and ``val`` (total_iters, epoch, loss, best, n).  The ``display_*`` flags are accepted and ignored.
-  * Refused with the reason: ``--netG primus`` (training the ViT is not part of this path), ``--ndims 2``, ``--gpu_ids -1`` (there
-    is no host path), ``--pretrained_name`` together with ``--continue_train`` (the reference calls them mutually exclusive and
-    then silently prefers one)."""
+  * ``--netG primus --primus_version v2`` trains ``PrimusV2`` (built as the reference's ``define_G`` builds it,
+    pretraining_networks.py:107-148) with single-scale NCE on the decoded volume (``nce_layers = [-1]``, supcl_model.py:403-410): eager
+    steps, the decoder on the sampled rows only (``PrimusV2.forward_train_sampled``), ``--primus_train_route {hip,torch}`` (the command
+    line's one further flag, default ``hip``) for the attention cores and the blocks' linears.  Everything in it that is not on those
+    kernels is fp32 torch autograd, and ``--precision`` (the UNet's storage precision) has no effect on it: the reference's bf16 autocast + GradScaler around the Primus step (supcl_model.py:565-574) is not
+    reproduced.  ``netG.txt`` is written as the reference writes it.  Validation volumes have the network's input shape; a crop whose
+    token grid the engine forward does not take (not a multiple of 64 tokens, e.g. ``--crop_size 48``) is validated on the torch modules.
+  * Refused with the reason: ``--netG primus`` with ``--primus_version v1`` (the default; there is no Primus v1 here), a patch size
+    other than 8, a ``crop_size`` that is no multiple of 8, a non-zero ``--primus_drop_path_rate`` or ``--graph on``; ``--ndims 2``,
+    ``--gpu_ids -1`` (there is no host path), ``--pretrained_name`` together with ``--continue_train`` (the reference calls them
+    mutually exclusive and then silently prefers one)."""
 import argparse
 import contextlib
 import copy
@@ -45,6 +53,7 @@ from . import checkpoints as ckpt
 from .schedulers import get_scheduler, update_learning_rate
 
 EXTRA_FLAGS = ("precision", "graph", "loader_seed", "out_log")
+PRIMUS_TRAIN_ROUTES = ("hip", "torch")
 
 # what the trainer's own parser would give for the options the launcher does not pass (tests/golden/pretrain_cli.json)
 TRAINER_DEFAULTS = dict(
@@ -76,9 +85,10 @@ def primus_out_norm_mode(v):
     raise argparse.ArgumentTypeError("expected one of none|instance|demean|layernorm|layernorm_affine (or a bool); got %r" % v)
 
 
-def build_parser():
+def build_parser(primus_route=False):
     """The launcher's flags in its order (scripts/pretrain_anatomix.py with options/primus_options.py), then ``--precision``,
-    ``--graph``, ``--loader_seed`` and ``--out_log``."""
+    ``--graph``, ``--loader_seed`` and ``--out_log``; ``primus_route=True`` (the command line, ``main``) adds
+    ``--primus_train_route`` behind them."""
     parser = argparse.ArgumentParser(description="Pretrain anatomix with configurable arguments.")
     add = parser.add_argument
     add("--ckpt_dir", type=str, default="../checkpoints/pretrain/", help="models are saved here")
@@ -174,11 +184,15 @@ def build_parser():
         help="Init std for register tokens (upstream 1e-6). Only used when --primus_num_register_tokens > 0.")
     # ---- this package's own
     add("--precision", type=str, default="bf16", help="storage precision of the UNet's HIP training path (bf16: what the reference's "
-                                                       "autocast trains in; f16, bf16x2 / strict)")
+                                                       "autocast trains in; f16, bf16x2 / strict); ignored with --netG primus")
     add("--graph", type=str, default="auto", choices=["auto", "off"],
         help="auto: replay the step from a HIP graph when grad_accum_iters is 1 and the batch has the captured shape; off: always eager")
     add("--loader_seed", type=int, default=0, help="seed of the loader's epoch order and augmentation parameters")
     add("--out_log", type=str, default=None, help="path of the JSON-lines log (default <ckpt_dir>/<name>/log.jsonl)")
+    if primus_route:
+        add("--primus_train_route", type=str, default="hip", choices=list(PRIMUS_TRAIN_ROUTES),
+            help="--netG primus: who runs the attention cores and the blocks' linear layers under autograd: hip (this package's "
+                 "kernels, PrimusV2.train_attention / train_linear) or torch")
     return parser
 
 
@@ -197,14 +211,28 @@ def options_from_args(args):
         if getattr(opt, k) in (None, "None"):
             setattr(opt, k, None)
     opt.isTrain = True
+    if not hasattr(opt, "primus_train_route"):
+        opt.primus_train_route = "hip"
     return opt
 
 
 def _refusals(opt):
     if opt.netG == "primus":
-        raise NotImplementedError("--netG primus: training the ViT is not part of this path (its forward is, anatomix_amd.model.vit3d)")
-    if opt.netG != "unet":
-        raise NotImplementedError(f"--netG {opt.netG}: only the UNet is built")
+        if opt.primus_version != "v2":
+            raise NotImplementedError(f"--netG primus --primus_version {opt.primus_version}: there is no Primus v1 class in this package "
+                                      "(its single-conv patch embed was never built); pass --primus_version v2")
+        if opt.primus_patch_size != 8:
+            raise NotImplementedError(f"--primus_patch_size {opt.primus_patch_size}: PrimusV2's deeper patch embed is hardwired to an 8x stride")
+        if opt.crop_size <= 0 or opt.crop_size % 8:
+            raise NotImplementedError(f"--crop_size {opt.crop_size}: a PrimusV2 input is a positive multiple of the patch size 8")
+        if opt.primus_drop_path_rate != 0:
+            raise NotImplementedError(f"--primus_drop_path_rate {opt.primus_drop_path_rate}: drop-path (stochastic depth) is not implemented")
+        if opt.graph == "on":
+            raise NotImplementedError("--graph on with --netG primus: the Primus step is not captured in a HIP graph, it runs eagerly")
+        if getattr(opt, "primus_train_route", "hip") not in PRIMUS_TRAIN_ROUTES:
+            raise NotImplementedError(f"--primus_train_route {opt.primus_train_route}: one of {PRIMUS_TRAIN_ROUTES}")
+    elif opt.netG != "unet":
+        raise NotImplementedError(f"--netG {opt.netG}: only the UNet and PrimusV2 are built")
     if opt.ndims != 3:
         raise NotImplementedError(f"--ndims {opt.ndims}: the HIP path is 3-D only (the reference supports only 3 as well)")
     if len(opt.gpu_ids) == 0:
@@ -245,19 +273,45 @@ def build_networks(opt, device):
     from ..model.network import Unet
     from .patch_sample import PatchSampleF
     from .supcon import SupPatchNCELoss
+    if not hasattr(opt, "nce_layers_list"):
+        opt.nce_layers_list, opt.nce_weights_list = _layers_and_weights(opt)
     with contextlib.redirect_stdout(io.StringIO()):
-        netG = Unet(opt.ndims, opt.input_nc, opt.output_nc, opt.num_downs, ngf=opt.ngf, norm=opt.normG, final_act="none",
-                    activation=opt.actG, pooling=opt.pool_type, interp=opt.interp_type, norm_eps=opt.norm_eps_G)
+        if opt.netG == "primus":
+            netG = _build_primus(opt)
+        else:
+            netG = Unet(opt.ndims, opt.input_nc, opt.output_nc, opt.num_downs, ngf=opt.ngf, norm=opt.normG, final_act="none",
+                        activation=opt.actG, pooling=opt.pool_type, interp=opt.interp_type, norm_eps=opt.norm_eps_G)
         netF = PatchSampleF(use_mlp=opt.use_mlp, init_type=opt.init_type, init_gain=opt.init_gain, nc=opt.netF_nc, n_mlps=opt.n_mlps,
                             activation=opt.actF, norm=opt.normF, norm_eps=opt.norm_eps_F)
-    _init_weights(netG, opt.init_type, opt.init_gain)
-    netG.precision = opt.precision
+    if opt.netG != "primus":                    # (define_G: initialize_weights=False for the ViT, pretraining_networks.py:146-148)
+        _init_weights(netG, opt.init_type, opt.init_gain)
+        netG.precision = opt.precision
     netG = netG.to(device).train()
     crits = [SupPatchNCELoss(opt) for _ in opt.nce_layers_list]
     return netG, netF, crits
 
 
+def _build_primus(opt):
+    """``define_G``'s PrimusV2 (pretraining_networks.py:107-148): the config's depth / heads / width, LayerScale 0.1, the inner
+    attention norm, the options' QK norm, output norm, register tokens and eps; no ``init_weights`` pass."""
+    from ..model.vit3d import PRIMUS_CONFIGS, PrimusV2
+    conf = PRIMUS_CONFIGS[opt.primus_config]
+    if opt.primus_num_register_tokens < 0:
+        raise ValueError("primus_num_register_tokens must be >= 0 (got %d)" % opt.primus_num_register_tokens)
+    ps, cs = opt.primus_patch_size, opt.crop_size
+    net = PrimusV2(input_channels=opt.input_nc, num_classes=opt.output_nc, embed_dim=conf["embed_dim"], eva_depth=conf["eva_depth"],
+                   eva_numheads=conf["eva_numheads"], patch_embed_size=(ps, ps, ps), input_shape=(cs, cs, cs),
+                   drop_path_rate=opt.primus_drop_path_rate, num_register_tokens=opt.primus_num_register_tokens, init_values=0.1,
+                   scale_attn_inner=True, qk_norm=opt.primus_qk_norm, out_norm=opt.primus_out_norm, out_norm_eps=opt.primus_v2_in_eps,
+                   register_init_std=opt.primus_register_init_std, in_eps=opt.primus_v2_in_eps)
+    net.train_attention = net.train_linear = getattr(opt, "primus_train_route", "hip")
+    return net
+
+
 def _layers_and_weights(opt):
+    if opt.netG == "primus":                    # supcl_model.py:403-410
+        print("3D ViT: single-scale NCE on the final feature map (logged as layer -1)")
+        return [-1], [1.0]
     layers = [int(i) for i in opt.nce_layers.split(",")] if opt.nce_layers != "" else []
     if opt.nce_weights != "1":
         w = [float(i) for i in opt.nce_weights.split(",")]
@@ -327,6 +381,9 @@ def pretrain(opt, train_loader=None, val_loader=None, on_step=None, sample_ids=N
     print(f"The number of training images = {train_size}")
 
     netG, netF, crits = build_networks(opt, device)
+    if opt.netG == "primus" and not os.path.exists(os.path.join(save_dir, "netG.txt")):      # supcl_model.py:449-454
+        with open(os.path.join(save_dir, "netG.txt"), "w") as f:
+            print(netG, file=f)
     okw = dict(lr=opt.lr, betas=(opt.beta1, opt.beta2), eps=opt.eps, weight_decay=opt.weight_decay)
     opt_G = FusedAdamW(netG.parameters(), max_norm=opt.max_norm_G if opt.clip_grad else None, **okw)
     optimizers, schedulers = [opt_G], []
@@ -413,7 +470,9 @@ def pretrain(opt, train_loader=None, val_loader=None, on_step=None, sample_ids=N
                     on_step(info)
 
                 shape = (tuple(A.shape), tuple(B.shape), tuple(seg.shape))
-                use_graph = opt.graph == "auto" and opt.grad_accum_iters == 1 and (graph_shape is None or shape == graph_shape)
+                # (a Primus step runs eagerly: --graph auto resolves to off for it, --graph on was refused)
+                use_graph = (opt.graph == "auto" and opt.netG != "primus" and opt.grad_accum_iters == 1 and
+                             (graph_shape is None or shape == graph_shape))
                 if use_graph:
                     if graphed is None:
                         graphed = GraphedContrastiveStep(netG, netF, crits, layers, tuple(optimizers), warmup=2, sample_ids=sample_ids,
@@ -496,7 +555,7 @@ def pretrain(opt, train_loader=None, val_loader=None, on_step=None, sample_ids=N
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(primus_route=True).parse_args(argv)
     return pretrain(options_from_args(args))
 
 

@@ -5,6 +5,7 @@ from collections.abc import Mapping
 
 import contextlib
 import gc
+import warnings
 import weakref
 import os
 
@@ -40,7 +41,7 @@ def _layer_streams(device, n):
 def _taps(netG, netF, reals, nce_layers, num_patches, sample_ids, capturing):
     """The network forward with its feature taps: ``(out, rows, coords, sizes)`` on the sampled route -- per tap the fp32 rows
     [views, P, C] at the drawn coordinates -- or ``(out, dense features, None, sizes)``."""
-    sampled = _sampled_route(netG, netF, reals, nce_layers, num_patches)
+    sampled = _sampled_route(netG, netF, reals, nce_layers, num_patches, sample_ids)
     if sampled is None:
         out, feats = netG(reals, list(nce_layers), False)
         return out, feats, None, [tuple(f.size()[2:]) for f in feats]
@@ -86,10 +87,37 @@ def _taps(netG, netF, reals, nce_layers, num_patches, sample_ids, capturing):
         def sampler(i, shape):
             seen[i] = tuple(shape)
             return netF.draw_coords(sampled[i], shape, num_patches, sample_ids, reals.device)
-    out, rows, coords, dims = _train.forward_train_sampled(netG, reals, list(nce_layers), sampler, draw_all)
+    if _is_primus(netG):
+        # one tap, the final volume: the rows come from the decoder's rows kernels, the dense volume is never formed (out is None)
+        out, rows, coords, dims = netG.forward_train_sampled(reals, list(nce_layers), _checked(sampler, sample_ids), draw_all)
+    else:
+        out, rows, coords, dims = _train.forward_train_sampled(netG, reals, list(nce_layers), sampler, draw_all)
     if shapes is None and sample_ids is None:
         tap_shapes[skey] = dict(seen)
     return out, rows, coords, dims
+
+
+def _is_primus(netG):
+    from ..model.vit3d import PrimusV2
+    return isinstance(netG, PrimusV2)
+
+
+def _checked(sampler, sample_ids):
+    """``sampler`` for a network whose rows kernels clamp whatever coordinates they get: a caller's ``sample_ids`` are refused here
+    when they leave the volume (one host read; coordinates drawn by netF's own sampler are in range by construction)."""
+    if sample_ids is None:
+        return sampler
+
+    def checking(i, shape):
+        coords = sampler(i, shape)
+        if not torch.is_tensor(coords) or coords.dim() != 2 or coords.shape[1] != len(shape) or coords.shape[0] < 1 or coords.is_floating_point():
+            raise ValueError(f"contrastive step: sample_ids of layer {i} are an integer tensor [P, {len(shape)}] "
+                             f"(got {tuple(coords.shape) if torch.is_tensor(coords) else type(coords).__name__})")
+        lo, hi = coords.amin(0).tolist(), coords.amax(0).tolist()
+        if min(lo) < 0 or any(h >= s for h, s in zip(hi, shape)):
+            raise ValueError(f"contrastive step: sample_ids of layer {i} span {lo} .. {hi}, outside the feature map {tuple(shape)}")
+        return coords
+    return checking
 
 
 def _head_route(netF, criterions, seg_A, rows, coords, sizes, capturing):
@@ -173,13 +201,24 @@ def _forward_backward(netG, netF, criterions, real_A, real_B, seg_A, nce_layers,
     return total, layer_losses, ids, out
 
 
-def _sampled_route(netG, netF, reals, nce_layers, num_patches):
+def _sampled_route(netG, netF, reals, nce_layers, num_patches, sample_ids=None):
     """{module id: netF's layer index} when the step can take the sampled-tap route, else None: our Unet on its HIP training path
-    with every tap at a conv id, our PatchSampleF, ascending distinct layer ids (netF's feature order = the forward's order)."""
+    with every tap at a conv id, our PatchSampleF, ascending distinct layer ids (netF's feature order = the forward's order) -- or a
+    PrimusV2 whose decoder runs on sampled rows."""
     from ..model import train as _train
     from ..model.network import Unet
     from .patch_sample import PatchSampleF
     layers = [int(l) for l in nce_layers]
+    if _is_primus(netG):
+        # the ViT's single tap is its decoded volume: sampled when the decoder and the output norm are per-voxel functions of a token
+        # (PrimusV2.sampled_unsupported_reason); ``allow_torch_path = True`` forces the dense modules, for comparison
+        # (rows per view: the caller's coordinates, else min(num_patches, voxels) as netF draws them)
+        given = sample_ids is not None and len(sample_ids) > 0 and torch.is_tensor(sample_ids[0]) and sample_ids[0].dim() >= 1
+        rows = int(sample_ids[0].shape[0]) if given else min(int(num_patches), reals[0, 0].numel())
+        ok = (type(netF) is PatchSampleF and num_patches > 0 and torch.is_grad_enabled() and len(layers) == 1 and
+              not getattr(netG, "allow_torch_path", False) and not (netG._forward_hooks or netG._forward_pre_hooks) and
+              netG.sampled_unsupported_reason(reals, rows) is None)
+        return {layers[0]: 0} if ok else None
     if not (isinstance(netG, Unet) and type(netF) is PatchSampleF and reals.is_cuda and num_patches > 0 and
             torch.is_grad_enabled() and layers == sorted(set(layers)) and not getattr(netG, "allow_torch_path", False)):
         return None
@@ -251,7 +290,8 @@ def contrastive_step(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, 
     """Two aligned views through the shared network with feature taps, same-coordinate patch sampling, per-layer
     SupPatchNCELoss, weighted sum, backward and (optionally) the optimizer steps.
 
-    netG: Unet (train mode: BatchNorm batch statistics over the two views, supcl_model.py:735-742);
+    netG: Unet (train mode: BatchNorm batch statistics over the two views, supcl_model.py:735-742) or PrimusV2 (nce_layers = [-1]: the
+    decoded volume is the one feature, supcl_model.py:403-410; eager steps only; ``out`` is None when the rows route ran);
     netF: PatchSampleF; criterions: one SupPatchNCELoss per nce layer; nce_weights default 1/len (supcl_model.py:388-393);
     optimizers: (opt_G, opt_F) or None (gradients only) -- ``FusedAdamW(max_norm=...)`` ones make it a clipping step: the norms then come
     from ``grad_norms`` (one launch pair for both networks) and each optimizer clips by its own as it steps, after ``unscale_``
@@ -324,6 +364,26 @@ def contrastive_step(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, 
                        out=out.detach() if torch.is_tensor(out) else out)
 
 
+def _eval_forward(netG, reals, nce_layers):
+    """``netG(reals, layers, False)`` in eval mode under no_grad.  A PrimusV2 whose configuration the engine forward does not cover
+    (amx_vit_forward wants a token grid of a multiple of 64 tokens and an even width; training has no such limit) is evaluated on the
+    torch composition of its modules (``use_engine = False``: the attention core still runs on amx_attention_qknorm_rope), said once."""
+    from .. import _lib
+    try:
+        return netG(reals, list(nce_layers), False)
+    except _lib.AmxEnvelopeError as e:
+        if not _is_primus(netG) or not netG.use_engine:
+            raise
+        if not netG.__dict__.get("_amx_eval_warned"):
+            netG.__dict__["_amx_eval_warned"] = True
+            warnings.warn(f"validation_loss: {e}; evaluating this PrimusV2 on its torch modules instead")
+        netG.use_engine = False
+        try:
+            return netG(reals, list(nce_layers), False)
+        finally:
+            netG.use_engine = True
+
+
 def validation_loss(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, nce_weights=None, num_patches=512, lambda_nce=1.0,
                     sample_ids=None):
     """The validation loss of one pair as the reference's training loop evaluates it (train.py:325-347 driving supcl_model.py:723-757,
@@ -334,7 +394,15 @@ def validation_loss(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, n
     Returns an OrderedDict(loss, per_layer, sample_ids)."""
     if nce_weights is None:
         nce_weights = [1.0 / len(nce_layers)] * len(nce_layers)
-    cfg = getattr(netG, "_cfg", None)
+    cfg = getattr(netG, "_cfg", None)          # (the UNet's; a PrimusV2 has none)
+    if _is_primus(netG):
+        # eval mode + no_grad is the engine forward (amx_vit_forward) on the dense volume, sampled below as for the UNet; the network
+        # was built for ONE input shape
+        want = tuple(8 * g for g in netG.grid)
+        for t in (real_A, real_B):
+            if t is not None and tuple(t.shape[2:]) != want:
+                raise ValueError(f"validation_loss: volume {tuple(t.shape[2:])} is not the input shape {want} this PrimusV2 was built "
+                                 "for (crop the validation volumes)")
     for t in (real_A, real_B):
         if t is not None and cfg is not None and any(int(v) % (1 << cfg["num_downs"]) for v in t.shape[2:]):
             raise ValueError(f"validation_loss: volume {tuple(t.shape[2:])} has a side that is no multiple of 2 ** num_downs = "
@@ -345,7 +413,7 @@ def validation_loss(netG, netF, criterions, real_A, real_B, seg_A, nce_layers, n
     try:
         with torch.no_grad():
             reals = torch.cat((real_A, real_B), dim=0) if real_B is not None else real_A
-            _, feats = netG(reals, list(nce_layers), False)
+            _, feats = _eval_forward(netG, reals, nce_layers)
             pooled, ids = netF(feats, num_patches, sample_ids, None, False)
             means = []
             for f_kq, sid, crit, feat in zip(pooled, ids, criterions, feats):

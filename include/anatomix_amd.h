@@ -554,6 +554,38 @@ int amx_linear_forward(const float* d_x, const float* d_w, const float* d_bias, 
 int amx_linear_backward(const float* d_x, const float* d_w, const float* d_dy, long long m, int k, int n, float* d_dx, float* d_dw,
                         float* d_dbias, void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- The ViT's patch decoder on sampled rows, under autograd --------------------------------------------------------------------
+ * Contrastive pretraining of the ViT is single-scale NCE on the decoded volume (pretraining/models/supcl_model.py:403-410,
+ * nce_layers = [-1]) and PatchSampleF reads num_patches voxels of it per view (pretraining_networks.py:472-480).  These entries
+ * replace the dense PatchDecode (three ConvTranspose3d(k = 2, s = 2), channel LayerNorm + erf-GELU between them; the up_projection of
+ * anatomix/model/vit3d/architectures.py:231-260), the per-voxel output norms (architectures.py:36-52, 55-86), that gather, and what
+ * torch autograd replays for them -- for the sampled voxels only.  Kernel == stride, so voxel (z, y, x) is a three-layer MLP on token
+ * t = ((z >> 3) grid_h + (y >> 3)) grid_w + (x >> 3): stage s = 1, 2, 3 applies W_s[:, :, kz, ky, kx] with (kz, ky, kx) = bit (3 - s)
+ * of (z, y, x).
+ *
+ * d_tokens: fp32 [n][grid_d grid_h grid_w][e], the tokens after the final norm without the register tokens.  d_coords: int64 [p][3]
+ * as (z, y, x), shared by the n views; any value is clamped into the volume.  params: HOST array of 12 device pointers, fp32, as the
+ * torch modules store them: {W1 [e][c1][2][2][2], b1, ln1 weight, ln1 bias, W2 [c1][c2][2][2][2], b2, ln2 weight, ln2 bias,
+ * W3 [c2][c][2][2][2], b3, output-norm weight, output-norm bias}; the conv biases may be NULL, the last two are read for
+ * out_norm == 2 only.  out_norm: 0 none, 1 layernorm (no affine), 2 layernorm_affine, with out_eps; ln_eps: the decoder norms'.
+ * d_rows: fp32 [n][p][c].  All arithmetic is fp32; no atomics, every sum in one fixed order: bit-identical results run to run.  No
+ * allocation, no synchronisation, no host read-back (capture-safe).
+ *
+ * amx_vit_decode_rows_scratch_bytes: bytes of d_scratch (16-byte aligned) for either entry; 0 outside the envelope (e, c1, c2 in
+ * 1 .. 1056, c in 1 .. 64, n in 1 .. 65535, n p <= 2^20), which the entries refuse with AMX_ERR_SHAPE. */
+size_t amx_vit_decode_rows_scratch_bytes(int n, int p, int e, int c1, int c2, int c);
+int amx_vit_decode_rows_forward(const float* d_tokens, const long long* d_coords, const void* const* params, int n, int p, int grid_d,
+                                int grid_h, int grid_w, int e, int c1, int c2, int c, float ln_eps, int out_norm, float out_eps,
+                                float* d_rows, void* d_scratch, size_t scratch_bytes, void* stream);
+/* From d_drows [n][p][c]: d_dtokens [n][tokens][e] (exact zeros where no row points) and grads, a HOST array of 12 device pointers in
+ * the order of params.  Every output is written, not accumulated, and may be NULL: it is then skipped and the others are unchanged
+ * bit for bit.  The weight slices of offsets no row selects get exact zeros.  The forward's passes are re-run into d_scratch: the
+ * call reads nothing an earlier call left there. */
+int amx_vit_decode_rows_backward(const float* d_tokens, const long long* d_coords, const void* const* params, int n, int p, int grid_d,
+                                 int grid_h, int grid_w, int e, int c1, int c2, int c, float ln_eps, int out_norm, float out_eps,
+                                 const float* d_drows, float* d_dtokens, void* const* grads, void* d_scratch, size_t scratch_bytes,
+                                 void* stream);
+
 /* ---- The whole 3D ViT variant `anatomix-dev-vit` (PrimusV2-S) as one forward ------------------------------------------------
  * Replaces PrimusV2.forward (anatomix/model/vit3d/architectures.py:231-260 with the wrapper's extensions :89-165, tokenizer
  * deep_tokenizer.py:12-68, registry entry load_from_hf.py:25-35): conv tokenizer (stem + three stride-2 residual stages + 1x1x1
