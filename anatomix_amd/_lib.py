@@ -152,6 +152,12 @@ SYMBOLS = {
     "amx_linear_train_scratch_bytes": (C.c_size_t, [C.c_longlong, _I, _I]),
     "amx_linear_forward": (_I, [_P, _P, _P, C.c_longlong, _I, _I, _P, _P, C.c_size_t, _P]),
     "amx_linear_backward": (_I, [_P, _P, _P, C.c_longlong, _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "amx_tokenizer_train_saved_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "amx_tokenizer_train_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "amx_tokenizer_train_forward": (_I, [_P, C.POINTER(_P), _I, _I, _I, _I, C.c_float, _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "amx_tokenizer_backward": (_I, [_P, _P, C.POINTER(_P), _P, _I, _I, _I, _I, C.c_float, C.POINTER(_P), _P, C.c_size_t, _P]),
+    "amx_tokenizer_train_export": (_I, [_P, _I, _I, _I, _I, _I, _P]),
+    "amx_tokenizer_train_route": (_I, [_I, _I, _I, _I, C.c_char_p, C.c_size_t]),
     "amx_vit_decode_rows_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I]),
     "amx_vit_decode_rows_forward": (_I, [_P, _P, C.POINTER(_P), _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, _I, C.c_float, _P, _P,
                                         C.c_size_t, _P]),

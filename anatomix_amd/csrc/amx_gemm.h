@@ -99,6 +99,7 @@ struct TokConvParams {
 };
 hipError_t launch_tokconv(const TokConvParams& p, int taps, int stride, hipStream_t st, VitLaunchInfo* info = nullptr);
 int tokconv_slots(const TokConvParams& p);      // waves per sample (= partial statistic slots per sample)
+void tokconv_report(const TokConvParams& p, int taps, int stride, VitLaunchInfo* info);   // the instance launch_tokconv runs for p, without launching
 hipError_t launch_pack_tokconv(const float* w, int Cout, int Cin, int taps, void* hi, void* lo, hipStream_t st);
 
 struct TokStemParams {

@@ -194,10 +194,16 @@ static int tokconv_mt(const TokConvParams& p) {          // 64 voxels per wave w
 }
 int tokconv_slots(const TokConvParams& p) { return (int)((long long)p.Do * p.Ho * p.Wo / (16 * tokconv_mt(p))); }
 
+static int tokconv_nt(const TokConvParams& p) { return p.Cout >= 64 ? 4 : 2; }
+// the instance launch_tokconv picks for `p`, as its report names it
+void tokconv_report(const TokConvParams& p, int taps, int stride, VitLaunchInfo* info) {
+  if (info) info->report("tokconv<%d,%d,%d,%d,%s>", taps, stride, tokconv_mt(p), tokconv_nt(p), p.x_lo ? "split" : "f16");
+}
+
 template <int TAPS, int STRIDE>
 static hipError_t launch_tokconv_ts(const TokConvParams& p, hipStream_t st, VitLaunchInfo* info) {
-  const int mt = tokconv_mt(p), nt = p.Cout >= 64 ? 4 : 2;
-  if (info) info->report("tokconv<%d,%d,%d,%d,%s>", TAPS, STRIDE, mt, nt, p.x_lo ? "split" : "f16");
+  const int mt = tokconv_mt(p), nt = tokconv_nt(p);
+  tokconv_report(p, TAPS, STRIDE, info);
   const long long waves = (long long)p.N * p.Do * p.Ho * p.Wo / (16 * mt);
   const dim3 grid((unsigned)(((waves + 3) / 4 + 7) / 8 * 8), p.Cout / (16 * nt)), block(256);      // a multiple of 8 workgroups (XCD-aware order)
 #define AMX_TC(M_, N_)                                                                                        \

@@ -16,14 +16,16 @@ LayerScale residuals, SwiGLU MLP), final norm, transposed-conv decoder, ChannelD
 (``amx_vit_forward``, csrc/amx_vit.hip: own MFMA kernels for the convolutions, the token-matrix products and the attention;
 no vendor GEMM / conv library).  Output norms other than none / demean are applied on the engine's output by their torch module.
 Under autograd or on the CPU the torch modules below compute the same network; ``PrimusV2.use_engine = False`` forces that
-composition on the GPU too (its attention core then still runs through ``amx_attention_qknorm_rope``).  Of training, two parts
+composition on the GPU too (its attention core then still runs through ``amx_attention_qknorm_rope``).  Of training, three parts
 are on the accelerated path, each behind its own switch with the default ``"torch"``: ``PrimusV2.train_attention = "hip"`` runs
 the attention core forward and backward on the library's kernels (``_AttentionCoreFn``: amx_attention_qknorm_rope_train /
 amx_attention_backward) instead of F.scaled_dot_product_attention, and ``PrimusV2.train_linear = "hip"`` runs the blocks' seven
-nn.Linear the same way (``_LinearFn``: amx_linear_forward / amx_linear_backward, f16 operands and fp32 sums).  A third part has no
+nn.Linear the same way (``_LinearFn``: amx_linear_forward / amx_linear_backward, f16 operands and fp32 sums).  Another part has no
 switch: ``PrimusV2.forward_train_sampled`` (what the contrastive step calls) computes the decoder and a per-voxel output norm only at
-the sampled voxels (``_DecodeRowsFn``: amx_vit_decode_rows_forward / _backward, fp32).  The LayerNorms, LayerScale, the SwiGLU
-product and the tokenizer are torch autograd either way, and so is the decoder in ``forward``.
+the sampled voxels (``_DecodeRowsFn``: amx_vit_decode_rows_forward / _backward, fp32).  ``PrimusV2.train_tokenizer = "hip"`` runs the
+conv tokenizer's stem and stages (``_TokenizerFn``: amx_tokenizer_train_forward / amx_tokenizer_backward, strict hi + lo f16 operands;
+``proj`` stays torch).  The LayerNorms, LayerScale and the SwiGLU product are torch autograd either way, and so is the decoder in
+``forward``.
 """
 from __future__ import annotations
 
@@ -150,8 +152,37 @@ class PatchEmbedDeeper(nn.Module):
             cin = c
         self.stages = nn.Sequential(*stages)
         self.proj = nn.Conv3d(cin, embed_dim, 1)
+        self.in_eps = float(in_eps)
+        self.train_route = "torch"           # "hip": stem + stages through ``_TokenizerFn`` under autograd (``PrimusV2.train_tokenizer``)
+
+    def tensors(self):
+        """The 37 parameters of stem + stages in the order of ``amx_tokenizer_train_forward``'s ``params``."""
+        out = [self.stem.conv.weight, self.stem.conv.bias, self.stem.norm.weight, self.stem.norm.bias]
+        for st in self.stages:
+            out += [st.conv1.weight, st.conv1.bias, st.norm1.weight, st.norm1.bias, st.conv2.weight, st.conv2.bias, st.norm2.weight,
+                    st.norm2.bias, st.skip.weight, st.skip_norm.weight, st.skip_norm.bias]
+        return out
+
+    def unsupported_reason(self, x):
+        """None when ``_TokenizerFn`` covers this module and input, else why not."""
+        if x.requires_grad:
+            return "the input requires a gradient: amx_tokenizer_backward computes none for it"
+        if not x.is_cuda:
+            return "the input is a CPU tensor: the tokenizer kernels have no host path"
+        if self.stem.conv.in_channels != 1 or self.stem.conv.out_channels != 32 or len(self.stages) != 3:
+            return "depth_per_level (1, 1, 1), one input channel and base width 32 are what the kernels cover"
+        if x.dim() != 5 or x.shape[1] != 1:
+            return f"the input {tuple(x.shape)} is not [N, 1, D, H, W]"
+        n, _, D, H, W = x.shape
+        with torch.cuda.device(x.device):
+            if _lib.load().amx_tokenizer_train_saved_bytes(n, D, H, W) == 0:
+                return (f"n = {n}, {D} x {H} x {W} is outside the envelope (W a multiple of 16, D and H of 8, a multiple of 64 tokens, "
+                        "at most 2^22 voxels in all)")
+        return None
 
     def forward(self, x):
+        if self.train_route == "hip" and torch.is_grad_enabled() and self.unsupported_reason(x) is None:
+            return self.proj(_TokenizerFn.apply(x, self.in_eps, *self.tensors()))
         return self.proj(self.stages(self.stem(x)))
 
 
@@ -294,6 +325,56 @@ class _LinearFn(torch.autograd.Function):
             _lib.check(lib.amx_linear_backward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(dy), M, K, N, _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
                                                _lib.ptr(scratch), nb, _lib.stream(dev)))
         return dx, dw, db
+
+
+class _TokenizerFn(torch.autograd.Function):
+    """Stem + the three residual stages of ``PatchEmbedDeeper`` under autograd on the library's own kernels
+    (csrc/amx_tokenizer_bwd.hip): ``amx_tokenizer_train_forward`` returns h3, the input of ``proj``, and fills ``saved`` -- a tensor
+    this node owns, not scratch -- with the raw conv outputs, the norm statistics and the hi + lo activation planes;
+    ``amx_tokenizer_backward`` writes the 37 parameter gradients (those nobody needs are passed as null).  No gradient for ``x``."""
+
+    @staticmethod
+    def _sizes(lib, shape):
+        n, _, D, H, W = shape
+        sb, nb = lib.amx_tokenizer_train_saved_bytes(n, D, H, W), lib.amx_tokenizer_train_scratch_bytes(n, D, H, W)
+        if sb == 0:
+            raise _lib.AmxEnvelopeError(_lib.AMX_ERR_SHAPE, f"tokenizer: input {tuple(shape)} is outside the envelope of amx_tokenizer_train_forward")
+        return (n, D, H, W), sb, nb
+
+    @staticmethod
+    def forward(ctx, x, eps, *params):
+        lib = _lib.load()
+        dev = x.device
+        xc, held = _lib.f32c(x.detach()), [_lib.f32c(p.detach()) for p in params]
+        with torch.cuda.device(dev):
+            dims, sb, nb = _TokenizerFn._sizes(lib, xc.shape)
+            n, D, H, W = dims
+            h3 = torch.empty(n, 128, D // 8, H // 8, W // 8, dtype=torch.float32, device=dev)
+            saved = torch.empty(sb, dtype=torch.uint8, device=dev)
+            scratch = _train_scratch(nb, dev)
+            arr = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
+            _lib.check(lib.amx_tokenizer_train_forward(_lib.ptr(xc), arr, *dims, float(eps), _lib.ptr(h3), _lib.ptr(saved), sb, _lib.ptr(scratch), nb,
+                                                       _lib.stream(dev)))
+        ctx.save_for_backward(xc, saved, *held)
+        ctx.eps = float(eps)
+        return h3
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh3):
+        xc, saved, *held = ctx.saved_tensors
+        lib = _lib.load()
+        dev = xc.device
+        need = ctx.needs_input_grad
+        grads = [torch.empty_like(t) if need[2 + i] else None for i, t in enumerate(held)]
+        with torch.cuda.device(dev):
+            dims, sb, nb = _TokenizerFn._sizes(lib, xc.shape)
+            scratch = _train_scratch(nb, dev)
+            arr = (ctypes.c_void_p * len(held))(*[t.data_ptr() for t in held])
+            garr = (ctypes.c_void_p * len(held))(*[None if g is None else g.data_ptr() for g in grads])
+            _lib.check(lib.amx_tokenizer_backward(_lib.ptr(_lib.f32c(dh3)), _lib.ptr(xc), arr, _lib.ptr(saved), *dims, ctx.eps, garr, _lib.ptr(scratch), nb,
+                                                  _lib.stream(dev)))
+        return (None, None, *grads)
 
 
 _DECODE_ROWS_MAX_WIDTH, _DECODE_ROWS_MAX_OUT, _DECODE_ROWS_MAX_ROWS = 1056, 64, 1 << 20          # the envelope of amx_vit_decode_rows_* (include/anatomix_amd.h)
@@ -561,6 +642,7 @@ class PrimusV2(nn.Module):
         self.use_engine = True
         self._train_attention = "torch"
         self._train_linear = "torch"
+        self._train_tokenizer = "torch"
         self._handle = None
         self._engine_sig = None
         self._engine_ws = None
@@ -569,7 +651,8 @@ class PrimusV2(nn.Module):
     def train_attention(self):
         """Who runs the attention core when autograd is on and the input is on a GPU: ``"torch"`` (the default:
         F.scaled_dot_product_attention) or ``"hip"`` (the library's flash forward + backward, ``_AttentionCoreFn``).  The
-        LayerNorms, tokenizer and decoder are torch autograd either way; the linears have their own switch, ``train_linear``."""
+        LayerNorms and decoder are torch autograd either way; the linears and the tokenizer have their own switches, ``train_linear``
+        and ``train_tokenizer``."""
         return self._train_attention
 
     @train_attention.setter
@@ -594,6 +677,27 @@ class PrimusV2(nn.Module):
         self._train_linear = value
         for blk in self.eva.blocks:
             blk.attn.train_linear = blk.mlp.train_linear = value
+
+    @property
+    def train_tokenizer(self):
+        """Who runs the conv tokenizer (stem + three residual stages; ``proj`` stays a torch module) when autograd is on and the input
+        is on a GPU: ``"torch"`` (the default: vendor convolutions under torch autograd) or ``"hip"`` (``_TokenizerFn``: the engine's
+        strict forward kernels plus the library's backward).  Independent of ``train_attention`` / ``train_linear``.  Where
+        ``tokenizer_unsupported_reason`` names a reason, the torch modules run whatever the switch says."""
+        return self._train_tokenizer
+
+    @train_tokenizer.setter
+    def train_tokenizer(self, value):
+        if value not in TRAIN_CORES:
+            raise ValueError(f"train_tokenizer must be one of {TRAIN_CORES}, got {value!r}")
+        self._train_tokenizer = value
+        self.down_projection.train_route = value
+
+    def tokenizer_unsupported_reason(self, x):
+        """None when ``train_tokenizer = "hip"`` covers this network and input, else why not: a CPU tensor, a shape outside the
+        envelope of ``amx_tokenizer_train_forward``, an input that requires a gradient, or a tokenizer other than one input channel,
+        base width 32 and ``depth_per_level`` (1, 1, 1)."""
+        return self.down_projection.unsupported_reason(x)
 
     # ------------------------------------------------------------------------------------------------------------------
     # HIP engine (one C-ABI call per forward)

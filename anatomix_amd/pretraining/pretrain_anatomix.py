@@ -26,8 +26,9 @@ What differs, on purpose:
     and ``val`` (total_iters, epoch, loss, best, n).  The ``display_*`` flags are accepted and ignored.
   * ``--netG primus --primus_version v2`` trains ``PrimusV2`` (built as the reference's ``define_G`` builds it,
     pretraining_networks.py:107-148) with single-scale NCE on the decoded volume (``nce_layers = [-1]``, supcl_model.py:403-410): eager
-    steps, the decoder on the sampled rows only (``PrimusV2.forward_train_sampled``), ``--primus_train_route {hip,torch}`` (the command
-    line's one further flag, default ``hip``) for the attention cores and the blocks' linears.  Everything in it that is not on those
+    steps, the decoder on the sampled rows only (``PrimusV2.forward_train_sampled``), ``--primus_train_route {hip,torch}`` (default
+    ``hip``) for the attention cores and the blocks' linears and ``--primus_train_tokenizer {torch,hip}`` (default ``torch``) for the
+    conv tokenizer's stem and stages -- the command line's two further flags.  Everything in it that is not on those
     kernels is fp32 torch autograd, and ``--precision`` (the UNet's storage precision) has no effect on it: the reference's bf16 autocast + GradScaler around the Primus step (supcl_model.py:565-574) is not
     reproduced.  ``netG.txt`` is written as the reference writes it.  Validation volumes have the network's input shape; a crop whose
     token grid the engine forward does not take (not a multiple of 64 tokens, e.g. ``--crop_size 48``) is validated on the torch modules.
@@ -193,6 +194,9 @@ def build_parser(primus_route=False):
         add("--primus_train_route", type=str, default="hip", choices=list(PRIMUS_TRAIN_ROUTES),
             help="--netG primus: who runs the attention cores and the blocks' linear layers under autograd: hip (this package's "
                  "kernels, PrimusV2.train_attention / train_linear) or torch")
+        add("--primus_train_tokenizer", type=str, default="torch", choices=list(PRIMUS_TRAIN_ROUTES),
+            help="--netG primus: who runs the conv tokenizer's stem and stages under autograd: torch (vendor convolutions) or hip (this "
+                 "package's kernels, PrimusV2.train_tokenizer)")
     return parser
 
 
@@ -213,6 +217,8 @@ def options_from_args(args):
     opt.isTrain = True
     if not hasattr(opt, "primus_train_route"):
         opt.primus_train_route = "hip"
+    if not hasattr(opt, "primus_train_tokenizer"):
+        opt.primus_train_tokenizer = "torch"
     return opt
 
 
@@ -231,6 +237,8 @@ def _refusals(opt):
             raise NotImplementedError("--graph on with --netG primus: the Primus step is not captured in a HIP graph, it runs eagerly")
         if getattr(opt, "primus_train_route", "hip") not in PRIMUS_TRAIN_ROUTES:
             raise NotImplementedError(f"--primus_train_route {opt.primus_train_route}: one of {PRIMUS_TRAIN_ROUTES}")
+        if getattr(opt, "primus_train_tokenizer", "torch") not in PRIMUS_TRAIN_ROUTES:
+            raise NotImplementedError(f"--primus_train_tokenizer {opt.primus_train_tokenizer}: one of {PRIMUS_TRAIN_ROUTES}")
     elif opt.netG != "unet":
         raise NotImplementedError(f"--netG {opt.netG}: only the UNet and PrimusV2 are built")
     if opt.ndims != 3:
@@ -305,6 +313,7 @@ def _build_primus(opt):
                    scale_attn_inner=True, qk_norm=opt.primus_qk_norm, out_norm=opt.primus_out_norm, out_norm_eps=opt.primus_v2_in_eps,
                    register_init_std=opt.primus_register_init_std, in_eps=opt.primus_v2_in_eps)
     net.train_attention = net.train_linear = getattr(opt, "primus_train_route", "hip")
+    net.train_tokenizer = getattr(opt, "primus_train_tokenizer", "torch")
     return net
 
 

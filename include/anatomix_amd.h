@@ -554,6 +554,38 @@ int amx_linear_forward(const float* d_x, const float* d_w, const float* d_bias, 
 int amx_linear_backward(const float* d_x, const float* d_w, const float* d_dy, long long m, int k, int n, float* d_dx, float* d_dw,
                         float* d_dbias, void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- The ViT's conv tokenizer under autograd --------------------------------------------------------------------------------------
+ * PatchEmbedDeeper without its 1x1x1 `proj` (deep_tokenizer.py:12-68): stem conv3(1 -> 32) - InstanceNorm - LeakyReLU(0.01) and three
+ * stride-2 residual stages 32 -> 32 -> 64 -> 128, one block per level.  Strict precision as in amx_vit_forward: fp32 raw conv outputs,
+ * hi + lo f16 operands, three MFMAs per product, fp32 sums; gradient operands are divided by one power of two per tensor, found on the
+ * device (2^e <= max / 8 < 2^(e+1)), before they are split.  No float atomics: every long sum is per-workgroup partials in a fixed order,
+ * combined in double; results are bit-identical run to run.  No allocation, no synchronisation, no host read-back (capture-safe).
+ *
+ * Envelope: one input channel, w % 16 == 0, d % 8 == 0, h % 8 == 0, (d / 8)(h / 8)(w / 8) % 64 == 0, n d h w <= 2^22 (two 128^3 views); the byte queries
+ * return 0 outside it and the entries refuse it with AMX_ERR_SHAPE before any launch.  params: HOST array of 37 device pointers, fp32,
+ * as the torch modules store them: stem conv weight [32][1][3][3][3], bias, norm weight, bias; then per stage conv1 weight, bias, norm1
+ * weight, bias, conv2 weight, bias, norm2 weight, bias, skip weight [cout][cin][1][1][1], skip_norm weight, bias.  Every device pointer
+ * is 16-byte aligned.
+ *
+ * amx_tokenizer_train_forward: d_x fp32 [n][1][d][h][w] -> d_h3 fp32 [n][128][d/8][h/8][w/8] (the input of proj), and in d_saved
+ * (amx_tokenizer_train_saved_bytes) what the backward reads: per norm the mean and 1 / sqrt(var + eps) per (n, c), the raw conv outputs
+ * of the stages, and the hi + lo planes of every activation a conv consumed.  d_saved is state the caller owns until the backward ran;
+ * d_scratch (amx_tokenizer_train_scratch_bytes, for either entry) is not: no call reads what an earlier call left there. */
+size_t amx_tokenizer_train_saved_bytes(int n, int d, int h, int w);
+size_t amx_tokenizer_train_scratch_bytes(int n, int d, int h, int w);
+int amx_tokenizer_train_forward(const float* d_x, const float* const* params, int n, int d, int h, int w, float in_eps, float* d_h3,
+                                void* d_saved, size_t saved_bytes, void* d_scratch, size_t scratch_bytes, void* stream);
+/* From d_dh3 [n][128][d/8][h/8][w/8] (contiguous): grads, a HOST array of 37 device pointers in the order of params.  Every output is
+ * written, not accumulated, and may be NULL: it is then skipped and the others are unchanged bit for bit.  The seven conv biases feed
+ * an InstanceNorm, which removes them: their gradients are exact zeros.  There is no gradient for d_x. */
+int amx_tokenizer_backward(const float* d_dh3, const float* d_x, const float* const* params, const void* d_saved, int n, int d, int h, int w,
+                           float in_eps, float* const* grads, void* d_scratch, size_t scratch_bytes, void* stream);
+/* Test aids.  _export: the saved activation of `site` 0 .. 6 (h0, a1 of stage 0, h1, a1 of stage 1, h2, a1 of stage 2, h3) as fp32
+ * [n][c][..] (the sum of its hi and lo planes); synchronises the device before and after.  _route: the kernel instances one forward
+ * and one backward launch at this shape, one name per line, in launch order, without launching anything. */
+int amx_tokenizer_train_export(const void* d_saved, int n, int d, int h, int w, int site, float* d_out);
+int amx_tokenizer_train_route(int n, int d, int h, int w, char* buf, size_t cap);
+
 /* ---- The ViT's patch decoder on sampled rows, under autograd --------------------------------------------------------------------
  * Contrastive pretraining of the ViT is single-scale NCE on the decoded volume (pretraining/models/supcl_model.py:403-410,
  * nce_layers = [-1]) and PatchSampleF reads num_patches voxels of it per view (pretraining_networks.py:472-480).  These entries
