@@ -152,6 +152,9 @@ SYMBOLS = {
     "amx_linear_train_scratch_bytes": (C.c_size_t, [C.c_longlong, _I, _I]),
     "amx_linear_forward": (_I, [_P, _P, _P, C.c_longlong, _I, _I, _P, _P, C.c_size_t, _P]),
     "amx_linear_backward": (_I, [_P, _P, _P, C.c_longlong, _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "amx_layernorm_train_scratch_bytes": (C.c_size_t, [C.c_longlong, _I]),
+    "amx_layernorm_train_forward": (_I, [_P, _P, _P, _P, C.c_float, C.c_longlong, _I, _P, _P, _P, _P]),
+    "amx_layernorm_backward": (_I, [_P, _P, _P, _P, _P, _P, C.c_longlong, _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "amx_tokenizer_train_saved_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "amx_tokenizer_train_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "amx_tokenizer_train_forward": (_I, [_P, C.POINTER(_P), _I, _I, _I, _I, C.c_float, _P, _P, C.c_size_t, _P, C.c_size_t, _P]),

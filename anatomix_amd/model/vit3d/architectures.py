@@ -24,8 +24,9 @@ nn.Linear the same way (``_LinearFn``: amx_linear_forward / amx_linear_backward,
 switch: ``PrimusV2.forward_train_sampled`` (what the contrastive step calls) computes the decoder and a per-voxel output norm only at
 the sampled voxels (``_DecodeRowsFn``: amx_vit_decode_rows_forward / _backward, fp32).  ``PrimusV2.train_tokenizer = "hip"`` runs the
 conv tokenizer's stem and stages (``_TokenizerFn``: amx_tokenizer_train_forward / amx_tokenizer_backward, strict hi + lo f16 operands;
-``proj`` stays torch).  The LayerNorms, LayerScale and the SwiGLU product are torch autograd either way, and so is the decoder in
-``forward``.
+``proj`` stays torch).  ``PrimusV2.train_norm = "hip"`` runs the blocks' four token LayerNorms, the SwiGLU product in front of
+``mlp.norm`` and the final norm (``_LayerNormFn`` / ``_GatedLayerNormFn``: amx_layernorm_train_forward / amx_layernorm_backward, fp32).
+LayerScale is torch autograd either way, and so is the dense decoder in ``forward``.
 """
 from __future__ import annotations
 
@@ -327,6 +328,86 @@ class _LinearFn(torch.autograd.Function):
         return dx, dw, db
 
 
+class _LayerNormFn(torch.autograd.Function):
+    """``F.layer_norm(x, (C,), w, b, eps)`` over the last axis under autograd on the library's own kernels
+    (csrc/amx_layernorm_train.hip): ``amx_layernorm_train_forward`` forward, ``amx_layernorm_backward`` backward (dx, dw and db in one
+    call; gradients nobody needs are passed as null).  fp32 throughout.  Saved: ``x``, ``w`` and the rows' mean and rstd [M] -- nothing
+    else of width C; the backward recomputes the normalised rows."""
+
+    @staticmethod
+    def _scratch(lib, M, C, dev):
+        nb = lib.amx_layernorm_train_scratch_bytes(M, C)
+        if nb == 0:
+            raise _lib.AmxError(f"layernorm: (M, C) = ({M}, {C}) is outside the envelope of amx_layernorm_train_forward "
+                                "(C a multiple of 4, 8 <= C <= 4096, M * C < 2^31)")
+        return _train_scratch(nb, dev), nb
+
+    @staticmethod
+    def _forward(ctx, gate, x, w, b, eps):
+        lib = _lib.load()
+        C, dev = x.shape[-1], x.device
+        xc, wc, bc = _lib.f32c(x), _lib.f32c(w), _lib.f32c(b)
+        gc = None if gate is None else _lib.f32c(gate)
+        M = xc.numel() // C
+        _LayerNormFn._scratch(lib, M, C, dev)          # the envelope, before anything is allocated
+        y = torch.empty_like(xc)
+        mean, rstd = torch.empty(M, dtype=torch.float32, device=dev), torch.empty(M, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.amx_layernorm_train_forward(_lib.ptr(xc), _lib.ptr(gc), _lib.ptr(wc), _lib.ptr(bc), float(eps), M, C, _lib.ptr(y),
+                                                       _lib.ptr(mean), _lib.ptr(rstd), _lib.stream(dev)))
+        if gate is None:
+            ctx.save_for_backward(xc, wc, mean, rstd)
+        else:
+            ctx.save_for_backward(xc, wc, mean, rstd, gc)
+        return y
+
+    @staticmethod
+    def _backward(ctx, dy, need_gate, need_x, need_w, need_b):
+        x, w, mean, rstd, *rest = ctx.saved_tensors
+        gate = rest[0] if rest else None
+        lib = _lib.load()
+        C, dev = x.shape[-1], x.device
+        M = x.numel() // C
+        dy = _lib.f32c(dy)
+        dx = torch.empty_like(x) if need_x else None
+        dgate = torch.empty_like(gate) if need_gate else None
+        dw = torch.empty_like(w) if need_w else None
+        db = torch.empty_like(w) if need_b else None
+        with torch.cuda.device(dev):
+            scratch, nb = _LayerNormFn._scratch(lib, M, C, dev)
+            _lib.check(lib.amx_layernorm_backward(_lib.ptr(x), _lib.ptr(gate), _lib.ptr(w), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(dy), M, C,
+                                                  _lib.ptr(dx), _lib.ptr(dgate), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(scratch), nb,
+                                                  _lib.stream(dev)))
+        return dgate, dx, dw, db
+
+    @staticmethod
+    def forward(ctx, x, w, b, eps):
+        return _LayerNormFn._forward(ctx, None, x, w, b, eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        need = ctx.needs_input_grad
+        return (*_LayerNormFn._backward(ctx, dy, False, need[0], need[1], need[2])[1:], None)
+
+
+class _GatedLayerNormFn(torch.autograd.Function):
+    """``F.layer_norm(F.silu(gate) * x, (C,), w, b, eps)`` -- the SwiGLU product and ``mlp.norm`` -- through the same two entries with
+    their gate argument: the product is formed in registers and never stored.  Saved: ``gate``, ``x``, ``w``, mean and rstd."""
+
+    @staticmethod
+    def forward(ctx, gate, x, w, b, eps):
+        if gate.shape != x.shape:
+            raise ValueError(f"gated layernorm: gate {tuple(gate.shape)} and x {tuple(x.shape)} differ")
+        return _LayerNormFn._forward(ctx, gate, x, w, b, eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        need = ctx.needs_input_grad
+        return (*_LayerNormFn._backward(ctx, dy, need[0], need[1], need[2], need[3]), None)
+
+
 class _TokenizerFn(torch.autograd.Function):
     """Stem + the three residual stages of ``PatchEmbedDeeper`` under autograd on the library's own kernels
     (csrc/amx_tokenizer_bwd.hip): ``amx_tokenizer_train_forward`` returns h3, the input of ``proj``, and fills ``saved`` -- a tensor
@@ -494,6 +575,24 @@ def _linear(layer, x, route):
     return layer(x)
 
 
+def _norm_on_hip(layer, x, route):
+    """Whether a token LayerNorm of ``x`` takes the library's kernels: the route is "hip", the input is on a GPU, autograd is on, the
+    layer is an affine nn.LayerNorm over the last axis and the rows are inside the envelope of ``amx_layernorm_train_forward``."""
+    if not (route == "hip" and x.is_cuda and torch.is_grad_enabled() and isinstance(layer, nn.LayerNorm)):
+        return False
+    if layer.weight is None or layer.bias is None or tuple(layer.normalized_shape) != (x.shape[-1],) or x.numel() == 0:
+        return False
+    return _lib.load().amx_layernorm_train_scratch_bytes(x.numel() // x.shape[-1], x.shape[-1]) != 0
+
+
+def _layer_norm(layer, x, route):
+    """``layer(x)`` for an nn.LayerNorm over the tokens' last axis: through ``_LayerNormFn`` where ``_norm_on_hip`` says so, else the
+    module itself (CPU tensors, ``torch.no_grad()``, widths outside the envelope, an nn.Identity in its place)."""
+    if _norm_on_hip(layer, x, route):
+        return _LayerNormFn.apply(x, layer.weight, layer.bias, layer.eps)
+    return layer(x)
+
+
 class EvaAttention(nn.Module):
     def __init__(self, dim, num_heads, qk_norm, scale_attn_inner):
         super().__init__()
@@ -508,6 +607,8 @@ class EvaAttention(nn.Module):
         self.train_core = "torch"
         # the four linears under autograd on a GPU: "torch" (nn.Linear) or "hip" (_LinearFn)
         self.train_linear = "torch"
+        # ``norm`` (the scale_attn_inner LayerNorm) under autograd on a GPU: "torch" (the module) or "hip" (_LayerNormFn)
+        self.train_norm = "torch"
 
     def core_hip_train(self, q, k, v, table, n_prefix):
         """``core_hip`` as a differentiable function of q, k, v and the norm parameters (fp32 contiguous CUDA tensors)."""
@@ -556,7 +657,7 @@ class EvaAttention(nn.Module):
             y = self.core_hip_train(q.float().contiguous(), k.float().contiguous(), v.float().contiguous(), table, n_prefix)
         else:
             y = self.core_torch(q, k, v, table, n_prefix)
-        return _linear(self.proj, self.norm(y), lin)
+        return _linear(self.proj, _layer_norm(self.norm, y, self.train_norm), lin)
 
 
 class SwiGLU(nn.Module):
@@ -566,10 +667,16 @@ class SwiGLU(nn.Module):
         self.norm = nn.LayerNorm(hidden, eps=1e-6)
         self.fc2 = nn.Linear(hidden, dim)
         self.train_linear = "torch"          # as EvaAttention.train_linear
+        self.train_norm = "torch"            # "hip": the gate product and ``norm`` through ``_GatedLayerNormFn``
 
     def forward(self, x):
         lin = self.train_linear
-        return _linear(self.fc2, self.norm(F.silu(_linear(self.fc1_g, x, lin)) * _linear(self.fc1_x, x, lin)), lin)
+        g, h = _linear(self.fc1_g, x, lin), _linear(self.fc1_x, x, lin)
+        if _norm_on_hip(self.norm, h, self.train_norm):
+            h = _GatedLayerNormFn.apply(g, h, self.norm.weight, self.norm.bias, self.norm.eps)
+        else:
+            h = self.norm(F.silu(g) * h)
+        return _linear(self.fc2, h, lin)
 
 
 class EvaBlock(nn.Module):
@@ -581,11 +688,12 @@ class EvaBlock(nn.Module):
         self.norm2 = nn.LayerNorm(dim, eps=1e-6)
         self.mlp = SwiGLU(dim, hidden)
         self.gamma_2 = nn.Parameter(init_values * torch.ones(dim)) if init_values is not None else None
+        self.train_norm = "torch"            # norm1 / norm2 under autograd on a GPU: "torch" (the modules) or "hip" (_LayerNormFn)
 
     def forward(self, x, table, n_prefix):
-        a = self.attn(self.norm1(x), table, n_prefix)
+        a = self.attn(_layer_norm(self.norm1, x, self.train_norm), table, n_prefix)
         x = x + (a if self.gamma_1 is None else self.gamma_1 * a)
-        m = self.mlp(self.norm2(x))
+        m = self.mlp(_layer_norm(self.norm2, x, self.train_norm))
         return x + (m if self.gamma_2 is None else self.gamma_2 * m)
 
 
@@ -643,6 +751,7 @@ class PrimusV2(nn.Module):
         self._train_attention = "torch"
         self._train_linear = "torch"
         self._train_tokenizer = "torch"
+        self._train_norm = "torch"
         self._handle = None
         self._engine_sig = None
         self._engine_ws = None
@@ -650,9 +759,9 @@ class PrimusV2(nn.Module):
     @property
     def train_attention(self):
         """Who runs the attention core when autograd is on and the input is on a GPU: ``"torch"`` (the default:
-        F.scaled_dot_product_attention) or ``"hip"`` (the library's flash forward + backward, ``_AttentionCoreFn``).  The
-        LayerNorms and decoder are torch autograd either way; the linears and the tokenizer have their own switches, ``train_linear``
-        and ``train_tokenizer``."""
+        F.scaled_dot_product_attention) or ``"hip"`` (the library's flash forward + backward, ``_AttentionCoreFn``).  LayerScale
+        and the dense decoder are torch autograd either way; the linears, the tokenizer and the token LayerNorms have their own
+        switches, ``train_linear``, ``train_tokenizer`` and ``train_norm``."""
         return self._train_attention
 
     @train_attention.setter
@@ -692,6 +801,23 @@ class PrimusV2(nn.Module):
             raise ValueError(f"train_tokenizer must be one of {TRAIN_CORES}, got {value!r}")
         self._train_tokenizer = value
         self.down_projection.train_route = value
+
+    @property
+    def train_norm(self):
+        """Who runs the token LayerNorms of every EVA block (``norm1``, ``attn.norm``, ``norm2``, ``mlp.norm`` with the SwiGLU product
+        ``silu(g) * x`` in front of it) and the final ``eva.norm`` when autograd is on and the input is on a GPU: ``"torch"`` (the
+        default: the modules under torch autograd) or ``"hip"`` (``_LayerNormFn`` / ``_GatedLayerNormFn``, fp32).  Independent of the
+        other three switches.  The per-head q / k norms belong to the attention core; LayerScale stays torch.  CPU tensors,
+        ``torch.no_grad()`` and widths outside the kernels' envelope keep the modules either way."""
+        return self._train_norm
+
+    @train_norm.setter
+    def train_norm(self, value):
+        if value not in TRAIN_CORES:
+            raise ValueError(f"train_norm must be one of {TRAIN_CORES}, got {value!r}")
+        self._train_norm = value
+        for blk in self.eva.blocks:
+            blk.train_norm = blk.attn.train_norm = blk.mlp.train_norm = value
 
     def tokenizer_unsupported_reason(self, x):
         """None when ``train_tokenizer = "hip"`` covers this network and input, else why not: a CPU tensor, a shape outside the
@@ -862,7 +988,7 @@ class PrimusV2(nn.Module):
             tok = torch.cat((self.register_tokens.expand(B, -1, -1), tok), 1)
         for blk in self.eva.blocks:
             tok = blk(tok, self.rope_table, nreg)
-        return self.eva.norm(tok)[:, nreg:]
+        return _layer_norm(self.eva.norm, tok, self._train_norm)[:, nreg:]
 
     def _body(self, x):
         tok = self._tokens(x)

@@ -554,6 +554,29 @@ int amx_linear_forward(const float* d_x, const float* d_w, const float* d_bias, 
 int amx_linear_backward(const float* d_x, const float* d_w, const float* d_dy, long long m, int k, int n, float* d_dx, float* d_dw,
                         float* d_dbias, void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- The blocks' token LayerNorms and the SwiGLU gate under autograd ---------------------------------------------------------------
+ * The row nn.LayerNorm of an EVA block (norm1, attn.norm, norm2, the final norm) and, with d_gate, the SwiGLU product in front of
+ * mlp.norm -- what torch autograd runs as F.silu, a multiply and F.layer_norm, each with its own saved tensor
+ * (anatomix/model/vit3d/architectures.py:231-260; the blocks are timm's EvaBlock / SwiGLU).  Everything is fp32; d_x, d_gate, d_y,
+ * d_dy, d_dx, d_dgate are row-major [m][c], d_w, d_b, d_dw, d_db are [c], d_mean, d_rstd are [m].
+ *   u = x, or silu(gate) * x with d_gate;   y = (u - mean) * rstd * w + b   (biased variance, eps inside the root, two-pass statistics)
+ * A wave keeps whole rows in registers: a row is read once and u is never stored.  No allocation, no synchronisation (capture-safe);
+ * no atomics and a grid that depends on (m, c) alone: bit-identical results run to run.
+ *
+ * amx_layernorm_train_scratch_bytes: bytes of d_scratch for the backward (per-workgroup partials of dw and db); 0 outside the
+ * envelope: c % 4 == 0, 8 <= c <= 4096, m >= 1, m * c < 2^31.  d_x, d_gate, d_w, d_b, d_y, d_dy, d_dx, d_dgate and d_scratch are
+ * 16-byte aligned. */
+size_t amx_layernorm_train_scratch_bytes(long long m, int c);
+int amx_layernorm_train_forward(const float* d_x, const float* d_gate, const float* d_w, const float* d_b, float eps, long long m, int c,
+                                float* d_y, float* d_mean, float* d_rstd, void* stream);
+/* With x^ = (u - mean) * rstd recomputed from d_x (and d_gate), d_mean and d_rstd, and t = dy * w:
+ *   du = rstd * (t - mean_c(t) - x^ * mean_c(t * x^));   d_dw = sum over rows of dy * x^;   d_db = sum over rows of dy
+ *   without d_gate: d_dx = du;   with it, s = sigmoid(gate): d_dx = du * gate * s,  d_dgate = du * x * s * (1 + gate * (1 - s))
+ * Each output is written, not accumulated, and may be NULL: it is then skipped and the others are unchanged bit for bit. */
+int amx_layernorm_backward(const float* d_x, const float* d_gate, const float* d_w, const float* d_mean, const float* d_rstd, const float* d_dy,
+                           long long m, int c, float* d_dx, float* d_dgate, float* d_dw, float* d_db, void* d_scratch, size_t scratch_bytes,
+                           void* stream);
+
 /* ---- The ViT's conv tokenizer under autograd --------------------------------------------------------------------------------------
  * PatchEmbedDeeper without its 1x1x1 `proj` (deep_tokenizer.py:12-68): stem conv3(1 -> 32) - InstanceNorm - LeakyReLU(0.01) and three
  * stride-2 residual stages 32 -> 32 -> 64 -> 128, one block per level.  Strict precision as in amx_vit_forward: fp32 raw conv outputs,
