@@ -166,6 +166,12 @@ SYMBOLS = {
                                         C.c_size_t, _P]),
     "amx_vit_decode_rows_backward": (_I, [_P, _P, C.POINTER(_P), _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, _I, C.c_float, _P, _P,
                                          C.POINTER(_P), _P, C.c_size_t, _P]),
+    "amx_vit_decoder_train_saved_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I, _I, _I]),
+    "amx_vit_decoder_train_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I, _I, _I]),
+    "amx_vit_decoder_train_forward": (_I, [_P, C.POINTER(_P), _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, _I, C.c_float, _P, _P, C.c_size_t, _P,
+                                          C.c_size_t, _P]),
+    "amx_vit_decoder_backward": (_I, [_P, _P, _P, C.POINTER(_P), _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, _I, C.c_float, _P,
+                                     C.POINTER(_P), _P, C.c_size_t, _P]),
     "amx_vit_create": (_I, [C.POINTER(_P), C.POINTER(VitCfg)]),
     "amx_vit_destroy": (None, [_P]),
     "amx_vit_num_params": (_I, [_P]),

@@ -26,7 +26,9 @@ the sampled voxels (``_DecodeRowsFn``: amx_vit_decode_rows_forward / _backward, 
 conv tokenizer's stem and stages (``_TokenizerFn``: amx_tokenizer_train_forward / amx_tokenizer_backward, strict hi + lo f16 operands;
 ``proj`` stays torch).  ``PrimusV2.train_norm = "hip"`` runs the blocks' four token LayerNorms, the SwiGLU product in front of
 ``mlp.norm`` and the final norm (``_LayerNormFn`` / ``_GatedLayerNormFn``: amx_layernorm_train_forward / amx_layernorm_backward, fp32).
-LayerScale is torch autograd either way, and so is the dense decoder in ``forward``.
+``PrimusV2.train_decoder = "hip"`` runs the dense decoder of ``forward`` and a spatial output norm (none / demean / instance)
+(``_DecoderFn``: amx_vit_decoder_train_forward / amx_vit_decoder_backward, fp32 on the f32-input MFMA) -- the path of a contrastive step
+whose output norm needs the whole volume, and of dense supervision.  LayerScale is torch autograd either way.
 """
 from __future__ import annotations
 
@@ -461,10 +463,9 @@ class _TokenizerFn(torch.autograd.Function):
 _DECODE_ROWS_MAX_WIDTH, _DECODE_ROWS_MAX_OUT, _DECODE_ROWS_MAX_ROWS = 1056, 64, 1 << 20          # the envelope of amx_vit_decode_rows_* (include/anatomix_amd.h)
 
 
-def _decode_rows_parts(decoder, out_norm):
-    """``(tensors, ln_eps, mode, out_eps)`` of a PatchDecode + output norm as ``amx_vit_decode_rows_*`` takes them -- the twelve
-    parameter tensors {W1, b1, ln1.w, ln1.b, W2, b2, ln2.w, ln2.b, W3, b3, out.w, out.b} (None where absent) -- or a string: why the
-    rows route does not cover these modules."""
+def _decoder_stages(decoder):
+    """``(convs, norms)`` of a three-stage PatchDecode -- what both decoder routes of the library restate -- or a string: why these
+    modules are something else."""
     mods = list(decoder.decode)
     if len(mods) != 3 or not all(isinstance(m, nn.Sequential) and len(m) == 3 for m in mods[:2]):
         return "the decoder is not three stages (patch size 8)"
@@ -475,6 +476,17 @@ def _decode_rows_parts(decoder, out_norm):
         return "the decoder's norms are not LayerNormNd with one eps"
     if not all(isinstance(m[2], nn.GELU) and m[2].approximate == "none" for m in mods[:2]):
         return "the decoder's activations are not the erf GELU"
+    return convs, norms
+
+
+def _decode_rows_parts(decoder, out_norm):
+    """``(tensors, ln_eps, mode, out_eps)`` of a PatchDecode + output norm as ``amx_vit_decode_rows_*`` takes them -- the twelve
+    parameter tensors {W1, b1, ln1.w, ln1.b, W2, b2, ln2.w, ln2.b, W3, b3, out.w, out.b} (None where absent) -- or a string: why the
+    rows route does not cover these modules."""
+    stages = _decoder_stages(decoder)
+    if isinstance(stages, str):
+        return stages
+    convs, norms = stages
     if isinstance(out_norm, LayerNormNd):
         mode, tail, out_eps = 2, [out_norm.weight, out_norm.bias], out_norm.eps
     elif isinstance(out_norm, ChannelLayerNorm):
@@ -566,6 +578,108 @@ def decode_rows(tokens, coords, decoder, out_norm=None, grid=None, check_coords=
             raise ValueError(f"decode rows: coordinates span {lo} .. {hi}, outside the volume {tuple(8 * g for g in grid)}")
     coords = coords.to(tokens.device).contiguous()
     return _DecodeRowsFn.apply(tokens, coords, grid, ln_eps, mode, out_eps, *tensors)
+
+
+_DECODER_NORM_MODES = {"none": 0, "demean": 1, "instance": 2}          # out_norm of amx_vit_decoder_train_forward (include/anatomix_amd.h)
+
+
+def _decoder_train_parts(decoder, out_norm):
+    """``(tensors, ln_eps, mode, out_eps, tail)`` of a PatchDecode + output norm as ``amx_vit_decoder_train_forward`` takes them -- the
+    ten parameter tensors {W1, b1, ln1.w, ln1.b, W2, b2, ln2.w, ln2.b, W3, b3}, the output norm the call applies itself (none /
+    demean / instance) and ``tail``, the torch module that runs on the call's output (a per-voxel norm; None otherwise) -- or a
+    string: why the dense route does not cover the decoder.  No output norm is a reason."""
+    stages = _decoder_stages(decoder)
+    if isinstance(stages, str):
+        return stages
+    convs, norms = stages
+    mode, out_eps, tail = 0, 0.0, None
+    if isinstance(out_norm, ChannelDemean):
+        mode = _DECODER_NORM_MODES["demean"]
+    elif isinstance(out_norm, nn.InstanceNorm3d) and not out_norm.affine and not out_norm.track_running_stats:
+        mode, out_eps = _DECODER_NORM_MODES["instance"], out_norm.eps
+    elif out_norm is not None and not isinstance(out_norm, nn.Identity):
+        tail = out_norm
+    tensors = [convs[0].weight, convs[0].bias, norms[0].weight, norms[0].bias, convs[1].weight, convs[1].bias, norms[1].weight,
+               norms[1].bias, convs[2].weight, convs[2].bias]
+    return tensors, float(norms[0].eps), mode, float(out_eps), tail
+
+
+class _DecoderFn(torch.autograd.Function):
+    """The dense patch decoder and a spatial output norm under autograd on the library's own kernels (csrc/amx_vit_decode_train.hip):
+    tokens [N, T, E] -> the planar fp32 volume [N, C, 8 gd, 8 gh, 8 gw] of ``out_norm(decoder(tokens as a volume))`` for the modes
+    none / demean / instance, all fp32 (products on the f32-input MFMA).  ``amx_vit_decoder_train_forward`` fills ``saved`` -- a
+    tensor this node owns, not scratch -- with the raw stage outputs and the norm statistics; ``amx_vit_decoder_backward`` writes
+    ``d_tokens`` and the ten parameter gradients (those nobody needs are passed as null).  Saved besides: the tokens, the parameters
+    and, for the instance norm, the output."""
+
+    @staticmethod
+    def _sizes(lib, n, grid, widths):
+        sb, nb = lib.amx_vit_decoder_train_saved_bytes(n, *grid, *widths), lib.amx_vit_decoder_train_scratch_bytes(n, *grid, *widths)
+        if sb == 0:
+            raise _lib.AmxEnvelopeError(_lib.AMX_ERR_SHAPE, f"decoder: views {n}, token grid {tuple(grid)}, widths {tuple(widths)} are outside "
+                                        "the envelope of amx_vit_decoder_train_forward")
+        return sb, nb
+
+    @staticmethod
+    def forward(ctx, tokens, grid, ln_eps, mode, out_eps, *params):
+        lib = _lib.load()
+        dev = tokens.device
+        tok = _lib.f32c(tokens.detach())
+        held = [None if t is None else _lib.f32c(t.detach()) for t in params]
+        widths = (held[0].shape[0], held[0].shape[1], held[4].shape[1], held[8].shape[1])
+        grid = tuple(int(g) for g in grid)
+        n = tok.shape[0]
+        if tok.dim() != 3 or tok.shape[1] != grid[0] * grid[1] * grid[2] or tok.shape[2] != widths[0]:
+            raise ValueError(f"decoder: tokens {tuple(tok.shape)} do not match the grid {grid} and the width {widths[0]}")
+        with torch.cuda.device(dev):
+            sb, nb = _DecoderFn._sizes(lib, n, grid, widths)
+            out = torch.empty(n, widths[3], *(8 * g for g in grid), dtype=torch.float32, device=dev)
+            saved = torch.empty(sb, dtype=torch.uint8, device=dev)
+            scratch = _train_scratch(nb, dev)
+            arr = (ctypes.c_void_p * 10)(*[None if t is None else t.data_ptr() for t in held])
+            _lib.check(lib.amx_vit_decoder_train_forward(_lib.ptr(tok), arr, n, *grid, *widths, float(ln_eps), int(mode), float(out_eps),
+                                                         _lib.ptr(out), _lib.ptr(saved), sb, _lib.ptr(scratch), nb, _lib.stream(dev)))
+        ctx.save_for_backward(tok, saved, *([out] if mode == _DECODER_NORM_MODES["instance"] else []), *[t for t in held if t is not None])
+        ctx.present = [t is not None for t in held]
+        ctx.cfg = (grid, widths, float(ln_eps), int(mode), float(out_eps))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        grid, widths, ln_eps, mode, out_eps = ctx.cfg
+        tok, saved, *rest = ctx.saved_tensors
+        out = rest.pop(0) if mode == _DECODER_NORM_MODES["instance"] else None
+        it = iter(rest)
+        held = [next(it) if on else None for on in ctx.present]
+        lib = _lib.load()
+        dev = tok.device
+        need = ctx.needs_input_grad
+        dtok = torch.empty_like(tok) if need[0] else None
+        grads = [torch.empty_like(t) if t is not None and need[5 + i] else None for i, t in enumerate(held)]
+        with torch.cuda.device(dev):
+            sb, nb = _DecoderFn._sizes(lib, tok.shape[0], grid, widths)
+            scratch = _train_scratch(nb, dev)
+            arr = (ctypes.c_void_p * 10)(*[None if t is None else t.data_ptr() for t in held])
+            garr = (ctypes.c_void_p * 10)(*[None if g is None else g.data_ptr() for g in grads])
+            _lib.check(lib.amx_vit_decoder_backward(_lib.ptr(_lib.f32c(dout)), _lib.ptr(out), _lib.ptr(tok), arr, _lib.ptr(saved), sb, tok.shape[0],
+                                                    *grid, *widths, ln_eps, mode, out_eps, _lib.ptr(dtok), garr, _lib.ptr(scratch), nb,
+                                                    _lib.stream(dev)))
+        return (dtok, None, None, None, None, *grads)
+
+
+def decode_dense(tokens, decoder, out_norm=None, grid=None):
+    """``out_norm(decoder(tokens as a volume))`` [N, C, 8 gd, 8 gh, 8 gw] through ``_DecoderFn``: ``tokens`` fp32 [N, T, E] on a GPU,
+    T = prod(grid) in C order, ``decoder`` a ``PatchDecode`` of patch size 8.  none / demean / instance run inside the call; any
+    other output norm module runs on the call's output.  Differentiable in the tokens and every parameter."""
+    parts = _decoder_train_parts(decoder, out_norm)
+    if isinstance(parts, str):
+        raise _lib.AmxEnvelopeError(_lib.AMX_ERR_SHAPE, f"decoder: {parts}")
+    if not tokens.is_cuda:
+        raise RuntimeError("decoder: the dense route runs on the GPU and has no host path")
+    tensors, ln_eps, mode, out_eps, tail = parts
+    vol = _DecoderFn.apply(tokens, tuple(int(g) for g in grid), ln_eps, mode, out_eps, *tensors)
+    return vol if tail is None else tail(vol)
 
 
 def _linear(layer, x, route):
@@ -752,6 +866,7 @@ class PrimusV2(nn.Module):
         self._train_linear = "torch"
         self._train_tokenizer = "torch"
         self._train_norm = "torch"
+        self._train_decoder = "torch"
         self._handle = None
         self._engine_sig = None
         self._engine_ws = None
@@ -760,8 +875,8 @@ class PrimusV2(nn.Module):
     def train_attention(self):
         """Who runs the attention core when autograd is on and the input is on a GPU: ``"torch"`` (the default:
         F.scaled_dot_product_attention) or ``"hip"`` (the library's flash forward + backward, ``_AttentionCoreFn``).  LayerScale
-        and the dense decoder are torch autograd either way; the linears, the tokenizer and the token LayerNorms have their own
-        switches, ``train_linear``, ``train_tokenizer`` and ``train_norm``."""
+        is torch autograd either way; the linears, the tokenizer, the token LayerNorms and the dense decoder have their own
+        switches, ``train_linear``, ``train_tokenizer``, ``train_norm`` and ``train_decoder``."""
         return self._train_attention
 
     @train_attention.setter
@@ -818,6 +933,38 @@ class PrimusV2(nn.Module):
         self._train_norm = value
         for blk in self.eva.blocks:
             blk.train_norm = blk.attn.train_norm = blk.mlp.train_norm = value
+
+    @property
+    def train_decoder(self):
+        """Who runs the dense patch decoder and a spatial output norm in ``forward`` when autograd is on and the input is on a GPU:
+        ``"torch"`` (the default: vendor transposed convolutions under torch autograd) or ``"hip"`` (``_DecoderFn``: fp32 products on
+        the f32-input MFMA, forward and every gradient on the library's kernels).  none / demean / instance run inside the call; a
+        per-voxel output norm (layernorm, layernorm_affine) keeps its torch module behind it.  Independent of the other four
+        switches; ``forward_train_sampled`` and the no-grad engine path do not look at it.  Where ``decoder_unsupported_reason``
+        names a reason, the torch modules run whatever the switch says."""
+        return self._train_decoder
+
+    @train_decoder.setter
+    def train_decoder(self, value):
+        if value not in TRAIN_CORES:
+            raise ValueError(f"train_decoder must be one of {TRAIN_CORES}, got {value!r}")
+        self._train_decoder = value
+
+    def decoder_unsupported_reason(self, x):
+        """None when ``train_decoder = "hip"`` covers this network and input, else why not: a CPU tensor, a decoder that is not the
+        three-stage ``PatchDecode``, or views / widths outside the envelope of ``amx_vit_decoder_train_forward``."""
+        if not x.is_cuda:
+            return "the input is a CPU tensor: the decoder kernels have no host path"
+        parts = _decoder_train_parts(self.up_projection, self.out_norm)
+        if isinstance(parts, str):
+            return parts
+        w = parts[0]
+        widths = (w[0].shape[0], w[0].shape[1], w[4].shape[1], w[8].shape[1])
+        with torch.cuda.device(x.device):
+            if _lib.load().amx_vit_decoder_train_saved_bytes(int(x.shape[0]), *self.grid, *widths) == 0:
+                return (f"{x.shape[0]} views, token grid {self.grid}, decoder widths {widths} are outside the envelope (multiples of 4 up "
+                        "to 1056 / 328 / 104, 1 .. 128 output channels, every tensor below 2^31 elements)")
+        return None
 
     def tokenizer_unsupported_reason(self, x):
         """None when ``train_tokenizer = "hip"`` covers this network and input, else why not: a CPU tensor, a shape outside the
@@ -1048,6 +1195,8 @@ class PrimusV2(nn.Module):
                     raise
                 raise _lib.AmxEnvelopeError(e.code, f"PrimusV2: the HIP engine does not cover this configuration ({e}); set "
                                             "`model.use_engine = False` to run the stock torch composition of the same modules") from e
+        elif self._train_decoder == "hip" and torch.is_grad_enabled() and self.decoder_unsupported_reason(x) is None:
+            output = decode_dense(self._tokens(x), self.up_projection, self.out_norm, self.grid)
         else:
             output = self.out_norm(self._body(x))
         if ret_mask:

@@ -28,8 +28,10 @@ What differs, on purpose:
     pretraining_networks.py:107-148) with single-scale NCE on the decoded volume (``nce_layers = [-1]``, supcl_model.py:403-410): eager
     steps, the decoder on the sampled rows only (``PrimusV2.forward_train_sampled``), ``--primus_train_route {hip,torch}`` (default
     ``hip``) for the attention cores and the blocks' linears, ``--primus_train_tokenizer {torch,hip}`` (default ``torch``) for the
-    conv tokenizer's stem and stages and ``--primus_train_norm {torch,hip}`` (default ``torch``) for the blocks' token LayerNorms, the
-    SwiGLU gate product and the final norm -- the command line's three further flags.  What is not on those kernels (LayerScale, the
+    conv tokenizer's stem and stages, ``--primus_train_norm {torch,hip}`` (default ``torch``) for the blocks' token LayerNorms, the
+    SwiGLU gate product and the final norm and ``--primus_train_decoder {torch,hip}`` (default ``torch``) for the dense decoder and a
+    spatial output norm (``--primus_out_norm demean`` / ``instance``, which the rows route does not take) -- the command line's four
+    further flags.  What is not on those kernels (LayerScale, the
     tokenizer's ``proj``, the heads) is fp32 torch autograd, and ``--precision`` (the UNet's storage precision) has no effect on it: the reference's bf16 autocast + GradScaler around the Primus step (supcl_model.py:565-574) is not
     reproduced.  ``netG.txt`` is written as the reference writes it.  Validation volumes have the network's input shape; a crop whose
     token grid the engine forward does not take (not a multiple of 64 tokens, e.g. ``--crop_size 48``) is validated on the torch modules.
@@ -90,7 +92,7 @@ def primus_out_norm_mode(v):
 def build_parser(primus_route=False):
     """The launcher's flags in its order (scripts/pretrain_anatomix.py with options/primus_options.py), then ``--precision``,
     ``--graph``, ``--loader_seed`` and ``--out_log``; ``primus_route=True`` (the command line, ``main``) adds
-    ``--primus_train_route``, ``--primus_train_tokenizer`` and ``--primus_train_norm`` behind them."""
+    ``--primus_train_route``, ``--primus_train_tokenizer``, ``--primus_train_norm`` and ``--primus_train_decoder`` behind them."""
     parser = argparse.ArgumentParser(description="Pretrain anatomix with configurable arguments.")
     add = parser.add_argument
     add("--ckpt_dir", type=str, default="../checkpoints/pretrain/", help="models are saved here")
@@ -201,6 +203,9 @@ def build_parser(primus_route=False):
         add("--primus_train_norm", type=str, default="torch", choices=list(PRIMUS_TRAIN_ROUTES),
             help="--netG primus: who runs the blocks' token LayerNorms, the SwiGLU gate product and the final norm under autograd: torch "
                  "(the modules) or hip (this package's kernels, PrimusV2.train_norm)")
+        add("--primus_train_decoder", type=str, default="torch", choices=list(PRIMUS_TRAIN_ROUTES),
+            help="--netG primus: who runs the dense patch decoder and a spatial output norm (demean, instance) under autograd: torch "
+                 "(vendor transposed convolutions) or hip (this package's kernels, PrimusV2.train_decoder)")
     return parser
 
 
@@ -225,6 +230,8 @@ def options_from_args(args):
         opt.primus_train_tokenizer = "torch"
     if not hasattr(opt, "primus_train_norm"):
         opt.primus_train_norm = "torch"
+    if not hasattr(opt, "primus_train_decoder"):
+        opt.primus_train_decoder = "torch"
     return opt
 
 
@@ -247,6 +254,8 @@ def _refusals(opt):
             raise NotImplementedError(f"--primus_train_tokenizer {opt.primus_train_tokenizer}: one of {PRIMUS_TRAIN_ROUTES}")
         if getattr(opt, "primus_train_norm", "torch") not in PRIMUS_TRAIN_ROUTES:
             raise NotImplementedError(f"--primus_train_norm {opt.primus_train_norm}: one of {PRIMUS_TRAIN_ROUTES}")
+        if getattr(opt, "primus_train_decoder", "torch") not in PRIMUS_TRAIN_ROUTES:
+            raise NotImplementedError(f"--primus_train_decoder {opt.primus_train_decoder}: one of {PRIMUS_TRAIN_ROUTES}")
     elif opt.netG != "unet":
         raise NotImplementedError(f"--netG {opt.netG}: only the UNet and PrimusV2 are built")
     if opt.ndims != 3:
@@ -323,6 +332,7 @@ def _build_primus(opt):
     net.train_attention = net.train_linear = getattr(opt, "primus_train_route", "hip")
     net.train_tokenizer = getattr(opt, "primus_train_tokenizer", "torch")
     net.train_norm = getattr(opt, "primus_train_norm", "torch")
+    net.train_decoder = getattr(opt, "primus_train_decoder", "torch")
     return net
 
 

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..model.network import Unet
+from ..model.vit3d.architectures import PrimusV2
 
 MAX_CLASSES, MAX_HEAD_CHANNELS = 32, 64
 CALLS = {"head": 0, "logits": 0}          # how often each fused autograd Function ran (tests, diagnostics)
@@ -237,11 +238,12 @@ def head_dice_ce(features, head, labels, loss):
 
 
 def finetune_loss(model, inputs, labels, loss):
-    """``loss(model(inputs), labels)`` (train_segmentation.py:144-145).  When ``model`` is ``nn.Sequential(Unet, head)`` with a
-    head made of one 1x1x1 convolution -- decided from the structure alone -- the head and the loss run fused
-    (``head_dice_ce``) on the Unet's features; any other model takes the plain composition."""
+    """``loss(model(inputs), labels)`` (train_segmentation.py:144-145).  When ``model`` is ``nn.Sequential(Unet, head)`` or
+    ``nn.Sequential(PrimusV2, head)`` with a head made of one 1x1x1 convolution -- decided from the structure alone -- the head and
+    the loss run fused (``head_dice_ce``) on the network's dense features (for the ViT those of ``PrimusV2.forward``, whose decoder
+    ``train_decoder`` routes); any other model takes the plain composition."""
     if (isinstance(model, nn.Sequential) and type(model).forward is nn.Sequential.forward and len(model) == 2 and
-            isinstance(model[0], Unet) and isinstance(loss, _SegLoss) and inputs.is_cuda and _single_conv_head(model[1]) is not None):
+            isinstance(model[0], (Unet, PrimusV2)) and isinstance(loss, _SegLoss) and inputs.is_cuda and _single_conv_head(model[1]) is not None):
         return head_dice_ce(model[0](inputs), model[1], labels, loss)
     return loss(model(inputs), labels)
 

@@ -641,6 +641,41 @@ int amx_vit_decode_rows_backward(const float* d_tokens, const long long* d_coord
                                  const float* d_drows, float* d_dtokens, void* const* grads, void* d_scratch, size_t scratch_bytes,
                                  void* stream);
 
+/* ---- The ViT's patch decoder on the whole volume, with the spatial output norms, under autograd -------------------------------------
+ * Replaces, for training, the dense PatchDecode (the up_projection of anatomix/model/vit3d/architectures.py:231-260: three
+ * ConvTranspose3d(k = 2, s = 2), channel LayerNorm + erf-GELU between them), the output norms that need the whole volume
+ * (architectures.py:28-33 ChannelDemean, architectures.py:55-86 nn.InstanceNorm3d(affine=False)) and what torch autograd replays for
+ * them: the path of a contrastive step whose output norm is spatial (pretraining/models/supcl_model.py:403-410) and of dense
+ * supervision on the ViT's features.  A stage is a row product [R, Cin] x [Cin, 8 Cout]; the rows stay in nested order (token, then
+ * the child offset of stage 1, then of stage 2), so a stage's output is the next one's input without moving data; only the last
+ * stage stores planar.
+ *
+ * d_tokens: fp32 [n][grid_d grid_h grid_w][e], the tokens after the final norm without the register tokens.  params: HOST array of 10
+ * device pointers, fp32, as the torch modules store them: {W1 [e][c1][2][2][2], b1, ln1 weight, ln1 bias, W2 [c1][c2][2][2][2], b2,
+ * ln2 weight, ln2 bias, W3 [c2][c][2][2][2], b3}; the conv biases may be NULL.  out_norm: 0 none, 1 demean (per (n, c): subtract the
+ * spatial mean), 2 instance ((x - mean) / sqrt(biased var + out_eps) per (n, c)); ln_eps: the decoder norms'.  d_out: fp32
+ * [n][c][8 grid_d][8 grid_h][8 grid_w].  Products run on the f32-input MFMA (exact fp32 products, fp32 sums); LayerNorm, GELU, their
+ * adjoints and every reduction are fp32, the per-(n, c) statistics are combined in double.  No atomics, every long sum through partials
+ * added in one fixed order: bit-identical results run to run.  No allocation, no synchronisation, no host read-back (capture-safe).
+ *
+ * d_saved (amx_vit_decoder_train_saved_bytes) is state the caller owns until the backward ran: the raw stage outputs a_1, a_2, the
+ * mean and rstd of their rows, the output norm's mean and rstd per (n, c).  d_scratch (amx_vit_decoder_train_scratch_bytes, for either
+ * entry) is not: no call reads what an earlier call left there.  Both sizes are 0 outside the envelope -- e, c1, c2 multiples of 4 up
+ * to 1056 / 328 / 104, c in 1 .. 128, any token grid with extents >= 1, n c <= 65535, every tensor below 2^31 elements -- which the
+ * entries refuse with AMX_ERR_SHAPE.  Both buffers are 16-byte aligned. */
+size_t amx_vit_decoder_train_saved_bytes(int n, int grid_d, int grid_h, int grid_w, int e, int c1, int c2, int c);
+size_t amx_vit_decoder_train_scratch_bytes(int n, int grid_d, int grid_h, int grid_w, int e, int c1, int c2, int c);
+int amx_vit_decoder_train_forward(const float* d_tokens, const void* const* params, int n, int grid_d, int grid_h, int grid_w, int e, int c1,
+                                  int c2, int c, float ln_eps, int out_norm, float out_eps, float* d_out, void* d_saved, size_t saved_bytes,
+                                  void* d_scratch, size_t scratch_bytes, void* stream);
+/* From d_dout (the gradient of d_out, contiguous) and, for out_norm == 2, d_out itself (else it may be NULL): d_dtokens
+ * [n][tokens][e] and grads, a HOST array of 10 device pointers in the order of params.  Every output is written, not accumulated, and
+ * may be NULL: it is then skipped and the others are unchanged bit for bit.  h_1, h_2 are recomputed from d_saved. */
+int amx_vit_decoder_backward(const float* d_dout, const float* d_out, const float* d_tokens, const void* const* params, const void* d_saved,
+                             size_t saved_bytes, int n, int grid_d, int grid_h, int grid_w, int e, int c1, int c2, int c, float ln_eps,
+                             int out_norm, float out_eps, float* d_dtokens, void* const* grads, void* d_scratch, size_t scratch_bytes,
+                             void* stream);
+
 /* ---- The whole 3D ViT variant `anatomix-dev-vit` (PrimusV2-S) as one forward ------------------------------------------------
  * Replaces PrimusV2.forward (anatomix/model/vit3d/architectures.py:231-260 with the wrapper's extensions :89-165, tokenizer
  * deep_tokenizer.py:12-68, registry entry load_from_hf.py:25-35): conv tokenizer (stem + three stride-2 residual stages + 1x1x1
